@@ -10,6 +10,11 @@ rotations -> <psi|H|psi>), i.e. B energy evaluations; all inputs (program, Hamil
 parameter blocks) are resident in HBM before the timed region; the B energies of a step are copied
 back to the host inside the step.  With N GPUs every rank evaluates its own
 batch of B vectors (replicas over the batch dimension, no data-path collective): weak scaling.
+
+A plain run sets up, warms up, times --steps steps and prints the line (`ms_per_step` = wall time of one timed step);
+--dump-outputs DIR also writes the energies of the last timed step.  Everything else (the dense-kernel cross-check, the
+sharded block, the 30-qubit HBM roofline sweeps, the side workloads and the CPU baseline with its oracle check of the timed
+batch) runs only with --full.
 """
 import argparse
 import json
@@ -744,6 +749,8 @@ def cpu_baseline_leg(ham, gens, hf, thetas, budget_s=12.0):
 
 
 LINE_LIMIT = 4096   # the driver's parser gave up on a 22-KB line (round 4): the printed line stays below this, tested
+POOL_BLOCKS = 32    # distinct B x K parameter blocks resident in HBM; steps beyond this many cycle through them
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much is written
 
 
 def _r(v, digits=6):
@@ -893,7 +900,14 @@ def main():
     ap.add_argument("--no-scale-proxy", action="store_true", help="skip the dry 8-rank leg of configs[4] (one rank of 34 qubits on this GPU)")
     ap.add_argument("--sharded-rotations", type=int, default=64)
     ap.add_argument("--sharded-terms", type=int, default=1000)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side legs: dense-kernel cross-check, sharded block, HBM roofline "
+                         "sweeps, side workloads, CPU baseline (each still subject to its --no-* flag); off: the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the energies of the last timed step (rank 0) to DIR/energies.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: this process has not touched the GPU and never will — it starts the N ranks
@@ -937,13 +951,15 @@ def main():
     G = len(set(ham.packed()[0].tolist()))
     B = args.batch
     rng = np.random.default_rng(140 + rank)
-    nbatches = args.steps + args.warmup
-    # inputs resident in HBM before the timed region: every step reads its own B x K parameter block from device
-    # memory and leaves B energies there; the energies of each step are copied back to the host inside the step.
+    # inputs resident in HBM before the timed region: every step reads a B x K parameter block from device memory and
+    # leaves B energies there; the energies of each step are copied back to the host inside the step.  Step k (warm-up
+    # steps first) uses block k % nblocks: up to POOL_BLOCKS steps every step has its own block, beyond that they cycle,
+    # so that memory does not grow with --steps (one block is B * K * 8 bytes: 73 MB at the defaults).
+    nblocks = min(args.steps + args.warmup, POOL_BLOCKS)
     dev = torch.device("cuda", local_rank)
-    thetas_host = rng.uniform(-0.1, 0.1, size=(nbatches, B, K))
+    thetas_host = rng.uniform(-0.1, 0.1, size=(nblocks, B, K))
     thetas_dev = torch.from_numpy(thetas_host).to(dev)
-    energies_dev = torch.empty((nbatches, B), dtype=torch.float64, device=dev)
+    energies_dev = torch.empty((nblocks, B), dtype=torch.float64, device=dev)
 
     sv = Statevector(n, device=local_rank)
     sv.set_hamiltonian(ham)
@@ -958,6 +974,7 @@ def main():
     host_energies = torch.empty((B,), dtype=torch.float64).pin_memory()   # where the optimiser reads them: no staging copy
 
     def step(k):
+        k %= nblocks
         sv.energy_batch_device(B, thetas_dev[k].data_ptr(), energies_dev[k].data_ptr())
         host_energies.copy_(energies_dev[k])   # blocking device-to-host copy: the step ends with the energies on the host
         return host_energies
@@ -983,23 +1000,33 @@ def main():
     total_evals = world * B * args.steps
     value = total_evals / elapsed
     e = e.numpy().copy()
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the timed path receives from the last timed step: its B energies (float64, B * 8 bytes; above
+        # DUMP_LIMIT_BYTES a fixed, seeded sample of them in index order)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dump = e.astype(np.float64)
+        if dump.nbytes > DUMP_LIMIT_BYTES:
+            keep = DUMP_LIMIT_BYTES // dump.itemsize
+            dump = dump[np.sort(np.random.default_rng(0).choice(dump.size, keep, replace=False))]
+        np.save(os.path.join(args.dump_outputs, "energies.npy"), dump)
 
     # the same steps on the dense LDS statevector kernel (support compaction off), rank 0, for the record
     dense = None
-    if rank == 0:
+    if rank == 0 and args.full:
         sv.set_option("force_path", 1)
         nd = max(1, min(args.steps, 3))
         bd = min(B, 8192)
+        slots = [(args.warmup + k) % nblocks for k in range(nd)]
         dense_out = torch.empty((nd, bd), dtype=torch.float64, device=dev)
         t0 = time.perf_counter()
         kd = 0.0
         for k in range(nd):
-            sv.energy_batch_device(bd, thetas_dev[args.warmup + k].data_ptr(), dense_out[k].data_ptr())
+            sv.energy_batch_device(bd, thetas_dev[slots[k]].data_ptr(), dense_out[k].data_ptr())
             kd += sv.last_batch_ms()
         torch.cuda.synchronize()
         dense = {"evals_per_s": nd * bd / (time.perf_counter() - t0), "kernel_only_evals_per_s": nd * bd / (kd * 1e-3),
                  "batch": bd, "max_abs_diff_vs_value_path": float(
-                     (dense_out - energies_dev[args.warmup:args.warmup + nd, :bd]).abs().max().item())}
+                     (dense_out - energies_dev[slots, :bd]).abs().max().item())}
         sv.set_option("force_path", 0)
 
     out = {
@@ -1026,7 +1053,7 @@ def main():
     # configs[4]: the index-bit-partitioned register through the same launch (every rank takes part; outside the timed steps).
     # Every collective wait of it sits under a deadline (openvqe_amd.distributed.DistWatchdog, OVQE_DIST_TIMEOUT_S, default 120 s
     # without progress): on expiry rank 0 prints the line with "sharded": {"error": ...} and every rank leaves with exit code 3
-    if not args.no_sharded:
+    if args.full and not args.no_sharded:
         from openvqe_amd import distributed as _dd
 
         def expired(phase, seconds):
@@ -1093,7 +1120,7 @@ def main():
                     "bank-conflict cycles cut by a third without any change in run time) but by instruction issue and the "
                     "latency of the dependent chain amplitudes -> rotate -> store of consecutive rows on one wave",
         }
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             sv.close()
             nq = args.roofline_qubits
             rows = roofline_leg(local_rank, nq)
@@ -1120,7 +1147,7 @@ def main():
                 "worst_string": worst,
                 "per_string": rows,
             }
-        if not args.no_extra and world == 1:  # side figures belong to the single-GPU line; N > 1 ranks only wait
+        if args.full and not args.no_extra and world == 1:  # side figures belong to the single-GPU line; N > 1 ranks only wait
             out["extra_workloads"] = extra_workloads_leg(local_rank)
             # what the reference's callers see on this workload (H2O/STO-3G UCCSD), lifted out of the side figures:
             # `value` is the resident-batch throughput; scipy's optimisers call ONE evaluation at a time
@@ -1160,15 +1187,16 @@ def main():
                     "n2_fci_627264_determinants": {k: n2["fci_of_the_sector_lanczos"][k] for k in ("energy", "iterations", "wall_s")},
                     "n2_fermionic_adapt_30_iterations": n2.get("fermionic_adapt_30_iterations"),
                 }
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             # the oracle evaluates the first `cores` parameter vectors of the FIRST TIMED step; the energies the timed launch
             # (k_sparse_vqe_rows, B-wide) left in HBM for those vectors are compared with them: the kernel behind `value` is
             # checked in the run that times it (the single-call kernel keeps its own check beside it)
             kt = args.warmup
-            cpu, cores = cpu_baseline_leg(ham, gens, hf, thetas_host[kt], args.cpu_seconds)
-            e_gpu0 = energy_check(ham, gens, hf, thetas_host[kt, 0], local_rank)
+            kb = kt % nblocks   # its parameter block (and energy slot, last written by a timed step on the same block)
+            cpu, cores = cpu_baseline_leg(ham, gens, hf, thetas_host[kb], args.cpu_seconds)
+            e_gpu0 = energy_check(ham, gens, hf, thetas_host[kb, 0], local_rank)
             nchk = min(cores, B)
-            e_timed = energies_dev[kt, :nchk].cpu().numpy()
+            e_timed = energies_dev[kb, :nchk].cpu().numpy()
             batch_diff = {lab: float(np.abs(e_timed - cpu[lab].pop("energies")[:nchk]).max()) for lab in ("fused", "gate_level")}
             out["cpu_baseline"] = {
                 "value": cpu["fused"]["evals_per_s"],

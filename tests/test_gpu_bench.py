@@ -56,7 +56,7 @@ def test_two_process_sharded_block_against_oracle(gpu_lib):
     # the PLAIN command, no launcher and no WORLD_SIZE: bench.py starts its own two ranks (a fresh child, never exec)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(OVQE_BENCH_BACKEND="gloo", OVQE_BENCH_SINGLE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--batch", "1024", "--no-roofline", "--no-cpu", "--no-extra", "--sharded-qubits", "15", "--sharded-rotations", "24",
            "--sharded-terms", "80"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
@@ -97,7 +97,7 @@ def test_stalled_rank_ends_the_sharded_leg_with_a_line_and_exit_code_3(gpu_lib):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(OVQE_BENCH_BACKEND="gloo", OVQE_BENCH_SINGLE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0",
                OVQE_DIST_TIMEOUT_S="6", OVQE_BENCH_INJECT_STALL_RANK="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--batch", "1024", "--no-roofline", "--no-cpu", "--no-extra", "--sharded-qubits", "15", "--sharded-rotations", "24",
            "--sharded-terms", "80"]
     t0 = time.perf_counter()
@@ -117,7 +117,7 @@ def test_failing_sharded_leg_still_prints_the_line(gpu_lib):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(OVQE_BENCH_BACKEND="gloo", OVQE_BENCH_SINGLE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0",
                OVQE_BENCH_INJECT_SHARDED_ERROR="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--batch", "1024", "--no-roofline", "--no-cpu", "--no-extra", "--sharded-qubits", "15", "--sharded-rotations", "24",
            "--sharded-terms", "80"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
@@ -130,7 +130,7 @@ def test_failing_sharded_leg_still_prints_the_line(gpu_lib):
 def test_single_gpu_sharded_leg_checks_its_energy_against_the_value_on_record(gpu_lib):
     """`sharded.energy_check`: the 31-qubit energy of configs[4]'s strong leg does not depend on the number of GPUs; the value of the
     one-GPU run is on record (bench.SHARDED_KNOWN) and every run compares with it to 1e-11 |H|_1.  Here: the record mechanism on a
-    small register against the bit-mask oracle (the 31-qubit leg itself is part of the default bench run)."""
+    small register against the bit-mask oracle (the 31-qubit leg itself is part of `bench.py --full`)."""
     import numpy as np
 
     import bench
@@ -152,3 +152,32 @@ def test_single_gpu_sharded_leg_checks_its_energy_against_the_value_on_record(gp
         assert not leg["energy_check"]["ok"]
     finally:
         del bench.SHARDED_KNOWN[(n, R, T)]
+
+
+def test_plain_run_times_the_headline_only_and_dumps_the_last_step(gpu_lib, tmp_path):
+    """`bench.py --gpus 1` without --full: the line carries the contract's keys and none of the side legs; --dump-outputs
+    writes the B energies of the last timed step, which equal the C oracle's on that step's parameter block (step 3 of
+    warm-up 1 + 3 timed steps: block 3 of the seeded draw)"""
+    import numpy as np
+
+    import bench
+    from oracle import cref
+    from openvqe_amd.backend import compile_ucc_program
+    B = 512
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B),
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _strict_json(r.stdout.strip().splitlines()[-1])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["dtype"] == "f64"
+    assert abs(out["value"] - B * 3 / (out["ms_per_step"] * 3e-3)) < 1e-6 * out["value"]
+    for side in ("roofline", "cpu_baseline", "sharded", "side"):
+        assert side not in out, side
+    e = np.load(os.path.join(str(tmp_path), "energies.npy"))
+    assert e.dtype == np.float64 and e.shape == (B,)
+    ham, gens, hf = bench.build_workload()
+    thetas = np.random.default_rng(140).uniform(-0.1, 0.1, size=(4, B, len(gens)))[3]
+    rx, rz, rc, pidx, _ = compile_ucc_program(ham.nbqbits, gens)
+    hx, hz, hc = ham.packed()
+    want = cref.ucc_energy_batch(ham.nbqbits, hf, rx, rz, rc, pidx, thetas[:16], hx, hz, hc.real.copy(), ham.constant_coeff)
+    assert np.abs(e[:16] - want).max() < 1e-10, np.abs(e[:16] - want).max()

@@ -109,7 +109,7 @@ def test_bench_distributed_path_over_rccl_at_world_size_one(gpu_lib):
     all_reduce of the wall time, the `sharded` block through the same group — and the JSON line is the LAST line."""
     env = dict(os.environ, OVQE_BENCH_FORCE_DIST="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4096",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4096",
            "--no-roofline", "--no-cpu", "--no-extra", "--sharded-qubits", "24", "--sharded-rotations", "16",
            "--sharded-terms", "60"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
