@@ -361,7 +361,12 @@ int ovqe_last_batch_ms(ovqe_handle h, double *ms);
  * forms of the sector path that served the handle since the program was set, as bits — 0 / 1 / 2 / 3 forward sweeps on pair words /
  * 64-bit words with rounds / per-wave streams / regular supports by bit arithmetic, 4..7 the backward sweeps of
  * ovqe_energy_gradient in the same order, 8 / 9 first / second form of the pair-table builder (the tests name the geometry behind
- * every form: DESIGN.md section 4) */
+ * every form: DESIGN.md section 4).  which = 7: the kernel forms of the support-compacted path (programs whose reachable support
+ * holds at most 4096 basis states) that served the handle since the program was set, as bits — 0 one evaluation per workgroup
+ * (batches <= 256), 1 / 2 one evaluation per wave with / without its op table staged in LDS, 3 two per wave on rows of 64-bit
+ * words (batches >= 2048), 4 / 5 two / four per wave without rows; 6 / 7 / 8 ovqe_energy_gradient per workgroup / per wave
+ * staged / per wave; 9 a call that wanted the path was served by the other paths (no compact support, or no form fits the
+ * program's LDS budget) */
 int ovqe_last_support(ovqe_handle h, int32_t which, int64_t *support);
 /* shape of the compiled program (diagnostics / tests), up to `count` entries of:
  *   [0] ops of the sequential program  [1] Pauli rotations  [2] literal X/H/CNOT ops  [3] streaming sweeps per

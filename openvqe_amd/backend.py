@@ -380,6 +380,15 @@ class Statevector:
         self._ck(self._L.ovqe_last_support(self._h, 6, ctypes.byref(out)))
         return {name for bit, name in enumerate(self.SECTOR_FORMS) if (out.value >> bit) & 1}
 
+    SPARSE_FORMS = ("wg", "staged1", "plain1", "rows2", "plain2", "plain4", "grad_wg", "grad_staged", "grad_plain", "declined")
+
+    def sparse_forms(self):
+        """names of the support-compacted kernel forms that served this handle since its program was set (ovqe_last_support,
+        which = 7); "declined": a call that wanted the compact path was served by the other paths"""
+        out = ctypes.c_int64()
+        self._ck(self._L.ovqe_last_support(self._h, 7, ctypes.byref(out)))
+        return {name for bit, name in enumerate(self.SPARSE_FORMS) if (out.value >> bit) & 1}
+
     def last_exp_support(self):
         """amplitudes the Taylor steps of the last ``apply_exp_pauli_sum`` call ran over (-1: the register)"""
         out = ctypes.c_int64()

@@ -35,7 +35,7 @@ int ovqe_set_program(ovqe_handle h, int64_t R, const uint64_t *x, const uint64_t
                      const double *phi0, const int32_t *pidx, int32_t K, uint64_t hf_index) try {
     OVQE_ENTER(h);
     if (h) h->prog_from_gates = false;
-    if (h) h->forms_used = 0;
+    if (h) h->forms_used = h->sp_forms = 0;
     if (!h || R < 0 || K < 0 || (R && (!x || !z || !coeff || !pidx))) return OVQE_ERR_INVALID;
     const int ntot = h->n_local + h->n_global;
     const uint64_t allmask = ntot >= 64 ? ~0ull : ((1ull << ntot) - 1ull);
@@ -90,7 +90,7 @@ int ovqe_set_gate_program(ovqe_handle h, int64_t G, const int32_t *opcode, const
     h->frame_open = false;
     h->prog_from_gates = false;
     h->prog_extends_prev = false;
-    h->forms_used = 0;
+    h->forms_used = h->sp_forms = 0;
     h->prev_x.clear();
     if (h->opt_clifford_frame) {
         bool done = false;
@@ -152,8 +152,14 @@ int ovqe_energy_batch(ovqe_handle h, int64_t B, const double *theta, int32_t K, 
             rc = build_sparse_program(h);
             if (rc) return rc;
         }
-        if (wanted && h->sp_valid) return run_sparse(h, B, theta, energies);
-        if (h->opt_force_path == 3) return fail(h, OVQE_ERR_STATE, "program has no compact support (sparse path forced)");
+        if (wanted && h->sp_valid) {
+            bool done = false;
+            rc = run_sparse(h, B, theta, energies, false, &done);
+            if (rc || done) return rc;
+        } else if (wanted) {
+            h->sp_forms |= SPF_DECLINED;
+        }
+        if (h->opt_force_path == 3) return fail(h, OVQE_ERR_STATE, "program has no compact form (sparse path forced)");
     }
     if (use_small_path(h, B)) return run_small(h, B, theta, energies);
     // a lone evaluation is not timed with events (ovqe_last_batch_ms reads 0, as on the fused kernels' zero-copy path): every path below
@@ -299,8 +305,14 @@ int ovqe_energy_batch_device(ovqe_handle h, int64_t B, const void *theta_dev, in
             rc = build_sparse_program(h);
             if (rc) return rc;
         }
-        if (h->sp_valid) return run_sparse(h, B, (const double *)theta_dev, (double *)energies_dev, true);
-        if (h->opt_force_path == 3) return fail(h, OVQE_ERR_STATE, "program has no compact support (sparse path forced)");
+        if (h->sp_valid) {
+            bool done = false;
+            rc = run_sparse(h, B, (const double *)theta_dev, (double *)energies_dev, true, &done);
+            if (rc || done) return rc;
+        } else {
+            h->sp_forms |= SPF_DECLINED;
+        }
+        if (h->opt_force_path == 3) return fail(h, OVQE_ERR_STATE, "program has no compact form (sparse path forced)");
     }
     if (h->n_global == 0 && h->n_local <= 16 && h->opt_force_path != 2)
         return run_small(h, B, (const double *)theta_dev, (double *)energies_dev, true);

@@ -347,6 +347,8 @@ struct ovqe_sv {
     // 2 third (per-wave streams), 3 regular supports (bit arithmetic); 4..7 the backward sweeps of ovqe_energy_gradient in the same order;
     // 8 / 9 the first / second form of the pair-table builder
     uint32_t forms_used = 0;
+    // ... and of the support-compacted path (ovqe_last_support which = 7, SPF_* in sparse_host.inc)
+    uint32_t sp_forms = 0;
     bool nz_super = false, nz_super_prev = false, state_exposed = false;
     uint64_t nz_super_count = 0;
     DevBuf d_tile_smasks, d_tile_lists, d_tile_counts;   // non-empty tiles per sweep of H psi on a listed state (k_tile_lists)  // support list of the screened state (k_pool_grad_nz)
@@ -1645,9 +1647,9 @@ int ovqe_get_rotation_program(ovqe_handle h, int64_t capacity, uint64_t *x, uint
 
 int ovqe_last_support(ovqe_handle h, int32_t which, int64_t *support) try {
     OVQE_ENTER(h);
-    if (!h || !support || which < 0 || which > 6) return OVQE_ERR_INVALID;
-    const int64_t v[7] = {h->last_screen_support, h->last_exp_support, h->last_screen_sector, h->last_fci_rounds, h->last_passes, h->last_pass_bytes,
-                          (int64_t)h->forms_used};
+    if (!h || !support || which < 0 || which > 7) return OVQE_ERR_INVALID;
+    const int64_t v[8] = {h->last_screen_support, h->last_exp_support, h->last_screen_sector, h->last_fci_rounds, h->last_passes, h->last_pass_bytes,
+                          (int64_t)h->forms_used, (int64_t)h->sp_forms};
     *support = v[which];
     return OVQE_OK;
 } OVQE_CATCH(h)

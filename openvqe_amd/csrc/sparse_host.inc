@@ -420,9 +420,50 @@ int launch_sparse(ovqe_handle h, const SparseArgs &A, int grid, size_t smem) {
     return OVQE_OK;
 }
 
-// on_device: theta / energies are device pointers (inputs already resident in HBM, results left there)
-int run_sparse(ovqe_handle h, int64_t B, const double *theta, double *energies, bool on_device = false) {
+// which forms served a handle since its program was set (ovqe_last_support which = 7; the tests name the geometry behind each)
+enum : uint32_t {
+    SPF_WG = 1u << 0,            // k_sparse_vqe_wg: one evaluation per workgroup (B <= 256)
+    SPF_STAGED1 = 1u << 1,       // k_sparse_vqe<1, true>: op table and pair words staged in LDS (B <= 1024)
+    SPF_PLAIN1 = 1u << 2,        // k_sparse_vqe<1, false>
+    SPF_ROWS2 = 1u << 3,         // k_sparse_vqe_rows<2>: the throughput form (B >= 2048)
+    SPF_PLAIN2 = 1u << 4,        // k_sparse_vqe<2, false> (no row tables)
+    SPF_PLAIN4 = 1u << 5,        // k_sparse_vqe<4, false> ("sparse_spw" = 4)
+    SPF_GRAD_WG = 1u << 6,       // k_sparse_grad_wg
+    SPF_GRAD_STAGED = 1u << 7,   // k_sparse_grad<true>
+    SPF_GRAD_PLAIN = 1u << 8,    // k_sparse_grad<false>
+    SPF_DECLINED = 1u << 9,      // a call wanted the compact path and no form of it fits: the other paths served it
+};
+
+// on_device: theta / energies are device pointers (inputs already resident in HBM, results left there).  *done = false: no compact
+// form fits this program's LDS budget (nothing was launched; the caller takes the other paths).
+int run_sparse(ovqe_handle h, int64_t B, const double *theta, double *energies, bool on_device, bool *done) {
+    *done = false;
     int rc = OVQE_OK;
+    SparseArgs A;
+    A.m = h->sp_mp;
+    A.mpad = (h->sp_mp + 1) & ~1;
+    A.hf = h->sp_hf;
+    A.K = h->K;
+    A.nops = h->sp_nops;
+    A.ntab = (int)h->srots.size();
+    A.nent = h->sp_nent;
+    A.npairs = (int)h->sp_npairs;
+    A.B = B;
+    A.constant = h->ham.constant;
+    A.dbg = h->opt_sparse_dbg;
+    const size_t per_eval = (size_t)A.mpad * sizeof(double) + (size_t)A.ntab * sizeof(double2);
+    static_assert(sizeof(double2) == 16 && sizeof(SpOp) == 16, "LDS carve-up of k_sparse_vqe assumes 16-byte records");
+    int spw = h->opt_sparse_spw;
+    if (spw != 1 && spw != 2 && spw != 4) spw = B >= 2048 ? 2 : 1;  // measured: 2 evaluations per wave is the sweet spot
+    if (B <= 1024) spw = 1;
+    while (spw > 1 && per_eval * spw > 64 * 1024) spw >>= 1;
+    // the workgroup form holds one cos/sin entry per distinct angle (at most 4094 of them, 64 KiB: its row tables exist only then)
+    // and fits whatever the whole table takes; every other form holds the whole table
+    const bool wg = B <= 256 && h->sp_nrows8 && h->opt_sparse_rows && h->opt_sparse_wg;
+    if (!wg && per_eval * spw > 150 * 1024) {
+        h->sp_forms |= SPF_DECLINED;
+        return OVQE_OK;
+    }
     const double *d_theta = theta;
     double *d_energies = energies;
     const bool zero_copy = !on_device && mapped_io(h, B);
@@ -442,31 +483,12 @@ int run_sparse(ovqe_handle h, int64_t B, const double *theta, double *energies, 
     }
     h->cur_theta = d_theta;
     h->cur_energies = d_energies;
-    SparseArgs A;
-    A.m = h->sp_mp;
-    A.mpad = (h->sp_mp + 1) & ~1;
-    A.hf = h->sp_hf;
-    A.K = h->K;
-    A.nops = h->sp_nops;
-    A.ntab = (int)h->srots.size();
-    A.nent = h->sp_nent;
-    A.npairs = (int)h->sp_npairs;
-    A.B = B;
-    A.constant = h->ham.constant;
-    A.dbg = h->opt_sparse_dbg;
-    const size_t per_eval = (size_t)A.mpad * sizeof(double) + (size_t)A.ntab * sizeof(double2);
-    static_assert(sizeof(double2) == 16 && sizeof(SpOp) == 16, "LDS carve-up of k_sparse_vqe assumes 16-byte records");
-    int spw = h->opt_sparse_spw;
-    if (spw != 1 && spw != 2 && spw != 4) spw = B >= 2048 ? 2 : 1;  // measured: 2 evaluations per wave is the sweet spot
-    if (B <= 1024) spw = 1;
-    while (spw > 1 && per_eval * spw > 64 * 1024) spw >>= 1;
-    if (per_eval * spw > 150 * 1024) return fail(h, OVQE_ERR_INVALID, "support too large for the compacted kernel");
     const int64_t nwork = (B + spw - 1) / spw;
     const int grid = (int)std::min<int64_t>(nwork, 256 * 32);
     if (!zero_copy) HIPC(h, hipEventRecord(h->ev0, h->stream));
     // latency path: op table + pair words staged in LDS (one wave per evaluation, occupancy does not matter)
     const size_t staged = per_eval + (size_t)A.nops * sizeof(SpOp) + (size_t)A.npairs * sizeof(uint32_t);
-    if (B <= 256 && h->sp_nrows8 && h->opt_sparse_rows && h->opt_sparse_wg) {
+    if (wg) {
         // latency path: one evaluation per 1024-thread workgroup, at most one workgroup per CU (k_sparse_vqe_wg; measured: H2O
         // B = 1 / 141 32 / 37 us against 60 / 61 us with one wave per evaluation, B = 1024 129 against 115 us)
         SparseArgs R = A;
@@ -483,9 +505,16 @@ int run_sparse(ovqe_handle h, int64_t B, const double *theta, double *energies, 
                            (const SmallRot *)h->d_sp_prim.p, (const uint64_t *)h->d_sp_rows64.p, h->sp_nrows8, (const SpEntry *)h->d_sp_entries.p,
                            h->cur_energies);
         HIPC(h, hipGetLastError());
+        h->sp_forms |= SPF_WG;
     }
-    else if (B <= 1024 && staged <= 96 * 1024) rc = launch_sparse<1, true>(h, A, grid, staged);
-    else if (spw == 4) rc = launch_sparse<4>(h, A, grid, per_eval * 4);
+    else if (B <= 1024 && staged <= 96 * 1024) {
+        rc = launch_sparse<1, true>(h, A, grid, staged);
+        h->sp_forms |= SPF_STAGED1;
+    }
+    else if (spw == 4) {
+        rc = launch_sparse<4>(h, A, grid, per_eval * 4);
+        h->sp_forms |= SPF_PLAIN4;
+    }
     else if (spw == 2 && h->sp_nrows4 && h->opt_sparse_rows) {
         SparseArgs R = A;
         R.mpad = (h->sp_mp + 64 + 1) & ~1;   // + the padded lanes' spare slots
@@ -508,10 +537,18 @@ int run_sparse(ovqe_handle h, int64_t B, const double *theta, double *energies, 
         }
 #undef OVQE_ROWS
         HIPC(h, hipGetLastError());
+        h->sp_forms |= SPF_ROWS2;
     }
-    else if (spw == 2) rc = launch_sparse<2>(h, A, grid, per_eval * 2);
-    else rc = launch_sparse<1>(h, A, grid, per_eval);
+    else if (spw == 2) {
+        rc = launch_sparse<2>(h, A, grid, per_eval * 2);
+        h->sp_forms |= SPF_PLAIN2;
+    }
+    else {
+        rc = launch_sparse<1>(h, A, grid, per_eval);
+        h->sp_forms |= SPF_PLAIN1;
+    }
     if (rc) return rc;
+    *done = true;
     if (zero_copy) {
         if (!poll || !poll_mapped_slots(h->h_io + (size_t)B * h->K, B)) HIPC(h, hipStreamSynchronize(h->stream));
         std::memcpy(energies, h->h_io + (size_t)B * h->K, (size_t)B * sizeof(double));
@@ -536,7 +573,10 @@ int run_sparse_gradient(ovqe_handle h, const double *theta, double *energy, doub
         rc = build_sparse_program(h);
         if (rc) return rc;
     }
-    if (!h->sp_valid) return OVQE_OK;
+    if (!h->sp_valid) {
+        h->sp_forms |= SPF_DECLINED;
+        return OVQE_OK;
+    }
     SparseArgs A;
     A.m = h->sp_mp;
     A.mpad = (h->sp_mp + 1) & ~1;
@@ -551,7 +591,10 @@ int run_sparse_gradient(ovqe_handle h, const double *theta, double *energy, doub
     const size_t base = 2 * (size_t)A.mpad * sizeof(double) + (size_t)A.ntab * (sizeof(double2) + sizeof(double)) +
                         (size_t)((A.K + 1) & ~1) * sizeof(double);
     const size_t staged = base + (size_t)A.nops * sizeof(SpOp) + (size_t)A.npairs * sizeof(uint32_t);
-    if (base > 150 * 1024) return OVQE_OK;
+    if (base > 150 * 1024) {
+        h->sp_forms |= SPF_DECLINED;
+        return OVQE_OK;
+    }
     const bool stage = staged <= 150 * 1024;
     static bool attr_done_dev[64] = {};
     bool &attr_done = attr_done_dev[h->device & 63];
@@ -577,6 +620,7 @@ int run_sparse_gradient(ovqe_handle h, const double *theta, double *energy, doub
         d_e = (double *)h->d_energies.p;
         d_g = d_e + 1;
     }
+    bool launched = false;
     if (h->sp_nrows8 && h->opt_sparse_rows && h->opt_sparse_wg) {
         SparseArgs R = A;
         R.mpad = (h->sp_mp + 128 + 1) & ~1;
@@ -592,19 +636,19 @@ int run_sparse_gradient(ovqe_handle h, const double *theta, double *energy, doub
         if (smem <= 150 * 1024) {
             hipLaunchKernelGGL((k_sparse_grad_wg<1024, 10>), dim3(1), dim3(1024), smem, h->stream, R, d_theta, (const SmallRot *)h->d_sp_prim.p,
                                (const uint64_t *)h->d_sp_rows64.p, h->sp_nrows8, (const SpEntry *)h->d_sp_entries.p, d_e, d_g);
-        } else if (stage) {
-            hipLaunchKernelGGL((k_sparse_grad<true>), dim3(1), dim3(64), staged, h->stream, A, d_theta, (const SmallRot *)h->d_rots.p,
-                               (const SpOp *)h->d_sp_ops.p, (const uint32_t *)h->d_sp_pairs.p, (const SpEntry *)h->d_sp_entries.p, d_e, d_g);
-        } else {
-            hipLaunchKernelGGL((k_sparse_grad<false>), dim3(1), dim3(64), base, h->stream, A, d_theta, (const SmallRot *)h->d_rots.p,
-                               (const SpOp *)h->d_sp_ops.p, (const uint32_t *)h->d_sp_pairs.p, (const SpEntry *)h->d_sp_entries.p, d_e, d_g);
+            h->sp_forms |= SPF_GRAD_WG;
+            launched = true;
         }
-    } else if (stage)
+    }
+    if (!launched && stage) {
         hipLaunchKernelGGL((k_sparse_grad<true>), dim3(1), dim3(64), staged, h->stream, A, d_theta, (const SmallRot *)h->d_rots.p,
                            (const SpOp *)h->d_sp_ops.p, (const uint32_t *)h->d_sp_pairs.p, (const SpEntry *)h->d_sp_entries.p, d_e, d_g);
-    else
+        h->sp_forms |= SPF_GRAD_STAGED;
+    } else if (!launched) {
         hipLaunchKernelGGL((k_sparse_grad<false>), dim3(1), dim3(64), base, h->stream, A, d_theta, (const SmallRot *)h->d_rots.p,
                            (const SpOp *)h->d_sp_ops.p, (const uint32_t *)h->d_sp_pairs.p, (const SpEntry *)h->d_sp_entries.p, d_e, d_g);
+        h->sp_forms |= SPF_GRAD_PLAIN;
+    }
     HIPC(h, hipGetLastError());
     if (zero_copy) {
         HIPC(h, hipStreamSynchronize(h->stream));

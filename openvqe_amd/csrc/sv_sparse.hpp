@@ -105,7 +105,7 @@ __global__ __launch_bounds__(64) void k_sparse_vqe(SparseArgs A, const double *_
                 // executes a wave's DS instructions in issue order, so only the COMPILER must not reorder across ops
                 asm volatile("" ::: "memory");
             }
-        } else {
+        } else if (A.nops > 0) {   // (a program with no active op on the support has no op record to fetch ahead)
             // op records and pair words stream from L2: the chain record -> pair word -> amplitudes of consecutive ops is
             // what bounds this kernel, so both are fetched AHEAD — the record of op o + 3 and the first pair words of ops o + 1,
             // o + 2 are in flight while op o rotates its pairs (most ops have fewer pairs than lanes: one word per lane)

@@ -96,3 +96,42 @@ def gate_cnot(psi, nbqbits, control, target):
     idx = np.arange(psi.shape[0], dtype=np.int64)
     src = np.where(idx & cb, idx ^ tb, idx)
     return psi[src]
+
+
+# ---------------------------------------------------------------- gradient
+def ucc_state(n, hf_index, rx, rz, rc, pidx, theta, phi0=None):
+    """psi = prod_r exp(-i phi_r P_r) |hf>, rotation 0 first; phi_r = rc_r theta[pidx_r] (+ phi0_r), a fixed phi0_r when pidx_r < 0."""
+    psi = np.zeros(1 << n, np.complex128)
+    psi[int(hf_index)] = 1.0
+    for r, phi in enumerate(_angles(rc, pidx, theta, phi0)):
+        psi = rotate(psi, int(rx[r]), int(rz[r]), phi)
+    return psi
+
+
+def _angles(rc, pidx, theta, phi0):
+    theta = np.asarray(theta, np.float64)
+    out = []
+    for r in range(len(rc)):
+        p = int(pidx[r])
+        phi = float(rc[r]) * float(theta[p]) if p >= 0 else 0.0
+        out.append(phi + (float(phi0[r]) if phi0 is not None else 0.0))
+    return out
+
+
+def ucc_energy_gradient(n, hf_index, rx, rz, rc, pidx, theta, hx, hz, hc, constant=0.0, phi0=None):
+    """E(theta) and all K = len(theta) derivatives dE/dtheta_k of E = <psi|H|psi> + constant (psi: ``ucc_state``) by the adjoint
+    method, complex128: forward rotations, lambda = H psi, then the rotations backwards on psi and lambda together —
+    dE/dphi_r = 2 Re <lambda| -i P_r |psi> = 2 Im <lambda|P_r|psi> on the states after rotation r, and dphi_r/dtheta_k = rc_r for
+    pidx_r = k.  -> (E, grad[K])"""
+    phis = _angles(rc, pidx, theta, phi0)
+    psi = ucc_state(n, hf_index, rx, rz, rc, pidx, theta, phi0)
+    lam = apply_pauli_sum(psi, hx, hz, hc)
+    energy = float(np.vdot(psi, lam).real) + float(np.real(constant))
+    grad = np.zeros(len(theta), np.float64)
+    for r in range(len(rc) - 1, -1, -1):
+        x, z = int(rx[r]), int(rz[r])
+        if int(pidx[r]) >= 0:
+            grad[int(pidx[r])] += 2.0 * float(rc[r]) * float(np.vdot(lam, pauli_apply(psi, x, z)).imag)
+        psi = rotate(psi, x, z, -phis[r])
+        lam = rotate(lam, x, z, -phis[r])
+    return energy, grad
