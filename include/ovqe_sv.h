@@ -146,21 +146,14 @@ int ovqe_set_stream(ovqe_handle h, void *hip_stream);
  *   "unknown option" and runs every one of them at its default:
  *   "fault_inject" (1: the next term-list build throws std::bad_alloc: the exception barrier's test), "sector_debug" (2: say on stderr why a
  *   program was left to the dense kernels; 4: wall time of the build's phases), "sector_sweep_dbg" / "sector_h_dbg" / "sparse_dbg" (kernels
- *   truncated after a given phase), "rot_variant", and the launch geometries and superseded forms kept for comparison: "unroll",
- *   "ham_tile_low", "expect_sparse", "expect_streams", "persist_blocks", "compact_cpp", "small_threads", "sparse_rows", "sparse_wg",
- *   "sparse_spw", "sparse_dealias", "sector_sweep" (circuit sweeps on an irregular support: 3 pair words in per-wave streams with barriers at
+ *   truncated after a given phase), and the launch geometries and superseded forms kept for comparison: "sparse_rows", "sparse_wg",
+ *   "sparse_spw", "sector_sweep" (circuit sweeps on an irregular support: 3 pair words in per-wave streams with barriers at
  *   run boundaries only — built on top of the tables of 2 —, 2 64-bit pair words in registers with a barrier per round, 1 first form; 2 on a
  *   handle built under 3 runs the second form on the same tables; 4: the streams for the states of a batch too — the product gives
  *   batches the second form: their workgroups hide each other's barriers and the streams gain them nothing), "sector_stream_waves" (0: waves that share a tile's rows from the pairs per
  *   op of the sweep's largest tile; 1, 2, 4, 8, 16), "sector_stream_arrange" (1: the lanes of a row chosen for the LDS banks), "sector_h_pack" (1: <H> sweeps with at most 1023
- *   magnitudes keep their coded words as 24-bit elements), "sector_chunk",
- *   "sector_depth2", "sector_many_tiles",
- *   "sector_h_lpt", "sector_h_threads", "sector_h_groups", "sector_apply_threads", "sector_eager_rots",
- *   "screen_tables", "sector_batch_threads" / "_nb" / "_sweep_threads" / "_dst_lds" / "_zfast", "tile_flat" (tiled <H>: entries of one
- *   or two merged terms as per-lane items 1 / per-wave entries 0 / items for real states only 2, the default), "sector_apply_seq" (1: lambda = H psi on the sector tables runs one launch per sweep in sequence with plain
- *   additions where one sweep fills the chip; 0: one launch, global atomics), "tile_unsplit" (1: tiled <H> of complex states takes groups
- *   of one or two terms as unsplit entries), "sector_coset_first" (1: a gate list in frame form takes the coset of its Z2 symmetries as
- *   its support without a probe run; the build checks afterwards that the coset is populated), "expect_dense" (1: the
+ *   magnitudes keep their coded words as 24-bit elements), "sector_eager_rots", "tile_flat" (tiled <H>: entries of one
+ *   or two merged terms as per-lane items 1 / per-wave entries 0 / items for real states only 2, the default), "expect_dense" (1: the
  *   first sweep of a tiled <H> of a complex register of 25+ qubits counts its sparse tiles; none: the other sweeps run without the
  *   sparse path's LDS, two workgroups per CU) */
 int ovqe_set_option(ovqe_handle h, const char *name, int64_t value);

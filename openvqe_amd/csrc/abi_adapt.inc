@@ -72,44 +72,42 @@ int ovqe_pool_gradients(ovqe_handle h, int64_t n_ops, const int64_t *offsets, co
             h->pg_valid = true;
             // pattern tables of the same-x runs (see PoolRun)
             h->pg_tables = false;
-            if (h->opt_screen_tables) {
-                std::vector<PoolRun> runs((size_t)std::max<int64_t>(T, 1), PoolRun{0ull, 0u, -1, 0, 0});
-                std::vector<double2> tabs;
-                for (int64_t k = 0; k < n_ops; ++k)
-                    for (int64_t t = offsets[k]; t < offsets[k + 1];) {
-                        int64_t te = t + 1;
-                        while (te < offsets[k + 1] && h->pg_xs[te] == h->pg_xs[t]) ++te;
-                        const uint64_t z0 = h->pg_terms[t].z;
-                        uint64_t V = 0;
-                        for (int64_t u = t; u < te; ++u) V |= h->pg_terms[u].z ^ z0;
-                        const int nv = __builtin_popcountll(V);
-                        if (te - t >= 2 && nv <= 4) {
-                            PoolRun r{z0, 0u, nv, (int32_t)tabs.size(), 0};
-                            int pos[4] = {0, 0, 0, 0}, c = 0;
-                            for (uint64_t mk = V; mk; mk &= mk - 1ull) pos[c++] = __builtin_ctzll(mk);
-                            r.vpos = (uint32_t)pos[0] | ((uint32_t)pos[1] << 6) | ((uint32_t)pos[2] << 12) | ((uint32_t)pos[3] << 18);
-                            for (int pat = 0; pat < (1 << nv); ++pat) {
-                                uint64_t bits = 0;   // the pattern placed on V
-                                for (int b = 0; b < nv; ++b)
-                                    if ((pat >> b) & 1) bits |= 1ull << pos[b];
-                                double dr = 0.0, di = 0.0;
-                                for (int64_t u = t; u < te; ++u) {   // same terms, same order, fma: the device loop's doubles
-                                    const double sg = (__builtin_popcountll(bits & (h->pg_terms[u].z ^ z0)) & 1) ? -1.0 : 1.0;
-                                    dr = std::fma(h->pg_terms[u].cr, sg, dr);
-                                    di = std::fma(h->pg_terms[u].ci, sg, di);
-                                }
-                                tabs.push_back(make_double2(dr, di));
+            std::vector<PoolRun> runs((size_t)std::max<int64_t>(T, 1), PoolRun{0ull, 0u, -1, 0, 0});
+            std::vector<double2> tabs;
+            for (int64_t k = 0; k < n_ops; ++k)
+                for (int64_t t = offsets[k]; t < offsets[k + 1];) {
+                    int64_t te = t + 1;
+                    while (te < offsets[k + 1] && h->pg_xs[te] == h->pg_xs[t]) ++te;
+                    const uint64_t z0 = h->pg_terms[t].z;
+                    uint64_t V = 0;
+                    for (int64_t u = t; u < te; ++u) V |= h->pg_terms[u].z ^ z0;
+                    const int nv = __builtin_popcountll(V);
+                    if (te - t >= 2 && nv <= 4) {
+                        PoolRun r{z0, 0u, nv, (int32_t)tabs.size(), 0};
+                        int pos[4] = {0, 0, 0, 0}, c = 0;
+                        for (uint64_t mk = V; mk; mk &= mk - 1ull) pos[c++] = __builtin_ctzll(mk);
+                        r.vpos = (uint32_t)pos[0] | ((uint32_t)pos[1] << 6) | ((uint32_t)pos[2] << 12) | ((uint32_t)pos[3] << 18);
+                        for (int pat = 0; pat < (1 << nv); ++pat) {
+                            uint64_t bits = 0;   // the pattern placed on V
+                            for (int b = 0; b < nv; ++b)
+                                if ((pat >> b) & 1) bits |= 1ull << pos[b];
+                            double dr = 0.0, di = 0.0;
+                            for (int64_t u = t; u < te; ++u) {   // same terms, same order, fma: the device loop's doubles
+                                const double sg = (__builtin_popcountll(bits & (h->pg_terms[u].z ^ z0)) & 1) ? -1.0 : 1.0;
+                                dr = std::fma(h->pg_terms[u].cr, sg, dr);
+                                di = std::fma(h->pg_terms[u].ci, sg, di);
                             }
-                            runs[t] = r;
+                            tabs.push_back(make_double2(dr, di));
                         }
-                        t = te;
+                        runs[t] = r;
                     }
-                rc = upload(h, h->d_pg_runs, runs.data(), runs.size() * sizeof(PoolRun));
-                if (tabs.empty()) tabs.push_back(make_double2(0.0, 0.0));
-                if (!rc) rc = upload(h, h->d_pg_tabs, tabs.data(), tabs.size() * sizeof(double2));
-                if (rc) return rc;
-                h->pg_tables = true;
-            }
+                    t = te;
+                }
+            rc = upload(h, h->d_pg_runs, runs.data(), runs.size() * sizeof(PoolRun));
+            if (tabs.empty()) tabs.push_back(make_double2(0.0, 0.0));
+            if (!rc) rc = upload(h, h->d_pg_tabs, tabs.data(), tabs.size() * sizeof(double2));
+            if (rc) return rc;
+            h->pg_tables = true;
         }
         // one workgroup per operator while the state re-streams from L2/MALL; above that 2^16 amplitudes per workgroup
         const int nchunks = on_support ? (int)std::min<uint64_t>(256, (support + 65535) >> 16)
@@ -128,7 +126,7 @@ int ovqe_pool_gradients(ovqe_handle h, int64_t n_ops, const int64_t *offsets, co
                                    (const amp_t *)sig, (const uint64_t *)h->d_nz_idx.p, (const amp_t *)h->d_nz_val.p, support,
                                    h->base, (const int64_t *)h->d_pg_off.p, (const uint64_t *)h->d_pg_xs.p,
                                    (const HTerm *)h->d_pg_terms.p, op0, part,
-                                   (h->pg_tables && h->opt_screen_tables) ? (const PoolRun *)h->d_pg_runs.p : (const PoolRun *)nullptr,
+                                   h->pg_tables ? (const PoolRun *)h->d_pg_runs.p : (const PoolRun *)nullptr,
                                    (const double2 *)h->d_pg_tabs.p);
             else
                 hipLaunchKernelGGL(k_pool_grad, dim3((unsigned)nchunks, (unsigned)cnt), dim3(256), 0, h->stream,

@@ -224,7 +224,7 @@ int ovqe_energy_batch(ovqe_handle h, int64_t B, const double *theta, int32_t K, 
             // compact cover: built at the second evaluation of a (program, Hamiltonian) pair — one-shot callers never pay
             HamDev &R = h->ham_real;
             CompactCover &C = h->cc;
-            if (R.tile_bits != tile_bits(h, true) || R.tile_low != ham_tile_low(h, true) || !R.tile_real) {
+            if (R.tile_bits != tile_bits(h, true) || R.tile_low != HAM_TILE_LOW || !R.tile_real) {
                 rc = build_ham_tiles(h, R, true);
                 if (rc) return rc;
             }
@@ -460,7 +460,6 @@ static int build_screen_sector(ovqe_handle h, uint64_t support) {
     free_buf(list);   // (the closure list: the largest of the three, not needed while the tables are built)
     E.K = K;
     E.M = sector_tile_bits(h);
-    E.chunk = (uint32_t)h->opt_sector_chunk;
     SectorScratch W;
     rc = ensure(h, W.inv_circ, (size_t)K * sizeof(uint32_t));
     if (rc) return rc == OVQE_ERR_ALLOC ? ((void)hipGetLastError(), OVQE_OK) : rc;

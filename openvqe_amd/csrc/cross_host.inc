@@ -45,7 +45,7 @@ int build_cross_cover(ovqe_handle h, CrossCover &C, std::vector<CrossRawGroup> g
     }
     const int M = std::min(real ? 13 : 12, m);   // (a real tile holds 2^13 doubles in the same 64 KB; index bit 0 = the pair bit is always inside)
     C.M = M;
-    const int L = std::min(ham_tile_low(h, real), M);
+    const int L = std::min(HAM_TILE_LOW, M);
     const uint64_t lowbits = (1ull << L) - 1ull;
     const int G = (int)groups.size();
     std::vector<char> done(G, 0);

@@ -403,11 +403,8 @@ int run_small(ovqe_handle h, int64_t B, const double *theta, double *energies, b
     const size_t state_bytes = (size_t)h->namps * amp_bytes;
     const bool lds_state = state_bytes <= 128 * 1024;
     const uint64_t npairs = h->namps >> 1;
-    int nt = (!lds_state || npairs >= 1024) ? 1024 : (npairs >= 256 ? 256 : 64);
-    if (lds_state && h->opt_small_threads && npairs >= (uint64_t)h->opt_small_threads &&
-        (h->opt_small_threads == 256 || h->opt_small_threads == 512 || h->opt_small_threads == 1024))
-        nt = h->opt_small_threads;
-    const int lbits = nt == 1024 ? 10 : (nt == 512 ? 9 : (nt == 256 ? 8 : 6));
+    const int nt = (!lds_state || npairs >= 1024) ? 1024 : (npairs >= 256 ? 256 : 64);
+    const int lbits = nt == 1024 ? 10 : (nt == 256 ? 8 : 6);
     int rc = build_exp_tables(h, lbits, real);
     if (rc) return rc;
     int max_slices = (int)std::max<size_t>(1, std::min<size_t>(512, ((size_t)512 << 20) / state_bytes));
@@ -451,13 +448,11 @@ int run_small(ovqe_handle h, int64_t B, const double *theta, double *energies, b
     if (real) {
         if (!lds_state) rc = launch_small<true, false, 1024, 10>(h, A, grid, smem);
         else if (nt == 1024) rc = launch_small<true, true, 1024, 10>(h, A, grid, smem);
-        else if (nt == 512) rc = launch_small<true, true, 512, 9>(h, A, grid, smem);
         else if (nt == 256) rc = launch_small<true, true, 256, 8>(h, A, grid, smem);
         else rc = launch_small<true, true, 64, 6>(h, A, grid, smem);
     } else {
         if (!lds_state) rc = launch_small<false, false, 1024, 10>(h, A, grid, smem);
         else if (nt == 1024) rc = launch_small<false, true, 1024, 10>(h, A, grid, smem);
-        else if (nt == 512) rc = launch_small<false, true, 512, 9>(h, A, grid, smem);
         else if (nt == 256) rc = launch_small<false, true, 256, 8>(h, A, grid, smem);
         else rc = launch_small<false, true, 64, 6>(h, A, grid, smem);
     }

@@ -237,7 +237,6 @@ struct SectorEngine {
     uint64_t npairs = 0, nnz = 0;
     size_t bytes = 0;
     size_t pad_elems = 0;         // doubles of a state buffer in tile-padded form (largest sweep; 0: no dst tables)
-    uint32_t chunk = 2048;        // pair words per chunk of the 64-bit tables (k_sec_widen)
     std::vector<SectorSeg> segs;
     std::vector<SectorHSweep> hs;
     DevBuf d_sup, d_buf[2], d_hdesc, d_flag;
@@ -364,7 +363,6 @@ struct ovqe_sv {
     int opt_sparse_spw = 0;       // evaluations per wave (0 = automatic)
     int opt_sparse_dbg = 0;       // measurement: k_sparse_vqe_rows without one of its phases (SparseArgs::dbg)
     int opt_clifford_phase_host = 1;   // global phase of a closed Clifford frame from a sparse host simulation (0: the gates run on the device)
-    int opt_sparse_dealias = 1;   // arrange the restricted-Hamiltonian entries against LDS bank conflicts
     int opt_sparse_renumber = 1;  // number the compact support against LDS bank conflicts of the circuit's pairs
     int opt_sparse_rows = 1;      // support-compacted evaluation, large batches: flat rows of padded 64-bit pair words (k_sparse_vqe_rows)
     int opt_sparse_wg = 1;        // small batches (<= 1024): one evaluation per 1024-thread workgroup (k_sparse_vqe_wg)
@@ -378,14 +376,11 @@ struct ovqe_sv {
     // one read of the state each) run side by side
     hipStream_t stream2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int opt_expect_streams = 2;
-    int opt_expect_diag_wht = 1;  // dense registers of 25+ qubits: the diagonal group of a tiled <H> by a Walsh-Hadamard transform per tile (k_tile_diag)
     int opt_real_state = 0;       // option "real_state": the state buffer holds 2^n_local DOUBLES (a shard of the partitioned register while
                                   // every applied rotation has an odd number of Y): ovqe_apply_pauli_rotations, ovqe_init_basis, ovqe_norm2
                                   // and the ovqe_xsum_expect_* calls work on 8-byte amplitudes
     CompactCover cc;              // of (current program, ham_real)
     int opt_compact = 1;          // allow the compact cover (real-amplitude streaming energies, 18..28 qubits)
-    int opt_compact_cpp = 1;      // host chunks (512 terms each) staged in LDS per pass of the compact-cover kernel
     int prog_version = 0;
     SectorEngine sec;             // of (current program, stored Hamiltonian)
     SectorEngine scr;             // ADAPT screens: <H> tables on a symmetry sector, no circuit (build_screen_sector)
@@ -407,27 +402,15 @@ struct ovqe_sv {
     int opt_sector_stream_arrange = 1; // third sweep form: lanes of a row chosen for the LDS banks (0: in list order; testing builds)
     int opt_sector_stream_waves = 0;   // third sweep form: waves that share a tile's rows (0: from the pairs per op of the sweep's largest tile); testing builds
     int opt_sector_sweep = 3;     // circuit sweep kernel: 3 = per-wave streams, barriers at run boundaries only (k_sector_sweep3; built on the tables of 2); 2 = scatter-on-write, pair words in registers (k_sector_sweep2); 1 = first form
-    int opt_sector_chunk = 2048;  // k_sector_sweep2: pair words per chunk = threads x words per thread (1024, 2048, 4096)
     int opt_sector_sweep_dbg = 0; // measurements only, k_sector_sweep2: 1 no ops, 2 empty kernel, 3 loads only — wrong results
     int opt_sector_h_pack = 1;     // <H> tables: coded words of a sweep with at most 1023 magnitudes stored as 24-bit elements (0: 32-bit words; testing builds)
-    int opt_sector_h_groups = 256; // workgroups per <H> sweep (they share the sweep's tiles round robin)
     int opt_sector_h_dbg = 0;     // measurements only, k_sector_expect: 1 tile loads only, 2 no tile loads, 3 metadata only — wrong results
     int opt_sector_adjoint = 3;   // backward sweeps of the gradient: 3 = on the per-wave streams (k_sector_adjoint3) where a sweep has them; 2 = on the 64-bit tables (k_sector_adjoint2) where they exist and fit; 1 = first form
-    int opt_sector_apply_threads = 0; // threads per workgroup of k_sector_apply (0 = automatic, 512, 1024)
-    int opt_sector_h_threads = 512; // threads per workgroup of k_sector_expect (512 or 1024)
-    int opt_sector_batch_sweep_threads = 512;    // workgroup size of a batch's circuit sweeps (512, 1024)
-    int opt_sector_batch_dst_lds = 0;            // their scatter indices staged in LDS (0: read when the tile is written — 44 instead of 64 KB
-                                                 // per workgroup at 24 qubits: three 512-thread workgroups per CU; B = 64: 0.82 -> 0.70 ms per evaluation)
-    int opt_sector_batch_zfast = 1;              // batched <H>: state group = fastest grid index (the groups share a tile's elements through the caches)
-    int opt_sector_batch_nb = 2;      // states per tile of the batched <H> (2 or 3)
-    int opt_sector_batch_threads = 1024;   // its workgroup size (512, 1024)
-    int opt_screen_tables = 1;        // ADAPT screens over the support list: pattern tables for the pool's same-x runs (PoolRun)
     int opt_screen_sector = 1;        // ADAPT screens: sigma = H psi from the materialised Hamiltonian of psi's symmetry sector (real states)
     int opt_screen_sector_min = 1024; // ... once psi lists at least this many amplitudes
     bool prog_from_gates = false;     // the stored program came from ovqe_set_gate_program (frame form): sector tables at the first evaluation
     int opt_expect_dense = 1;         // tiled <H> of dense complex registers (25+ qubits): census of the first sweep, then two workgroups per CU
     DevBuf d_tile_cnt;
-    int opt_tile_unsplit = 1;         // tiled <H> of complex states: groups of one or two terms as unsplit entries (see build_ham_tiles)
     int opt_tile_flat = 2;            // tiled <H>: entries of one or two merged terms as per-LANE items (1), per-wave entries (0), items for real
                                       // states only (2, default: on dense complex tiles the items' LDS reads conflict 16 ways — 78 % of the LDS cycles,
                                       // profiles/r5_tilexp — and the per-wave entries are 10 % faster once two workgroups share a CU)
@@ -436,12 +419,7 @@ struct ovqe_sv {
     int opt_sector_reg_threads = 256; // workgroup size of those sweeps
     int opt_sector_reg_adjoint = 1;   // ovqe_energy_gradient on a regular support: backward sweeps from bit arithmetic too (0: pair-word sweeps)
     int opt_sector_reg_pairs = 1;     // two consecutive three-bit ops that share two bits run as one 16-slot block
-    int opt_sector_apply_seq = 1;     // lambda = H psi on the sector tables: one launch per sweep in sequence, plain additions (0: one launch, global atomics)
-    int opt_sector_coset_first = 1;   // gate lists in frame form: the coset of their Z2 symmetries as support, no probe run (checked afterwards)
     int opt_sector_reg_runs = 1;      // runs of consecutive ops whose waves stay inside their own slots: no barrier inside a run
-    int opt_sector_depth2 = 1;        // first form of the sweeps: two chunks of pair words ahead where every op of a tile fits a staging buffer
-    int opt_sector_many_tiles = 1;    // single evaluations with >= 768 tiles: the workgroup shape of the batches (512 threads, scatter indices from memory)
-    int opt_sector_h_lpt = 1;         // <H> kernels take the tiles of a sweep largest first
     int opt_sector_batch = 1;     // ovqe_energy_batch on the sector tables: whole batches per pass (0: one evaluation at a time)
     float last_batch_ms = 0.f;
     const double *cur_theta = nullptr;  // device pointers of the batch being evaluated
@@ -450,16 +428,12 @@ struct ovqe_sv {
     int opt_force_path = 0;       // 0 auto, 1 small kernel, 2 streaming kernels
     int opt_small_max = 14;       // always-small up to this many qubits
     int opt_small_batch_max = 16; // small kernel for batches up to this many qubits
-    int opt_unroll = 4;
     int opt_index_streams = 1;    // precompute the pair-index streams of OP_TAB ops on the host
     int opt_table_fusion = 1;     // turn commuting same-x runs into single sparse pair rotations (OP_TAB)
-    int opt_rot_variant = 0;      // tuning variant of the streaming pair sweep (0 = default kernel)
     int64_t last_passes = 0;      // passes over the state buffer (kernel launches that stream it) of the last ovqe_apply_pauli_rotations /
     int64_t last_pass_bytes = 0;  // ovqe_bilinear call and the bytes they move by construction (bench.py: the sharded block's real traffic)
     int64_t last_fci_rounds = 0;  // matvec rounds the last ovqe_sector_ground_state needed to saturate the block of |hf>
     int fault_inject = 0;         // option "fault_inject" (tests of the ABI's exception barrier): 1 = the next term-list build throws std::bad_alloc
-    int opt_persist_blocks = 2048;
-    int opt_small_threads = 0;    // 0: automatic; 256/512/1024: workgroup size of the fused kernel
     int opt_real_mode = 1;        // allow the real-amplitude specialisation of the fused kernel
     // LDS-tiled multi-op sweeps of the streaming path (sv_tile.hpp)
     int opt_tile_bits = -1;       // -1: automatic (12 when the state streams from HBM, n >= 25; else 11);
@@ -467,16 +441,12 @@ struct ovqe_sv {
     double2 init_amp = make_double2(1.0, 0.0);  // amplitude of |hf> (global phase of a folded Clifford part)
     int opt_clifford_frame = 1;   // gate programs: 0 literal, 1 Clifford-frame form when the frame closes, 2 forced
     int opt_tile_low = 4;         // lowest index bits always inside the tile (contiguous 16 B << low chunks)
-    int opt_ham_tile_low = 2;     // the same for the tile cover of the Hamiltonian (-1: opt_tile_low): fewer forced bits = fewer
-                                  // sweeps per H psi / <H> (N2/cc-pVDZ at 24 qubits: 102 sweeps at 4; 25.4 ms per H psi at 2, 30.1 at 4)
     TilePlan tp;                  // of the stored program
     TilePlan tp_real;             // same program on a real-amplitude state (built on first use)
     bool tp_real_built = false;
     bool prog_real_ok = false;    // every rotation has an odd number of Y and there is no diagonal run
     int opt_apply_min_tiles = 256;  // H psi goes through the tile cover from this many tiles on
     int opt_real_stream = 1;      // streaming energies of such programs keep the state as 2^n doubles
-    int opt_expect_sparse = 4;    // tiled <H>: a tile with at most 1/den of its amplitudes non-zero is evaluated over the
-                                  // compacted list of those amplitudes (0 = always the dense entry walks)
     HamDev ham_real;              // tile cover of the stored Hamiltonian for the real-amplitude state
     TilePlan tp_adhoc;            // of the rotation list of the current ovqe_apply_pauli_rotations call
     std::vector<CrossSum *> xsums;   // ovqe_xsum_create (slots of destroyed sums are nullptr)
@@ -689,7 +659,7 @@ int upload(ovqe_handle h, DevBuf &b, const void *src, size_t bytes) {
 }
 
 // ---- streaming-path launches -------------------------------------------------------------------
-// Launch geometry of the streaming sweeps, from measurements on MI355X (tools/exp_rot*.py, profiles/):
+// Launch geometry of the streaming sweeps, from measurements on MI355X (docs/rounds/DESIGN_rounds1-4.md):
 // one pair (resp. amplitude) per thread and small workgroups win — more independent workgroups in flight
 // beat more loads in flight per thread — and non-temporal accesses help exactly when the state is far
 // beyond the 256 MiB Infinity Cache:
@@ -697,70 +667,51 @@ int upload(ovqe_handle h, DevBuf &b, const void *src, size_t bytes) {
 //   21..24        : 256-thread groups, cached accesses (the state lives in the Infinity Cache)
 //   14..20        : 64-thread groups (L2-resident)
 //   smaller       : legacy multi-pair kernels (launch-bound anyway)
-// "rot_variant" > 0 forces one geometry (experiments); -1 forces the legacy kernel.
 int launch_rot_run(ovqe_handle h, uint64_t x, const RotParam *d_rp, int nrot) {
     if (nrot <= 0) return OVQE_OK;
     const int nl = h->n_local;
-    int variant = h->opt_rot_variant;
     if (x == 0) {
         const uint64_t n = h->namps;
 #define OVQE_LAUNCH_D(NT, U, NTL)                                                                                \
     hipLaunchKernelGGL((k_rot_diag_v<NT, U, NTL>), dim3((unsigned)((n + (uint64_t)NT * U - 1) / ((uint64_t)NT * U))), \
                        dim3(NT), 0, h->stream, h->state, n, h->base, d_rp, nrot);
-        if (variant == 0 && nl >= 14) variant = nl >= 32 ? 105 : (nl >= 25 ? 100 : (nl >= 21 ? 108 : 100));
-        if (nl < 14 || variant < 100) variant = (variant == -1 || nl < 14) ? -1 : 100;
-        switch (variant) {
-        case 100: OVQE_LAUNCH_D(64, 1, true) break;
-        case 101: OVQE_LAUNCH_D(128, 1, true) break;
-        case 102: OVQE_LAUNCH_D(256, 1, true) break;
-        case 104: OVQE_LAUNCH_D(128, 2, true) break;
-        case 105: OVQE_LAUNCH_D(64, 4, true) break;  // n >= 32: a launch holds fewer than 2^32 threads
-        case 108: OVQE_LAUNCH_D(256, 1, false) break;
-        default:
-            if (h->opt_unroll >= 4 && n >= 256u * 4u) {
-                hipLaunchKernelGGL(k_rot_diag<4>, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, h->stream, h->state,
-                                   n, h->base, d_rp, nrot);
-            } else {
-                hipLaunchKernelGGL(k_rot_diag<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->state,
-                                   n, h->base, d_rp, nrot);
-            }
+        if (nl >= 32) {
+            OVQE_LAUNCH_D(64, 4, true)   // a launch holds fewer than 2^32 threads
+        } else if (nl >= 21 && nl < 25) {
+            OVQE_LAUNCH_D(256, 1, false)
+        } else if (nl >= 14) {
+            OVQE_LAUNCH_D(64, 1, true)
+        } else if (n >= 256u * 4u) {
+            hipLaunchKernelGGL(k_rot_diag<4>, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, h->stream, h->state,
+                               n, h->base, d_rp, nrot);
+        } else {
+            hipLaunchKernelGGL(k_rot_diag<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->state,
+                               n, h->base, d_rp, nrot);
         }
 #undef OVQE_LAUNCH_D
     } else {
         const uint64_t np = h->namps >> 1;
         const int pivot = 63 - __builtin_clzll(x);
-#define OVQE_LAUNCH_V(NT, U, NTL, PERSIST)                                                                          \
-    {                                                                                                              \
-        const uint64_t ntiles = (np + (uint64_t)NT * U - 1) / ((uint64_t)NT * U);                                  \
-        const unsigned grid = (unsigned)(PERSIST ? std::min<uint64_t>(ntiles, (uint64_t)h->opt_persist_blocks) : ntiles); \
-        hipLaunchKernelGGL((k_rot_pairs_v<NT, U, NTL, PERSIST>), dim3(grid), dim3(NT), 0, h->stream, h->state, np,  \
-                           pivot, x, h->base, d_rp, nrot);                                                         \
-    }
-        if (variant == 0 && nl >= 14)
-            variant = nl >= 32 ? 21 : (nl >= 25 ? (pivot >= 7 ? 16 : 13) : (nl >= 21 ? 17 : 16));
-        if (nl < 14 || variant >= 100) variant = -1;
-        switch (variant) {
-        case 1: OVQE_LAUNCH_V(256, 4, true, false) break;
-        case 4: OVQE_LAUNCH_V(256, 4, false, true) break;
-        case 8: OVQE_LAUNCH_V(256, 2, true, false) break;
-        case 12: OVQE_LAUNCH_V(256, 1, true, false) break;
-        case 13: OVQE_LAUNCH_V(128, 1, true, false) break;
-        case 14: OVQE_LAUNCH_V(512, 1, true, false) break;
-        case 16: OVQE_LAUNCH_V(64, 1, true, false) break;
-        case 17: OVQE_LAUNCH_V(256, 1, false, false) break;
-        case 19: OVQE_LAUNCH_V(64, 2, true, false) break;
-        case 21: OVQE_LAUNCH_V(64, 4, true, false) break;  // n >= 32: a launch holds fewer than 2^32 threads
-        default:
-            if (h->opt_unroll >= 4 && np >= 256u * 4u) {
-                hipLaunchKernelGGL(k_rot_pairs<4>, dim3((unsigned)((np + 1023) / 1024)), dim3(256), 0, h->stream,
-                                   h->state, np, pivot, x, h->base, d_rp, nrot);
-            } else if (h->opt_unroll >= 2 && np >= 256u * 2u) {
-                hipLaunchKernelGGL(k_rot_pairs<2>, dim3((unsigned)((np + 511) / 512)), dim3(256), 0, h->stream, h->state,
-                                   np, pivot, x, h->base, d_rp, nrot);
-            } else {
-                hipLaunchKernelGGL(k_rot_pairs<1>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, h->stream, h->state,
-                                   np, pivot, x, h->base, d_rp, nrot);
-            }
+#define OVQE_LAUNCH_V(NT, U, NTL)                                                                                    \
+    hipLaunchKernelGGL((k_rot_pairs_v<NT, U, NTL>), dim3((unsigned)((np + (uint64_t)NT * U - 1) / ((uint64_t)NT * U))), \
+                       dim3(NT), 0, h->stream, h->state, np, pivot, x, h->base, d_rp, nrot);
+        if (nl >= 32) {
+            OVQE_LAUNCH_V(64, 4, true)   // a launch holds fewer than 2^32 threads
+        } else if (nl >= 25 && pivot < 7) {
+            OVQE_LAUNCH_V(128, 1, true)
+        } else if (nl >= 21 && nl < 25) {
+            OVQE_LAUNCH_V(256, 1, false)
+        } else if (nl >= 14) {
+            OVQE_LAUNCH_V(64, 1, true)
+        } else if (np >= 256u * 4u) {
+            hipLaunchKernelGGL(k_rot_pairs<4>, dim3((unsigned)((np + 1023) / 1024)), dim3(256), 0, h->stream,
+                               h->state, np, pivot, x, h->base, d_rp, nrot);
+        } else if (np >= 256u * 2u) {
+            hipLaunchKernelGGL(k_rot_pairs<2>, dim3((unsigned)((np + 511) / 512)), dim3(256), 0, h->stream, h->state,
+                               np, pivot, x, h->base, d_rp, nrot);
+        } else {
+            hipLaunchKernelGGL(k_rot_pairs<1>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, h->stream, h->state,
+                               np, pivot, x, h->base, d_rp, nrot);
         }
 #undef OVQE_LAUNCH_V
     }
@@ -856,11 +807,9 @@ inline bool tile_ok(ovqe_handle h, bool real) {
            h->opt_tile_low <= 8;
 }
 
-// lowest index bits forced into every tile of the Hamiltonian's cover
-inline int ham_tile_low(ovqe_handle h, bool real) {
-    const int l = h->opt_ham_tile_low >= 0 ? h->opt_ham_tile_low : h->opt_tile_low;
-    return std::min(8, std::max(l, real ? 1 : 0));   // (a real amplitude is 8 bytes: at least 16-byte chunks)
-}
+// lowest index bits forced into every tile of the Hamiltonian's cover (a real amplitude is 8 bytes: at least one, for 16-byte chunks):
+// fewer forced bits = fewer sweeps per H psi / <H> (N2/cc-pVDZ at 24 qubits: 102 sweeps at 4; 25.4 ms per H psi at 2, 30.1 at 4)
+constexpr int HAM_TILE_LOW = 2;
 
 inline uint32_t extract_bits(uint64_t v, uint64_t mask) {  // pext
     uint32_t r = 0;
@@ -1234,6 +1183,14 @@ int ovqe_set_stream(ovqe_handle h, void *hip_stream) try {
     return OVQE_OK;
 } OVQE_CATCH(h)
 
+// an option that the sector tables are built under: they are dropped and the path may be tried again from the next evaluation
+static void reset_sector(ovqe_handle h) {
+    free_sector(h->sec);
+    h->sec.disabled = false;
+    h->sec.seen = 0;
+    h->sec.prog_version = -1;
+}
+
 int ovqe_set_option(ovqe_handle h, const char *name, int64_t value) try {
     OVQE_ENTER(h);
     if (!h || !name) return OVQE_ERR_INVALID;
@@ -1246,9 +1203,6 @@ int ovqe_set_option(ovqe_handle h, const char *name, int64_t value) try {
     else if (k == "real_state") h->opt_real_state = value ? 1 : 0;
     else if (k == "small_max_qubits") h->opt_small_max = (int)value;
     else if (k == "small_batch_max_qubits") h->opt_small_batch_max = (int)value;
-#ifdef OVQE_TESTING
-    else if (k == "unroll") h->opt_unroll = (int)value;
-#endif
     else if (k == "real_mode") {
         h->opt_real_mode = (int)value;
         h->sp_tried = false;
@@ -1276,45 +1230,23 @@ int ovqe_set_option(ovqe_handle h, const char *name, int64_t value) try {
         (k == "sector" ? h->opt_sector : k == "sector_bits" ? h->opt_sector_bits : k == "sector_max_gb" ? h->opt_sector_max_gb
          : k == "sector_h" ? h->opt_sector_h : k == "sector_h_bits" ? h->opt_sector_h_bits : k == "sector_dict" ? h->opt_sector_dict
                                                                                                               : h->opt_sector_min_qubits) = (int)value;
-        free_sector(h->sec);
-        h->sec.disabled = false;
-        h->sec.seen = 0;
-        h->sec.prog_version = -1;
+        reset_sector(h);
     }
     else if (k == "sector_threads") h->opt_sector_threads = (value == 0 || value == 64 || value == 512 || value == 1024) ? (int)value : 256;
 #ifdef OVQE_TESTING
-    else if (k == "sector_h_groups") h->opt_sector_h_groups = (int)value;
     else if (k == "sector_h_dbg") h->opt_sector_h_dbg = (int)value;
 #endif
     else if (k == "sector_adjoint") h->opt_sector_adjoint = value == 1 ? 1 : (value == 2 ? 2 : 3);
-#ifdef OVQE_TESTING
-    else if (k == "sector_apply_threads") h->opt_sector_apply_threads = value == 1024 ? 1024 : (value == 512 ? 512 : 0);
-    else if (k == "sector_h_threads") h->opt_sector_h_threads = value == 1024 ? 1024 : 512;
-#endif
     else if (k == "sector_batch") h->opt_sector_batch = (int)value;
-#ifdef OVQE_TESTING
-    else if (k == "sector_h_lpt") h->opt_sector_h_lpt = (int)value;
-    else if (k == "sector_many_tiles") h->opt_sector_many_tiles = (int)value;
-    else if (k == "sector_depth2") h->opt_sector_depth2 = (int)value;
-#endif
     else if (k == "sector_regular") {
         h->opt_sector_regular = (int)value;
-        free_sector(h->sec);
-        h->sec.disabled = false;
-        h->sec.seen = 0;
-        h->sec.prog_version = -1;
+        reset_sector(h);
     } else if (k == "sector_reg_pairs") {
         h->opt_sector_reg_pairs = (int)value;
-        free_sector(h->sec);
-        h->sec.disabled = false;
-        h->sec.seen = 0;
-        h->sec.prog_version = -1;
+        reset_sector(h);
     } else if (k == "sector_reg_adjoint") {
         h->opt_sector_reg_adjoint = (int)value;   // (0 needs the pair words a large regular support does without: the tables are rebuilt)
-        free_sector(h->sec);
-        h->sec.disabled = false;
-        h->sec.seen = 0;
-        h->sec.prog_version = -1;
+        reset_sector(h);
     }
     else if (k == "sector_reg_threads") h->opt_sector_reg_threads = value == 512 ? 512 : (value == 1024 ? 1024 : (value == 128 ? 128 : 256));
 #ifdef OVQE_TESTING
@@ -1324,16 +1256,8 @@ int ovqe_set_option(ovqe_handle h, const char *name, int64_t value) try {
     else if (k == "poll_result") h->opt_poll_result = (int)value;
     else if (k == "sector_pairs_form") h->opt_sector_pairs_form = (int)value;
     else if (k == "screen_sector") h->opt_screen_sector = (int)value;
-#ifdef OVQE_TESTING
-    else if (k == "screen_tables") h->opt_screen_tables = (int)value;
-#endif
     else if (k == "screen_sector_min") h->opt_screen_sector_min = (int)value;
 #ifdef OVQE_TESTING
-    else if (k == "sector_batch_sweep_threads") h->opt_sector_batch_sweep_threads = value == 512 ? 512 : (value == 256 ? 256 : 1024);
-    else if (k == "sector_batch_dst_lds") h->opt_sector_batch_dst_lds = (int)value;
-    else if (k == "sector_batch_zfast") h->opt_sector_batch_zfast = (int)value;
-    else if (k == "sector_batch_nb") h->opt_sector_batch_nb = value == 3 ? 3 : 2;
-    else if (k == "sector_batch_threads") h->opt_sector_batch_threads = value == 512 ? 512 : 1024;
     else if (k == "sector_debug") h->opt_sector_debug = (int)value;
     else if (k == "sector_sweep") h->opt_sector_sweep = value == 1 ? 1 : (value == 2 ? 2 : (value == 4 ? 4 : 3));   // (2 on tables built under 3: the second form on the same tables; 4: the streams for batches too)
     else if (k == "sector_sweep_dbg") h->opt_sector_sweep_dbg = (int)value;
@@ -1343,63 +1267,34 @@ int ovqe_set_option(ovqe_handle h, const char *name, int64_t value) try {
 #endif
     else if (k == "sector_reg_runs") {   // runs of ops without barriers (planned at build time: the tables are rebuilt)
         h->opt_sector_reg_runs = (int)value;
-        free_sector(h->sec);
-        h->sec.disabled = false;
-        h->sec.seen = 0;
-        h->sec.prog_version = -1;
+        reset_sector(h);
     }
-#ifdef OVQE_TESTING
-    else if (k == "sector_chunk") h->opt_sector_chunk = (value == 1024 || value == 4096) ? (int)value : 2048;
-#endif
     else if (k == "sector_profile") h->opt_sector_profile = (int)value;
     else if (k == "sector_sparsity" || k == "sector_tile_cap") {
         (k == "sector_sparsity" ? h->opt_sector_sparsity : h->opt_sector_tile_cap) = (int)value;
-        free_sector(h->sec);
-        h->sec.disabled = false;
-        h->sec.seen = 0;
-        h->sec.prog_version = -1;
+        reset_sector(h);
     }
     else if (k == "lanczos_keep_gb") h->opt_lanczos_keep_gb = (int)value;
     else if (k == "screen_sparse") h->opt_screen_sparse = (int)std::max<int64_t>(0, value);
 #ifdef OVQE_TESTING
-    else if (k == "rot_variant") h->opt_rot_variant = (int)value;
     else if (k == "tile_flat") h->opt_tile_flat = (int)value;
-    else if (k == "tile_unsplit") h->opt_tile_unsplit = (int)value;
-    else if (k == "sector_coset_first") h->opt_sector_coset_first = (int)value;
-    else if (k == "sector_apply_seq") h->opt_sector_apply_seq = (int)value;
     else if (k == "expect_dense") h->opt_expect_dense = (int)value;
-    else if (k == "expect_diag_wht") {
-        h->opt_expect_diag_wht = (int)value;
-        for (HamDev *H : {&h->ham, &h->ham_adhoc, &h->ham_real, &h->ham_conj}) H->tile_bits = -1;   // covers rebuilt on their next use
-        for (CrossSum *X : h->xsums)
-            if (X) X->local.tile_bits = -1;
-    }
     else if (k == "fault_inject") h->fault_inject = (int)value;
 #endif
     else if (k == "real_stream") h->opt_real_stream = (int)value;
     else if (k == "apply_min_tiles") h->opt_apply_min_tiles = (int)value;
     else if (k == "clifford_frame") h->opt_clifford_frame = (int)value;  // applies to the next ovqe_set_gate_program
-#ifdef OVQE_TESTING
-    else if (k == "ham_tile_low") h->opt_ham_tile_low = (int)value;
-#endif
     else if (k == "tile_bits" || k == "tile_low") {
         (k == "tile_bits" ? h->opt_tile_bits : h->opt_tile_low) = (int)value;
         h->tp_real_built = false;  // the real-amplitude plan follows on its next use
         if (h->prog_set) return build_tile_program(h);
     }
 #ifdef OVQE_TESTING
-    else if (k == "sparse_dealias") {
-        h->opt_sparse_dealias = value ? 1 : 0;
-        h->sp_tried = false;
-    }
     else if (k == "sparse_wg") h->opt_sparse_wg = value ? 1 : 0;
     else if (k == "sparse_rows") {
         h->opt_sparse_rows = value ? 1 : 0;
         h->sp_tried = false;
     }
-    else if (k == "expect_sparse") h->opt_expect_sparse = (int)std::max<int64_t>(0, value);
-    else if (k == "expect_streams") h->opt_expect_streams = value >= 2 ? 2 : 1;
-    else if (k == "compact_cpp") h->opt_compact_cpp = (int)std::min<int64_t>(4, std::max<int64_t>(1, value));
 #endif
     else if (k == "compact") {
         h->opt_compact = value ? 1 : 0;
@@ -1407,13 +1302,6 @@ int ovqe_set_option(ovqe_handle h, const char *name, int64_t value) try {
         h->cc.disabled = false;
         h->cc.seen = 0;
     }
-#ifdef OVQE_TESTING
-    else if (k == "persist_blocks") h->opt_persist_blocks = (int)value;
-    else if (k == "small_threads") {
-        h->opt_small_threads = (int)value;
-        h->exp_lbits = -1;
-    }
-#endif
     else if (k == "table_fusion") {
         if (h->opt_table_fusion != (int)value && h->prog_set) {
             h->opt_table_fusion = (int)value;

@@ -186,8 +186,7 @@ int build_wave_streams(ovqe_handle h, SectorEngine &E, SectorScratch &W, SectorS
     if (sg.nops == 0 || sg.L.max_tile > 0x7ffeu) return OVQE_OK;
     // the streams are walked by 1024-thread workgroups, one per tile (run_sector_circuit): registers with three or more tiles per CU take
     // 512-thread workgroups of the second form, three to a CU, and so does a handle told to use another workgroup size
-    if ((h->opt_sector_threads != 0 && h->opt_sector_threads != 1024) ||
-        (h->opt_sector_threads == 0 && ((sg.L.ntiles >= 768u && h->opt_sector_many_tiles) || h->opt_sector_many_tiles == 2)))
+    if ((h->opt_sector_threads != 0 && h->opt_sector_threads != 1024) || (h->opt_sector_threads == 0 && sg.L.ntiles >= 768u))
         return OVQE_OK;
     int NW = h->opt_sector_stream_waves;
     if (NW != 1 && NW != 2 && NW != 4 && NW != 8 && NW != 16) NW = sec_stream_wave_count((double)maxp / (double)sg.nops, SEC_STREAM_WAVES);
@@ -633,17 +632,16 @@ int build_sector_h(ovqe_handle h, SectorEngine &E, SectorScratch &W, size_t budg
     if (!E.h_tables) drop_h();
     // the order in which the workgroups of the <H> kernels take a sweep's tiles: largest first (tile populations are products of
     // binomials, 100 ... 4900 at 24 qubits; numbered order left the longest tiles to the end of a sweep)
-    if (h->opt_sector_h_lpt)
-        for (SectorHSweep &hw : E.hs) {
-            std::vector<uint32_t> hoff((size_t)hw.L.ntiles + 1);
-            HIPC(h, hipMemcpyAsync(hoff.data(), hw.L.d_off.p, hoff.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-            HIPC(h, hipStreamSynchronize(h->stream));
-            std::vector<uint32_t> ord((size_t)hw.L.ntiles);
-            std::iota(ord.begin(), ord.end(), 0u);
-            std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return hoff[a + 1] - hoff[a] > hoff[b + 1] - hoff[b]; });
-            rc = upload(h, hw.d_torder, ord.data(), ord.size() * sizeof(uint32_t));
-            if (rc) return rc;
-        }
+    for (SectorHSweep &hw : E.hs) {
+        std::vector<uint32_t> hoff((size_t)hw.L.ntiles + 1);
+        HIPC(h, hipMemcpyAsync(hoff.data(), hw.L.d_off.p, hoff.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, hipStreamSynchronize(h->stream));
+        std::vector<uint32_t> ord((size_t)hw.L.ntiles);
+        std::iota(ord.begin(), ord.end(), 0u);
+        std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return hoff[a + 1] - hoff[a] > hoff[b + 1] - hoff[b]; });
+        rc = upload(h, hw.d_torder, ord.data(), ord.size() * sizeof(uint32_t));
+        if (rc) return rc;
+    }
     std::vector<SecHSweep> desc;
     for (const SectorHSweep &hw : E.hs)
         desc.push_back(SecHSweep{(const uint32_t *)hw.L.d_src.p, (const uint32_t *)hw.L.d_off.p, (const uint16_t *)hw.d_order.p,
@@ -674,7 +672,6 @@ int build_sector_tables_impl(ovqe_handle h, bool allow_regular) {
     free_sector(E);
     E.last_eval_us = 0.0;
     E.disabled = true;   // until everything below succeeded
-    E.chunk = (uint32_t)h->opt_sector_chunk;
     E.prog_version = h->prog_version;
     E.ham_version = h->ham.version;
     if (!h->prog_real_ok || h->n_global != 0 || h->n_local > 32 || h->n_local < 8 || !h->ham.set) SEC_DECLINE("program not real-amplitude / sharded / register outside 8..32 qubits / no Hamiltonian");
@@ -727,7 +724,7 @@ int build_sector_tables_impl(ovqe_handle h, bool allow_regular) {
     // here with coset_first off when it is not (a number-conserving gate list: 1/7 of the coset at 24 qubits).
     const int tsym = (int)freebits.size();
     // (at most eight symmetries fit the coset descriptor; a list with more takes the probe path below, as before the coset shortcut)
-    const bool coset_first = h->prog_from_gates && h->opt_sector_coset_first && !E.coset_rejected && E.probe_mode == 0 && tsym >= 1 && tsym <= 8 &&
+    const bool coset_first = h->prog_from_gates && !E.coset_rejected && E.probe_mode == 0 && tsym >= 1 && tsym <= 8 &&
                              h->n_local - tsym >= 8 && h->n_local - tsym <= 30 &&
                              (1ull << (h->n_local - tsym)) * (uint64_t)std::max(h->opt_sector_sparsity, 2) <= h->namps;
     E.coset_assumed = coset_first;
@@ -980,12 +977,12 @@ int build_sector_tables_impl(ovqe_handle h, bool allow_regular) {
                 uint32_t maxp = 0;
                 for (uint32_t tt = 0; tt < nt; ++tt)
                     maxp = std::max(maxp, poff[(size_t)(tt + 1) * (sg.nops + 1) - 1] - poff[(size_t)tt * (sg.nops + 1)]);
-                sg.maxchunks = std::max(1u, (maxp + E.chunk - 1u) / E.chunk);
+                sg.maxchunks = std::max(1u, (maxp + SEC_CHUNK - 1u) / SEC_CHUNK);
                 rc = ensure(h, sg.d_wide, (size_t)std::max<uint64_t>(run, 1) * sizeof(uint64_t));
                 if (!rc) rc = ensure(h, sg.d_rounds, (size_t)nt * sg.maxchunks * sizeof(uint16_t));
                 if (rc) return rc;
                 hipLaunchKernelGGL(k_sec_widen, dim3(nt), dim3(256), 0, h->stream, (const uint32_t *)sg.d_pairs.p, (const uint32_t *)sg.d_poff.p,
-                                   (const int32_t *)sg.d_tab0.p, sg.nops, sg.rot0, sb_max, sg.maxchunks, E.chunk, (uint64_t *)sg.d_wide.p,
+                                   (const int32_t *)sg.d_tab0.p, sg.nops, sg.rot0, sb_max, sg.maxchunks, SEC_CHUNK, (uint64_t *)sg.d_wide.p,
                                    (uint16_t *)sg.d_rounds.p);
                 HIPC(h, hipGetLastError());
                 E.bytes += (size_t)run * 8 + (size_t)nt * sg.maxchunks * 2;
@@ -1104,7 +1101,7 @@ int build_sector_tables_impl(ovqe_handle h, bool allow_regular) {
             E.bytes += (size_t)sg.L.ntiles * cap * sizeof(uint32_t);
         }
         // sweeps with several tiles per CU take them largest first (k_sector_sweep2's torder)
-        for (size_t si = 0; fits && !rc && h->opt_sector_h_lpt && si < E.segs.size(); ++si) {
+        for (size_t si = 0; fits && !rc && si < E.segs.size(); ++si) {
             SectorSeg &sg = E.segs[si];
             if (sg.L.ntiles < 512u) continue;
             std::vector<uint32_t> hoff((size_t)sg.L.ntiles + 1), ord((size_t)sg.L.ntiles);
@@ -1234,7 +1231,8 @@ int launch_sector_sweeps(ovqe_handle h, SectorEngine &E, int *last) {
         const uint32_t cap = std::max(sg.L.max_tile, 1u);
         const size_t smem = (size_t)((cap + 1u) & ~1u) * sizeof(double) + (size_t)sg.nrot * sizeof(double2) +
                             ((size_t)sg.nops + 2) * sizeof(SecOpLds) + 2 * (size_t)SEC_STAGE_WORDS * sizeof(uint32_t);
-        const bool d2 = NT > 64 && h->opt_sector_depth2 && sg.max_op_pairs <= SEC_STAGE_WORDS && !(h->opt_sector_debug & 1);
+        // two chunks of pair words ahead where every op of a tile fits a staging buffer
+        const bool d2 = NT > 64 && sg.max_op_pairs <= SEC_STAGE_WORDS && !(h->opt_sector_debug & 1);
         h->forms_used |= 1u;
         if (d2)
             hipLaunchKernelGGL((k_sector_sweep<NT, true>), dim3(sg.L.ntiles), dim3(NT), smem, h->stream, (const double *)E.d_buf[cur ^ 1].p,
@@ -1274,7 +1272,7 @@ int launch_sector_sweeps2(ovqe_handle h, SectorEngine &E, double *buf0, double *
         const size_t smem = (size_t)((cap + 2u) & ~1u) * sizeof(double) + (size_t)sg.nrot * sizeof(double2) +
                             (dst_lds ? (size_t)cap * sizeof(uint32_t) : 0) + (size_t)sg.maxchunks * sizeof(uint32_t);
         if (smem > 160 * 1024 || sg.maxchunks > (uint32_t)NT) return fail(h, OVQE_ERR_INVALID, "internal: sector tile exceeds LDS");
-        const bool bfast = B > 1 && h->opt_sector_batch_zfast != 0 && sg.L.ntiles <= 65535u;
+        const bool bfast = B > 1 && sg.L.ntiles <= 65535u;
         if constexpr (NT == 64 * SEC_STREAM_WAVES) {
             const size_t smem3 = (size_t)((cap + 2u) & ~1u) * sizeof(double) + (size_t)sg.nrot * sizeof(double2) +
                                  (dst_lds ? (size_t)cap * sizeof(uint32_t) : 0);
@@ -1318,20 +1316,18 @@ int launch_sector_sweeps2(ovqe_handle h, SectorEngine &E, double *buf0, double *
 // contiguous (K doubles at b * stride) in buf[*last]
 int sector_sweeps2(ovqe_handle h, SectorEngine &E, int nt, double *buf0, double *buf1, size_t stride, const RotParam *rp, size_t rp_stride,
                    int B, int *last, bool dst_lds = true) {
-    const int wpt = (int)(E.chunk / (uint32_t)nt);
-#define OVQE_SW2(NT_, WPT_) if (nt == NT_ && wpt == WPT_) return launch_sector_sweeps2<NT_, WPT_>(h, E, buf0, buf1, stride, rp, rp_stride, B, last, dst_lds)
-    OVQE_SW2(1024, 4); OVQE_SW2(1024, 2); OVQE_SW2(1024, 1); OVQE_SW2(512, 8); OVQE_SW2(512, 4); OVQE_SW2(512, 2); OVQE_SW2(256, 8); OVQE_SW2(256, 4);
-#undef OVQE_SW2
-    return fail(h, OVQE_ERR_INVALID, "sector_threads x words per thread does not match sector_chunk");
+    switch (nt) {   // words per thread: SEC_CHUNK / threads
+    case 1024: return launch_sector_sweeps2<1024, SEC_CHUNK / 1024>(h, E, buf0, buf1, stride, rp, rp_stride, B, last, dst_lds);
+    case 512: return launch_sector_sweeps2<512, SEC_CHUNK / 512>(h, E, buf0, buf1, stride, rp, rp_stride, B, last, dst_lds);
+    case 256: return launch_sector_sweeps2<256, SEC_CHUNK / 256>(h, E, buf0, buf1, stride, rp, rp_stride, B, last, dst_lds);
+    }
+    return fail(h, OVQE_ERR_INVALID, "no second sweep form for this workgroup size");
 }
 
-// whether the second form has an instantiation for this workgroup size / chunk and every tile of the engine fits its LDS: checked
+// whether the second form has an instantiation for this workgroup size and every tile of the engine fits its LDS: checked
 // BEFORE the first launch, so that a caller can take the first form (or the one-at-a-time path) instead of failing half way
 bool sector_sweeps2_fits(const SectorEngine &E, int nt, bool dst_lds) {
-    const int wpt = nt > 0 ? (int)(E.chunk / (uint32_t)nt) : 0;
-    const bool inst = (nt == 1024 && (wpt == 4 || wpt == 2 || wpt == 1)) || (nt == 512 && (wpt == 8 || wpt == 4 || wpt == 2)) ||
-                      (nt == 256 && (wpt == 8 || wpt == 4));
-    if (!inst || (uint32_t)(wpt * nt) != E.chunk) return false;
+    if (nt != 1024 && nt != 512 && nt != 256) return false;
     for (const SectorSeg &sg : E.segs) {
         const uint32_t cap = std::max(sg.L.max_tile, 1u);
         const size_t smem = (size_t)((cap + 2u) & ~1u) * sizeof(double) + (size_t)sg.nrot * sizeof(double2) +
@@ -1343,9 +1339,8 @@ bool sector_sweeps2_fits(const SectorEngine &E, int nt, bool dst_lds) {
 
 // launch geometry of the <H> kernels: workgroups per sweep, dynamic LDS (tile [+ lambda] + dictionary)
 constexpr int SEC_H_THREADS = 512;
-uint32_t sector_h_groups(ovqe_handle h, const SectorEngine &E) {
-    return std::min<uint32_t>(E.hs[0].L.ntiles, (uint32_t)std::max(h->opt_sector_h_groups, 1));
-}
+constexpr uint32_t SEC_H_GROUPS = 256;   // workgroups per <H> sweep (they share the sweep's tiles round robin)
+uint32_t sector_h_groups(const SectorEngine &E) { return std::min<uint32_t>(E.hs[0].L.ntiles, SEC_H_GROUPS); }
 size_t sector_h_smem(const SectorEngine &E, int tiles) {
     return (size_t)tiles * ((std::max(E.h_max_tile, 1u) + 1u) & ~1u) * sizeof(double) + ((size_t)E.h_max_dict + 2 + 64) * sizeof(double);   // + 64: the dummy slots of k_sector_apply
 }
@@ -1424,7 +1419,7 @@ int run_sector_circuit(ovqe_handle h, const double *theta, int *last) {
     if (h->opt_sector_sweep >= 2 && E.pad_elems && E.segs[0].d_wide.p && h->opt_sector_threads != 64) {
         // three or more tiles per CU (26 qubits and beyond): what a batch gains from co-resident workgroups a single state gains
         // too — 512-thread workgroups that read their scatter indices at the end, three per CU instead of two of 1024 threads
-        const bool many = (E.segs[0].L.ntiles >= 768u && h->opt_sector_many_tiles) || h->opt_sector_many_tiles == 2;   // (2: always, experiments)
+        const bool many = E.segs[0].L.ntiles >= 768u;
         const int nt2 = h->opt_sector_threads != 0 ? nt : (many ? 512 : 1024);
         if (sector_sweeps2_fits(E, nt2, !(many && h->opt_sector_threads == 0)))   // else: the first form below serves every geometry
         return sector_sweeps2(h, E, nt2, (double *)E.d_buf[0].p, (double *)E.d_buf[1].p, std::max<size_t>(E.K, E.pad_elems),
@@ -1493,21 +1488,15 @@ int run_sector_energy(ovqe_handle h, const double *theta, double2 *out, bool *ok
     int rc = run_sector_circuit(h, theta, &last);
     if (rc) return rc;
     if (profile) HIPC(h, hipEventRecord(E.ev[1], h->stream));
-    const uint32_t nt = sector_h_groups(h, E);
+    const uint32_t nt = sector_h_groups(E);
     const size_t nparts = (size_t)nt * E.hs.size();
     rc = ensure(h, h->d_partials, nparts * sizeof(double2));
     if (!rc) rc = ensure(h, h->d_result, 64 * sizeof(double2));
-    static bool attr_done_dev[64] = {}, attr_done_dev2[64] = {};
+    static bool attr_done_dev[64] = {};
     if (!rc) rc = sector_h_attr(h, &k_sector_expect<SEC_H_THREADS>, attr_done_dev[h->device & 63]);
-    if (!rc) rc = sector_h_attr(h, &k_sector_expect<1024>, attr_done_dev2[h->device & 63]);
     if (rc) return rc;
     // "sector_fused_reduce" (default): the reduction writes energy + flag into mapped host memory (no copies behind it)
     const bool fused = h->opt_sector_fused_reduce && sector_fin_ready(h);
-    if (h->opt_sector_h_threads == 1024)
-        hipLaunchKernelGGL((k_sector_expect<1024>), dim3(nt, (unsigned)E.hs.size()), dim3(1024), sector_expect_smem(E),
-                           h->stream, (const double *)E.d_buf[last].p, (const SecHSweep *)E.d_hdesc.p, (double2 *)h->d_partials.p,
-                           std::max(E.h_max_tile, 1u), h->opt_sector_h_dbg);
-    else
     hipLaunchKernelGGL((k_sector_expect<SEC_H_THREADS>), dim3(nt, (unsigned)E.hs.size()), dim3(SEC_H_THREADS), sector_expect_smem(E),
                        h->stream, (const double *)E.d_buf[last].p, (const SecHSweep *)E.d_hdesc.p, (double2 *)h->d_partials.p,
                        std::max(E.h_max_tile, 1u), h->opt_sector_h_dbg);
@@ -1557,13 +1546,19 @@ int sector_matvec(ovqe_handle h, SectorEngine &E, const double *in, double *out)
 // slices and angle tables), <H> holds NB = 2 states per tile so the table streams once per pair of states.
 // theta: B x K on the host or (theta_on_device) on the device; energies likewise.  *ok = false: an orphan pair was hit by
 // some state (the caller falls back to one evaluation at a time, which sorts out which tables to drop).
-constexpr int SEC_BATCH_NB = 2;   // smallest number of states per tile (sector_batch_ready sizes LDS for it)
-template <int NT, int NB>
-int run_sector_energy_batch_t(ovqe_handle h, int64_t B, const double *theta, bool theta_on_device, double *energies, bool *ok) {
+// States per tile of the batched <H> and its workgroup size: two states with 512 threads leave ONE workgroup per CU (8 waves)
+// where the single-state kernel keeps two or three; measured at 24 qubits, B = 64 (ms per evaluation): see DESIGN.md §4
+constexpr int SEC_BATCH_NB = 2;   // (sector_batch_ready sizes LDS for it)
+constexpr int SEC_BATCH_H_THREADS = 1024;
+// the batch's circuit sweeps: 512-thread workgroups that read their scatter indices when the tile is written (44 instead of 64 KB
+// per workgroup at 24 qubits: three workgroups per CU; B = 64: 0.82 -> 0.70 ms per evaluation)
+constexpr int SEC_BATCH_SWEEP_THREADS = 512;
+int run_sector_energy_batch(ovqe_handle h, int64_t B, const double *theta, bool theta_on_device, double *energies, bool *ok) {
+    constexpr int NT = SEC_BATCH_H_THREADS, NB = SEC_BATCH_NB;
     SectorEngine &E = h->sec;
     *ok = false;
-    if (!sector_sweeps2_fits(E, h->opt_sector_batch_sweep_threads, h->opt_sector_batch_dst_lds != 0))
-        return OVQE_OK;   // an option combination the batched sweeps have no kernel for: one evaluation at a time still works
+    if (!sector_sweeps2_fits(E, SEC_BATCH_SWEEP_THREADS, false))
+        return OVQE_OK;   // a tile the batched sweeps cannot hold: one evaluation at a time still works
     const size_t S = h->srots.size();
     const size_t stride = std::max<size_t>(E.K, E.pad_elems);
     // states per pass: the two state buffers stay below ~4 GB (and the launch grid inside its limits)
@@ -1575,10 +1570,10 @@ int run_sector_energy_batch_t(ovqe_handle h, int64_t B, const double *theta, boo
     if (!rc) rc = ensure(h, E.d_brp, (size_t)chunk * std::max<size_t>(S, 1) * sizeof(RotParam));
     if (!rc) rc = ensure(h, E.d_benergies, (size_t)chunk * sizeof(double));
     if (!rc && !theta_on_device) rc = ensure(h, h->d_theta, (size_t)chunk * std::max(1, h->K) * sizeof(double));
-    const uint32_t ng = sector_h_groups(h, E);
+    const uint32_t ng = sector_h_groups(E);
     const size_t nparts = (size_t)ng * E.hs.size();
     if (!rc) rc = ensure(h, h->d_partials, (size_t)(chunk / NB) * nparts * NB * sizeof(double));
-    static bool attr_done_dev[64] = {};   // (one per instantiation)
+    static bool attr_done_dev[64] = {};
     if (!rc) rc = sector_h_attr(h, &k_sector_expect_batch<NT, NB>, attr_done_dev[h->device & 63]);
     if (rc == OVQE_ERR_ALLOC) {   // no room for the state slices of a batch next to the tables: the serial path needs none of them
         for (DevBuf *b : {&E.d_bbuf[0], &E.d_bbuf[1], &E.d_brp, &E.d_benergies}) free_buf(*b);
@@ -1602,10 +1597,11 @@ int run_sector_energy_batch_t(ovqe_handle h, int64_t B, const double *theta, boo
                                        S * sizeof(RotParam), hipMemcpyDeviceToDevice, h->stream));
         }
         int last = 0;
-        rc = sector_sweeps2(h, E, h->opt_sector_batch_sweep_threads, (double *)E.d_bbuf[0].p, (double *)E.d_bbuf[1].p, stride, (const RotParam *)E.d_brp.p, S,
-                            (int)nbp, &last, h->opt_sector_batch_dst_lds != 0);
+        rc = sector_sweeps2(h, E, SEC_BATCH_SWEEP_THREADS, (double *)E.d_bbuf[0].p, (double *)E.d_bbuf[1].p, stride, (const RotParam *)E.d_brp.p, S,
+                            (int)nbp, &last, false);
         if (rc) return rc;
-        const bool zfast = h->opt_sector_batch_zfast != 0 && nbp / NB <= 65535 && E.hs.size() <= 65535;
+        // state group = fastest grid index (the groups share a tile's elements through the caches)
+        const bool zfast = nbp / NB <= 65535 && E.hs.size() <= 65535;
         hipLaunchKernelGGL((k_sector_expect_batch<NT, NB>),
                            zfast ? dim3((unsigned)(nbp / NB), ng, (unsigned)E.hs.size()) : dim3(ng, (unsigned)E.hs.size(), (unsigned)(nbp / NB)),
                            dim3(NT), sector_h_smem(E, NB), h->stream, (const double *)E.d_bbuf[last].p, stride,
@@ -1630,17 +1626,6 @@ int run_sector_energy_batch_t(ovqe_handle h, int64_t B, const double *theta, boo
     }
     *ok = true;
     return OVQE_OK;
-}
-
-// states per tile of the batched <H> and its workgroup size: two states with 512 threads leave ONE workgroup per CU (8 waves)
-// where the single-state kernel keeps two or three; measured at 24 qubits, B = 64 (ms per evaluation): see DESIGN.md §4
-int run_sector_energy_batch(ovqe_handle h, int64_t B, const double *theta, bool theta_on_device, double *energies, bool *ok) {
-    int nb = h->opt_sector_batch_nb, nt = h->opt_sector_batch_threads;
-    if (nb == 3 && sector_h_smem(h->sec, 3) > 156 * 1024) nb = 2;
-    if (nb == 3) return nt == 512 ? run_sector_energy_batch_t<512, 3>(h, B, theta, theta_on_device, energies, ok)
-                                  : run_sector_energy_batch_t<1024, 3>(h, B, theta, theta_on_device, energies, ok);
-    return nt == 512 ? run_sector_energy_batch_t<512, 2>(h, B, theta, theta_on_device, energies, ok)
-                     : run_sector_energy_batch_t<1024, 2>(h, B, theta, theta_on_device, energies, ok);
 }
 
 // dE/dtheta for all parameters on the sector tables (adjoint method): forward circuit, lambda = H psi on the support, one
@@ -1691,7 +1676,7 @@ size_t sector_adjoint3_smem(const SectorSeg &sg) {
            (size_t)std::max(sg.stream_waves, 1) * sg.nrot * sizeof(double) + (size_t)cap * sizeof(uint32_t);
 }
 bool sector_adjoint2_fits(ovqe_handle h, const SectorEngine &E) {
-    if (h->opt_sector_adjoint < 2 || h->opt_sector_sweep < 2 || !E.pad_elems || E.chunk != 2048u || E.segs.empty()) return false;
+    if (h->opt_sector_adjoint < 2 || h->opt_sector_sweep < 2 || !E.pad_elems || E.segs.empty()) return false;
     for (size_t s = 0; s < E.segs.size(); ++s) {
         const SectorSeg &sg = E.segs[s];
         if (!sg.d_wide.p || (s && !sg.d_bdst.p) || sg.maxchunks > 1024u || sector_adjoint2_smem(sg, 1024) > 160 * 1024) return false;
@@ -1892,16 +1877,15 @@ int sector_matvec(ovqe_handle h, SectorEngine &E, const double *in, double *out)
     // kernel needs 109 registers (161 before: the 1024-thread form spilled 24 of them) and 1024 threads also win where two 512-thread
     // workgroups would fit (N2 QUCCSD tables, tiles of 4096: gradient 14.2 -> 13.8 ms; UCCSD 2.91 -> 2.83 ms)
     const size_t smem = sector_h_smem(E, 2);
-    int nt = h->opt_sector_apply_threads;
-    if (nt == 0) nt = smem > 48 * 1024 ? 1024 : 512;
+    const int nt = smem > 48 * 1024 ? 1024 : 512;
     // one launch per sweep, in sequence: no global atomics (k_sector_apply, modes 1 / 2), the first sweep stores; every support
     // entry sits in exactly one tile of every sweep, so sweep 0's stores cover the whole vector (no memset)
     const unsigned nsw = (unsigned)E.hs.size();
     // (only where ONE sweep fills the chip: the N2 UCCSD tables have 83 tiles per sweep — seven sweeps side by side 3.3 ms per gradient,
     // in sequence 4.1; the QUCCSD tables 1024 per sweep: 14.9 -> 14.2 ms)
-    const bool seq = h->opt_sector_apply_seq && nsw >= 1 && (uint64_t)E.K >= 512ull * std::max(E.h_max_tile, 1u);
+    const bool seq = nsw >= 1 && (uint64_t)E.K >= 512ull * std::max(E.h_max_tile, 1u);
     if (!seq) HIPC(h, hipMemsetAsync(out, 0, (size_t)E.K * sizeof(double), h->stream));
-    const dim3 grid(sector_h_groups(h, E), seq ? 1u : nsw);
+    const dim3 grid(sector_h_groups(E), seq ? 1u : nsw);
     for (unsigned s0 = 0; s0 < (seq ? nsw : 1u); ++s0) {
         const int mode = seq ? (s0 == 0 ? 2 : 1) : 0;
         if (nt == 1024) {

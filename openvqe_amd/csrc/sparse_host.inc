@@ -244,7 +244,7 @@ int build_sparse_program(ovqe_handle h) {
     // 32-lane groups, bank = double slot mod 32).  The entries are a plain sum, so their order is free: they are
     // re-arranged greedily so that inside every aligned group of 32 the first indices are distinct mod 32 and so are the
     // second ones — conflict-free reads wherever the entry set allows it (a fixed order: results stay reproducible).
-    if (h->opt_sparse_dealias && entries.size() > 64) {
+    if (entries.size() > 64) {
         std::vector<std::vector<uint32_t>> by_bank(32);
         for (uint32_t e = 0; e < (uint32_t)entries.size(); ++e) by_bank[entries[e].ij & 31u].push_back(e);
         std::vector<SpEntry> arranged;

@@ -158,17 +158,17 @@ __global__ __launch_bounds__(256) void k_rot_pairs(amp_t *__restrict__ st, uint6
     }
 }
 
-// tuning variants of the pair sweep (selected with ovqe_set_option("rot_variant", v)):
-//   NT threads per block, U pairs per thread per trip, NTL non-temporal loads/stores, PERSIST grid-stride loop
+// launch geometries of the pair sweep (chosen by launch_rot_run): NT threads per block, U pairs per thread, NTL non-temporal
+// loads/stores; one tile of NT x U pairs per workgroup
 typedef double v2d __attribute__((ext_vector_type(2)));
 
-template <int NT, int U, bool NTL, bool PERSIST>
+template <int NT, int U, bool NTL>
 __global__ __launch_bounds__(NT) void k_rot_pairs_v(amp_t *__restrict__ st, uint64_t npairs, int pivot, uint64_t x,
                                                     uint64_t base, const RotParam *__restrict__ rp, int nrot) {
     v2d *p = reinterpret_cast<v2d *>(st);
     const uint64_t tile = (uint64_t)NT * U;
     const uint64_t ntiles = (npairs + tile - 1) / tile;
-    for (uint64_t t = blockIdx.x; t < ntiles; t += PERSIST ? gridDim.x : ntiles) {
+    for (uint64_t t = blockIdx.x; t < ntiles; t += ntiles) {
         const uint64_t k0 = t * tile + threadIdx.x;
         amp_t u[U], v[U];
         uint64_t ii[U];

@@ -632,7 +632,7 @@ __global__ __launch_bounds__(NT) void k_sector_sweep(const double *__restrict__ 
 //      build time (k_sec_widen), ops without pairs in the tile have no round;
 //  (c) per round that leaves: compare -> two LDS reads -> rotate -> two writes -> barrier.
 // blockIdx.y = state of a batch (own in / out slices and angle tables).
-constexpr uint32_t SEC_CHUNK = 4096;            // pair words per chunk (k_sector_sweep2: NT x WPT), option "sector_chunk"
+constexpr uint32_t SEC_CHUNK = 2048;            // pair words per chunk of the 64-bit tables (k_sec_widen) = NT x WPT of k_sector_sweep2
 constexpr uint32_t SEC_NO_ROUND = 0xfffu;
 constexpr uint32_t SEC_WIDE_MAX_PAIRS = 16u << 20;   // pairs of a sweep up to which the 64-bit tables are built (128 MB of words)
 __device__ __forceinline__ uint64_t sec_word64(uint32_t si, uint32_t sj, uint32_t sign, uint32_t csidx, uint32_t round) {

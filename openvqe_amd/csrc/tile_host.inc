@@ -38,7 +38,7 @@ void fill_entry_basis(ExEntryT &en, const std::vector<ExTermT> &tterms, bool rea
 }
 
 int build_ham_tiles(ovqe_handle h, HamDev &H, bool real) {
-    const int M = tile_bits(h, real), L = ham_tile_low(h, real);
+    const int M = tile_bits(h, real), L = HAM_TILE_LOW;
     H.tile_bits = M;
     H.tile_low = L;
     H.tile_real = real;
@@ -161,7 +161,7 @@ int build_ham_tiles(ovqe_handle h, HamDev &H, bool real) {
             // cutting it into 2^(w-1) pattern entries only multiplies the per-entry set-up (a quarter of the kernel's instructions at
             // w = 4: 25 per pair).  Its 2^(M-1) pairs (pivot bit of i clear) are walked in pieces of 512 with the x part of z left in
             // the terms' masks; en.x = the pivot bit alone (what the index walk skips), en.pad = the mask that leads to the partner.
-            if (!real && w >= 2 && gr.t1 - gr.t0 <= 2 && h->opt_tile_unsplit && M - 1 >= 9) {
+            if (!real && w >= 2 && gr.t1 - gr.t0 <= 2 && M - 1 >= 9) {
                 if ((int)tterms.size() - ck.t0 + (gr.t1 - gr.t0) > TILE_TERM_CAP) {
                     ck.g1 = (int32_t)tgroups.size();
                     ck.t1 = (int32_t)tterms.size();
@@ -302,7 +302,7 @@ int build_ham_tiles(ovqe_handle h, HamDev &H, bool real) {
     H.n_rest = (int)rest.size();
     // the diagonal group in Walsh-Hadamard form (k_tile_diag): contiguous tiles of 2^12 amplitudes, the terms grouped by their z mask
     // on the tile bits (ascending mask, the group's term order inside: a fixed summation order)
-    if (H.diag_sweep >= 0 && h->n_local >= 25 && h->opt_expect_diag_wht) {
+    if (H.diag_sweep >= 0 && h->n_local >= 25) {
         const HGroup *dg = nullptr;
         for (const HGroup &g : H.groups)
             if (g.x == 0) dg = &g;
@@ -372,7 +372,9 @@ int launch_tile_expect(ovqe_handle h, const HamDev &H, const ExSweep &sw, double
                               (NT / 64 + 2) * sizeof(int);
     const size_t smem = dense_only ? smem_dense : smem_full;
     const dim3 grid((unsigned)(h->namps >> M), (unsigned)expect_ysplit(h, M));
-    const int sparse_den = dense_only ? (skip_diag ? -2 : -1) : ((H.d_agroups.p && sw.a1 > sw.a0) ? h->opt_expect_sparse : 0);
+    // a tile with at most 1/SPARSE_DEN of its amplitudes non-zero is evaluated over the compacted list of those amplitudes
+    constexpr int SPARSE_DEN = 4;
+    const int sparse_den = dense_only ? (skip_diag ? -2 : -1) : ((H.d_agroups.p && sw.a1 > sw.a0) ? SPARSE_DEN : 0);
     static bool attr_done_dev[64] = {};  // function attributes are per device
     bool &attr_done = attr_done_dev[h->device & 63];
     if (!attr_done) {
@@ -402,7 +404,7 @@ int launch_tile_expect(ovqe_handle h, const HamDev &H, const ExSweep &sw, double
 // <state|H|state> of the stored Hamiltonian through the tile cover; *used = false when there is no cover
 int run_expectation_tiled(ovqe_handle h, HamDev &H, double2 *out, bool *used, bool real = false) {
     *used = false;
-    if (H.tile_bits != tile_bits(h, real) || H.tile_low != ham_tile_low(h, real) || H.tile_real != real) {
+    if (H.tile_bits != tile_bits(h, real) || H.tile_low != HAM_TILE_LOW || H.tile_real != real) {
         int rc = build_ham_tiles(h, H, real);
         if (rc) return rc;
     }
@@ -422,7 +424,7 @@ int run_expectation_tiled(ovqe_handle h, HamDev &H, double2 *out, bool *used, bo
     const int ns = (int)H.tsweeps.size();
     // (shards too: the second stream forks from and joins the handle's stream by events, so what the caller ordered behind that
     // stream — the RCCL transfers of the partitioned register — stays ordered behind both)
-    const bool dual = h->opt_expect_streams >= 2 && ns >= 8 && h->n_local >= 20;
+    const bool dual = ns >= 8 && h->n_local >= 20;
     if (dual && !h->stream2) {
         HIPC(h, hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
         HIPC(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
@@ -436,7 +438,7 @@ int run_expectation_tiled(ovqe_handle h, HamDev &H, double2 *out, bool *used, bo
     // under every tile bit set and the remaining sweeps run without that area: two workgroups per CU, of either stream.  (One stream
     // synchronisation per evaluation: only where there are at least four sweeps of at least half a gigabyte.)
     // (round 6: real states too — the float64 shards of the partitioned register: tiles of 2^13 doubles)
-    const bool try_dense = ((!real && M == 12) || (real && M == 13)) && h->n_local >= 25 && ns >= 4 && h->opt_expect_sparse > 0 && h->opt_expect_dense;
+    const bool try_dense = ((!real && M == 12) || (real && M == 13)) && h->n_local >= 25 && ns >= 4 && h->opt_expect_dense;
     bool dense_only = false;
     int census_k = -1;      // the sweep that ran first, as the census
     if (try_dense) {
@@ -641,7 +643,8 @@ template <int M>
 int launch_tile_expect_compact(ovqe_handle h, const HamDev &H, double2 *partials) {
     constexpr int NT = 1 << TILE_EXPECT_LOG_NT;
     const CompactCover &C = h->cc;
-    const int cpp = h->opt_compact_cpp, term_cap = cpp * TILE_TERM_CAP, group_cap = cpp * TILE_APPLY_GROUPS;
+    constexpr int cpp = 1;   // host chunks (512 terms each) staged in LDS per pass
+    const int term_cap = cpp * TILE_TERM_CAP, group_cap = cpp * TILE_APPLY_GROUPS;
     const size_t smem = ((size_t)8 << M) + (size_t)term_cap * sizeof(ExTermLds) + (size_t)group_cap * sizeof(ExAGroupT) +
                         (NT / 64) * sizeof(double2) + (((size_t)C.max_nnz * 2 + 15) & ~(size_t)15);
     static bool attr_done_dev[64] = {};
@@ -734,7 +737,7 @@ int launch_tile_apply(ovqe_handle h, const HamDev &H, const ExSweep &sw, const a
 int apply_hamiltonian(ovqe_handle h, amp_t *out, const amp_t *in, double ident, const uint64_t *in_idx = nullptr,
                       uint64_t in_count = 0, HamDev *which = nullptr) {
     HamDev &H = which ? *which : h->ham;   // (which: the local part of a planned cross-shard sum, cross_host.inc)
-    if (H.tile_bits != tile_bits(h, false) || H.tile_low != ham_tile_low(h, false) || H.tile_real) {
+    if (H.tile_bits != tile_bits(h, false) || H.tile_low != HAM_TILE_LOW || H.tile_real) {
         int rc = build_ham_tiles(h, H, false);
         if (rc) return rc;
     }

@@ -1,5 +1,5 @@
 """tiled <H> and H psi on a 2*m-qubit random state for the first `terms` strings of a molecule-shaped Hamiltonian: time per call for
-tile-cover settings given as --opt=name=value (e.g. ham_tile_low).  python tools/exp_hexp_big.py 15 2000 --opt=ham_tile_low=4"""
+tile-cover settings given as --opt=name=value (e.g. tile_bits).  python tools/exp_hexp_big.py 15 2000 --opt=tile_bits=11"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -1,5 +1,5 @@
-"""k_sector_expect (the materialised <H> of the sector path) over launch geometries: HIP-event microseconds per evaluation and
-the rate at which the table streams.  usage: exp_hexpect.py [m o]"""
+"""k_sector_expect (the materialised <H> of the sector path) with phases switched off (testing library: OVQE_LIB=testing): HIP-event
+microseconds per evaluation and the rate at which the table streams.  usage: exp_hexpect.py [m o]"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -23,10 +23,7 @@ with Statevector(2 * m) as sv:
             sv.energy(theta); us.append(sv.program_info()["sector_expect_us"])
         print(f"dbg {dbg} (1 tile loads only, 2 no tile loads, 3 tile loads + slice metadata only): {min(us[1:])} us", flush=True)
     sv.set_option("sector_h_dbg", 0)
-    for threads in (512, 1024):
-        for groups in (64, 128, 256, 512):
-            sv.set_option("sector_h_threads", threads); sv.set_option("sector_h_groups", groups)
-            us = []
-            for _ in range(6):
-                e = sv.energy(theta); us.append(sv.program_info()["sector_expect_us"])
-            print(f"threads {threads} groups {groups}: {min(us[1:])} us = {hb / min(us[1:]) / 1e6:.2f} TB/s, dE {e - e0:.1e}", flush=True)
+    us = []
+    for _ in range(6):
+        e = sv.energy(theta); us.append(sv.program_info()["sector_expect_us"])
+    print(f"full kernel: {min(us[1:])} us = {hb / min(us[1:]) / 1e6:.2f} TB/s, dE {e - e0:.1e}", flush=True)
