@@ -56,6 +56,10 @@ int ovqe_xsum_expect_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chun
 int ovqe_xsum_expect_finish(ovqe_handle h, int32_t id, double *out_re_im);
 int ovqe_xsum_apply_local(ovqe_handle h, int32_t id, void *out_dev, double ident);
 int ovqe_xsum_apply_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chunk, const void *ket_chunk, void *out_dev);
+int ovqe_shard_pack(ovqe_handle h, uint64_t local_bit_mask, uint64_t block, int64_t first, int64_t count, void *dst,
+                    int real_parts_only);
+int ovqe_shard_unpack(ovqe_handle h, uint64_t local_bit_mask, uint64_t block, int64_t first, int64_t count, const void *src,
+                      int real_parts_only);
 int ovqe_set_hamiltonian(ovqe_handle h, int64_t T, const uint64_t *x, const uint64_t *z, const double *coeff,
                          double constant);
 int ovqe_set_program(ovqe_handle h, int64_t R, const uint64_t *x, const uint64_t *z, const double *coeff,

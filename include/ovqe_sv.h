@@ -248,6 +248,20 @@ int ovqe_xsum_apply_local(ovqe_handle h, int32_t id, void *out_dev, double ident
 /* out += H_d ket for one received chunk (out: the 2^n_local-amplitude buffer being accumulated) */
 int ovqe_xsum_apply_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chunk, const void *ket_chunk, void *out_dev);
 
+/* ---- k-bit shard exchange of a partitioned register (openvqe_amd/distributed.py: k global index bits traded for k local ones in one
+ * all-to-all among the 2^k ranks of a sub-cube; the many-device form of the state that qpu.submit keeps on one host,
+ * ref:openvqe/ucc_family/get_energy_ucc.py:46-48).  local_bit_mask: the k = 1..6 local physical bits L being exchanged (anywhere below
+ * n_local); block: a k-bit value b.  The block's 2^(n_local - k) amplitudes in ascending order: position j sits at
+ * deposit(j, ~L) | deposit(b, L) in the shard.  pack: dst[j - first] = state[that index] for j in [first, first + count); unpack is the
+ * inverse scatter (amplitudes outside the range untouched).  Elements are what the handle stores: 16-byte complex, or 8-byte doubles
+ * under option "real_state"; with complex storage and real_parts_only != 0 the stream holds the real parts only (8 bytes each) and
+ * unpack writes exact zero imaginary parts.  Both only enqueue on the handle's stream (ovqe_set_stream): no synchronisation, no
+ * allocation.  The buffer is device memory aligned to its elements. */
+int ovqe_shard_pack(ovqe_handle h, uint64_t local_bit_mask, uint64_t block, int64_t first, int64_t count, void *dst,
+                    int real_parts_only);
+int ovqe_shard_unpack(ovqe_handle h, uint64_t local_bit_mask, uint64_t block, int64_t first, int64_t count, const void *src,
+                      int real_parts_only);
+
 /* ---- compiled evaluation: E(theta) of a whole ansatz circuit */
 /* observable H = constant + sum_t coeff[t] P_t (real coefficients; ref:...get_energy_ucc.py:47) */
 int ovqe_set_hamiltonian(ovqe_handle h, int64_t T, const uint64_t *x, const uint64_t *z, const double *coeff,

@@ -67,6 +67,8 @@ SIGNATURES = {
     "ovqe_xsum_expect_finish": (_int, [_H, ctypes.c_int32, _f64p]),
     "ovqe_xsum_apply_local": (_int, [_H, ctypes.c_int32, _vp, _dbl]),
     "ovqe_xsum_apply_remote": (_int, [_H, ctypes.c_int32, _u64, _u64, _vp, _vp]),
+    "ovqe_shard_pack": (_int, [_H, _u64, _u64, _i64, _i64, _vp, _int]),
+    "ovqe_shard_unpack": (_int, [_H, _u64, _u64, _i64, _i64, _vp, _int]),
     "ovqe_set_hamiltonian": (_int, [_H, _i64, _u64p, _u64p, _f64p, _dbl]),
     "ovqe_set_program": (_int, [_H, _i64, _u64p, _u64p, _f64p, _OptF64, _i32p, ctypes.c_int32, _u64]),
     "ovqe_set_gate_program": (_int, [_H, _i64, _i32p, _i32p, _i32p, _f64p, _f64p, _i32p, ctypes.c_int32, _u64]),

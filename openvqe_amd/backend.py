@@ -239,6 +239,17 @@ class Statevector:
     def xsum_expect_remote(self, sid, d, chunk, ket_ptr):
         self._ck(self._L.ovqe_xsum_expect_remote(self._h, int(sid), int(d), int(chunk), ctypes.c_void_p(ket_ptr)))
 
+    # -- k-bit shard exchange: one block of the shard <-> a contiguous stream (ovqe_shard_pack / ovqe_shard_unpack; enqueue only) ----
+    def shard_pack(self, local_bit_mask, block, first, count, dst_ptr, real_parts_only=False):
+        """dst[j - first] = amplitude j of block ``block`` of the local bits ``local_bit_mask``, j in [first, first + count)"""
+        self._ck(self._L.ovqe_shard_pack(self._h, int(local_bit_mask), int(block), int(first), int(count), ctypes.c_void_p(dst_ptr),
+                                         1 if real_parts_only else 0))
+
+    def shard_unpack(self, local_bit_mask, block, first, count, src_ptr, real_parts_only=False):
+        """the inverse scatter of ``shard_pack`` (real parts only: the imaginary parts become exact zeros)"""
+        self._ck(self._L.ovqe_shard_unpack(self._h, int(local_bit_mask), int(block), int(first), int(count), ctypes.c_void_p(src_ptr),
+                                           1 if real_parts_only else 0))
+
     def xsum_expect_finish(self, sid):
         out = np.zeros(2, np.float64)
         self._ck(self._L.ovqe_xsum_expect_finish(self._h, int(sid), out))

@@ -256,3 +256,71 @@ int ovqe_expectation(ovqe_handle h, int64_t T, const uint64_t *x, const uint64_t
     *out = res[0] + constant;
     return OVQE_OK;
 } OVQE_CATCH(h)
+
+// ---- k-bit shard exchange: pack / unpack of one block (csrc/sv_kernels.hpp, k_shard_copy).  Both only enqueue on the handle's stream.
+extern "C++" {
+namespace {
+template <bool PACK>
+int shard_copy(ovqe_handle h, uint64_t mask, uint64_t block, int64_t first, int64_t count, void *buf, int real_parts_only) {
+    const char *who = PACK ? "ovqe_shard_pack" : "ovqe_shard_unpack";
+    if (!h) return OVQE_ERR_INVALID;
+    if (!buf) return fail(h, OVQE_ERR_INVALID, std::string(who) + ": null buffer");
+    const int k = __builtin_popcountll(mask);
+    if (mask == 0 || (mask & ~local_mask(h)) || k > 6)
+        return fail(h, OVQE_ERR_INVALID, std::string(who) + ": the mask names 1 to 6 local bits of this shard");
+    if (block >> k) return fail(h, OVQE_ERR_INVALID, std::string(who) + ": block value beyond the exchanged bits");
+    const uint64_t bsize = h->namps >> k;
+    if (first < 0 || count < 0 || (uint64_t)first > bsize || (uint64_t)count > bsize - (uint64_t)first)
+        return fail(h, OVQE_ERR_INVALID, std::string(who) + ": range past the block");
+    const bool stored_real = h->opt_real_state != 0;
+    if (stored_real && real_parts_only) real_parts_only = 0;   // (8-byte amplitudes travel as they are)
+    if ((uintptr_t)buf & ((stored_real || real_parts_only) ? 7u : 15u))
+        return fail(h, OVQE_ERR_INVALID, std::string(who) + ": buffer not aligned to its elements");
+    if (count == 0) return OVQE_OK;
+    // 16-byte units of two 8-byte elements where the shard side keeps them adjacent (bit 0 not exchanged, even range, aligned buffer)
+    const bool pair = (stored_real || real_parts_only) && !(mask & 1) && !(first & 1) && !(count & 1) && !((uintptr_t)buf & 15u) &&
+                      h->n_local >= 2;
+    const int sh = pair ? 1 : 0;
+    uint64_t m = mask >> sh, fixed = 0;
+    BitRuns R = {};
+    for (int bit = 0, i = 0; bit < 64 - sh; ++bit)   // deposit(block, mask), in units
+        if ((m >> bit) & 1) fixed |= ((block >> i++) & 1ull) << bit;
+    R.fixed = fixed;
+    while (m) {
+        const int pos = __builtin_ctzll(m);
+        int len = 0;
+        while ((m >> (pos + len)) & 1) ++len;
+        R.pos[R.n] = (uint8_t)pos;
+        R.len[R.n] = (uint8_t)len;
+        ++R.n;
+        m &= ~(((1ull << len) - 1ull) << pos);
+    }
+    const uint64_t f = (uint64_t)first >> sh, c = (uint64_t)count >> sh;
+    if (real_parts_only) {
+        const dim3 grid((unsigned)std::min<uint64_t>(1u << 30, (c + 511) / 512));   // (one trip per lane: see k_shard_copy)
+        if (pair) hipLaunchKernelGGL((k_shard_copy_re<true, PACK>), grid, dim3(256), 0, h->stream, h->state, (double *)buf, f, c, R);
+        else hipLaunchKernelGGL((k_shard_copy_re<false, PACK>), grid, dim3(256), 0, h->stream, h->state, (double *)buf, f, c, R);
+    } else {
+        const dim3 grid((unsigned)std::min<uint64_t>(1u << 30, (c + 1023) / 1024));
+        if (stored_real && !pair)
+            hipLaunchKernelGGL((k_shard_copy<double, PACK>), grid, dim3(256), 0, h->stream, (double *)h->state, (double *)buf, f, c, R);
+        else
+            hipLaunchKernelGGL((k_shard_copy<double2, PACK>), grid, dim3(256), 0, h->stream, (double2 *)h->state, (double2 *)buf, f, c, R);
+    }
+    HIPC(h, hipGetLastError());
+    return OVQE_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int ovqe_shard_pack(ovqe_handle h, uint64_t local_bit_mask, uint64_t block, int64_t first, int64_t count, void *dst,
+                    int real_parts_only) try {
+    OVQE_ENTER(h);
+    return shard_copy<true>(h, local_bit_mask, block, first, count, dst, real_parts_only);
+} OVQE_CATCH(h)
+
+int ovqe_shard_unpack(ovqe_handle h, uint64_t local_bit_mask, uint64_t block, int64_t first, int64_t count, const void *src,
+                      int real_parts_only) try {
+    OVQE_ENTER(h);
+    return shard_copy<false>(h, local_bit_mask, block, first, count, const_cast<void *>(src), real_parts_only);
+} OVQE_CATCH(h)

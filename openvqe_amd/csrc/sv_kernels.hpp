@@ -1067,4 +1067,90 @@ __global__ __launch_bounds__(256) void k_gather(const amp_t *__restrict__ st, in
     if (i < count) out[i] = st[idx[i]];
 }
 
+// ---- k-bit shard exchange: pack / unpack of one block (ovqe_shard_pack / ovqe_shard_unpack) ----------------------------------------
+// The exchanged local bits L split a shard into 2^k blocks; block b = the amplitudes whose L bits spell b.  Position j of a block
+// (its amplitudes in ascending order) sits at deposit(j, ~L) | deposit(b, L) in the shard.  L arrives as its runs of adjacent bits,
+// lowest first: the deposit is one shift-and-mask per run (at most six), `fixed` = deposit(b, L) comes from the host.
+struct BitRuns {
+    uint64_t fixed;
+    int32_t n;
+    uint8_t pos[6], len[6];
+};
+
+__device__ __forceinline__ uint64_t deposit_runs(uint64_t j, const BitRuns &R) {
+    uint64_t i = j;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+        if (r < R.n) i = ((i >> R.pos[r]) << (R.pos[r] + R.len[r])) | (i & ((1ull << R.pos[r]) - 1ull));
+    return i | R.fixed;
+}
+
+// every byte is touched once: loads and stores that do not displace the cache contents (measured on 2^27-amplitude blocks,
+// profiles/r7_exchange/README.md: 5.2 -> 6.0 TB/s together with one trip per lane)
+__device__ __forceinline__ double nt_load(const double *p) { return __builtin_nontemporal_load(p); }
+__device__ __forceinline__ double2 nt_load(const double2 *p) {
+    return make_double2(__builtin_nontemporal_load(&p->x), __builtin_nontemporal_load(&p->y));
+}
+__device__ __forceinline__ void nt_store(double v, double *p) { __builtin_nontemporal_store(v, p); }
+__device__ __forceinline__ void nt_store(double2 v, double2 *p) {
+    __builtin_nontemporal_store(v.x, &p->x);
+    __builtin_nontemporal_store(v.y, &p->y);
+}
+
+// Pure streaming copies (HBM-bound): units of T (16 bytes wherever the lowest exchanged bit leaves them contiguous, else 8), the packed
+// side contiguous per wave, the shard side contiguous in runs of 2^(lowest bit of L) units; four independent units per lane and trip.
+// The host launches one workgroup per 1024 units (one trip: faster than a grid capped at the CUs, same file), the loop covers the rest.
+// PACK: buf[j - first] = st[index(j)];  else st[index(j)] = buf[j - first]   for j in [first, first + count)
+template <typename T, bool PACK>
+__global__ __launch_bounds__(256) void k_shard_copy(T *__restrict__ st, T *__restrict__ buf, uint64_t first, uint64_t count, BitRuns R) {
+    const uint64_t stride = (uint64_t)gridDim.x * 1024u;
+    for (uint64_t c0 = (uint64_t)blockIdx.x * 1024u + threadIdx.x; c0 < count; c0 += stride) {
+        T v[4];
+        uint64_t at[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint64_t c = c0 + 256u * u;
+            at[u] = deposit_runs(first + c, R);
+            if (c < count) v[u] = nt_load(PACK ? st + at[u] : buf + c);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint64_t c = c0 + 256u * u;
+            if (c < count) {
+                nt_store(v[u], PACK ? buf + c : st + at[u]);
+            }
+        }
+    }
+}
+
+// Complex shard, stream of real parts (8 bytes per amplitude; unpack writes exact zero imaginary parts).  PAIR: the lowest exchanged
+// bit is above bit 0 and the range is even, so a lane takes two neighbouring amplitudes: 16-byte accesses on both sides.
+template <bool PAIR, bool PACK>
+__global__ __launch_bounds__(256) void k_shard_copy_re(amp_t *__restrict__ st, double *__restrict__ buf, uint64_t first, uint64_t count,
+                                                       BitRuns R) {
+    // (PAIR: first, count and R are given in units of two amplitudes)
+    const uint64_t stride = (uint64_t)gridDim.x * 512u;
+    for (uint64_t c0 = (uint64_t)blockIdx.x * 512u + threadIdx.x; c0 < count; c0 += stride) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const uint64_t c = c0 + 256u * u;
+            if (c >= count) continue;
+            const uint64_t at = deposit_runs(first + c, R);
+            if (PAIR) {
+                if (PACK) {
+                    const amp_t a = nt_load(st + 2 * at), b = nt_load(st + 2 * at + 1);
+                    nt_store(make_double2(a.x, b.x), (double2 *)buf + c);
+                } else {
+                    const double2 r = ((const double2 *)buf)[c];     // (plain stores here: the non-temporal ones measured 27 % slower)
+                    st[2 * at] = make_double2(r.x, 0.0);
+                    st[2 * at + 1] = make_double2(r.y, 0.0);
+                }
+            } else {
+                if (PACK) nt_store(nt_load(st + at).x, buf + c);
+                else st[at] = make_double2(buf[c], 0.0);
+            }
+        }
+    }
+}
+
 }  // namespace ovqe

@@ -8,12 +8,15 @@ decision, not a fixed property of the register.
 Per Pauli rotation exp(-i phi P), P = (x, z):
   * z on a global bit  -> a rank-dependent sign inside the local kernel, zero traffic;
   * x only on local bits -> the local HIP sweep of libovqe_sv (shard handle, ``ovqe_create_shard``);
-  * x on a global bit  -> that logical qubit is first made local by a HALF-SHARD EXCHANGE with the
-    partner rank (swap of one global with one local physical bit: each rank sends the half of its shard
-    it no longer owns and receives the half it now owns — S/2 bytes each way over one xGMI link), after
-    which the rotation is local.  The swap is NOT undone: the permutation is updated instead, and the
-    victim local bit is chosen Belady-style (the qubit whose next X/Y use is farthest away), so a run of
-    rotations touching the same qubits pays for one exchange only.
+  * x on a global bit  -> that logical qubit is first made local by a SHARD EXCHANGE: k global physical
+    bits are traded for k local ones in one all-to-all among the 2^k ranks of a sub-cube — every rank
+    keeps 1/2^k of its shard and sends S/2^k to each of its 2^k - 1 partners, each over its own xGMI
+    link (k = 1: the half-shard exchange with one partner, S/2 over one link) —, packed and unpacked by
+    the shard handle's kernels (``ovqe_shard_pack`` / ``ovqe_shard_unpack``), after which the rotation
+    is local.  The exchange is NOT undone: the permutation is updated instead, and the qubits sent away
+    are chosen Belady-style (farthest next X/Y use), so a run of rotations touching the same qubits pays
+    for one exchange only; because a larger exchange is cheaper per link, it also brings in every global
+    qubit that is needed sooner than a local one it can send away (``max_exchange_bits``).
 
 Expectation values: Hamiltonian terms are grouped by the global part of their x mask; the x_g = 0 group
 is a local partial sum; the <= 2^g - 1 other groups read their partner's shard in CHUNKS (2^26 amplitudes =
@@ -24,7 +27,7 @@ shard (bra) with the received chunk (ket), the index bits above the chunk folded
 on the host; one scalar all-reduce at the end.
 The ADAPT gradient screen shards the same way (``apply_hamiltonian`` builds the sigma shard group by
 group, ``pool_gradients`` contracts the pool per partner shard in one batched launch each, one
-all-reduce of the pool-sized result).  Half-shard exchanges travel in pipelined pieces.  No other
+all-reduce of the pool-sized result).  Exchanges travel in pipelined pieces.  No other
 collective exists on the data path.
 """
 from __future__ import annotations
@@ -184,6 +187,14 @@ class HipShardEngine:
         return self.sv.bilinear_batch(offsets, xs, zs, coeffs, bra_ptr=bra.data_ptr(),
                                       ket_ptr=None if ket is None else ket.data_ptr())
 
+    # -- k-bit exchange: block ``block`` of the local bits ``mask`` <-> a contiguous stream of the shard's elements (or of the real parts
+    # of a complex shard); positions [first, first + count) of the block; only enqueued on the engine's stream
+    def pack(self, mask, block, first, count, dst, real_parts_only=False):
+        self.sv.shard_pack(mask, block, first, count, dst.data_ptr(), real_parts_only)
+
+    def unpack(self, mask, block, first, count, src, real_parts_only=False):
+        self.sv.shard_unpack(mask, block, first, count, src.data_ptr(), real_parts_only)
+
     # -- Pauli sums planned once per (Hamiltonian, permutation): ovqe_xsum_* (csrc/cross_host.inc, csrc/sv_cross.hpp).  Masks in the
     # physical bit space of the whole register; the remote calls only enqueue kernels on the engine's stream
     def plan_sum(self, xs, zs, coeffs, chunk_bits):
@@ -261,11 +272,18 @@ class ShardedStatevector:
         self._dist = dist.is_initialized() and not self.dry
         self.stats = {"swaps": 0, "bytes_sent": 0, "full_shard_reads": 0, "chunk_reads": 0, "partners_per_read": 0, "pieces": 0,
                       "swap_s": 0.0, "shard_read_s": 0.0, "real_exchanges": 0, "real_chunk_reads": 0,
+                      # exchanges: bytes to ONE partner per exchange, summed (the busiest link: all partners of an exchange are served
+                      # at once, each over its own link), and the sum of the bits traded
+                      "link_bytes": 0, "exchange_bits": 0,
                       # seconds this rank's kernels ran, by phase (each section ends with a device synchronisation)
                       "local_sweeps_s": 0.0, "expectation_local_s": 0.0, "expectation_remote_s": 0.0, "apply_s": 0.0}
         # Several ranks on ONE device (the gloo runs of the tests and of bench.py's single-device mode) would time each other's
         # kernels: with a lock file every compute section takes the device alone (flock), so its seconds are this rank's own
         self.compute_lock = None
+        # Most index bits one exchange trades (a k-bit exchange is an all-to-all among 2^k ranks: S/2^k per link instead of S/2).  1:
+        # half-shard exchanges only, planned one missing qubit at a time
+        import os
+        self.max_exchange_bits = max(1, min(max(g, 1), int(os.environ.get("OVQE_EXCHANGE_BITS", max(g, 1)))))
         self._tmp = None
         self._chunk_bufs = None
         self._chunk_real = None
@@ -368,7 +386,8 @@ class ShardedStatevector:
         return pending
 
     def _exchange(self, partner, make_send, recv_pieces, on_arrival):
-        """piece p: ``make_send(p)`` (pack, on the compute stream) then its send / receive with ``partner`` is posted —
+        """the piece pattern of an exchange with ONE partner and caller-made pieces (the transport check under RCCL,
+        tests/test_gpu_nccl.py; ``_swap_bits`` posts its batches itself): piece p: ``make_send(p)`` then its send / receive is posted —
         RCCL orders each transfer behind the pack it depends on and runs the transfers in sequence on its own stream, so
         pack p + 1 and transfer p overlap; then every received piece is handed to ``on_arrival`` as soon as it has
         landed, while the later pieces are still on the link.  Lower rank sends first in a pair (gloo needs an order)."""
@@ -390,61 +409,132 @@ class ShardedStatevector:
             on_arrival(p)
             _progress()
 
-    def _swap(self, gbit, lbit):
-        """exchange physical global bit ``gbit`` with physical local bit ``lbit``: each rank sends the half of its shard
-        it no longer owns and receives the half it now owns (S/2 bytes each way on one xGMI link), in EXCHANGE_PIECES
-        pipelined pieces; a strided half (lbit below the top local bit) is packed piece by piece, never as a whole"""
-        k = gbit - self.n_local
-        alpha = (self.rank >> k) & 1
-        partner = self.rank ^ (1 << k)
-        t = self.engine.tensor.view(1 << (self.n_local - 1 - lbit), 2, 1 << lbit)
-        mine_out = t[:, 1 - alpha, :]          # (A, B): the half this rank gives away / receives into
-        A, B = mine_out.shape
-        half = A * B
-        P = self.EXCHANGE_PIECES
-        recv = self._tmp_buffer(half)
-        if A >= P or A >= B:                    # pieces = row blocks (strided rows of length B)
-            P = max(1, min(P, A))               # never a zero-length piece: an empty send/recv pair is still a group launch
-            views = [mine_out[(A * p) // P:(A * (p + 1)) // P, :] for p in range(P)]
-        else:                                   # few long rows: cut the columns
-            P = max(1, min(P, B))
-            views = [mine_out[:, (B * p) // P:(B * (p + 1)) // P] for p in range(P)]
-        sizes = [v.numel() for v in views]
-        starts = [sum(sizes[:p]) for p in range(P)]
-        recv_pieces = [recv[starts[p]:starts[p] + sizes[p]] for p in range(P)]
-        self.engine.sync()
-        _progress("half-shard exchange")
-        t_swap = time.perf_counter()
+    #: piece sets of an exchange in flight: while set p is on the links, set p + 1 is packed and set p - 1 unpacked
+    EXCHANGE_DEPTH = 2
 
+    def _scratch(self, count, real):
+        """``count`` elements of exchange scratch: the shard's elements, or doubles for the real parts of a complex shard"""
+        if real:
+            return torch.view_as_real(self._tmp_buffer((count + 1) // 2)).reshape(-1)[:count]
+        return self._tmp_buffer(count)
+
+    def _block_index(self, mask, block, first, count):
+        """shard positions of the amplitudes [first, first + count) of block ``block`` of the local bits ``mask`` (engines without
+        pack / unpack: torch indexing)"""
+        j = torch.arange(first, first + count, dtype=torch.int64, device=self.engine.tensor.device)
+        fixed, i = 0, 0
+        for bit in range(self.n_local):
+            if (mask >> bit) & 1:
+                j = ((j >> bit) << (bit + 1)) | (j & ((1 << bit) - 1))
+                fixed |= ((block >> i) & 1) << bit
+                i += 1
+        return j | fixed
+
+    def _pack(self, mask, block, first, count, dst, real):
+        if hasattr(self.engine, "pack"):
+            self.engine.pack(mask, block, first, count, dst, real)
+        else:
+            src = self.engine.tensor[self._block_index(mask, block, first, count)]
+            dst.copy_(torch.view_as_real(src)[:, 0] if real else src)
+
+    def _unpack(self, mask, block, first, count, src, real):
+        if hasattr(self.engine, "unpack"):
+            self.engine.unpack(mask, block, first, count, src, real)
+        else:
+            self.engine.tensor[self._block_index(mask, block, first, count)] = torch.complex(src, torch.zeros_like(src)) if real else src
+
+    def _swap_bits(self, gbits, lbits):
+        """exchange the k physical global bits ``gbits`` with the k physical local bits ``lbits`` (pairwise) in one step: an all-to-all
+        among the 2^k ranks of the sub-cube that ``gbits`` span.  The local bits split the shard into 2^k blocks; the rank with
+        sub-cube coordinate a (its values on ``gbits``) keeps block a where it is and sends block b to the rank with coordinate b,
+        where it lands as block a: S/2^k amplitudes to each of the 2^k - 1 partners, every partner over its own link, instead of S/2
+        over one link k times.  A block travels in EXCHANGE_PIECES pieces; the pieces p of all partners are posted as one batch, and
+        EXCHANGE_DEPTH batches are in flight: pack p + 1 and unpack p - 1 run while batch p is on the links.  Block b is received
+        into scratch (its slot is the one being sent to b) and unpacked when its own piece has been packed: scratch is
+        2 x EXCHANGE_DEPTH x (2^k - 1) pieces, (1 - 2^-k) S / 2 at the default sizes.  k = 1 is the half-shard exchange."""
+        k = len(gbits)
+        pairs = sorted(zip(lbits, gbits))               # block values count the local bits in ascending order
+        lb, gb = [p[0] for p in pairs], [p[1] for p in pairs]
+        if k < 1 or len(set(lb)) != k or len(set(gb)) != k or lb[-1] >= self.n_local or min(gb) < self.n_local or max(gb) >= self.n:
+            raise ValueError("an exchange trades k distinct global bits for k distinct local bits")
+        mask = sum(1 << b for b in lb)
+        a = sum(((self.rank >> (gb[i] - self.n_local)) & 1) << i for i in range(k))
+        gmask = sum(1 << (b - self.n_local) for b in gb)
+
+        def rank_of(b):
+            return (self.rank & ~gmask) | sum(((b >> i) & 1) << (gb[i] - self.n_local) for i in range(k))
+
+        blocks = [b for b in range(1 << k) if b != a]
+        bsize = 1 << (self.n_local - k)
+        P = self.EXCHANGE_PIECES
+        if k == 1:      # (the piece count of the half-shard exchange as it always was: rows of the strided half, or columns of few long rows)
+            A, B = 1 << (self.n_local - 1 - lb[0]), 1 << lb[0]
+            P = max(1, min(P, A)) if (A >= P or A >= B) else max(1, min(P, B))
+        else:
+            P = max(1, min(P, bsize))                   # never a zero-length piece: an empty send/recv pair is still a group launch
+        cuts = [(bsize * p) // P for p in range(P + 1)]
+        piece = max(cuts[p + 1] - cuts[p] for p in range(P))
         stored_real = self._storage_real()             # float64 shards travel as they are
         real = self.real and self.real_transfers and not stored_real     # (the same on every rank: the flag follows the rotation list)
-        if real:
-            rrecv = torch.view_as_real(recv).reshape(-1)[:half]        # the receive buffer's first half, as doubles
-            recv_pieces = [rrecv[starts[p]:starts[p] + sizes[p]] for p in range(P)]
+        # a block that is contiguous in the shard (the top local bits) is sent from where it lies
+        in_place = mask == ((1 << k) - 1) << (self.n_local - k) and not real
+        depth = max(1, min(self.EXCHANGE_DEPTH, P))
+        nb = len(blocks)
+        scratch = self._scratch(depth * nb * piece * (1 if in_place else 2), real)
+        recv_sets = [[scratch[(s * nb + i) * piece:(s * nb + i + 1) * piece] for i in range(nb)] for s in range(depth)]
+        send_sets = None if in_place else [[scratch[((depth + s) * nb + i) * piece:((depth + s) * nb + i + 1) * piece]
+                                            for i in range(nb)] for s in range(depth)]
+        self.engine.sync()
+        _progress("half-shard exchange" if k == 1 else "%d-bit shard exchange" % k)
+        t_swap = time.perf_counter()
 
-        def pack(p):
-            v = views[p]
-            if real:
-                return torch.view_as_real(v)[..., 0].contiguous().view(-1)
-            return v.reshape(-1) if v.is_contiguous() else v.contiguous().view(-1)
+        class _Done:
+            def wait(_self):
+                pass
 
-        def unpack(p):
-            if real:
-                dst = torch.view_as_real(views[p])
-                dst[..., 0].copy_(recv_pieces[p].view(views[p].shape))
-                dst[..., 1].zero_()
-            else:
-                views[p].copy_(recv_pieces[p].view(views[p].shape))
+        def post(p):
+            first, count = cuts[p], cuts[p + 1] - cuts[p]
+            s = p % depth
+            items = []
+            for i, b in enumerate(blocks):
+                if in_place:
+                    snd = self.engine.tensor[b * bsize + first:b * bsize + first + count]
+                else:
+                    snd = send_sets[s][i][:count]
+                    self._pack(mask, b, first, count, snd, real)
+                rcv = recv_sets[s][i][:count]
+                if self.dry:     # (one rank alone: the piece it would send stands in for the piece it would receive)
+                    rcv.copy_(snd)
+                else:            # one tag per (piece, partner): gloo matches by tag, and both ends of a pair agree on it
+                    items.append((snd, rcv, rank_of(b), (p << k) | (a ^ b)))
+            return _Done() if self.dry else self._post_multi(items)
 
-        self._exchange(partner, pack, recv_pieces, unpack)
+        def arrived(p, work):
+            work.wait()
+            first, count = cuts[p], cuts[p + 1] - cuts[p]
+            for i, b in enumerate(blocks):
+                self._unpack(mask, b, first, count, recv_sets[p % depth][i][:count], real)
+            _progress()
+
+        pending = []
+        for p in range(P):
+            pending.append((p, post(p)))
+            if len(pending) == depth:        # the buffers of this set are used again by piece p + 1
+                arrived(*pending.pop(0))
+        while pending:
+            arrived(*pending.pop(0))
         self.engine.sync()
         self.stats["swap_s"] += time.perf_counter() - t_swap
         _progress("local sweeps")
-        # the logical qubits living on these two physical bits trade places
-        la, lb = self.perm.index(gbit), self.perm.index(lbit)
-        self.perm[la], self.perm[lb] = lbit, gbit
+        # the logical qubits living on each pair of physical bits trade places
+        for lbit, gbit in pairs:
+            la, lb_ = self.perm.index(gbit), self.perm.index(lbit)
+            self.perm[la], self.perm[lb_] = lbit, gbit
+        ebytes = 8 if (real or stored_real) else 16
         self.stats["swaps"] += 1
-        self.stats["bytes_sent"] += half * (8 if (real or stored_real) else 16)
+        self.stats["exchange_bits"] += k
+        self.stats["bytes_sent"] += nb * bsize * ebytes
+        self.stats["link_bytes"] += bsize * ebytes
         self.stats["real_exchanges"] += 1 if (real or stored_real) else 0
         self.stats["pieces"] += P
 
@@ -466,7 +556,9 @@ class ShardedStatevector:
         sequence (else scanned); ``swap``: what performs an exchange (default: the real one; the planner records instead)"""
         import bisect
         lmask = self._local_mask()
-        swap = swap or self._swap
+        swap = swap or self._swap_bits
+        if self.max_exchange_bits > 1:
+            return self._localise_multi(x_logical_seq, r, uses if uses is not None else self._use_lists(x_logical_seq, self.n), swap)
         while True:
             xp = self._phys(x_logical_seq[r])
             xg = xp & ~lmask
@@ -494,7 +586,41 @@ class ShardedStatevector:
                     best, best_next = lbit, nxt
             if best is None:
                 raise ValueError("rotation touches more qubits than fit in one shard")
-            swap(gbit, best)
+            swap([gbit], [best])
+
+    def _localise_multi(self, x_logical_seq, r, uses, swap):
+        """``_localise`` with exchanges of up to ``max_exchange_bits`` bits.  A k-bit exchange puts S/2^k on each of 2^k - 1 links
+        where k half-shard exchanges put S/2 on one link k times, so the exchange that serves rotation r also brings in every global
+        qubit that is needed sooner than a local qubit it can send away: the new global set is the g qubits outside r's x mask whose
+        next X/Y use is farthest (never again = farthest; ties stay where they are — qubits global now first —, then the qubit on the
+        highest physical bit: high local bits leave the longest contiguous runs to pack and unpack).  More
+        moves than one exchange may trade: the qubits rotation r needs first, then those needed soonest, against the farthest local
+        ones; the rest is planned again while r still has a global X/Y qubit.  Depends on the rotation list and the permutation
+        only: the same plan on every rank."""
+        import bisect
+        lmask = self._local_mask()
+        x, R = int(x_logical_seq[r]), len(x_logical_seq)
+
+        def nxt(q):
+            u = uses[q]
+            i = bisect.bisect_right(u, r)
+            return u[i] if i < len(u) else R + 1
+
+        while True:
+            xp = self._phys(x)
+            if not xp & ~lmask:
+                return xp
+            cand = [q for q in range(self.n) if not (x >> q) & 1]
+            if len(cand) < self.g:
+                raise ValueError("rotation touches more qubits than fit in one shard")
+            is_global = [self.perm[q] >= self.n_local for q in range(self.n)]
+            cand.sort(key=lambda q: (-nxt(q), 0 if is_global[q] else 1, -self.perm[q]))
+            keep = set(cand[:self.g])
+            entering = [q for q in cand[:self.g] if not is_global[q]]                       # farthest next use first
+            leaving = sorted((q for q in range(self.n) if is_global[q] and q not in keep),
+                             key=lambda q: (0 if (x >> q) & 1 else 1, nxt(q), q))            # rotation r's own, then soonest
+            m = min(len(leaving), self.max_exchange_bits)
+            swap([self.perm[q] for q in leaving[:m]], [self.perm[q] for q in entering[:m]])
 
     # -- state ------------------------------------------------------------------------------
     def init_basis(self, logical_index):
@@ -537,7 +663,7 @@ class ShardedStatevector:
                                           np.array(batch_p, np.float64))
                 batch_x.clear(); batch_z.clear(); batch_p.clear()
 
-        uses = self._use_lists(xs, self.n) if len(xs) > 8 else None
+        uses = self._use_lists(xs, self.n) if (len(xs) > 8 or self.max_exchange_bits > 1) else None
         for r in range(len(xs)):
             if self._phys(xs[r]) & ~self._local_mask():
                 flush()  # the permutation is about to change: masks already queued used the old one
@@ -894,10 +1020,11 @@ class ShardedStatevector:
         uses = self._use_lists(xs, self.n)
         steps, batch = [], []
 
-        def record_swap(gbit, lbit):
-            la, lb = self.perm.index(gbit), self.perm.index(lbit)
-            self.perm[la], self.perm[lb] = lbit, gbit
-            steps.append(("swap", gbit, lbit))
+        def record_swap(gbits, lbits):
+            for gbit, lbit in zip(gbits, lbits):
+                la, lb = self.perm.index(gbit), self.perm.index(lbit)
+                self.perm[la], self.perm[lb] = lbit, gbit
+            steps.append(("swap", tuple(gbits), tuple(lbits)))
 
         def flush():
             if batch:
@@ -919,6 +1046,8 @@ class ShardedStatevector:
                     "phi0": None if rot_phi0 is None else np.asarray(rot_phi0, np.float64),
                     "hf": int(hf_index), "perm": final_perm, "real": all(bin(x & z).count("1") & 1 for x, z in zip(xs, zs)),
                     "swaps": sum(1 for st in steps if st[0] == "swap"), "ham": None,
+                    # bits per exchange, in order: exchange e puts S / 2^k_e on its busiest link and sends (1 - 2^-k_e) S in all
+                    "exchange_bits": [len(st[1]) for st in steps if st[0] == "swap"],
                     "n_params": int(np.asarray(rot_pidx, np.int64).max(initial=-1)) + 1}
             if hamiltonian is not None:
                 hx, hz, hc, const = hamiltonian
@@ -945,7 +1074,7 @@ class ShardedStatevector:
             phis = phis + prog["phi0"]
         for st in prog["steps"]:
             if st[0] == "swap":
-                self._swap(st[1], st[2])
+                self._swap_bits(st[1], st[2])
             else:
                 with self._compute("local_sweeps"):
                     self.engine.rotations(st[1], st[2], phis[st[3]])

@@ -125,7 +125,7 @@ class PartitionedStatevector:
 
     def program_info(self):
         prog = self._program()
-        return {"rotations": int(len(prog["coeff"])), "exchanges": int(prog["swaps"]), "real_stream": int(bool(prog["real"])),
+        return {"rotations": int(len(prog["coeff"])), "exchanges": int(prog["swaps"]), "exchange_bits": int(sum(prog["exchange_bits"])), "real_stream": int(bool(prog["real"])),
                 "partitioned_over": self.sharded.world}
 
     # -- the state of the ADAPT screens ------------------------------------------------------------------------------------------
