@@ -127,7 +127,7 @@ int ovqe_set_stream(ovqe_handle h, void *hip_stream);
  *
  * (B) GEOMETRY — defaults are the measured optimum on MI355X
  *   streaming path: "tile_bits" (-1 automatic: 12 for n >= 25, else 11; 0 = one sweep per op), "tile_low" (4), "apply_min_tiles" (256),
- *                     "index_streams"
+ *                     "index_streams"; "adjoint_tile_bits" (-1 automatic: 12 for n >= 25, else 11; 0 = one backward pass per run) of ovqe_adjoint_rotations
  *   fused / support-compacted kernels: "small_max_qubits", "small_batch_max_qubits", "sparse_grad" (1: all derivatives of a register of at most
  *                     16 qubits in one fused launch on the compact support; 0: the streaming adjoint pass), "sparse_renumber" (1)
  *   sector path: "sector_bits" / "sector_h_bits" (index bits per circuit / <H> tile, 0 automatic), "sector_tile_cap" (6500 amplitudes per
@@ -319,6 +319,22 @@ int ovqe_apply_exp_pauli_sum(ovqe_handle h, int64_t T, const uint64_t *x, const 
  * pass on them: forward circuit,
  * lambda = H psi from the materialised Hamiltonian, backward sweeps over the pair lists. */
 int ovqe_energy_gradient(ovqe_handle h, const double *theta, int32_t K, double *energy, double *grad);
+
+/* ---- backward step of the adjoint method on a (psi, lambda) pair the CALLER holds: what a partitioned register runs between
+ * its shard exchanges (openvqe_amd/distributed.py: program_energy_gradient), so that the exact Jacobian of
+ * ref:openvqe/ucc_family/get_energy_ucc.py:42-50 (the energy the optimiser differentiates) exists above one device.  Valid on plain
+ * handles and on shard handles (ovqe_create_shard: the shard's rank bits enter every z parity).
+ * R rotations exp(-i phi_r P_r) given in FORWARD order, masks on the handle's local bits (physical bit space), applied last to
+ * first to the handle's state psi and to lam_dev (2^n_local complex amplitudes, same layout):
+ *   w[r] = Im sum_i conj(lam_i) (P_r psi)_i  over this handle's amplitudes, on the states AFTER rotation r,
+ *   then psi <- U_r^+ psi, lam <- U_r^+ lam.
+ * Consecutive same-x runs whose x masks fit a tile are un-applied in ONE pass over both vectors (k_tile_adjoint: the psi and the
+ * lambda tile in LDS; option "adjoint_tile_bits": -1 automatic, 11 / 12 the tile size, 0 one pass per run of at most 16 rotations);
+ * ovqe_last_screen_support(which = 4 / 5) reports the passes and their bytes (64 per amplitude and pass).  The sums are reduced
+ * in a fixed order.  Synchronises before it returns.
+ * Refused under option "real_state" (OVQE_ERR_STATE) and when lam_dev is the state buffer. */
+int ovqe_adjoint_rotations(ovqe_handle h, void *lam_dev, int64_t R, const uint64_t *x, const uint64_t *z,
+                           const double *phi, double *w);
 
 /* ---- lowest eigenpair of the stored Hamiltonian (Lanczos on the device, two-pass: tridiagonal matrix, then the Ritz
  * vector by the same recurrence; random start vector from `seed`, so every symmetry sector is reached — the global

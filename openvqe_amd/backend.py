@@ -147,6 +147,17 @@ class Statevector:
         phis = np.ascontiguousarray(phis, np.float64)
         self._ck(self._L.ovqe_apply_pauli_rotations(self._h, xs.shape[0], xs, zs, phis))
 
+    def adjoint_rotations(self, lam_ptr, xs, zs, phis):
+        """backward step of the adjoint method (ovqe_adjoint_rotations): the rotations (forward order, local physical masks) are
+        un-applied last to first from the state and from the 2^n_local complex amplitudes at device pointer ``lam_ptr``
+        -> w[r] = Im <lam|P_r|psi> over this handle's amplitudes on the states after rotation r"""
+        xs = np.ascontiguousarray(xs, np.uint64)
+        zs = np.ascontiguousarray(zs, np.uint64)
+        phis = np.ascontiguousarray(phis, np.float64)
+        w = np.zeros(xs.shape[0], np.float64)
+        self._ck(self._L.ovqe_adjoint_rotations(self._h, ctypes.c_void_p(int(lam_ptr)), xs.shape[0], xs, zs, phis, w))
+        return w
+
     def rotate(self, op, qbits, phi):
         """exp(-i phi P) with P given as (pauli string, reference qubit list)."""
         x, z = pack_string(self.nbqbits, op, qbits)

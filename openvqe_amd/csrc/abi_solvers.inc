@@ -299,7 +299,8 @@ extern "C" int ovqe_energy_gradient(ovqe_handle h, const double *theta, int32_t 
     int rc = check_theta(h, theta, K);
     if (rc) return rc;
     if (!h->ham.set) return fail(h, OVQE_ERR_STATE, "no Hamiltonian set (ovqe_set_hamiltonian)");
-    if (h->n_global) return fail(h, OVQE_ERR_INVALID, "ovqe_energy_gradient is single-device");
+    if (h->n_global) return fail(h, OVQE_ERR_INVALID, "ovqe_energy_gradient is single-device: on a shard handle run the backward steps with ovqe_adjoint_rotations "
+                                                     "(openvqe_amd/distributed.py: program_energy_gradient)");
     FrameHamGuard frame_guard(h);
     {   // small registers: forward, H psi and the backward pass in one launch on the compact support
         bool done = false;
@@ -389,5 +390,103 @@ extern "C" int ovqe_energy_gradient(ovqe_handle h, const double *theta, int32_t 
         if (sr.pidx >= 0) grad[sr.pidx] += 2.0 * sr.coeff * ((sr.ny & 2) ? -w[r] : w[r]);
     }
     *energy = e.x + h->ham.constant;
+    return OVQE_OK;
+} OVQE_CATCH(h)
+
+// ---- backward step of the adjoint method on a caller-held (psi, lambda) pair: plain handles and shard handles -------------
+extern "C" int ovqe_adjoint_rotations(ovqe_handle h, void *lam_dev, int64_t R, const uint64_t *x, const uint64_t *z,
+                                      const double *phi, double *w) try {
+    OVQE_ENTER(h);
+    if (!h || R < 0 || !lam_dev || (R && (!x || !z || !phi || !w))) return OVQE_ERR_INVALID;
+    if (h->opt_real_state)
+        return fail(h, OVQE_ERR_STATE, "ovqe_adjoint_rotations works on complex amplitudes: clear \"real_state\" and widen the buffer first");
+    if (lam_dev == (void *)h->state) return fail(h, OVQE_ERR_STATE, "ovqe_adjoint_rotations: lam_dev is the state buffer");
+    if (R == 0) return OVQE_OK;
+    if (R >= (1ll << 30)) return fail(h, OVQE_ERR_INVALID, "too many rotations in one call");
+    const uint64_t lmask = local_mask(h);
+    const int ntot = h->n_local + h->n_global;
+    const uint64_t allmask = ntot >= 64 ? ~0ull : ((1ull << ntot) - 1ull);
+    for (int64_t r = 0; r < R; ++r) {
+        if ((x[r] | z[r]) & ~allmask) return fail(h, OVQE_ERR_INVALID, "Pauli mask has bits beyond the register");
+        if (x[r] & ~lmask)
+            return fail(h, OVQE_ERR_INVALID,
+                        "x mask touches global (rank) bits: exchange shards first (openvqe_amd/distributed.py)");
+    }
+    int rc = ensure_rp(h, (size_t)R);
+    if (rc) return rc;
+    for (int64_t r = 0; r < R; ++r) h->h_rp[r] = make_rot(x[r], z[r], phi[r]);
+    HIPC(h, hipMemcpyAsync(h->d_rp.p, h->h_rp, (size_t)R * sizeof(RotParam), hipMemcpyHostToDevice, h->stream));
+    // the op list of ovqe_apply_pauli_rotations (same-x runs), cut into tile segments for the BACKWARD kernel's tile size
+    std::vector<SmallOp> ops;
+    std::vector<SmallRot> rots((size_t)R);
+    for (int64_t r0 = 0; r0 < R;) {
+        int64_t r1 = r0 + 1;
+        while (r1 < R && x[r1] == x[r0]) ++r1;
+        SmallOp op = {};
+        op.x = x[r0];
+        op.kind = x[r0] ? OP_PAIR : OP_DIAG;
+        op.first = (int32_t)r0;
+        op.count = (int32_t)(r1 - r0);
+        op.pivot = x[r0] ? 63 - __builtin_clzll(x[r0]) : 0;
+        ops.push_back(op);
+        for (int64_t r = r0; r < r1; ++r) rots[(size_t)r].z = z[r];
+        r0 = r1;
+    }
+    TilePlan &tp = h->tp_adjoint;
+    const int M = adjoint_tile_bits(h);
+    if (M && ops.size() >= 2) {
+        rc = build_tile_plan(h, ops, rots, std::vector<uint64_t>(ops.size(), 0), tp, false, M, tile_adj_rot_cap(M));
+        if (rc) return rc;
+    } else {
+        tp.plan.assign(ops.size(), 0);
+        for (size_t i = 0; i < ops.size(); ++i) tp.plan[i] = -1 - (int32_t)i;
+    }
+    // partial sums per workgroup and rotation: the streaming kernels as in ovqe_energy_gradient, the tile kernel one grid per CU set
+    const int nb = (int)std::min<uint64_t>(65536, std::max<uint64_t>(1, (h->namps / 2 + 255) / 256));
+    const int tgrid = M ? adjoint_tile_grid(h, M) : 0;
+    rc = ensure(h, h->d_partials, std::max((size_t)ADJ_MAX_ROT * nb, (size_t)TILE_ROT_CAP * std::max(tgrid, 1)) * sizeof(double2));
+    DevBuf d_w;
+    if (!rc) rc = ensure(h, d_w, (size_t)R * sizeof(double));
+    if (rc) return rc;
+    amp_t *lam = (amp_t *)lam_dev;
+    double *partials = (double *)h->d_partials.p;
+    const RotParam *d_rp = (const RotParam *)h->d_rp.p;
+    int64_t passes = 0;
+    for (int si = (int)tp.plan.size() - 1; si >= 0 && !rc; --si) {
+        const int32_t step = tp.plan[si];
+        if (step >= 0) {
+            const TileSeg &sg = tp.tsegs[step];
+            rc = launch_tile_adjoint(h, lam, tp, sg, partials, tgrid);
+            if (!rc)
+                hipLaunchKernelGGL(k_reduce_rows, dim3(sg.rot1 - sg.rot0), dim3(256), 0, h->stream, (const double *)partials, tgrid,
+                                   (double *)d_w.p + sg.rot0);
+            ++passes;
+            continue;
+        }
+        const SmallOp &op = ops[-1 - step];
+        for (int hi = op.count; hi > 0; hi -= ADJ_MAX_ROT) {  // chunks from the end of the run backwards
+            const int lo = std::max(0, hi - ADJ_MAX_ROT), cnt = hi - lo;
+            if (op.kind == OP_PAIR)
+                hipLaunchKernelGGL(k_adjoint_pairs, dim3(nb), dim3(256), 0, h->stream, h->state, lam, h->namps >> 1, op.pivot, op.x,
+                                   h->base, d_rp + op.first + lo, cnt, partials);
+            else
+                hipLaunchKernelGGL(k_adjoint_diag, dim3(nb), dim3(256), 0, h->stream, h->state, lam, h->namps, h->base,
+                                   d_rp + op.first + lo, cnt, partials);
+            hipLaunchKernelGGL(k_reduce_rows, dim3(cnt), dim3(256), 0, h->stream, (const double *)partials, nb,
+                               (double *)d_w.p + op.first + lo);
+            ++passes;
+        }
+    }
+    if (!rc && hipGetLastError() != hipSuccess) rc = fail(h, OVQE_ERR_HIP, "adjoint_rotations: launch failed");
+    if (!rc && hipMemcpyAsync(w, d_w.p, (size_t)R * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+        rc = fail(h, OVQE_ERR_HIP, "adjoint_rotations: copy failed");
+    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(h, OVQE_ERR_HIP, "adjoint_rotations: sync failed");
+    if (d_w.p) (void)hipFree(d_w.p);
+    if (rc) return rc;
+    // the kernels sum Re (odd ny) / Im (even ny) of sum_i s_i conj(lam_i) psi_j; <lam|P|psi> carries i^ny on top
+    for (int64_t r = 0; r < R; ++r)
+        if (__builtin_popcountll(x[r] & z[r]) & 2) w[r] = -w[r];
+    h->last_passes = passes;                                 // every pass reads and writes psi and lam once
+    h->last_pass_bytes = (int64_t)(64.0 * (double)h->namps * (double)passes);
     return OVQE_OK;
 } OVQE_CATCH(h)

@@ -449,6 +449,9 @@ struct ovqe_sv {
     int opt_real_stream = 1;      // streaming energies of such programs keep the state as 2^n doubles
     HamDev ham_real;              // tile cover of the stored Hamiltonian for the real-amplitude state
     TilePlan tp_adhoc;            // of the rotation list of the current ovqe_apply_pauli_rotations call
+    TilePlan tp_adjoint;          // of the rotation list of the current ovqe_adjoint_rotations call (cut for k_tile_adjoint)
+    int opt_adjoint_tile_bits = -1;  // -1: automatic (12 for n >= 25, else 11); 11 / 12: tile size of k_tile_adjoint; 0: k_adjoint_pairs / k_adjoint_diag only
+    int num_cus = 0;              // compute units of the device (first use)
     std::vector<CrossSum *> xsums;   // ovqe_xsum_create (slots of destroyed sums are nullptr)
 };
 
@@ -1152,7 +1155,7 @@ int ovqe_destroy(ovqe_handle h) try {
                                   &h->d_theta, &h->d_energies, &h->d_workspace, &h->d_egroups, &h->d_eterms, &h->d_echunks,
                                   &h->d_eflat, &h->d_sp_ops, &h->d_sp_rows, &h->d_sp_rows64, &h->d_sp_prim, &h->d_sp_pairs, &h->d_sp_entries, &h->d_pg_off, &h->d_pg_xs, &h->d_pg_terms, &h->d_pg_runs, &h->d_pg_tabs,
                                   &h->d_pg_out, &h->d_pg_part, &h->d_nz_cnt, &h->d_nz_start, &h->d_nz_idx, &h->d_nz_val, &h->d_nz_bitmap, &h->d_exp_groups, &h->d_exp_terms, &h->d_tile_smasks, &h->d_tile_lists, &h->d_tile_counts, &h->cc.d_sup, &h->cc.d_psic, &h->cc.d_loc, &h->cc.d_cid, &h->cc.d_off, &h->cc.d_sweeps};
-    for (TilePlan *tp : {&h->tp, &h->tp_adhoc, &h->tp_real}) bufs.insert(bufs.end(), {&tp->d_tops, &tp->d_trots});
+    for (TilePlan *tp : {&h->tp, &h->tp_adhoc, &h->tp_real, &h->tp_adjoint}) bufs.insert(bufs.end(), {&tp->d_tops, &tp->d_trots});
     for (HamDev *H : {&h->ham, &h->ham_adhoc, &h->ham_real, &h->ham_conj})
         bufs.insert(bufs.end(), {&H->d_groups, &H->d_terms, &H->d_tchunks, &H->d_tgroups, &H->d_tterms, &H->d_tflats,
                                  &H->d_titems, &H->d_rest, &H->d_achunks, &H->d_agroups, &H->d_aterms, &H->d_dzin, &H->d_doff, &H->d_dterms});
@@ -1282,6 +1285,7 @@ int ovqe_set_option(ovqe_handle h, const char *name, int64_t value) try {
     else if (k == "fault_inject") h->fault_inject = (int)value;
 #endif
     else if (k == "real_stream") h->opt_real_stream = (int)value;
+    else if (k == "adjoint_tile_bits") h->opt_adjoint_tile_bits = (int)value;
     else if (k == "apply_min_tiles") h->opt_apply_min_tiles = (int)value;
     else if (k == "clifford_frame") h->opt_clifford_frame = (int)value;  // applies to the next ovqe_set_gate_program
     else if (k == "tile_bits" || k == "tile_low") {

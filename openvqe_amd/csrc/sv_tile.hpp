@@ -159,6 +159,194 @@ __global__ __launch_bounds__(NT) void k_tile_sweep(void *__restrict__ st, uint64
     }
 }
 
+// ---- backward twin of k_tile_sweep: the adjoint method on tiles (ovqe_adjoint_rotations) ---------------------------------
+// One segment of the plan, its ops LAST to first, on psi and lam together: the psi tile and the lam tile of the same index
+// set lie in LDS (2 x 16 B x 2^M, both bank-swizzled like the forward tile); per op every thread holds its pairs of both
+// vectors in registers (2^M / 2 / NT pairs: 4 at M = 12) and walks the run's rotations backwards — for rotation r first
+//   w_r += sum_pairs [ s_i conj(lam_i) psi_j + s_j conj(lam_j) psi_i ]      (real part for odd ny, imaginary for even:
+//                                                                            k_adjoint_pairs' convention, sv_kernels.hpp)
+// then psi <- U_r^+ psi, lam <- U_r^+ lam.  A segment holds up to tile_adj_rot_cap(M) rotations, so the sums cannot live in
+// registers: each rotation's pairs are summed over the wave (DPP, no LDS crossbar) as its op is processed, and lane 63
+// adds the wave's sum to the wave's own slot of an LDS table (waves x rotations doubles: no two writers per slot).
+// The grid is sized to the CUs and a workgroup walks tiles blockIdx.x, blockIdx.x + gridDim.x, ...: the slots accumulate
+// over all of them in a fixed order, and ONE partial per (workgroup, rotation) leaves the kernel —
+// partials[(r - rot0) * gridDim.x + blockIdx.x], reduced by k_reduce_rows.  No atomics: the result is reproducible.
+// The z bits of a rotation outside the tile are a per-tile sign of sin (folded into the LDS table, as in the forward
+// kernel) AND of the rotation's sum (RotLds::pad).
+constexpr int TILE_ADJ_LOG_NT = 9;
+// rotations per backward segment: two 2^11 tiles + the tables of 128 rotations are 76 KiB (two workgroups per CU), two 2^12
+// tiles + the tables of 256 are 152 KiB of the 160 KiB (one)
+constexpr int tile_adj_rot_cap(int m) { return m >= 12 ? TILE_ROT_CAP : TILE_ROT_CAP / 2; }
+
+template <int M, int NT, bool NTL>
+__global__ __launch_bounds__(NT) void k_tile_adjoint(amp_t *__restrict__ psi, amp_t *__restrict__ lam, uint64_t base,
+                                                     uint32_t ntiles, TileSeg seg, const TileOp *__restrict__ ops,
+                                                     const TileRot *__restrict__ trot, const RotParam *__restrict__ rp,
+                                                     double *__restrict__ partials) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr uint32_t NEL = 1u << M;
+    constexpr int TRIPS = NEL / NT;       // amplitudes per thread and vector
+    constexpr int PP = NEL / 2 / NT;      // pairs per thread
+    constexpr int NW = NT / 64;
+    constexpr int CAP = tile_adj_rot_cap(M);
+    double2 *tp = reinterpret_cast<double2 *>(smem);   // psi tile, element e at tile_swz_v(e)
+    double2 *tl = tp + NEL;                            // lam tile
+    RotLds *tab = reinterpret_cast<RotLds *>(tl + NEL);
+    double *wacc = reinterpret_cast<double *>(tab + CAP);   // [NW][CAP]
+    v2d *gp = reinterpret_cast<v2d *>(psi), *gl = reinterpret_cast<v2d *>(lam);
+    const int nrot = seg.rot1 - seg.rot0;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t lane = threadIdx.x & 63u;
+    double *wmine = wacc + wave * CAP;
+    for (int r = (int)threadIdx.x; r < NW * CAP; r += NT) wacc[r] = 0.0;
+    const uint64_t glow = spread_bits(threadIdx.x, seg.mask_lo);
+
+    for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        uint64_t tb = t;
+        for (uint64_t mk = seg.smask; mk; mk &= mk - 1ull) tb = insert_zero(tb, __ffsll((long long)mk) - 1);
+        const uint64_t gbase = base | tb;
+        v2d rpsi[TRIPS], rlam[TRIPS];
+#pragma unroll
+        for (int j = 0; j < TRIPS; ++j) {
+            const uint64_t g = tb | glow | spread_bits((uint32_t)j, seg.mask_hi);
+            rpsi[j] = NTL ? __builtin_nontemporal_load(&gp[g]) : gp[g];
+            rlam[j] = NTL ? __builtin_nontemporal_load(&gl[g]) : gl[g];
+        }
+        __syncthreads();   // the previous tile has left LDS (and the accumulators are zeroed)
+        for (int r = seg.rot0 + (int)threadIdx.x; r < seg.rot1; r += NT) {
+            const RotParam rr = rp[r];
+            const TileRot tr = trot[r];
+            const bool neg = parity64(gbase & tr.zout);
+            RotLds rl;
+            rl.c = rr.c;
+            rl.s = neg ? -rr.s : rr.s;
+            rl.z = tr.zin;
+            rl.odd = (uint32_t)rr.odd;
+            rl.pad = neg ? 1ull : 0ull;
+            tab[r - seg.rot0] = rl;
+        }
+#pragma unroll
+        for (int j = 0; j < TRIPS; ++j) {
+            const uint32_t e = tile_swz_v(threadIdx.x + j * NT);
+            tp[e] = make_double2(rpsi[j].x, rpsi[j].y);
+            tl[e] = make_double2(rlam[j].x, rlam[j].y);
+        }
+        __syncthreads();
+
+        for (int o = seg.op1 - 1; o >= seg.op0; --o) {
+            const TileOp top = ops[o];
+            const RotLds *rt = tab + (top.first - seg.rot0);
+            double *wr = wmine + (top.first - seg.rot0);
+            if (top.kind == OP_PAIR) {
+                const uint32_t x = top.x, low = (1u << top.pivot) - 1u;
+                uint32_t ii[PP];
+                double2 u[PP], v[PP], lu[PP], lv[PP];
+#pragma unroll
+                for (int m = 0; m < PP; ++m) {
+                    ii[m] = insert_zero32(threadIdx.x + m * NT, low);
+                    const uint32_t ei = tile_swz_v(ii[m]), ej = tile_swz_v(ii[m] ^ x);
+                    u[m] = tp[ei];
+                    v[m] = tp[ej];
+                    lu[m] = tl[ei];
+                    lv[m] = tl[ej];
+                }
+                for (int r = top.count - 1; r >= 0; --r) {
+                    const RotLds rl = rt[r];
+                    double part = 0.0;
+#pragma unroll
+                    for (int m = 0; m < PP; ++m) {
+                        const int pi = __popc(ii[m] & rl.z) & 1, pj = pi ^ (int)rl.odd;
+                        const double gi = pj ? -1.0 : 1.0, gj = pi ? -1.0 : 1.0;
+                        // t = s_i conj(lam_i) psi_j + s_j conj(lam_j) psi_i
+                        if (rl.odd)
+                            part += gi * (lu[m].x * v[m].x + lu[m].y * v[m].y) + gj * (lv[m].x * u[m].x + lv[m].y * u[m].y);
+                        else
+                            part += gi * (lu[m].x * v[m].y - lu[m].y * v[m].x) + gj * (lv[m].x * u[m].y - lv[m].y * u[m].x);
+                        const double si = pj ? rl.s : -rl.s, sj = pi ? rl.s : -rl.s;   // U^+ = exp(+i phi P): sin negated
+                        if (rl.odd) {
+                            mix_real(u[m].x, v[m].x, rl.c, si, sj);
+                            mix_real(u[m].y, v[m].y, rl.c, si, sj);
+                            mix_real(lu[m].x, lv[m].x, rl.c, si, sj);
+                            mix_real(lu[m].y, lv[m].y, rl.c, si, sj);
+                        } else {
+                            const double ux = rl.c * u[m].x + si * v[m].y, uy = rl.c * u[m].y - si * v[m].x;
+                            const double vx = rl.c * v[m].x + sj * u[m].y, vy = rl.c * v[m].y - sj * u[m].x;
+                            u[m] = make_double2(ux, uy);
+                            v[m] = make_double2(vx, vy);
+                            const double lx = rl.c * lu[m].x + si * lv[m].y, ly = rl.c * lu[m].y - si * lv[m].x;
+                            const double mx = rl.c * lv[m].x + sj * lu[m].y, my = rl.c * lv[m].y - sj * lu[m].x;
+                            lu[m] = make_double2(lx, ly);
+                            lv[m] = make_double2(mx, my);
+                        }
+                    }
+                    part = sec_wave_sum63(part);
+                    if (lane == 63u) wr[r] += rl.pad ? -part : part;
+                }
+#pragma unroll
+                for (int m = 0; m < PP; ++m) {
+                    const uint32_t ei = tile_swz_v(ii[m]), ej = tile_swz_v(ii[m] ^ x);
+                    tp[ei] = u[m];
+                    tp[ej] = v[m];
+                    tl[ei] = lu[m];
+                    tl[ej] = lv[m];
+                }
+            } else {   // OP_DIAG: w_r = sum_i Im[ s_i conj(lam_i) psi_i ]; un-rotation a <- (c + i s sigma) a
+                double2 a[TRIPS], l[TRIPS];
+#pragma unroll
+                for (int j = 0; j < TRIPS; ++j) {
+                    const uint32_t e = tile_swz_v(threadIdx.x + j * NT);
+                    a[j] = tp[e];
+                    l[j] = tl[e];
+                }
+                for (int r = top.count - 1; r >= 0; --r) {
+                    const RotLds rl = rt[r];
+                    double part = 0.0;
+#pragma unroll
+                    for (int j = 0; j < TRIPS; ++j) {
+                        const bool odd = __popc((threadIdx.x + j * NT) & rl.z) & 1;
+                        const double im = l[j].x * a[j].y - l[j].y * a[j].x;
+                        part += odd ? -im : im;
+                        const double s = odd ? rl.s : -rl.s;   // forward: (c - i s sg) a
+                        a[j] = make_double2(rl.c * a[j].x + s * a[j].y, rl.c * a[j].y - s * a[j].x);
+                        l[j] = make_double2(rl.c * l[j].x + s * l[j].y, rl.c * l[j].y - s * l[j].x);
+                    }
+                    part = sec_wave_sum63(part);
+                    if (lane == 63u) wr[r] += rl.pad ? -part : part;
+                }
+#pragma unroll
+                for (int j = 0; j < TRIPS; ++j) {
+                    const uint32_t e = tile_swz_v(threadIdx.x + j * NT);
+                    tp[e] = a[j];
+                    tl[e] = l[j];
+                }
+            }
+            __syncthreads();
+        }
+
+#pragma unroll
+        for (int j = 0; j < TRIPS; ++j) {
+            const uint32_t e = tile_swz_v(threadIdx.x + j * NT);
+            const double2 a = tp[e], l = tl[e];
+            const v2d va = {a.x, a.y}, vl = {l.x, l.y};
+            const uint64_t g = tb | glow | spread_bits((uint32_t)j, seg.mask_hi);
+            if (NTL) {
+                __builtin_nontemporal_store(va, &gp[g]);
+                __builtin_nontemporal_store(vl, &gl[g]);
+            } else {
+                gp[g] = va;
+                gl[g] = vl;
+            }
+        }
+    }
+    __syncthreads();
+    for (int r = (int)threadIdx.x; r < nrot; r += NT) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) s += wacc[w * CAP + r];
+        partials[(size_t)r * gridDim.x + blockIdx.x] = s;
+    }
+}
+
 // ---- <psi|H|psi> on tiles --------------------------------------------------------------------------------
 // The x-groups of a Hermitian Pauli sum are covered by tile bit sets: every group whose x mask lies inside the sweep's
 // set S is evaluated from the LDS copy of the tile (E_g = 2 Re sum_pairs D(j) conj(a_i) a_j, the pair trick of

@@ -843,20 +843,76 @@ int launch_tile_segment(ovqe_handle h, const TilePlan &tp, const TileSeg &sg, bo
     return fail(h, OVQE_ERR_INVALID, "corrupt tile segment");
 }
 
+// backward twin (k_tile_adjoint): psi and lam tiles of 2^M amplitudes, a grid sized to the CUs whose workgroups walk the tiles
+// (adjoint_tile_grid) -> partials[(r - sg.rot0) * grid + workgroup]
+inline int adjoint_tile_bits(ovqe_handle h) {
+    const int m = h->opt_adjoint_tile_bits >= 0 ? h->opt_adjoint_tile_bits : (h->n_local >= 25 ? 12 : 11);
+    return (m == 11 || m == 12) && h->n_local >= m + 2 ? m : 0;   // 0: the streaming kernels only
+}
+inline int adjoint_tile_grid(ovqe_handle h, int m) {
+    if (h->num_cus <= 0) {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus <= 0) cus = 256;
+        h->num_cus = cus;
+    }
+    return (int)std::min<uint64_t>(h->namps >> m, (uint64_t)h->num_cus * (m >= 12 ? 1 : 2));
+}
+template <int M>
+int launch_tile_adjoint_m(ovqe_handle h, amp_t *lam, const TilePlan &tp, const TileSeg &sg, double *partials, int grid) {
+    constexpr int NT = 1 << TILE_ADJ_LOG_NT;
+    constexpr int CAP = tile_adj_rot_cap(M);
+    const size_t smem = ((size_t)32 << M) + CAP * sizeof(RotLds) + (size_t)(NT / 64) * CAP * sizeof(double);
+    const bool ntl = h->n_local >= 25;
+    static bool attr_done_dev[64] = {};  // function attributes are per device
+    bool &attr_done = attr_done_dev[h->device & 63];
+    if (!attr_done) {
+        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_adjoint<M, NT, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_adjoint<M, NT, false>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        attr_done = true;
+    }
+    const uint32_t ntiles = (uint32_t)(h->namps >> M);
+    if (ntl) {
+        hipLaunchKernelGGL((k_tile_adjoint<M, NT, true>), dim3((unsigned)grid), dim3(NT), smem, h->stream, h->state, lam, h->base,
+                           ntiles, sg, (const TileOp *)tp.d_tops.p, (const TileRot *)tp.d_trots.p, (const RotParam *)h->d_rp.p,
+                           partials);
+    } else {
+        hipLaunchKernelGGL((k_tile_adjoint<M, NT, false>), dim3((unsigned)grid), dim3(NT), smem, h->stream, h->state, lam, h->base,
+                           ntiles, sg, (const TileOp *)tp.d_tops.p, (const TileRot *)tp.d_trots.p, (const RotParam *)h->d_rp.p,
+                           partials);
+    }
+    HIPC(h, hipGetLastError());
+    return OVQE_OK;
+}
+
+int launch_tile_adjoint(ovqe_handle h, amp_t *lam, const TilePlan &tp, const TileSeg &sg, double *partials, int grid) {
+    for (int o = sg.op0; o < sg.op1; ++o)
+        if (tp.tops[o].kind != OP_PAIR && tp.tops[o].kind != OP_DIAG) return fail(h, OVQE_ERR_INVALID, "corrupt tile segment");
+    switch (__builtin_popcountll(sg.smask)) {
+    case 11: return launch_tile_adjoint_m<11>(h, lam, tp, sg, partials, grid);
+    case 12: return launch_tile_adjoint_m<12>(h, lam, tp, sg, partials, grid);
+    }
+    return fail(h, OVQE_ERR_INVALID, "corrupt tile segment");
+}
+
 // Greedy segmentation of the (table-fused) program into tile sweeps: consecutive ops are taken while the union of
 // their mixing bits (x mask / gate target) and the mandatory low bits fits the tile; ops that do not fit, and
 // segments of a single op, keep their own full-bandwidth sweep.  Commuting runs enter a tile in their OP_TAB form
 // (one rotation per active pair pattern, see try_table_op): inside a fused sweep the arithmetic, not HBM, is the
 // cost, and the table form does 1/64 of it for a JW double excitation.
+// ``tile_m`` > 0: cut for a kernel with tiles of 2^tile_m amplitudes and ``rot_cap`` table entries instead of the forward
+// sweep's (the backward kernel keeps two tiles in LDS: launch_tile_adjoint).
 int build_tile_plan(ovqe_handle h, const std::vector<SmallOp> &sops, const std::vector<SmallRot> &srots,
-                    const std::vector<uint64_t> &sop_zc, TilePlan &tp, bool real = false) {
+                    const std::vector<uint64_t> &sop_zc, TilePlan &tp, bool real = false, int tile_m = 0,
+                    int rot_cap = TILE_ROT_CAP) {
     tp.tsegs.clear();
     tp.tops.clear();
     tp.trots.assign(srots.size(), TileRot{0, 0, 0});
     tp.plan.clear();
-    const int M = tile_bits(h, real);
+    const int M = tile_m > 0 ? tile_m : tile_bits(h, real);
     const int nops = (int)sops.size();
-    const bool tiled = tile_ok(h, real);
+    const bool tiled = tile_m > 0 ? (h->n_local >= M + 2 && h->opt_tile_low >= 0 && h->opt_tile_low <= 8) : tile_ok(h, real);
     if (!tiled) {
         for (int i = 0; i < nops; ++i) tp.plan.push_back(-1 - i);
         return OVQE_OK;
@@ -880,7 +936,7 @@ int build_tile_plan(ovqe_handle h, const std::vector<SmallOp> &sops, const std::
             const SmallOp &op = sops[j];
             const uint64_t nb = S | need(op);
             if (__builtin_popcountll(nb) > M) break;
-            if (is_rot(op) && nrot + op.count > TILE_ROT_CAP) break;
+            if (is_rot(op) && nrot + op.count > rot_cap) break;
             if (is_rot(op)) nrot += op.count;
             S = nb;
             ++j;

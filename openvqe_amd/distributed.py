@@ -29,6 +29,11 @@ The ADAPT gradient screen shards the same way (``apply_hamiltonian`` builds the 
 group, ``pool_gradients`` contracts the pool per partner shard in one batched launch each, one
 all-reduce of the pool-sized result).  Exchanges travel in pipelined pieces.  No other
 collective exists on the data path.
+
+Exact gradient (``program_energy_gradient``): the adjoint method on shards — forward plan, lambda = H psi sharded like psi,
+then the plan's steps in reverse on psi AND lambda: a rotation step is one ``ovqe_adjoint_rotations`` call per shard (local
+sums w_r, both vectors un-rotated), an exchange step the same k-bit exchange for both vectors (a swap of disjoint bit pairs is
+its own inverse); one all-reduce of the R sums at the end.
 """
 from __future__ import annotations
 
@@ -123,7 +128,7 @@ class HipShardEngine:
         # what the local kernels really did: passes over the shard (launches that stream it) and the bytes they move by
         # construction — fused same-x runs and LDS-tiled multi-run sweeps make this smaller than one sweep per rotation
         self.counters = {"rotations": 0, "rotation_passes": 0, "rotation_bytes": 0, "contraction_calls": 0, "contraction_passes": 0,
-                         "contraction_bytes": 0}
+                         "contraction_bytes": 0, "adjoint_passes": 0, "adjoint_bytes": 0}
 
     def check_stream(self):
         if torch.cuda.current_stream(self.device).cuda_stream != self.stream.cuda_stream:
@@ -182,6 +187,24 @@ class HipShardEngine:
     def rotations(self, xs, zs, phis):
         self.sv.apply_pauli_rotations(xs, zs, phis)
         self._count("rotation", self.sv, len(xs))
+
+    def adjoint_rotations(self, lam, xs, zs, phis):
+        """backward step of the adjoint method on the shard and on ``lam`` (a shard-sized complex buffer): the rotations are
+        un-applied last to first from both -> the local sums w[r] = Im <lam|P_r|psi> (``ovqe_adjoint_rotations``)"""
+        w = self.sv.adjoint_rotations(lam.data_ptr(), xs, zs, phis)
+        passes, nbytes = self.sv.last_passes()
+        self.counters["adjoint_passes"] += passes
+        self.counters["adjoint_bytes"] += nbytes
+        return w
+
+    def set_tensor(self, tensor):
+        """make another shard-sized complex buffer the shard the handle works on (the exchange of lambda in the backward pass:
+        pack / unpack read and write the handle's state); the previous buffer stays with the caller"""
+        if tensor.dtype != torch.complex128 or tensor.numel() != self.tensor.numel() or self.is_real:
+            raise ValueError("set_tensor: a complex buffer of the shard's size on a complex shard")
+        self.sync()
+        self.tensor = tensor
+        self.sv.adopt_state(tensor.data_ptr())
 
     def bilinear_batch(self, offsets, xs, zs, coeffs, bra, ket=None):
         return self.sv.bilinear_batch(offsets, xs, zs, coeffs, bra_ptr=bra.data_ptr(),
@@ -276,7 +299,8 @@ class ShardedStatevector:
                       # at once, each over its own link), and the sum of the bits traded
                       "link_bytes": 0, "exchange_bits": 0,
                       # seconds this rank's kernels ran, by phase (each section ends with a device synchronisation)
-                      "local_sweeps_s": 0.0, "expectation_local_s": 0.0, "expectation_remote_s": 0.0, "apply_s": 0.0}
+                      "local_sweeps_s": 0.0, "expectation_local_s": 0.0, "expectation_remote_s": 0.0, "apply_s": 0.0,
+                      "adjoint_sweeps_s": 0.0}
         # Several ranks on ONE device (the gloo runs of the tests and of bench.py's single-device mode) would time each other's
         # kernels: with a lock file every compute section takes the device alone (flock), so its seconds are this rank's own
         self.compute_lock = None
@@ -443,7 +467,13 @@ class ShardedStatevector:
         else:
             self.engine.tensor[self._block_index(mask, block, first, count)] = torch.complex(src, torch.zeros_like(src)) if real else src
 
-    def _swap_bits(self, gbits, lbits):
+    def _set_engine_tensor(self, tensor):
+        if hasattr(self.engine, "set_tensor"):
+            self.engine.set_tensor(tensor)
+        else:
+            self.engine.tensor = tensor
+
+    def _swap_bits(self, gbits, lbits, also=None):
         """exchange the k physical global bits ``gbits`` with the k physical local bits ``lbits`` (pairwise) in one step: an all-to-all
         among the 2^k ranks of the sub-cube that ``gbits`` span.  The local bits split the shard into 2^k blocks; the rank with
         sub-cube coordinate a (its values on ``gbits``) keeps block a where it is and sends block b to the rank with coordinate b,
@@ -451,7 +481,10 @@ class ShardedStatevector:
         over one link k times.  A block travels in EXCHANGE_PIECES pieces; the pieces p of all partners are posted as one batch, and
         EXCHANGE_DEPTH batches are in flight: pack p + 1 and unpack p - 1 run while batch p is on the links.  Block b is received
         into scratch (its slot is the one being sent to b) and unpacked when its own piece has been packed: scratch is
-        2 x EXCHANGE_DEPTH x (2^k - 1) pieces, (1 - 2^-k) S / 2 at the default sizes.  k = 1 is the half-shard exchange."""
+        2 x EXCHANGE_DEPTH x (2^k - 1) pieces, (1 - 2^-k) S / 2 at the default sizes.  k = 1 is the half-shard exchange.
+        ``also``: a second shard-sized buffer (lambda of the backward pass) that makes the same move right after the shard, as the
+        engine's tensor for the duration of its run, through the same scratch: ONE exchange step — the permutation and
+        stats["swaps"] advance once, the bytes count both vectors."""
         k = len(gbits)
         pairs = sorted(zip(lbits, gbits))               # block values count the local bits in ascending order
         lb, gb = [p[0] for p in pairs], [p[1] for p in pairs]
@@ -476,6 +509,8 @@ class ShardedStatevector:
         piece = max(cuts[p + 1] - cuts[p] for p in range(P))
         stored_real = self._storage_real()             # float64 shards travel as they are
         real = self.real and self.real_transfers and not stored_real     # (the same on every rank: the flag follows the rotation list)
+        if also is not None and (real or stored_real):
+            raise ValueError("a second vector travels with a complex shard only")
         # a block that is contiguous in the shard (the top local bits) is sent from where it lies
         in_place = mask == ((1 << k) - 1) << (self.n_local - k) and not real
         depth = max(1, min(self.EXCHANGE_DEPTH, P))
@@ -516,14 +551,24 @@ class ShardedStatevector:
                 self._unpack(mask, b, first, count, recv_sets[p % depth][i][:count], real)
             _progress()
 
-        pending = []
-        for p in range(P):
-            pending.append((p, post(p)))
-            if len(pending) == depth:        # the buffers of this set are used again by piece p + 1
+        def move():
+            pending = []
+            for p in range(P):
+                pending.append((p, post(p)))
+                if len(pending) == depth:        # the buffers of this set are used again by piece p + 1
+                    arrived(*pending.pop(0))
+            while pending:
                 arrived(*pending.pop(0))
-        while pending:
-            arrived(*pending.pop(0))
-        self.engine.sync()
+            self.engine.sync()
+
+        move()
+        if also is not None:
+            shard = self.engine.tensor
+            self._set_engine_tensor(also)
+            try:
+                move()
+            finally:
+                self._set_engine_tensor(shard)
         self.stats["swap_s"] += time.perf_counter() - t_swap
         _progress("local sweeps")
         # the logical qubits living on each pair of physical bits trade places
@@ -531,12 +576,13 @@ class ShardedStatevector:
             la, lb_ = self.perm.index(gbit), self.perm.index(lbit)
             self.perm[la], self.perm[lb_] = lbit, gbit
         ebytes = 8 if (real or stored_real) else 16
+        vectors = 1 if also is None else 2
         self.stats["swaps"] += 1
         self.stats["exchange_bits"] += k
-        self.stats["bytes_sent"] += nb * bsize * ebytes
-        self.stats["link_bytes"] += bsize * ebytes
+        self.stats["bytes_sent"] += vectors * nb * bsize * ebytes
+        self.stats["link_bytes"] += vectors * bsize * ebytes
         self.stats["real_exchanges"] += 1 if (real or stored_real) else 0
-        self.stats["pieces"] += P
+        self.stats["pieces"] += vectors * P
 
     @staticmethod
     def _use_lists(x_logical_seq, n):
@@ -1056,6 +1102,17 @@ class ShardedStatevector:
             self.perm = saved
         return prog
 
+    @staticmethod
+    def _program_angles(prog, theta):
+        """rotation r: exp(-i (coeff_r theta[pidx_r] + phi0_r) P_r); pidx_r < 0: a constant angle — phi0_r when the program carries
+        constants (ovqe_set_program's convention), else coeff_r"""
+        pidx = prog["pidx"]
+        fixed = 1.0 if prog.get("phi0") is None else 0.0
+        phis = prog["coeff"] * (np.where(pidx >= 0, theta[np.maximum(pidx, 0)], fixed) if theta.size else fixed)
+        if prog.get("phi0") is not None:
+            phis = phis + prog["phi0"]
+        return phis
+
     def run_program(self, prog, theta):
         """|hf> -> the program's state at ``theta`` (the plan's exchanges and local sweeps; no planning)"""
         theta = np.asarray(theta, np.float64).reshape(-1)
@@ -1065,13 +1122,7 @@ class ShardedStatevector:
         self._choose_storage(prog["real"])
         self.init_basis(prog["hf"])
         self.real = prog["real"]      # (a list with one even-Y string anywhere travels complex from the start: the flag is per program)
-        pidx = prog["pidx"]
-        # rotation r: exp(-i (coeff_r theta[pidx_r] + phi0_r) P_r); pidx_r < 0: a constant angle — phi0_r when the program carries
-        # constants (ovqe_set_program's convention), else coeff_r
-        fixed = 1.0 if prog.get("phi0") is None else 0.0
-        phis = prog["coeff"] * (np.where(pidx >= 0, theta[np.maximum(pidx, 0)], fixed) if theta.size else fixed)
-        if prog.get("phi0") is not None:
-            phis = phis + prog["phi0"]
+        phis = self._program_angles(prog, theta)
         for st in prog["steps"]:
             if st[0] == "swap":
                 self._swap_bits(st[1], st[2])
@@ -1086,6 +1137,52 @@ class ShardedStatevector:
             raise ValueError("compile_program was called without a Hamiltonian")
         self.run_program(prog, theta)
         return self._expectation_planned(prog["ham"])
+
+    def program_energy_gradient(self, prog, theta):
+        """E(theta) and dE/dtheta[K] by the adjoint method on the shards (same values on every rank): the forward plan, lambda = H psi
+        with the program's Hamiltonian plan (E = Re <psi|lambda> + constant comes from it: nothing is planned or contracted twice),
+        then the plan's steps in REVERSE on psi and lambda together — a rotation step gives this shard's sums
+        w_r = Im <lambda|P_r|psi> and un-rotates both vectors (``engine.adjoint_rotations``), an exchange step is replayed for both
+        (disjoint bit swaps are their own inverse) —, ONE all-reduce of the R sums and the energy;
+        dE/dtheta_p = sum_{r: pidx_r = p} 2 coeff_r w_r (constant-angle rotations are un-rotated and contribute nothing).
+        A real program runs forward on float64 shards and is widened once, before lambda.  The backward pass works in place on the
+        shard and on the sigma buffer of ``apply_hamiltonian``: no further shard-sized allocation.
+        AFTER the call the register holds |hf> (complex storage, identity permutation) and the sigma buffer U^+ H psi — NOT
+        psi(theta); ``run_program`` prepares it again."""
+        if prog["ham"] is None:
+            raise ValueError("compile_program was called without a Hamiltonian")
+        if not hasattr(self.engine, "adjoint_rotations"):
+            raise NotImplementedError("this shard engine has no adjoint_rotations")
+        theta = np.asarray(theta, np.float64).reshape(-1)
+        self.run_program(prog, theta)
+        phis = self._program_angles(prog, theta)
+        plan = prog["ham"]
+        self._complex_storage()
+        lam = self.apply_hamiltonian(None, None, None, 0.0, plan=plan)   # (partner reads of a real psi still move real parts only)
+        self.real = False             # lambda = H psi is complex in general: from here both vectors travel as complex amplitudes
+        one = self.engine.bilinear_batch(np.array([0, 1], np.int64), np.zeros(1, np.uint64), np.zeros(1, np.uint64),
+                                         np.ones(1, np.complex128), lam, None)      # <lambda|psi> over this shard
+        w = np.zeros(len(prog["coeff"]) + 1, np.float64)
+        w[-1] = float(np.real(np.asarray(one).reshape(-1)[0]))
+        for st in reversed(prog["steps"]):
+            if st[0] == "swap":
+                self._swap_bits(st[1], st[2], also=lam)
+            else:
+                _progress("adjoint sweeps")
+                with self._compute("adjoint_sweeps"):
+                    w[st[3]] = self.engine.adjoint_rotations(lam, st[1], st[2], phis[st[3]])
+        assert self.perm == list(range(self.n))
+        buf = torch.from_numpy(w).to(self.engine.tensor.device)
+        _progress("all-reduce of the gradient")
+        if self._dist:
+            dist.all_reduce(buf, group=self.group)
+        w = buf.cpu().numpy()
+        _progress("local sweeps")
+        pidx = prog["pidx"]
+        grad = np.zeros(prog["n_params"], np.float64)
+        live = pidx >= 0
+        np.add.at(grad, pidx[live], 2.0 * prog["coeff"][live] * w[:-1][live])
+        return float(w[-1]) + plan["const"], grad
 
     def energy(self, ham_xs, ham_zs, ham_coeffs, constant, rot_xs, rot_zs, rot_phis, hf_index):
         """one whole evaluation: |hf> -> rotations -> <H>"""

@@ -7,11 +7,13 @@ rank calls the same methods with the same arguments and gets the same numbers ba
 What maps to what:
   ``set_hamiltonian`` + ``set_ucc_program`` / ``set_rotation_program``  ->  ``compile_program`` (exchange plan + cross-shard <H> plan, once)
   ``energy(theta)``                                                      ->  ``program_energy``
+  ``energy_gradient(theta)``  (``EnergyUCC.adjoint_gradient = True``)     ->  ``program_energy_gradient``: the adjoint method on shards, one forward
+                                                                             and one backward pass over the plan for all K derivatives
   ``init_basis`` / ``apply_exp_pauli_sum``  (the ADAPT screen state)     ->  rotations when the operator's strings commute (every JW single /
                                                                              double excitation, every pool string), else a Taylor series of sigma = A psi
   ``pool_gradients``                                                     ->  ``ShardedStatevector.pool_gradients``
 Not offered on the partitioned register (each raises with a plain message): literal gate programs (the QUCCSD templates stop at 24
-qubits in every config), the adjoint gradient, device Lanczos.
+qubits in every config), device Lanczos.
 """
 from __future__ import annotations
 
@@ -109,8 +111,15 @@ class PartitionedStatevector:
         return np.array([self.energy(t) for t in thetas])
 
     def energy_gradient(self, theta):
-        raise NotImplementedError("the adjoint gradient is a one-device path; on the partitioned register use the default "
-                                  "(forward-difference) Jacobian of the optimiser")
+        """E(theta) and the exact gradient dE/dtheta by the adjoint method on the partitioned register (one forward + one backward
+        pass over the exchange plan for all K derivatives; same values on every rank) -> (energy, grad[K]).  The register holds
+        |hf> afterwards, not psi(theta): ``prepare_state`` restores it."""
+        if self._ham is None:
+            raise RuntimeError("no Hamiltonian set")
+        e, grad = self.sharded.program_energy_gradient(self._program(), self._theta(theta))
+        out = np.zeros(self._K, np.float64)
+        out[: grad.shape[0]] = grad       # (parameters past the last one a rotation uses have a zero derivative)
+        return e, out
 
     def prepare_state(self, theta):
         self.sharded.run_program(self._program(), self._theta(theta))
