@@ -147,7 +147,7 @@ int ovqe_set_stream(ovqe_handle h, void *hip_stream);
  *   "fault_inject" (1: the next term-list build throws std::bad_alloc: the exception barrier's test), "sector_debug" (2: say on stderr why a
  *   program was left to the dense kernels; 4: wall time of the build's phases), "sector_sweep_dbg" / "sector_h_dbg" / "sparse_dbg" (kernels
  *   truncated after a given phase), and the launch geometries and superseded forms kept for comparison: "sparse_rows", "sparse_wg",
- *   "sparse_spw", "sector_sweep" (circuit sweeps on an irregular support: 3 pair words in per-wave streams with barriers at
+ *   "sparse_shared" (0: large batches of the rows form on one wave per pair of evaluations instead of the workgroup geometry, 2: that geometry below its batch threshold too), "sparse_spw", "sector_sweep" (circuit sweeps on an irregular support: 3 pair words in per-wave streams with barriers at
  *   run boundaries only — built on top of the tables of 2 —, 2 64-bit pair words in registers with a barrier per round, 1 first form; 2 on a
  *   handle built under 3 runs the second form on the same tables; 4: the streams for the states of a batch too — the product gives
  *   batches the second form: their workgroups hide each other's barriers and the streams gain them nothing), "sector_stream_waves" (0: waves that share a tile's rows from the pairs per

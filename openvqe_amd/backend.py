@@ -411,6 +411,17 @@ class Statevector:
         self._ck(self._L.ovqe_last_support(self._h, 7, ctypes.byref(out)))
         return {name for bit, name in enumerate(self.SPARSE_FORMS) if (out.value >> bit) & 1}
 
+    #: launch geometries of the "rows2" form, bits 10... of the same word (sparse_host.inc: SPG_*)
+    SPARSE_GEOMETRIES = ("per_wave", "shared_e37_s4104", "shared_e13_s2568")
+
+    def sparse_geometries(self):
+        """launch geometries that served the "rows2" form on this handle since its program was set: "per_wave" (k_sparse_vqe_rows<2>,
+        one wave per pair of evaluations) or an instance of the workgroup geometry with the Hamiltonian's entries in registers
+        (k_sparse_vqe_rows_shared: entries per thread, bytes between the states in LDS)"""
+        out = ctypes.c_int64()
+        self._ck(self._L.ovqe_last_support(self._h, 7, ctypes.byref(out)))
+        return {name for bit, name in enumerate(self.SPARSE_GEOMETRIES) if (out.value >> (10 + bit)) & 1}
+
     def last_exp_support(self):
         """amplitudes the Taylor steps of the last ``apply_exp_pauli_sum`` call ran over (-1: the register)"""
         out = ctypes.c_int64()

@@ -361,11 +361,12 @@ struct ovqe_sv {
     bool pg_valid = false;
     int opt_sparse = 1;           // allow the support-compacted path
     int opt_sparse_spw = 0;       // evaluations per wave (0 = automatic)
-    int opt_sparse_dbg = 0;       // measurement: k_sparse_vqe_rows without one of its phases (SparseArgs::dbg)
+    int opt_sparse_dbg = 0;       // measurement: k_sparse_vqe_rows / k_sparse_vqe_rows_shared without one of their phases (SparseArgs::dbg)
     int opt_clifford_phase_host = 1;   // global phase of a closed Clifford frame from a sparse host simulation (0: the gates run on the device)
     int opt_sparse_renumber = 1;  // number the compact support against LDS bank conflicts of the circuit's pairs
     int opt_sparse_rows = 1;      // support-compacted evaluation, large batches: flat rows of padded 64-bit pair words (k_sparse_vqe_rows)
     int opt_sparse_wg = 1;        // small batches (<= 1024): one evaluation per 1024-thread workgroup (k_sparse_vqe_wg)
+    int opt_sparse_shared = 1;    // large batches: the workgroup geometry of the rows form, Hamiltonian entries in registers (k_sparse_vqe_rows_shared; 0: one wave per pair of evaluations, 2: below its batch threshold too)
     int opt_sparse_grad = 1;      // ovqe_energy_gradient on the compact support in one launch (n <= 16)
     // pair-index-space expectation tables of the fused kernel, built per (thread bits, real mode)
     DevBuf d_egroups, d_eterms, d_echunks, d_eflat;
@@ -1295,6 +1296,7 @@ int ovqe_set_option(ovqe_handle h, const char *name, int64_t value) try {
     }
 #ifdef OVQE_TESTING
     else if (k == "sparse_wg") h->opt_sparse_wg = value ? 1 : 0;
+    else if (k == "sparse_shared") h->opt_sparse_shared = (int)value;
     else if (k == "sparse_rows") {
         h->opt_sparse_rows = value ? 1 : 0;
         h->sp_tried = false;

@@ -425,14 +425,76 @@ enum : uint32_t {
     SPF_WG = 1u << 0,            // k_sparse_vqe_wg: one evaluation per workgroup (B <= 256)
     SPF_STAGED1 = 1u << 1,       // k_sparse_vqe<1, true>: op table and pair words staged in LDS (B <= 1024)
     SPF_PLAIN1 = 1u << 2,        // k_sparse_vqe<1, false>
-    SPF_ROWS2 = 1u << 3,         // k_sparse_vqe_rows<2>: the throughput form (B >= 2048)
+    SPF_ROWS2 = 1u << 3,         // k_sparse_vqe_rows<2> / k_sparse_vqe_rows_shared: the throughput form (B >= 2048), geometry in SPG_*
     SPF_PLAIN2 = 1u << 4,        // k_sparse_vqe<2, false> (no row tables)
     SPF_PLAIN4 = 1u << 5,        // k_sparse_vqe<4, false> ("sparse_spw" = 4)
     SPF_GRAD_WG = 1u << 6,       // k_sparse_grad_wg
     SPF_GRAD_STAGED = 1u << 7,   // k_sparse_grad<true>
     SPF_GRAD_PLAIN = 1u << 8,    // k_sparse_grad<false>
     SPF_DECLINED = 1u << 9,      // a call wanted the compact path and no form of it fits: the other paths served it
+    // launch geometry of SPF_ROWS2 (bits the form names do not reach: Statevector.sparse_geometries())
+    SPG_PER_WAVE = 1u << 10,     // k_sparse_vqe_rows<2>: one wave per pair of evaluations, the Hamiltonian's entries streamed from L2
+    SPG_SHARED_37 = 1u << 11,    // k_sparse_vqe_rows_shared<4, 37, 4104>: entries in registers (H2O: 441 states, 9443 entries)
+    SPG_SHARED_13 = 1u << 12,    // k_sparse_vqe_rows_shared<4, 13, 2568>  (LiH: 225 states)
 };
+
+// the workgroup geometry of the rows form: batches from SHARED_MIN_B on — measured (tools/exp_shared_sweep.py, profiles/shared_rows): it
+// wins beyond the spread at every batch size the rows form takes, 2048 included (H2O: 35.6 against 40.3 us)
+constexpr int64_t SHARED_MIN_B = 2048;
+constexpr size_t SHARED_MAX_LDS = 80 * 1024;   // two workgroups per CU
+
+template <int NW, int EPT, int SSTRIDE, int DBG>
+int launch_rows_shared_dbg(ovqe_handle h, const SparseArgs &R, size_t smem) {
+    constexpr int NS = 2 * NW;
+    struct PerDevice {
+        bool attr = false;
+        size_t smem = 0;
+        int per_cu = 0;   // workgroups one CU holds at once, at this much LDS
+    };
+    static PerDevice per_dev[64];   // function attributes are per device
+    PerDevice &pd = per_dev[h->device & 63];
+    const auto kern = &k_sparse_vqe_rows_shared<NW, EPT, SSTRIDE, DBG>;
+    if (!pd.attr) {
+        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        pd.attr = true;
+    }
+    if (pd.smem != smem) {
+        int n = 0;
+        HIPC(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, NW * 64, smem));
+        pd.per_cu = std::min(std::max(n, 1), 32 / NW);
+        pd.smem = smem;
+    }
+    if (h->num_cus <= 0) {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus <= 0) cus = 256;
+        h->num_cus = cus;
+    }
+    // persistent: as many workgroups as the chip holds at once, each walks work items of 2 NW evaluations
+    const int grid = (int)std::min<int64_t>((R.B + NS - 1) / NS, (int64_t)h->num_cus * pd.per_cu);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), smem, h->stream, R, h->cur_theta, (const SmallRot *)h->d_sp_prim.p,
+                       (const uint64_t *)h->d_sp_rows.p, h->sp_nrows4, (const SpEntry *)h->d_sp_entries.p, h->cur_energies);
+    HIPC(h, hipGetLastError());
+    return OVQE_OK;
+}
+
+// One instance of the workgroup geometry.  *taken = false: it does not hold this program (nothing launched): more entries than
+// its threads keep in registers, a support beyond its stride, or states + cos/sin tables beyond the LDS of half a CU.
+template <int NW, int EPT, int SSTRIDE>
+int launch_rows_shared(ovqe_handle h, const SparseArgs &R, bool *taken) {
+    constexpr int NS = 2 * NW;
+    const size_t smem = (size_t)NS * SSTRIDE + (size_t)NS * (R.ntab + 1) * sizeof(double2) + (size_t)NW * NS * sizeof(double);
+    *taken = R.nent >= 1 && R.nent <= NW * 64 * EPT && (size_t)R.mpad * sizeof(double) <= (size_t)SSTRIDE && smem <= SHARED_MAX_LDS;
+    if (!*taken) return OVQE_OK;
+#ifdef OVQE_TESTING
+    switch (h->opt_sparse_dbg) {
+    case 1: return launch_rows_shared_dbg<NW, EPT, SSTRIDE, 1>(h, R, smem);
+    case 2: return launch_rows_shared_dbg<NW, EPT, SSTRIDE, 2>(h, R, smem);
+    case 3: return launch_rows_shared_dbg<NW, EPT, SSTRIDE, 3>(h, R, smem);
+    default: break;
+    }
+#endif
+    return launch_rows_shared_dbg<NW, EPT, SSTRIDE, 0>(h, R, smem);
+}
 
 // on_device: theta / energies are device pointers (inputs already resident in HBM, results left there).  *done = false: no compact
 // form fits this program's LDS budget (nothing was launched; the caller takes the other paths).
@@ -520,23 +582,40 @@ int run_sparse(ovqe_handle h, int64_t B, const double *theta, double *energies, 
         R.mpad = (h->sp_mp + 64 + 1) & ~1;   // + the padded lanes' spare slots
         R.ntab = h->sp_nprim;                // one entry per distinct angle
         const size_t per_eval_r = (size_t)R.mpad * sizeof(double) + (size_t)(R.ntab + 1) * sizeof(double2);
-        static bool attr_rows_dev[64] = {};
-        bool &attr_rows = attr_rows_dev[h->device & 63];
-        if (!attr_rows) {
-            HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_vqe_rows<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_rows = true;
+        // batches that fill the chip: the workgroup geometry when one of its instances holds the program — a pure function of the
+        // program and B; smaller instance first
+        bool shared = false;
+        if ((B >= SHARED_MIN_B && h->opt_sparse_shared) || h->opt_sparse_shared >= 2) {   // (2: the threshold sweep)
+            if (!rc && !shared) {
+                rc = launch_rows_shared<4, 13, 2568>(h, R, &shared);
+                if (shared) h->sp_forms |= SPG_SHARED_13;
+            }
+            if (!rc && !shared) {
+                rc = launch_rows_shared<4, 37, 4104>(h, R, &shared);
+                if (shared) h->sp_forms |= SPG_SHARED_37;
+            }
+            if (rc) return rc;
         }
+        if (!shared) {
+            static bool attr_rows_dev[64] = {};
+            bool &attr_rows = attr_rows_dev[h->device & 63];
+            if (!attr_rows) {
+                HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_vqe_rows<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                attr_rows = true;
+            }
 #define OVQE_ROWS(DBG_)                                                                                                                       \
     hipLaunchKernelGGL((k_sparse_vqe_rows<2, DBG_>), dim3(grid), dim3(64), per_eval_r * 2, h->stream, R, h->cur_theta, (const SmallRot *)h->d_sp_prim.p, \
                        (const uint64_t *)h->d_sp_rows.p, h->sp_nrows4, (const SpEntry *)h->d_sp_entries.p, h->cur_energies)
-        switch (h->opt_sparse_dbg) {   // (measurement variants carry their own LDS attribute: set on the fly)
-        case 1: HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_vqe_rows<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); OVQE_ROWS(1); break;
-        case 2: HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_vqe_rows<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); OVQE_ROWS(2); break;
-        case 3: HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_vqe_rows<2, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); OVQE_ROWS(3); break;
-        default: OVQE_ROWS(0);
-        }
+            switch (h->opt_sparse_dbg) {   // (measurement variants carry their own LDS attribute: set on the fly)
+            case 1: HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_vqe_rows<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); OVQE_ROWS(1); break;
+            case 2: HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_vqe_rows<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); OVQE_ROWS(2); break;
+            case 3: HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_vqe_rows<2, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); OVQE_ROWS(3); break;
+            default: OVQE_ROWS(0);
+            }
 #undef OVQE_ROWS
-        HIPC(h, hipGetLastError());
+            HIPC(h, hipGetLastError());
+            h->sp_forms |= SPG_PER_WAVE;
+        }
         h->sp_forms |= SPF_ROWS2;
     }
     else if (spw == 2) {

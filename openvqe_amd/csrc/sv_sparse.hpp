@@ -44,7 +44,7 @@ struct SparseArgs {
     int hf;       // compact slot of |hf>
     int64_t B;
     double constant;
-    int dbg = 0;  // measurements ("sparse_dbg"; k_sparse_vqe_rows only): 1 no sincos, 2 no circuit rows, 3 no Hamiltonian entries
+    int dbg = 0;  // measurements ("sparse_dbg"; the rows kernels take it as a template argument): 1 no sincos, 2 no circuit rows, 3 no Hamiltonian entries
 };
 
 // STAGE = true (small batches, the latency path of one-evaluation-per-call optimisers): the op table and the pair
@@ -250,6 +250,133 @@ __global__ __launch_bounds__(64) void k_sparse_vqe_rows(SparseArgs A, const doub
             if (lane == 0 && b0 + q < A.B) energies[b0 + q] = tot + A.constant;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+}
+
+// ---- throughput form, workgroup geometry: the restricted Hamiltonian in REGISTERS ----------------------------------------------------
+// Half of k_sparse_vqe_rows<2> on the H2O workload is its entry loop: every wave streams the whole entry table from L2 (151 KB)
+// for every pair of evaluations, one 16-byte load + unpacking + two address computations per entry, lane and state.  Here NW
+// waves share a workgroup.  Each wave runs the circuit of ITS two evaluations exactly as above (same row table, rows four ahead,
+// no barrier between rows); the 2 NW states lie side by side in LDS at the compile-time stride SSTRIDE (bytes), the cos/sin
+// tables behind them.  Thread t holds entries t, t + NT, ... (EPT of them, the tail padded with coefficient 0) in registers
+// for the whole launch — both byte offsets in one VGPR, the coefficient in two — and after ONE barrier every wave contracts
+// its entries against ALL 2 NW states: the addresses are offset + q * SSTRIDE, instruction immediates (two states per
+// ds_read_b64), no global traffic, no address arithmetic.  Partial sums of the NW waves go through LDS and are added in
+// wave order (no floating-point atomics: the energy of a parameter vector depends neither on its position in the batch nor on
+// the run).  The second barrier also frees the states for the next work item of the persistent loop.
+// Two things the compiler needs: the stride at compile time (with a run-time stride it hoists all 2 NW x EPT x 2 addresses out of
+// the work loop and spills), and the accumulators pinned after each entry (otherwise it finishes state 0 over all entries first
+// and parks every other state's loads in scratch).  SSTRIDE is the state rounded up to 512 bytes PLUS 8: at a multiple of 512
+// the compiler pairs the reads of two states into ds_read2st64_b64, which the LDS serves at half the rate of two ds_read_b64
+// (8 against 2 x 2 cycles per wave) and in groups of 16 lanes against 32 banks, where the host's arrangement of the entries
+// (conflict-free inside aligned groups of 32 against 64 banks) does not hold — measured on the H2O workload: 0.73 ms per
+// 65 536 evaluations with a stride of 4096 (no gain over the per-wave geometry).  With + 8 every state is shifted by one slot against its neighbour: the same
+// shift for all lanes of an instruction, the arrangement keeps its meaning.  DBG as k_sparse_vqe_rows.
+template <int NW, int EPT, int SSTRIDE, int DBG = 0>
+__global__ __launch_bounds__(NW * 64) void k_sparse_vqe_rows_shared(SparseArgs A, const double *__restrict__ theta,
+                                                                    const SmallRot *__restrict__ tabrots, const uint64_t *__restrict__ rows,
+                                                                    int nrows4, const SpEntry *__restrict__ entries,
+                                                                    double *__restrict__ energies) {
+    constexpr int NT = NW * 64, NS = 2 * NW, SD = SSTRIDE / 8;
+    static_assert(SSTRIDE % 8 == 0 && SSTRIDE % 512 != 0 && NS * SSTRIDE <= 65536 && (NS * SSTRIDE) % 16 == 0,
+                  "state offsets are DS instruction immediates; a stride the ds_read2 forms cannot encode (see above)");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int ntab1 = A.ntab + 1;
+    double2 *cs = reinterpret_cast<double2 *>(smem + (size_t)NS * SSTRIDE);   // [NS][ntab + 1]: the last entry is the identity
+    double *red = reinterpret_cast<double *>(cs + (size_t)NS * ntab1);        // [NW][NS] partial sums
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = lane >> 5, l = lane & 31, my = 2 * wave + s;                // my: this half-wave's state of the workgroup
+    unsigned char *sbase = smem + (size_t)my * SSTRIDE;
+    double *sst = reinterpret_cast<double *>(sbase);
+    double2 *csm = cs + (size_t)my * ntab1;
+    unsigned char *cbase = reinterpret_cast<unsigned char *>(csm);
+    // this thread's entries: loaded once per launch
+    uint32_t oij[EPT];
+    double ec[EPT];
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) {
+        const int e = tid + k * NT;
+        const SpEntry en = entries[min(e, A.nent - 1)];
+        oij[k] = ((en.ij & 0xfffu) * 8u) | ((((en.ij >> 12) & 0xfffu) * 8u) << 16);
+        ec[k] = e < A.nent ? en.c : 0.0;
+    }
+    const int64_t nwork = (A.B + NS - 1) / NS;
+    const uint64_t *rp = rows + l;
+    for (int64_t w = blockIdx.x; w < nwork; w += gridDim.x) {
+        const int64_t b0 = w * NS;
+        uint64_t w0 = rp[0], w1 = rp[32], w2 = rp[64], w3 = rp[96];   // (the table ends with four spare rows)
+        for (int i = l; i < SD; i += 32) sst[i] = i == A.hf ? 1.0 : 0.0;
+        {
+            const int64_t b = b0 + my < A.B ? b0 + my : A.B - 1;
+            const double *th = theta + b * A.K;
+            for (int e = l; e < A.ntab; e += 32) {
+                const SmallRot sr = tabrots[e];
+                double sn, c;
+                if (DBG == 1) {
+                    sn = sr.coeff * th[sr.pidx];
+                    c = 1.0;
+                } else {
+                    sincos(sr.coeff * th[sr.pidx], &sn, &c);
+                }
+                csm[e] = make_double2(c, sn);
+            }
+            if (l == 0) csm[A.ntab] = make_double2(1.0, 0.0);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        auto apply = [&](uint64_t word) {
+            const uint32_t lo = (uint32_t)word, hi = (uint32_t)(word >> 32);
+            double *pi = reinterpret_cast<double *>(sbase + (lo & 0xffffu));
+            double *pj = reinterpret_cast<double *>(sbase + (lo >> 16));
+            const double2 t = *reinterpret_cast<const double2 *>(cbase + (hi & 0xffffu));
+            const double sn = __hiloint2double(__double2hiint(t.y) ^ (int)(hi & 0x80000000u), __double2loint(t.y));
+            const double u = *pi, v = *pj;
+            *pi = t.x * u + sn * v;
+            *pj = t.x * v - sn * u;
+            asm volatile("" ::: "memory");   // a wave's DS instructions execute in issue order (see k_sparse_vqe_rows)
+        };
+        for (int r = 0; r < (DBG == 2 ? 0 : nrows4); r += 4) {
+            const uint64_t *nx = rp + (size_t)(r + 4) * 32;
+            apply(w0);
+            w0 = nx[0];
+            apply(w1);
+            w1 = nx[32];
+            apply(w2);
+            w2 = nx[64];
+            apply(w3);
+            w3 = nx[96];
+        }
+        __syncthreads();   // all 2 NW states of the workgroup are final
+        double acc[NS];
+#pragma unroll
+        for (int q = 0; q < NS; ++q) acc[q] = 0.0;
+        if (DBG != 3) {
+#pragma unroll
+            for (int k = 0; k < EPT; ++k) {
+                uint32_t pk = oij[k];
+                asm volatile("" : "+v"(pk));   // (keeps the unpacking inside the loop: 2 EPT registers less)
+                const uint32_t oi = pk & 0xffffu, oj = pk >> 16;
+#pragma unroll
+                for (int q = 0; q < NS; ++q) {
+                    const double ai = *reinterpret_cast<const double *>(smem + oi + q * SSTRIDE);
+                    const double aj = *reinterpret_cast<const double *>(smem + oj + q * SSTRIDE);
+                    acc[q] += ec[k] * ai * aj;
+                }
+#pragma unroll
+                for (int q = 0; q < NS; ++q) asm volatile("" : "+v"(acc[q]));
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < NS; ++q) {
+            const double tot = wave_sum(acc[q]);
+            if (lane == 0) red[wave * NS + q] = tot;
+        }
+        __syncthreads();   // partial sums complete; the states may be overwritten
+        if (tid < NS && b0 + tid < A.B) {
+            double e = 0.0;
+#pragma unroll
+            for (int v = 0; v < NW; ++v) e += red[v * NS + tid];
+            energies[b0 + tid] = e + A.constant;
+        }
     }
 }
 
