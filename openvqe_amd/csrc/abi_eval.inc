@@ -131,7 +131,7 @@ static bool sector_batch_ready(ovqe_handle h) {
     const bool real = h->opt_real_stream && h->prog_real_ok && h->n_global == 0 && tile_ok(h, true) && h->ham.groups.size() >= 3;
     return real && h->opt_sector && h->opt_sector_batch && E.valid && E.h_tables && E.pad_elems && !E.segs.empty() && E.segs[0].d_wide.p &&
            E.prog_version == h->prog_version && E.ham_version == h->ham.version &&
-           sector_h_smem(E, SEC_BATCH_NB) <= 156 * 1024;
+           sec_h_lds_bytes(std::max(E.h_max_tile, 1u), SEC_BATCH_NB, (uint32_t)E.h_max_dict) <= SEC_LDS_MAX;
 }
 
 int ovqe_energy_batch(ovqe_handle h, int64_t B, const double *theta, int32_t K, double *energies) try {

@@ -151,14 +151,8 @@ template <int M, bool DOT>
 int launch_tile_cross(ovqe_handle h, const CrossCover &C, const CrossPass &ps, const amp_t *ket, amp_t *other, uint64_t ket_gbase,
                       uint64_t chunk_off, unsigned grid, double2 *partials) {
     constexpr int NT = 1 << TILE_EXPECT_LOG_NT;
-    const size_t smem = ((size_t)16 << M) + TILE_TERM_CAP * sizeof(ExTermLds) + TILE_APPLY_GROUPS * sizeof(ExAGroupT) + (NT / 64) * sizeof(double2);
-    static bool attr_done_dev[64] = {};  // function attributes are per device
-    bool &attr_done = attr_done_dev[h->device & 63];
-    if (!attr_done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_cross<M, NT, true, DOT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_cross<M, NT, false, DOT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_done = true;
-    }
+    constexpr size_t smem = tile_apply_lds<M>(sizeof(double2), NT / 64).bytes;
+    if (int rc = lds_opt_in<&k_tile_cross<M, NT, true, DOT>, &k_tile_cross<M, NT, false, DOT>>(h, smem)) return rc;
     if (h->n_local >= 25)
         hipLaunchKernelGGL((k_tile_cross<M, NT, true, DOT>), dim3(grid), dim3(NT), smem, h->stream, ket, other, ket_gbase, chunk_off, ps,
                            (const ExChunkT *)C.d_achunks.p, (const ExAGroupT *)C.d_agroups.p, (const ExTermT *)C.d_aterms.p, partials);
@@ -173,14 +167,8 @@ template <int M>
 int launch_tile_cross_real(ovqe_handle h, const CrossCover &C, const CrossPass &ps, const double *ket, const double *bra, uint64_t ket_gbase,
                            uint64_t chunk_off, unsigned grid, double2 *partials) {
     constexpr int NT = 1 << TILE_EXPECT_LOG_NT;
-    const size_t smem = ((size_t)8 << M) + TILE_TERM_CAP * sizeof(ExTermLds) + TILE_APPLY_GROUPS * sizeof(ExAGroupT) + (NT / 64) * sizeof(double2);
-    static bool attr_done_dev[64] = {};
-    bool &attr_done = attr_done_dev[h->device & 63];
-    if (!attr_done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_cross_real<M, NT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_cross_real<M, NT, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_done = true;
-    }
+    constexpr size_t smem = tile_apply_lds<M>(sizeof(double), NT / 64).bytes;
+    if (int rc = lds_opt_in<&k_tile_cross_real<M, NT, true>, &k_tile_cross_real<M, NT, false>>(h, smem)) return rc;
     if (h->n_local >= 26)
         hipLaunchKernelGGL((k_tile_cross_real<M, NT, true>), dim3(grid), dim3(NT), smem, h->stream, ket, bra, ket_gbase, chunk_off, ps,
                            (const ExChunkT *)C.d_achunks.p, (const ExAGroupT *)C.d_agroups.p, (const ExTermT *)C.d_aterms.p, partials);

@@ -200,13 +200,7 @@ bool use_small_path(ovqe_handle h, int64_t B) {
 
 template <bool REAL, bool LDS, int NT, int LBITS>
 int launch_small(ovqe_handle h, const SmallArgs &A, int grid, size_t smem) {
-    static bool attr_done_dev[64] = {};  // function attributes are per device
-    bool &attr_done = attr_done_dev[h->device & 63];
-    if (!attr_done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_small_vqe<REAL, LDS, NT, LBITS>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done = true;
-    }
+    if (int rc = lds_opt_in<&k_small_vqe<REAL, LDS, NT, LBITS>>(h, LDS_WG_MAX)) return rc;
     hipLaunchKernelGGL((k_small_vqe<REAL, LDS, NT, LBITS>), dim3(grid), dim3(NT), smem, h->stream, A,
                        h->cur_theta, (const SmallOp *)h->d_ops.p, (const SmallRot *)h->d_rots.p,
                        (const SmallSeg *)h->d_segs.p, (const ExpGroup *)h->d_egroups.p, (const ExpChunk *)h->d_echunks.p,
@@ -443,7 +437,7 @@ int run_small(ovqe_handle h, int64_t B, const double *theta, double *energies, b
     A.B = B;
     A.constant = h->ham.constant;
     A.hf = h->hf;
-    const size_t smem = (lds_state ? state_bytes : 0) + (size_t)h->cs_capacity * sizeof(RotLds) + SMALL_OPS_CAP * sizeof(SmallOp) + 16 * sizeof(double2);
+    const size_t smem = small_lds(real, lds_state, n, h->cs_capacity).bytes;
     if (!zero_copy) HIPC(h, hipEventRecord(h->ev0, h->stream));
     if (real) {
         if (!lds_state) rc = launch_small<true, false, 1024, 10>(h, A, grid, smem);

@@ -507,6 +507,30 @@ int translate_exception(ovqe_handle h) noexcept {
             return fail(h, OVQE_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));            \
     } while (0)
 
+// LDS budgets.  The first is the hardware's: what one workgroup may have on gfx950 (the 160 KiB of a CU).  The others are policy.
+constexpr size_t LDS_WG_MAX = 160 * 1024;
+constexpr size_t LDS_WG_BUDGET = 150 * 1024;    // what a form that takes a CU for one workgroup plans with
+constexpr size_t LDS_TWO_PER_CU = 80 * 1024;    // two workgroups per CU
+constexpr size_t SEC_LDS_MAX = 156 * 1024;      // the sector <H> kernels and table builders
+
+// Dynamic LDS beyond the default 64 KiB needs an opt-in per kernel instance and device: made once, before the first launch that may
+// need it.  Two threads with a handle each may both make it (the same call with the same value); neither skips it before it is made.
+template <auto Kernel>
+int lds_opt_in(ovqe_handle h, size_t bytes) {
+    static std::atomic<bool> done[64];
+    std::atomic<bool> &d = done[h->device & 63];
+    if (!d.load(std::memory_order_acquire)) {
+        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        d.store(true, std::memory_order_release);
+    }
+    return OVQE_OK;
+}
+template <auto K0, auto K1, auto... Ks>   // the instances one launcher chooses from, the same value for each
+int lds_opt_in(ovqe_handle h, size_t bytes) {
+    const int rc = lds_opt_in<K0>(h, bytes);
+    return rc ? rc : lds_opt_in<K1, Ks...>(h, bytes);
+}
+
 void free_hamdev(HamDev &H) {
     for (DevBuf *b : {&H.d_groups, &H.d_terms, &H.d_tchunks, &H.d_tgroups, &H.d_tterms, &H.d_tflats, &H.d_titems, &H.d_rest, &H.d_achunks,
                       &H.d_agroups, &H.d_aterms, &H.d_dzin, &H.d_doff, &H.d_dterms})

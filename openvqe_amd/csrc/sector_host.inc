@@ -1,6 +1,10 @@
 // sector_host.inc — host side of the sector path (sv_sector.hpp); included by ovqe_sv.hip inside its anonymous namespace.
 // Everything here is one-time table construction (on the device) plus the per-evaluation launch sequence.
 
+// LDS the staged forms of the table builders (k_sec_pairs2, k_sec_hbuild) may take, key map included: a whole CU's budget behind the
+// dense map, 60 KiB behind a tile's sorted keys
+constexpr size_t sec_staged_budget(bool dense_map) { return dense_map ? LDS_WG_BUDGET : (size_t)60 * 1024; }
+
 void free_buf(DevBuf &b) {
     release_block(b.p, b.cap);   // (kept for the running build's next allocations, else hipFree: DevBlockCache)
     b.p = nullptr;
@@ -220,7 +224,7 @@ int build_wave_streams(ovqe_handle h, SectorEngine &E, SectorScratch &W, SectorS
     if (!rc) rc = ensure(h, d_wof, (size_t)nt * nruns * (1u << SEC_STREAM_CLASS_BITS));
     if (rc) return done(rc);
     const uint32_t pcap = (std::max(sg.L.max_tile, 1u) + 3u) & ~3u;
-    const size_t smem = (size_t)pcap * 5 + ((size_t)sg.nops + 1 + 2 * (size_t)sg.nops * NW) * sizeof(uint32_t) + 16;   // slots: basis index + owner; ops: offsets, counters, flags
+    const size_t smem = sec_wave_plan_lds(pcap, sg.nops, NW).bytes;
     if (smem > 64 * 1024) return done(OVQE_OK);   // (a sweep of hundreds of ops over 16 waves: the second form serves it)
     hipLaunchKernelGGL((k_sec_wave_plan<false>), dim3(nt), dim3(256), smem, h->stream, (const uint32_t *)E.d_sup.p, (const uint32_t *)sg.L.d_cid.p,
                        (const uint32_t *)sg.L.d_off.p, (const uint32_t *)sg.d_pairs.p, (const uint32_t *)sg.d_poff.p, sg.nops,
@@ -447,25 +451,14 @@ int build_sector_h(ovqe_handle h, SectorEngine &E, SectorScratch &W, size_t budg
         if (!rc) rc = ensure(h, W.ecnt, ((size_t)K + 1) * sizeof(uint32_t));
         if (!rc) rc = ensure(h, W.ecnt2, ((size_t)K + 1) * sizeof(uint32_t));
         if (rc) return rc;
-        const size_t smem = (size_t)std::max(hw.L.max_tile, 1u) * sizeof(uint32_t);
         HIPC(h, hipMemsetAsync(W.cnt.p, 0, (nsl + 1) * sizeof(uint32_t), h->stream));
         HIPC(h, hipMemsetAsync(W.cnt2.p, 0, (nsl + 1) * sizeof(uint32_t), h->stream));
         const bool dense_map = Mh <= 16;
-        const size_t map_bytes = dense_map ? ((size_t)2 << Mh) : ((smem + 15) & ~(size_t)15);
-        const size_t staged_bytes = (gl.size() + tl.size()) * 16;
-        const int staged = map_bytes + staged_bytes <= (size_t)(dense_map ? 150 : 60) * 1024 ? 1 : 0;
-        const size_t smem_h = map_bytes + (staged ? staged_bytes : 0);
-        {
-            static bool attr_done_dev[64] = {};
-            bool &attr_done = attr_done_dev[h->device & 63];
-            if (!attr_done) {
-                HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sec_hbuild<false, NTB, true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-                HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sec_hbuild<true, NTB, true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-                attr_done = true;
-            }
-        }
+        const size_t map_bytes = sec_map_bytes(dense_map, Mh, hw.L.max_tile, true);
+        const int staged = sec_hbuild_lds(map_bytes, (int)gl.size(), (int)tl.size(), true).bytes <= sec_staged_budget(dense_map) ? 1 : 0;
+        const size_t smem_h = sec_hbuild_lds(map_bytes, (int)gl.size(), (int)tl.size(), staged != 0).bytes;
+        rc = lds_opt_in<&k_sec_hbuild<false, NTB, true>, &k_sec_hbuild<true, NTB, true>>(h, SEC_LDS_MAX);
+        if (rc) return rc;
 #define OVQE_HBUILD(FILL, DENSE, ...)                                                                                      \
     hipLaunchKernelGGL((k_sec_hbuild<FILL, NTB, DENSE>), dim3(hw.L.ntiles), dim3(NTB), smem_h, h->stream,                    \
                        (const uint32_t *)E.d_sup.p, (const uint32_t *)W.keys.p, (const uint32_t *)hw.L.d_cid.p,             \
@@ -905,30 +898,19 @@ int build_sector_tables_impl(ovqe_handle h, bool allow_regular) {
             if (rc) return rc;
             constexpr int NTB = 1024;   // (one workgroup per tile: 1024 threads build a tile's pair lists four times as fast as 256 — the table build is part of the time to the first energy)
             const bool dense_map = M <= 16;
-            const size_t map_bytes = dense_map ? ((size_t)2 << M) : (((size_t)std::max(sg.L.max_tile, 1u) * sizeof(uint32_t) + 15) & ~(size_t)15);
+            const size_t map_bytes = sec_map_bytes(dense_map, M, sg.L.max_tile, true);
             // second form of the builder (k_sec_pairs2: ops staged in LDS, no barrier per op) whenever its LDS fits; "sector_pairs_form" 1: first form
-            const size_t staged_bytes = sops.size() * sizeof(SecBuildOp) + spats.size() * sizeof(SecPat) + sops.size() * 4 * (1 + NTB / 64);
-            const bool form2 = h->opt_sector_pairs_form != 1 && map_bytes + staged_bytes <= (size_t)(dense_map ? 150 : 60) * 1024;
-            const size_t smem = form2 ? map_bytes + staged_bytes : (dense_map ? ((size_t)2 << M) : (size_t)std::max(sg.L.max_tile, 1u) * sizeof(uint32_t));
+            const size_t smem2 = sec_pairs2_lds(map_bytes, (int)sops.size(), (int)spats.size(), NTB / 64).bytes;
+            const bool form2 = h->opt_sector_pairs_form != 1 && smem2 <= sec_staged_budget(dense_map);
+            const size_t smem = form2 ? smem2 : sec_map_bytes(dense_map, M, sg.L.max_tile, false);
             if (form2) {
                 rc = ensure(h, W.wbase, (size_t)nt * sg.nops * (NTB / 64) * sizeof(uint32_t));
                 if (rc) return rc;
             }
-            {
-                static bool attr_done_dev[64] = {};
-                bool &attr_done = attr_done_dev[h->device & 63];
-                if (!attr_done) {
-                    HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sec_pairs<false, NTB, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-                    HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sec_pairs<true, NTB, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-                    HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sec_pairs2<false, NTB, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-                    HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sec_pairs2<true, NTB, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-                    attr_done = true;
-                }
-            }
+            constexpr size_t PAIRS_LDS_MAX = 144 * 1024;   // (the first form holds the key map alone)
+            rc = lds_opt_in<&k_sec_pairs<false, NTB, true>, &k_sec_pairs<true, NTB, true>>(h, PAIRS_LDS_MAX);
+            if (!rc) rc = lds_opt_in<&k_sec_pairs2<false, NTB, true>, &k_sec_pairs2<true, NTB, true>>(h, SEC_LDS_MAX);
+            if (rc) return rc;
             h->forms_used |= form2 ? 512u : 256u;
 #define OVQE_PAIRS(FILL, DENSE, CNT, POFF, PAIRS)                                                                            \
     do {                                                                                                                    \
@@ -1216,21 +1198,12 @@ int build_sector(ovqe_handle h) {
 
 template <int NT>
 int launch_sector_sweeps(ovqe_handle h, SectorEngine &E, int *last) {
-    static bool attr_done_dev[64] = {};  // function attributes are per device
-    bool &attr_done = attr_done_dev[h->device & 63];
-    if (!attr_done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sector_sweep<NT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024));
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sector_sweep<NT, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024));
-        attr_done = true;
-    }
+    if (int rc = lds_opt_in<&k_sector_sweep<NT>, &k_sector_sweep<NT, true>>(h, LDS_WG_MAX)) return rc;
     int cur = 0;
     for (size_t s = 0; s < E.segs.size(); ++s) {
         const SectorSeg &sg = E.segs[s];
         const uint32_t cap = std::max(sg.L.max_tile, 1u);
-        const size_t smem = (size_t)((cap + 1u) & ~1u) * sizeof(double) + (size_t)sg.nrot * sizeof(double2) +
-                            ((size_t)sg.nops + 2) * sizeof(SecOpLds) + 2 * (size_t)SEC_STAGE_WORDS * sizeof(uint32_t);
+        const size_t smem = sec_sweep_lds(cap, sg.nrot, sg.nops).bytes;
         // two chunks of pair words ahead where every op of a tile fits a staging buffer
         const bool d2 = NT > 64 && sg.max_op_pairs <= SEC_STAGE_WORDS && !(h->opt_sector_debug & 1);
         h->forms_used |= 1u;
@@ -1257,34 +1230,21 @@ int launch_sector_sweeps(ovqe_handle h, SectorEngine &E, int *last) {
 template <int NT, int WPT>
 int launch_sector_sweeps2(ovqe_handle h, SectorEngine &E, double *buf0, double *buf1, size_t stride, const RotParam *rp, size_t rp_stride,
                           int B, int *last, bool dst_lds) {
-    static bool attr_done_dev[64] = {};
-    bool &attr_done = attr_done_dev[h->device & 63];
-    if (!attr_done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sector_sweep2<NT, WPT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024));
-        attr_done = true;
-    }
+    if (int rc = lds_opt_in<&k_sector_sweep2<NT, WPT>>(h, LDS_WG_MAX)) return rc;
     double *buf[2] = {buf0, buf1};
     int cur = 0;
     for (size_t s = 0; s < E.segs.size(); ++s) {
         const SectorSeg &sg = E.segs[s];
         const uint32_t cap = std::max(sg.L.max_tile, 1u);
-        const size_t smem = (size_t)((cap + 2u) & ~1u) * sizeof(double) + (size_t)sg.nrot * sizeof(double2) +
-                            (dst_lds ? (size_t)cap * sizeof(uint32_t) : 0) + (size_t)sg.maxchunks * sizeof(uint32_t);
-        if (smem > 160 * 1024 || sg.maxchunks > (uint32_t)NT) return fail(h, OVQE_ERR_INVALID, "internal: sector tile exceeds LDS");
+        const size_t smem = sec_sweep2_lds(cap, sg.nrot, dst_lds, sg.maxchunks).bytes;
+        if (smem > LDS_WG_MAX || sg.maxchunks > (uint32_t)NT) return fail(h, OVQE_ERR_INVALID, "internal: sector tile exceeds LDS");
         const bool bfast = B > 1 && sg.L.ntiles <= 65535u;
         if constexpr (NT == 64 * SEC_STREAM_WAVES) {
-            const size_t smem3 = (size_t)((cap + 2u) & ~1u) * sizeof(double) + (size_t)sg.nrot * sizeof(double2) +
-                                 (dst_lds ? (size_t)cap * sizeof(uint32_t) : 0);
+            const size_t smem3 = sec_sweep2_lds(cap, sg.nrot, dst_lds, 0).bytes;   // (no round counts)
             // third form: per-wave streams, barriers at the run boundaries — for ONE state: the workgroups of a batch hide each other's barriers, and the
             // streams gain them nothing (24 qubits, per evaluation: batches of 64 0.509 ms on the second form / 0.512 on the streams, of 8 0.649 / 0.656)
-            if (sg.nruns > 0 && h->opt_sector_sweep >= 3 && smem3 <= 160 * 1024 && (B == 1 || h->opt_sector_sweep >= 4)) {
-                static bool attr3_dev[64] = {};
-                if (!attr3_dev[h->device & 63]) {
-                    HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sector_sweep3<NT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                160 * 1024));
-                    attr3_dev[h->device & 63] = true;
-                }
+            if (sg.nruns > 0 && h->opt_sector_sweep >= 3 && smem3 <= LDS_WG_MAX && (B == 1 || h->opt_sector_sweep >= 4)) {
+                if (int rc = lds_opt_in<&k_sector_sweep3<NT>>(h, LDS_WG_MAX)) return rc;
                 h->forms_used |= 4u;
                 hipLaunchKernelGGL((k_sector_sweep3<NT>), bfast ? dim3((unsigned)B, sg.L.ntiles) : dim3(sg.L.ntiles, (unsigned)B), dim3(NT),
                                    smem3, h->stream,
@@ -1330,49 +1290,26 @@ bool sector_sweeps2_fits(const SectorEngine &E, int nt, bool dst_lds) {
     if (nt != 1024 && nt != 512 && nt != 256) return false;
     for (const SectorSeg &sg : E.segs) {
         const uint32_t cap = std::max(sg.L.max_tile, 1u);
-        const size_t smem = (size_t)((cap + 2u) & ~1u) * sizeof(double) + (size_t)sg.nrot * sizeof(double2) +
-                            (dst_lds ? (size_t)cap * sizeof(uint32_t) : 0) + (size_t)sg.maxchunks * sizeof(uint32_t);
-        if (smem > 160 * 1024 || sg.maxchunks > (uint32_t)nt) return false;
+        if (sec_sweep2_lds(cap, sg.nrot, dst_lds, sg.maxchunks).bytes > LDS_WG_MAX || sg.maxchunks > (uint32_t)nt) return false;
     }
     return true;
 }
 
-// launch geometry of the <H> kernels: workgroups per sweep, dynamic LDS (tile [+ lambda] + dictionary)
+// launch geometry of the <H> kernels: workgroups per sweep (their dynamic LDS: sec_h_lds_bytes / sec_expect_lds_bytes, sv_sector.hpp)
 constexpr int SEC_H_THREADS = 512;
 constexpr uint32_t SEC_H_GROUPS = 256;   // workgroups per <H> sweep (they share the sweep's tiles round robin)
 uint32_t sector_h_groups(const SectorEngine &E) { return std::min<uint32_t>(E.hs[0].L.ntiles, SEC_H_GROUPS); }
-size_t sector_h_smem(const SectorEngine &E, int tiles) {
-    return (size_t)tiles * ((std::max(E.h_max_tile, 1u) + 1u) & ~1u) * sizeof(double) + ((size_t)E.h_max_dict + 2 + 64) * sizeof(double);   // + 64: the dummy slots of k_sector_apply
-}
-// the single-state <H> kernel: tile + dictionary + its null element, nothing else (at 24 qubits 54 272 bytes: three workgroups per CU)
-size_t sector_expect_smem(const SectorEngine &E) {
-    return std::max<size_t>(512,   // (the workgroup's reduction scratch lives in the same block)
-                            (size_t)((std::max(E.h_max_tile, 1u) + 1u) & ~1u) * sizeof(double) + ((size_t)E.h_max_dict + 1) * sizeof(double));
-}
-template <typename Kernel>
-int sector_h_attr(ovqe_handle h, Kernel kernel, bool &done) {
-    if (!done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-        done = true;
-    }
-    return OVQE_OK;
-}
 
 // sweeps of a regular support (k_sector_sweep_reg): no pair words, every tile 2^reg_m slots
 template <int NT>
 int launch_sector_sweeps_reg(ovqe_handle h, SectorEngine &E, int *last) {
-    static bool attr_done_dev[64] = {};
-    bool &attr_done = attr_done_dev[h->device & 63];
-    if (!attr_done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sector_sweep_reg<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done = true;
-    }
+    if (int rc = lds_opt_in<&k_sector_sweep_reg<NT>>(h, LDS_WG_MAX)) return rc;
     hipLaunchKernelGGL(k_sec_reg_angles, dim3((E.nregtab + 255u) / 256u), dim3(256), 0, h->stream, (const uint32_t *)E.d_regmap.p, E.nregtab,
                        (const RotParam *)h->d_rp.p, (double2 *)E.d_regtab.p);
     int cur = 0;
     for (size_t s = 0; s < E.segs.size(); ++s) {
         const SectorSeg &sg = E.segs[s];
-        const size_t smem = ((size_t)sizeof(double) << E.reg_m) + (size_t)sg.nops * SEC_REG_TSTRIDE * sizeof(double2);
+        const size_t smem = sec_reg_lds(E.reg_m, 1, sg.nops, 0, 0).bytes;
         h->forms_used |= 8u;
         hipLaunchKernelGGL((k_sector_sweep_reg<NT>), dim3(sg.L.ntiles), dim3(NT), smem, h->stream, (const double *)E.d_buf[cur ^ 1].p,
                            (double *)E.d_buf[cur].p,
@@ -1390,7 +1327,7 @@ int launch_sector_sweeps_reg(ovqe_handle h, SectorEngine &E, int *last) {
 bool sector_reg_fits(const SectorEngine &E) {
     if (!E.regular || E.segs.empty()) return false;
     for (const SectorSeg &sg : E.segs)
-        if (!sg.d_regops.p || ((size_t)sizeof(double) << E.reg_m) + (size_t)sg.nops * SEC_REG_TSTRIDE * sizeof(double2) > 160 * 1024) return false;
+        if (!sg.d_regops.p || sec_reg_lds(E.reg_m, 1, sg.nops, 0, 0).bytes > LDS_WG_MAX) return false;
     return true;
 }
 
@@ -1492,12 +1429,12 @@ int run_sector_energy(ovqe_handle h, const double *theta, double2 *out, bool *ok
     const size_t nparts = (size_t)nt * E.hs.size();
     rc = ensure(h, h->d_partials, nparts * sizeof(double2));
     if (!rc) rc = ensure(h, h->d_result, 64 * sizeof(double2));
-    static bool attr_done_dev[64] = {};
-    if (!rc) rc = sector_h_attr(h, &k_sector_expect<SEC_H_THREADS>, attr_done_dev[h->device & 63]);
+    if (!rc) rc = lds_opt_in<&k_sector_expect<SEC_H_THREADS>>(h, SEC_LDS_MAX);
     if (rc) return rc;
     // "sector_fused_reduce" (default): the reduction writes energy + flag into mapped host memory (no copies behind it)
     const bool fused = h->opt_sector_fused_reduce && sector_fin_ready(h);
-    hipLaunchKernelGGL((k_sector_expect<SEC_H_THREADS>), dim3(nt, (unsigned)E.hs.size()), dim3(SEC_H_THREADS), sector_expect_smem(E),
+    hipLaunchKernelGGL((k_sector_expect<SEC_H_THREADS>), dim3(nt, (unsigned)E.hs.size()), dim3(SEC_H_THREADS),
+                       sec_expect_lds_bytes(std::max(E.h_max_tile, 1u), (uint32_t)E.h_max_dict),
                        h->stream, (const double *)E.d_buf[last].p, (const SecHSweep *)E.d_hdesc.p, (double2 *)h->d_partials.p,
                        std::max(E.h_max_tile, 1u), h->opt_sector_h_dbg);
     if (profile) HIPC(h, hipEventRecord(E.ev[2], h->stream));
@@ -1573,8 +1510,7 @@ int run_sector_energy_batch(ovqe_handle h, int64_t B, const double *theta, bool 
     const uint32_t ng = sector_h_groups(E);
     const size_t nparts = (size_t)ng * E.hs.size();
     if (!rc) rc = ensure(h, h->d_partials, (size_t)(chunk / NB) * nparts * NB * sizeof(double));
-    static bool attr_done_dev[64] = {};
-    if (!rc) rc = sector_h_attr(h, &k_sector_expect_batch<NT, NB>, attr_done_dev[h->device & 63]);
+    if (!rc) rc = lds_opt_in<&k_sector_expect_batch<NT, NB>>(h, SEC_LDS_MAX);
     if (rc == OVQE_ERR_ALLOC) {   // no room for the state slices of a batch next to the tables: the serial path needs none of them
         for (DevBuf *b : {&E.d_bbuf[0], &E.d_bbuf[1], &E.d_brp, &E.d_benergies}) free_buf(*b);
         (void)hipGetLastError();
@@ -1604,7 +1540,7 @@ int run_sector_energy_batch(ovqe_handle h, int64_t B, const double *theta, bool 
         const bool zfast = nbp / NB <= 65535 && E.hs.size() <= 65535;
         hipLaunchKernelGGL((k_sector_expect_batch<NT, NB>),
                            zfast ? dim3((unsigned)(nbp / NB), ng, (unsigned)E.hs.size()) : dim3(ng, (unsigned)E.hs.size(), (unsigned)(nbp / NB)),
-                           dim3(NT), sector_h_smem(E, NB), h->stream, (const double *)E.d_bbuf[last].p, stride,
+                           dim3(NT), sec_h_lds_bytes(std::max(E.h_max_tile, 1u), NB, (uint32_t)E.h_max_dict), h->stream, (const double *)E.d_bbuf[last].p, stride,
                            (const SecHSweep *)E.d_hdesc.p, (double *)h->d_partials.p, std::max(E.h_max_tile, 1u), zfast ? 1 : 0);
         double *d_out = theta_on_device ? energies + b0 : (double *)E.d_benergies.p;
         if (theta_on_device && nbp > nb) d_out = (double *)E.d_benergies.p;   // (room for the duplicated state)
@@ -1630,23 +1566,15 @@ int run_sector_energy_batch(ovqe_handle h, int64_t B, const double *theta, bool 
 
 // dE/dtheta for all parameters on the sector tables (adjoint method): forward circuit, lambda = H psi on the support, one
 // backward pass.  *ok as run_sector_energy.
-size_t sector_adjoint_smem(const SectorSeg &sg, int nt);
-
 template <int NT>
 int launch_sector_adjoint(ovqe_handle h, SectorEngine &E, int last) {
-    static bool attr_done_dev[64] = {};  // function attributes are per device
-    bool &attr_done = attr_done_dev[h->device & 63];
-    if (!attr_done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sector_adjoint<NT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024));
-        attr_done = true;
-    }
+    if (int rc = lds_opt_in<&k_sector_adjoint<NT>>(h, LDS_WG_MAX)) return rc;
     int cur = last, lcur = 0;   // psi in d_buf[cur], lambda in d_lam[lcur]
     for (int s = (int)E.segs.size() - 1; s >= 0; --s) {
         const SectorSeg &sg = E.segs[s];
         const uint32_t cap = std::max(sg.L.max_tile, 1u);
-        const size_t smem = sector_adjoint_smem(sg, NT);
-        if (smem > 160 * 1024) return fail(h, OVQE_ERR_INVALID, "internal: sector adjoint tile exceeds LDS");
+        const size_t smem = sec_adjoint_lds(cap, sg.nrot, sg.nops, NT / 64).bytes;
+        if (smem > LDS_WG_MAX) return fail(h, OVQE_ERR_INVALID, "internal: sector adjoint tile exceeds LDS");
         h->forms_used |= 16u;
         hipLaunchKernelGGL((k_sector_adjoint<NT>), dim3(sg.L.ntiles), dim3(NT), smem, h->stream, (const double *)E.d_buf[cur].p,
                            (const double *)E.d_lam[lcur].p, (double *)E.d_buf[cur ^ 1].p, (double *)E.d_lam[lcur ^ 1].p,
@@ -1663,64 +1591,48 @@ int launch_sector_adjoint(ovqe_handle h, SectorEngine &E, int last) {
     return OVQE_OK;
 }
 
-// second form (k_sector_adjoint2, 1024 threads): LDS per sweep, launches
-size_t sector_adjoint2_smem(const SectorSeg &sg, int nt) {
-    const uint32_t cap = std::max(sg.L.max_tile, 1u);
-    return 2 * (size_t)((cap + 2u) & ~1u) * sizeof(double) + (size_t)sg.nrot * sizeof(double2) +
-           (size_t)(nt / 64) * sg.nrot * sizeof(double) + (size_t)cap * sizeof(uint32_t) + (size_t)sg.maxchunks * sizeof(uint32_t);
-}
-// third form (k_sector_adjoint3, on the per-wave streams): one row of partial sums per wave that shares the rows
-size_t sector_adjoint3_smem(const SectorSeg &sg) {
-    const uint32_t cap = std::max(sg.L.max_tile, 1u);
-    return 2 * (size_t)((cap + 2u) & ~1u) * sizeof(double) + (size_t)sg.nrot * sizeof(double2) +
-           (size_t)std::max(sg.stream_waves, 1) * sg.nrot * sizeof(double) + (size_t)cap * sizeof(uint32_t);
-}
+// second form (k_sector_adjoint2, 1024 threads) and third (k_sector_adjoint3, on the per-wave streams)
 bool sector_adjoint2_fits(ovqe_handle h, const SectorEngine &E) {
     if (h->opt_sector_adjoint < 2 || h->opt_sector_sweep < 2 || !E.pad_elems || E.segs.empty()) return false;
     for (size_t s = 0; s < E.segs.size(); ++s) {
         const SectorSeg &sg = E.segs[s];
-        if (!sg.d_wide.p || (s && !sg.d_bdst.p) || sg.maxchunks > 1024u || sector_adjoint2_smem(sg, 1024) > 160 * 1024) return false;
+        if (!sg.d_wide.p || (s && !sg.d_bdst.p) || sg.maxchunks > 1024u ||
+            sec_adjoint2_lds(std::max(sg.L.max_tile, 1u), sg.nrot, 1024 / 64, sg.maxchunks).bytes > LDS_WG_MAX)
+            return false;
     }
     return true;
 }
 int launch_sector_adjoint2(ovqe_handle h, SectorEngine &E, int last) {
     constexpr int NT = 1024, WPT = 2;
-    static bool attr_done_dev[64] = {};
-    bool &attr_done = attr_done_dev[h->device & 63];
-    if (!attr_done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sector_adjoint2<NT, WPT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024));
-        attr_done = true;
-    }
+    if (int rc = lds_opt_in<&k_sector_adjoint2<NT, WPT>>(h, LDS_WG_MAX)) return rc;
     int cur = last, lcur = 0;   // psi in d_buf[cur], lambda in d_lam[lcur]
     for (int s = (int)E.segs.size() - 1; s >= 0; --s) {
         const SectorSeg &sg = E.segs[s];
-        if (sg.nruns > 0 && h->opt_sector_sweep >= 3 && h->opt_sector_adjoint >= 3 && sector_adjoint3_smem(sg) <= 160 * 1024) {   // on the per-wave streams
-            static bool attr3_dev[64] = {};
-            if (!attr3_dev[h->device & 63]) {
-                HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sector_adjoint3<NT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            160 * 1024));
-                attr3_dev[h->device & 63] = true;
-            }
+        const uint32_t cap = std::max(sg.L.max_tile, 1u);
+        // third form: one row of partial sums per wave that shares the rows, no round counts
+        const size_t smem3 = sec_adjoint2_lds(cap, sg.nrot, std::max(sg.stream_waves, 1), 0).bytes;
+        if (sg.nruns > 0 && h->opt_sector_sweep >= 3 && h->opt_sector_adjoint >= 3 && smem3 <= LDS_WG_MAX) {   // on the per-wave streams
+            if (int rc = lds_opt_in<&k_sector_adjoint3<NT>>(h, LDS_WG_MAX)) return rc;
             h->forms_used |= 64u;
-            hipLaunchKernelGGL((k_sector_adjoint3<NT>), dim3(sg.L.ntiles), dim3(NT), sector_adjoint3_smem(sg), h->stream,
+            hipLaunchKernelGGL((k_sector_adjoint3<NT>), dim3(sg.L.ntiles), dim3(NT), smem3, h->stream,
                                (const double *)E.d_buf[cur].p, (const double *)E.d_lam[lcur].p, (double *)E.d_buf[cur ^ 1].p,
                                (double *)E.d_lam[lcur ^ 1].p, s + 1 == (int)E.segs.size() ? 1 : 0,
                                s ? (const uint32_t *)sg.d_bdst.p : (const uint32_t *)nullptr, (const uint32_t *)sg.L.d_off.p,
                                (const uint32_t *)sg.d_rowinfo.p, sg.nruns, sg.stream_waves, (const uint32_t *)sg.d_stream.p,
-                               (const uint16_t *)sg.d_rowhdr.p, (const RotParam *)h->d_rp.p, sg.rot0, sg.nrot, std::max(sg.L.max_tile, 1u),
+                               (const uint16_t *)sg.d_rowhdr.p, (const RotParam *)h->d_rp.p, sg.rot0, sg.nrot, cap,
                                (double *)E.d_wpart.p, (int)h->srots.size(), E.sb);
             cur ^= 1;
             lcur ^= 1;
             continue;
         }
         h->forms_used |= 32u;
-        hipLaunchKernelGGL((k_sector_adjoint2<NT, WPT>), dim3(sg.L.ntiles), dim3(NT), sector_adjoint2_smem(sg, NT), h->stream,
+        hipLaunchKernelGGL((k_sector_adjoint2<NT, WPT>), dim3(sg.L.ntiles), dim3(NT),
+                           sec_adjoint2_lds(cap, sg.nrot, NT / 64, sg.maxchunks).bytes, h->stream,
                            (const double *)E.d_buf[cur].p, (const double *)E.d_lam[lcur].p, (double *)E.d_buf[cur ^ 1].p,
                            (double *)E.d_lam[lcur ^ 1].p, s + 1 == (int)E.segs.size() ? 1 : 0,
                            s ? (const uint32_t *)sg.d_bdst.p : (const uint32_t *)nullptr, (const uint32_t *)sg.L.d_off.p,
                            (const uint32_t *)sg.d_poff.p, sg.nops, (const uint64_t *)sg.d_wide.p, (const uint16_t *)sg.d_rounds.p,
-                           sg.maxchunks, (const RotParam *)h->d_rp.p, sg.rot0, sg.nrot, std::max(sg.L.max_tile, 1u),
+                           sg.maxchunks, (const RotParam *)h->d_rp.p, sg.rot0, sg.nrot, cap,
                            (double *)E.d_wpart.p, (int)h->srots.size());
         cur ^= 1;
         lcur ^= 1;
@@ -1734,51 +1646,35 @@ int launch_sector_adjoint2(ovqe_handle h, SectorEngine &E, int last) {
 
 // the backward sweeps hold psi and lambda of a tile in LDS, plus one partial sum per wave and table entry: the largest
 // workgroup size (<= want) whose sweeps all fit, 0 if none does
-size_t sector_adjoint_smem(const SectorSeg &sg, int nt) {
-    const uint32_t cap = std::max(sg.L.max_tile, 1u);
-    return 2 * (size_t)((cap + 1u) & ~1u) * sizeof(double) + (size_t)sg.nrot * sizeof(double2) +
-           (size_t)(nt / 64) * sg.nrot * sizeof(double) + ((size_t)sg.nops + 2) * sizeof(SecOpLds) +
-           2 * (size_t)SEC_STAGE_WORDS * sizeof(uint32_t);
-}
 int sector_adjoint_threads(ovqe_handle h, int want) {
     const SectorEngine &E = h->sec;
     for (int nt : {1024, 512, 256}) {
         if (nt > want) continue;
         bool fits = true;
-        for (const SectorSeg &sg : E.segs) fits = fits && sector_adjoint_smem(sg, nt) <= 160 * 1024;
+        for (const SectorSeg &sg : E.segs) fits = fits && sec_adjoint_lds(std::max(sg.L.max_tile, 1u), sg.nrot, sg.nops, nt / 64).bytes <= LDS_WG_MAX;
         if (fits) return nt;
     }
     return 0;
 }
-// backward sweeps of a regular support (k_sector_adjoint_reg): psi and lambda tiles + the sweep's table + the waves' rows in LDS
-// (rows: two banks of `runcap` units x two ops of a block x the waves' eight sums)
-size_t sector_adjoint_reg_smem(const SectorEngine &E, const SectorSeg &sg, int nt, int runcap) {
-    return ((size_t)2 * sizeof(double) << E.reg_m) + (size_t)sg.nops * SEC_REG_TSTRIDE * sizeof(double2) +
-           (size_t)2 * runcap * 2 * (nt / 64) * SEC_REG_WROWS * 8 * sizeof(double);
-}
+// backward sweeps of a regular support (k_sector_adjoint_reg; LDS: sec_reg_lds with psi's and lambda's tile).
 // units of a run whose rows wait in LDS: as many as keep two workgroups on a CU (80 KB each), 1..16
 int sector_adjoint_reg_runcap(const SectorEngine &E, const SectorSeg &sg, int nt) {
-    const size_t base = sector_adjoint_reg_smem(E, sg, nt, 0), per = sector_adjoint_reg_smem(E, sg, nt, 1) - base;
-    const size_t room = base < (size_t)80 * 1024 ? (size_t)80 * 1024 - base : 0;
+    const size_t base = sec_reg_lds(E.reg_m, 2, sg.nops, nt / 64, 0).bytes, per = sec_reg_lds(E.reg_m, 2, sg.nops, nt / 64, 1).bytes - base;
+    const size_t room = base < LDS_TWO_PER_CU ? LDS_TWO_PER_CU - base : 0;
     return (int)std::max<size_t>(1, std::min<size_t>(16, room / per));
 }
 bool sector_adjoint_reg_fits(ovqe_handle h, const SectorEngine &E) {
     if (!h->opt_sector_regular || !sector_reg_fits(E)) return false;
     for (const SectorSeg &sg : E.segs)
-        if (sector_adjoint_reg_smem(E, sg, 256, 1) > 160 * 1024) return false;
+        if (sec_reg_lds(E.reg_m, 2, sg.nops, 256 / 64, 1).bytes > LDS_WG_MAX) return false;
     return true;
 }
 int launch_sector_adjoint_reg(ovqe_handle h, SectorEngine &E, int last) {
     constexpr int NT = 256;
-    static bool attr_done_dev[64] = {};
-    bool &attr_done = attr_done_dev[h->device & 63];
-    if (!attr_done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sector_adjoint_reg<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done = true;
-    }
     size_t wmax = 1;
     for (const SectorSeg &sg : E.segs) wmax = std::max(wmax, (size_t)sg.L.ntiles * sg.nops * 8);
-    int rc = ensure(h, E.d_wpart, wmax * sizeof(double));
+    int rc = lds_opt_in<&k_sector_adjoint_reg<NT>>(h, LDS_WG_MAX);
+    if (!rc) rc = ensure(h, E.d_wpart, wmax * sizeof(double));
     if (rc) return rc;
     HIPC(h, hipMemsetAsync(E.d_w.p, 0, std::max<size_t>(h->srots.size(), 1) * sizeof(double), h->stream));
     int cur = last, lcur = 0;   // psi in E.d_buf[cur], lambda in E.d_lam[lcur], both in the last sweep's (canonical) order
@@ -1786,7 +1682,7 @@ int launch_sector_adjoint_reg(ovqe_handle h, SectorEngine &E, int last) {
         const SectorSeg &sg = E.segs[si];
         const int runcap = (E.reg_plan_threads == NT && h->opt_sector_reg_runs) ? sector_adjoint_reg_runcap(E, sg, NT) : 1;
         h->forms_used |= 128u;
-        hipLaunchKernelGGL((k_sector_adjoint_reg<NT>), dim3(sg.L.ntiles), dim3(NT), sector_adjoint_reg_smem(E, sg, NT, runcap), h->stream,
+        hipLaunchKernelGGL((k_sector_adjoint_reg<NT>), dim3(sg.L.ntiles), dim3(NT), sec_reg_lds(E.reg_m, 2, sg.nops, NT / 64, runcap).bytes, h->stream,
                            (const double *)E.d_buf[cur].p, (const double *)E.d_lam[lcur].p, (double *)E.d_buf[cur ^ 1].p,
                            (double *)E.d_lam[lcur ^ 1].p,
                            si ? (const uint32_t *)(sg.d_regsrc.p ? sg.d_regsrc.p : sg.d_srcpad.p) : (const uint32_t *)nullptr,
@@ -1871,12 +1767,11 @@ int run_sector_gradient(ovqe_handle h, const double *theta, double *energy, doub
 // spin-conserving ansatz on a Hartree-Fock determinant: the FCI energy of that symmetry sector), by two-pass Lanczos on
 // the sector tables: the matrix-vector product is lambda = H v of the gradient path.
 int sector_matvec(ovqe_handle h, SectorEngine &E, const double *in, double *out) {
-    static bool attr_done_dev[2][64] = {};
     // lambda needs a second tile in LDS: where that leaves one 512-thread workgroup per CU (expect: two or three), 1024 threads
     // keep 16 waves on the CU (24 qubits: 1.33 -> 1.19 ms per pass).  Round 5: with two loads in flight per lane instead of four the
     // kernel needs 109 registers (161 before: the 1024-thread form spilled 24 of them) and 1024 threads also win where two 512-thread
     // workgroups would fit (N2 QUCCSD tables, tiles of 4096: gradient 14.2 -> 13.8 ms; UCCSD 2.91 -> 2.83 ms)
-    const size_t smem = sector_h_smem(E, 2);
+    const size_t smem = sec_h_lds_bytes(std::max(E.h_max_tile, 1u), 2, (uint32_t)E.h_max_dict);
     const int nt = smem > 48 * 1024 ? 1024 : 512;
     // one launch per sweep, in sequence: no global atomics (k_sector_apply, modes 1 / 2), the first sweep stores; every support
     // entry sits in exactly one tile of every sweep, so sweep 0's stores cover the whole vector (no memset)
@@ -1889,13 +1784,11 @@ int sector_matvec(ovqe_handle h, SectorEngine &E, const double *in, double *out)
     for (unsigned s0 = 0; s0 < (seq ? nsw : 1u); ++s0) {
         const int mode = seq ? (s0 == 0 ? 2 : 1) : 0;
         if (nt == 1024) {
-            int rc = sector_h_attr(h, &k_sector_apply<1024>, attr_done_dev[1][h->device & 63]);
-            if (rc) return rc;
+            if (int rc = lds_opt_in<&k_sector_apply<1024>>(h, SEC_LDS_MAX)) return rc;
             hipLaunchKernelGGL((k_sector_apply<1024>), grid, dim3(1024), smem, h->stream, in, (const SecHSweep *)E.d_hdesc.p, out,
                                std::max(E.h_max_tile, 1u), (int)s0, mode);
         } else {
-            int rc = sector_h_attr(h, &k_sector_apply<SEC_H_THREADS>, attr_done_dev[0][h->device & 63]);
-            if (rc) return rc;
+            if (int rc = lds_opt_in<&k_sector_apply<SEC_H_THREADS>>(h, SEC_LDS_MAX)) return rc;
             hipLaunchKernelGGL((k_sector_apply<SEC_H_THREADS>), grid, dim3(SEC_H_THREADS), smem, h->stream, in, (const SecHSweep *)E.d_hdesc.p,
                                out, std::max(E.h_max_tile, 1u), (int)s0, mode);
         }

@@ -406,13 +406,7 @@ int build_sparse_program(ovqe_handle h) {
 
 template <int SPW, bool STAGE = false>
 int launch_sparse(ovqe_handle h, const SparseArgs &A, int grid, size_t smem) {
-    static bool attr_done_dev[64] = {};  // function attributes are per device
-    bool &attr_done = attr_done_dev[h->device & 63];
-    if (!attr_done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_vqe<SPW, STAGE>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done = true;
-    }
+    if (int rc = lds_opt_in<&k_sparse_vqe<SPW, STAGE>>(h, LDS_WG_MAX)) return rc;
     hipLaunchKernelGGL((k_sparse_vqe<SPW, STAGE>), dim3(grid), dim3(64), smem, h->stream, A, h->cur_theta,
                        (const SmallRot *)h->d_rots.p, (const SpOp *)h->d_sp_ops.p, (const uint32_t *)h->d_sp_pairs.p,
                        (const SpEntry *)h->d_sp_entries.p, h->cur_energies);
@@ -441,36 +435,30 @@ enum : uint32_t {
 // the workgroup geometry of the rows form: batches from SHARED_MIN_B on — measured (tools/exp_shared_sweep.py, profiles/shared_rows): it
 // wins beyond the spread at every batch size the rows form takes, 2048 included (H2O: 35.6 against 40.3 us)
 constexpr int64_t SHARED_MIN_B = 2048;
-constexpr size_t SHARED_MAX_LDS = 80 * 1024;   // two workgroups per CU
 
 template <int NW, int EPT, int SSTRIDE, int DBG>
 int launch_rows_shared_dbg(ovqe_handle h, const SparseArgs &R, size_t smem) {
     constexpr int NS = 2 * NW;
-    struct PerDevice {
-        bool attr = false;
-        size_t smem = 0;
-        int per_cu = 0;   // workgroups one CU holds at once, at this much LDS
-    };
-    static PerDevice per_dev[64];   // function attributes are per device
-    PerDevice &pd = per_dev[h->device & 63];
-    const auto kern = &k_sparse_vqe_rows_shared<NW, EPT, SSTRIDE, DBG>;
-    if (!pd.attr) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        pd.attr = true;
-    }
-    if (pd.smem != smem) {
+    // workgroups one CU holds at once at this much LDS, cached per device: both in ONE word (smem << 8 | per_cu; smem <= 80 KiB,
+    // per_cu <= 32), so that two threads with a handle each never see one without the other
+    static std::atomic<uint32_t> per_dev[64];
+    constexpr auto kern = &k_sparse_vqe_rows_shared<NW, EPT, SSTRIDE, DBG>;
+    if (int rc = lds_opt_in<kern>(h, LDS_WG_MAX)) return rc;
+    uint32_t pd = per_dev[h->device & 63].load(std::memory_order_relaxed);
+    if ((pd >> 8) != smem) {
         int n = 0;
         HIPC(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, NW * 64, smem));
-        pd.per_cu = std::min(std::max(n, 1), 32 / NW);
-        pd.smem = smem;
+        pd = (uint32_t)smem << 8 | (uint32_t)std::min(std::max(n, 1), 32 / NW);
+        per_dev[h->device & 63].store(pd, std::memory_order_relaxed);
     }
+    const int per_cu = (int)(pd & 255u);
     if (h->num_cus <= 0) {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus <= 0) cus = 256;
         h->num_cus = cus;
     }
     // persistent: as many workgroups as the chip holds at once, each walks work items of 2 NW evaluations
-    const int grid = (int)std::min<int64_t>((R.B + NS - 1) / NS, (int64_t)h->num_cus * pd.per_cu);
+    const int grid = (int)std::min<int64_t>((R.B + NS - 1) / NS, (int64_t)h->num_cus * per_cu);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), smem, h->stream, R, h->cur_theta, (const SmallRot *)h->d_sp_prim.p,
                        (const uint64_t *)h->d_sp_rows.p, h->sp_nrows4, (const SpEntry *)h->d_sp_entries.p, h->cur_energies);
     HIPC(h, hipGetLastError());
@@ -482,8 +470,8 @@ int launch_rows_shared_dbg(ovqe_handle h, const SparseArgs &R, size_t smem) {
 template <int NW, int EPT, int SSTRIDE>
 int launch_rows_shared(ovqe_handle h, const SparseArgs &R, bool *taken) {
     constexpr int NS = 2 * NW;
-    const size_t smem = (size_t)NS * SSTRIDE + (size_t)NS * (R.ntab + 1) * sizeof(double2) + (size_t)NW * NS * sizeof(double);
-    *taken = R.nent >= 1 && R.nent <= NW * 64 * EPT && (size_t)R.mpad * sizeof(double) <= (size_t)SSTRIDE && smem <= SHARED_MAX_LDS;
+    const size_t smem = sp_rows_shared_lds<NW, SSTRIDE>(R.ntab).bytes;
+    *taken = R.nent >= 1 && R.nent <= NW * 64 * EPT && (size_t)R.mpad * sizeof(double) <= (size_t)SSTRIDE && smem <= LDS_TWO_PER_CU;
     if (!*taken) return OVQE_OK;
 #ifdef OVQE_TESTING
     switch (h->opt_sparse_dbg) {
@@ -513,16 +501,14 @@ int run_sparse(ovqe_handle h, int64_t B, const double *theta, double *energies, 
     A.B = B;
     A.constant = h->ham.constant;
     A.dbg = h->opt_sparse_dbg;
-    const size_t per_eval = (size_t)A.mpad * sizeof(double) + (size_t)A.ntab * sizeof(double2);
-    static_assert(sizeof(double2) == 16 && sizeof(SpOp) == 16, "LDS carve-up of k_sparse_vqe assumes 16-byte records");
     int spw = h->opt_sparse_spw;
     if (spw != 1 && spw != 2 && spw != 4) spw = B >= 2048 ? 2 : 1;  // measured: 2 evaluations per wave is the sweet spot
     if (B <= 1024) spw = 1;
-    while (spw > 1 && per_eval * spw > 64 * 1024) spw >>= 1;
+    while (spw > 1 && sp_vqe_lds(A, spw, false).bytes > 64 * 1024) spw >>= 1;
     // the workgroup form holds one cos/sin entry per distinct angle (at most 4094 of them, 64 KiB: its row tables exist only then)
     // and fits whatever the whole table takes; every other form holds the whole table
     const bool wg = B <= 256 && h->sp_nrows8 && h->opt_sparse_rows && h->opt_sparse_wg;
-    if (!wg && per_eval * spw > 150 * 1024) {
+    if (!wg && sp_vqe_lds(A, spw, false).bytes > LDS_WG_BUDGET) {
         h->sp_forms |= SPF_DECLINED;
         return OVQE_OK;
     }
@@ -549,20 +535,16 @@ int run_sparse(ovqe_handle h, int64_t B, const double *theta, double *energies, 
     const int grid = (int)std::min<int64_t>(nwork, 256 * 32);
     if (!zero_copy) HIPC(h, hipEventRecord(h->ev0, h->stream));
     // latency path: op table + pair words staged in LDS (one wave per evaluation, occupancy does not matter)
-    const size_t staged = per_eval + (size_t)A.nops * sizeof(SpOp) + (size_t)A.npairs * sizeof(uint32_t);
+    const size_t staged = sp_vqe_lds(A, 1, true).bytes;
     if (wg) {
         // latency path: one evaluation per 1024-thread workgroup, at most one workgroup per CU (k_sparse_vqe_wg; measured: H2O
         // B = 1 / 141 32 / 37 us against 60 / 61 us with one wave per evaluation, B = 1024 129 against 115 us)
         SparseArgs R = A;
         R.mpad = (h->sp_mp + 128 + 1) & ~1;
         R.ntab = h->sp_nprim;
-        const size_t smem = (size_t)R.mpad * sizeof(double) + (size_t)(R.ntab + 1) * sizeof(double2);
-        static bool attr_wg_dev[64] = {};
-        bool &attr_wg = attr_wg_dev[h->device & 63];
-        if (!attr_wg) {
-            HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_vqe_wg<1024, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-            attr_wg = true;
-        }
+        const size_t smem = sp_rows_lds(R, 1).bytes;
+        rc = lds_opt_in<&k_sparse_vqe_wg<1024, 10>>(h, LDS_WG_BUDGET);
+        if (rc) return rc;
         hipLaunchKernelGGL((k_sparse_vqe_wg<1024, 10>), dim3((unsigned)std::min<int64_t>(B, 1024)), dim3(1024), smem, h->stream, R, h->cur_theta,
                            (const SmallRot *)h->d_sp_prim.p, (const uint64_t *)h->d_sp_rows64.p, h->sp_nrows8, (const SpEntry *)h->d_sp_entries.p,
                            h->cur_energies);
@@ -574,14 +556,13 @@ int run_sparse(ovqe_handle h, int64_t B, const double *theta, double *energies, 
         h->sp_forms |= SPF_STAGED1;
     }
     else if (spw == 4) {
-        rc = launch_sparse<4>(h, A, grid, per_eval * 4);
+        rc = launch_sparse<4>(h, A, grid, sp_vqe_lds(A, 4, false).bytes);
         h->sp_forms |= SPF_PLAIN4;
     }
     else if (spw == 2 && h->sp_nrows4 && h->opt_sparse_rows) {
         SparseArgs R = A;
         R.mpad = (h->sp_mp + 64 + 1) & ~1;   // + the padded lanes' spare slots
         R.ntab = h->sp_nprim;                // one entry per distinct angle
-        const size_t per_eval_r = (size_t)R.mpad * sizeof(double) + (size_t)(R.ntab + 1) * sizeof(double2);
         // batches that fill the chip: the workgroup geometry when one of its instances holds the program — a pure function of the
         // program and B; smaller instance first
         bool shared = false;
@@ -597,19 +578,18 @@ int run_sparse(ovqe_handle h, int64_t B, const double *theta, double *energies, 
             if (rc) return rc;
         }
         if (!shared) {
-            static bool attr_rows_dev[64] = {};
-            bool &attr_rows = attr_rows_dev[h->device & 63];
-            if (!attr_rows) {
-                HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_vqe_rows<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                attr_rows = true;
-            }
 #define OVQE_ROWS(DBG_)                                                                                                                       \
-    hipLaunchKernelGGL((k_sparse_vqe_rows<2, DBG_>), dim3(grid), dim3(64), per_eval_r * 2, h->stream, R, h->cur_theta, (const SmallRot *)h->d_sp_prim.p, \
-                       (const uint64_t *)h->d_sp_rows.p, h->sp_nrows4, (const SpEntry *)h->d_sp_entries.p, h->cur_energies)
-            switch (h->opt_sparse_dbg) {   // (measurement variants carry their own LDS attribute: set on the fly)
-            case 1: HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_vqe_rows<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); OVQE_ROWS(1); break;
-            case 2: HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_vqe_rows<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); OVQE_ROWS(2); break;
-            case 3: HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_vqe_rows<2, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); OVQE_ROWS(3); break;
+    do {                                                                                                                                      \
+        rc = lds_opt_in<&k_sparse_vqe_rows<2, DBG_>>(h, LDS_WG_MAX);                                                                          \
+        if (rc) return rc;                                                                                                                    \
+        hipLaunchKernelGGL((k_sparse_vqe_rows<2, DBG_>), dim3(grid), dim3(64), sp_rows_lds(R, 2).bytes, h->stream, R, h->cur_theta,            \
+                           (const SmallRot *)h->d_sp_prim.p, (const uint64_t *)h->d_sp_rows.p, h->sp_nrows4, (const SpEntry *)h->d_sp_entries.p, \
+                           h->cur_energies);                                                                                                  \
+    } while (0)
+            switch (h->opt_sparse_dbg) {   // (measurement variants)
+            case 1: OVQE_ROWS(1); break;
+            case 2: OVQE_ROWS(2); break;
+            case 3: OVQE_ROWS(3); break;
             default: OVQE_ROWS(0);
             }
 #undef OVQE_ROWS
@@ -619,11 +599,11 @@ int run_sparse(ovqe_handle h, int64_t B, const double *theta, double *energies, 
         h->sp_forms |= SPF_ROWS2;
     }
     else if (spw == 2) {
-        rc = launch_sparse<2>(h, A, grid, per_eval * 2);
+        rc = launch_sparse<2>(h, A, grid, sp_vqe_lds(A, 2, false).bytes);
         h->sp_forms |= SPF_PLAIN2;
     }
     else {
-        rc = launch_sparse<1>(h, A, grid, per_eval);
+        rc = launch_sparse<1>(h, A, grid, sp_vqe_lds(A, 1, false).bytes);
         h->sp_forms |= SPF_PLAIN1;
     }
     if (rc) return rc;
@@ -667,21 +647,14 @@ int run_sparse_gradient(ovqe_handle h, const double *theta, double *energy, doub
     A.npairs = (int)h->sp_npairs;
     A.B = 1;
     A.constant = h->ham.constant;
-    const size_t base = 2 * (size_t)A.mpad * sizeof(double) + (size_t)A.ntab * (sizeof(double2) + sizeof(double)) +
-                        (size_t)((A.K + 1) & ~1) * sizeof(double);
-    const size_t staged = base + (size_t)A.nops * sizeof(SpOp) + (size_t)A.npairs * sizeof(uint32_t);
-    if (base > 150 * 1024) {
+    const size_t base = sp_grad_lds(A, false).bytes, staged = sp_grad_lds(A, true).bytes;
+    if (base > LDS_WG_BUDGET) {
         h->sp_forms |= SPF_DECLINED;
         return OVQE_OK;
     }
-    const bool stage = staged <= 150 * 1024;
-    static bool attr_done_dev[64] = {};
-    bool &attr_done = attr_done_dev[h->device & 63];
-    if (!attr_done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_grad<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_grad<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done = true;
-    }
+    const bool stage = staged <= LDS_WG_BUDGET;
+    rc = lds_opt_in<&k_sparse_grad<true>, &k_sparse_grad<false>>(h, LDS_WG_MAX);
+    if (rc) return rc;
     const bool zero_copy = mapped_io(h, 2);   // theta [K] | energy | gradient [K] in the pinned, device-mapped buffer
     const double *d_theta;
     double *d_e, *d_g;
@@ -704,15 +677,10 @@ int run_sparse_gradient(ovqe_handle h, const double *theta, double *energy, doub
         SparseArgs R = A;
         R.mpad = (h->sp_mp + 128 + 1) & ~1;
         R.ntab = h->sp_nprim;
-        const size_t smem = 2 * (size_t)R.mpad * sizeof(double) + (size_t)(R.ntab + 1) * sizeof(double2) + (size_t)((R.ntab + 2) & ~1) * sizeof(double) +
-                            (size_t)((R.K + 1) & ~1) * sizeof(double);
-        static bool attr_gwg_dev[64] = {};
-        bool &attr_gwg = attr_gwg_dev[h->device & 63];
-        if (!attr_gwg) {
-            HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sparse_grad_wg<1024, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-            attr_gwg = true;
-        }
-        if (smem <= 150 * 1024) {
+        const size_t smem = sp_grad_wg_lds(R).bytes;
+        rc = lds_opt_in<&k_sparse_grad_wg<1024, 10>>(h, LDS_WG_BUDGET);
+        if (rc) return rc;
+        if (smem <= LDS_WG_BUDGET) {
             hipLaunchKernelGGL((k_sparse_grad_wg<1024, 10>), dim3(1), dim3(1024), smem, h->stream, R, d_theta, (const SmallRot *)h->d_sp_prim.p,
                                (const uint64_t *)h->d_sp_rows64.p, h->sp_nrows8, (const SpEntry *)h->d_sp_entries.p, d_e, d_g);
             h->sp_forms |= SPF_GRAD_WG;

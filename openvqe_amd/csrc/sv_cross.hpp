@@ -36,9 +36,10 @@ __global__ __launch_bounds__(NT) void k_tile_cross(const amp_t *__restrict__ ket
     constexpr uint32_t NEL = 1u << M;
     constexpr int TRIPS = NEL / NT;
     double2 *tile = reinterpret_cast<double2 *>(smem);
-    ExTermLds *lt = reinterpret_cast<ExTermLds *>(smem + (size_t)NEL * sizeof(double2));
-    ExAGroupT *lg = reinterpret_cast<ExAGroupT *>(lt + TILE_TERM_CAP);
-    double2 *red = reinterpret_cast<double2 *>(lg + TILE_APPLY_GROUPS);
+    constexpr TileApplyLds L = tile_apply_lds<M>(sizeof(double2), NT / 64);
+    ExTermLds *lt = reinterpret_cast<ExTermLds *>(smem + L.terms);
+    ExAGroupT *lg = reinterpret_cast<ExAGroupT *>(smem + L.groups);
+    double2 *red = reinterpret_cast<double2 *>(smem + L.red);
     const v2d *p = reinterpret_cast<const v2d *>(ket);
     v2d *q = reinterpret_cast<v2d *>(other);
 
@@ -171,9 +172,10 @@ __global__ __launch_bounds__(NT) void k_tile_cross_real(const double *__restrict
     constexpr int TRIPS = NELV / NT;
     double *tile = reinterpret_cast<double *>(smem);
     double2 *tilev = reinterpret_cast<double2 *>(smem);
-    ExTermLds *lt = reinterpret_cast<ExTermLds *>(smem + (size_t)NEL * sizeof(double));
-    ExAGroupT *lg = reinterpret_cast<ExAGroupT *>(lt + TILE_TERM_CAP);
-    double2 *red = reinterpret_cast<double2 *>(lg + TILE_APPLY_GROUPS);
+    constexpr TileApplyLds L = tile_apply_lds<M>(sizeof(double), NT / 64);
+    ExTermLds *lt = reinterpret_cast<ExTermLds *>(smem + L.terms);
+    ExAGroupT *lg = reinterpret_cast<ExAGroupT *>(smem + L.groups);
+    double2 *red = reinterpret_cast<double2 *>(smem + L.red);
     const v2d *p = reinterpret_cast<const v2d *>(ket);
     const v2d *q = reinterpret_cast<const v2d *>(bra);
 

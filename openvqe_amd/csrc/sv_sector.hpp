@@ -224,6 +224,14 @@ __device__ __forceinline__ int sec_find(const uint32_t *lk, int n, uint32_t key)
     return -1;
 }
 
+// Dynamic LDS of the table builders (k_sec_pairs, k_sec_pairs2, k_sec_hbuild) starts with the tile's key map: a table of 2^M
+// 16-bit slots (dense) or the tile's sorted local keys.  `staged`: arrays follow the map (the staged forms below), which is then
+// rounded up to 16 bytes; the result is what those kernels receive as map_bytes.
+__host__ __device__ inline size_t sec_map_bytes(bool dense, int M, uint32_t max_tile, bool staged) {
+    const size_t keys = (size_t)(max_tile > 1u ? max_tile : 1u) * sizeof(uint32_t);
+    return dense ? ((size_t)2 << M) : (staged ? ((keys + 15) & ~(size_t)15) : keys);
+}
+
 // ---- pair lists of one circuit sweep ----------------------------------------------------------------------------------
 // One workgroup per tile.  FILL = false: cnt[tile * nops + o] = pairs of op o in the tile;  FILL = true: the pair words at
 // poff[tile * (nops + 1) + o], in ascending slot order (a fixed order: results are reproducible).  A member of an active
@@ -310,6 +318,14 @@ __global__ __launch_bounds__(NT) void k_sec_pairs(const uint32_t *__restrict__ s
     }
 }
 
+struct SecPairs2Lds { size_t ops, pats, xl, wcnt, bytes; };   // the key map is at 0
+__host__ __device__ inline SecPairs2Lds sec_pairs2_lds(size_t map_bytes, int nops, int npats, int nw) {
+    const size_t ops = map_bytes;                                  // [nops] SecBuildOp
+    const size_t pats = ops + (size_t)nops * sizeof(SecBuildOp);   // [npats] SecPat
+    const size_t xl = pats + (size_t)npats * sizeof(SecPat);       // [nops]
+    const size_t wcnt = xl + (size_t)nops * sizeof(uint32_t);      // [nops][nw], count pass only
+    return {ops, pats, xl, wcnt, wcnt + (size_t)nops * nw * sizeof(uint32_t)};
+}
 // Second form of the builder (round 4): no workgroup barrier inside the loop over the ops.  Every WAVE owns a contiguous range of the
 // tile's entries (a multiple of 64), so the pairs of an op come out in ascending slot order — the layout of the first form, bit for
 // bit — from a ballot inside the wave and, between the waves, from per-(op, wave) counts: the count pass leaves their exclusive
@@ -333,13 +349,12 @@ __global__ __launch_bounds__(NT) void k_sec_pairs2(const uint32_t *__restrict__ 
             for (int o = threadIdx.x; o < nops; o += NT) cnt[(size_t)t * nops + o] = 0u;
         return;
     }
-    unsigned char *p = reinterpret_cast<unsigned char *>(sec_lk) + map_bytes;
-    SecBuildOp *lops = reinterpret_cast<SecBuildOp *>(p);
-    p += (size_t)nops * sizeof(SecBuildOp);
-    SecPat *lpats = reinterpret_cast<SecPat *>(p);
-    p += (size_t)npats * sizeof(SecPat);
-    uint32_t *lxl = reinterpret_cast<uint32_t *>(p);
-    uint32_t *wcnt = lxl + nops;   // [nops][NW], count pass only
+    const SecPairs2Lds L = sec_pairs2_lds(map_bytes, nops, npats, NW);
+    unsigned char *const lds = reinterpret_cast<unsigned char *>(sec_lk);
+    SecBuildOp *lops = reinterpret_cast<SecBuildOp *>(lds + L.ops);
+    SecPat *lpats = reinterpret_cast<SecPat *>(lds + L.pats);
+    uint32_t *lxl = reinterpret_cast<uint32_t *>(lds + L.xl);
+    uint32_t *wcnt = reinterpret_cast<uint32_t *>(lds + L.wcnt);
     {
         const uint32_t *src = reinterpret_cast<const uint32_t *>(ops);
         uint32_t *dst = reinterpret_cast<uint32_t *>(lops);
@@ -445,6 +460,13 @@ __device__ __forceinline__ void sec_rotate(double *tile, const double2 *tab, uin
     tile[si] = r.x * u + s * v;
     tile[sj] = r.x * v - s * u;
 }
+struct SecSweepLds { size_t cs, ops, wbuf, bytes; };   // the tile is at 0
+__host__ __device__ inline SecSweepLds sec_sweep_lds(uint32_t tile_cap, int nrot, int nops) {
+    const size_t cs = (size_t)((tile_cap + 1u) & ~1u) * sizeof(double);   // [nrot] cos/sin
+    const size_t ops = cs + (size_t)nrot * sizeof(double2);               // [nops + 2] SecOpLds
+    const size_t wbuf = ops + ((size_t)nops + 2) * sizeof(SecOpLds);      // two staging buffers of pair words
+    return {cs, ops, wbuf, wbuf + 2 * (size_t)SEC_STAGE_WORDS * sizeof(uint32_t)};
+}
 // D2: two chunks of pair words ahead in registers instead of one (sweeps whose tiles are dense: the reference's QUCCSD templates at
 // 24 qubits stream 3.5 G pair words per evaluation, two ops per chunk — a chunk's rotations take less time than a trip to HBM,
 // and with one chunk ahead the sweep ran at the bytes-in-flight limit, 2.4 TB/s); requires that no op of a tile exceeds a
@@ -462,10 +484,11 @@ __global__ __launch_bounds__(NT) void k_sector_sweep(const double *__restrict__ 
     constexpr uint32_t W = SEC_STAGE_WORDS;
     constexpr int SEC_WORDS_PER_THREAD = SEC_STAGE_WORDS / NT;
     extern __shared__ __attribute__((aligned(16))) unsigned char sec_smem[];
+    const SecSweepLds L = sec_sweep_lds(tile_cap, nrot, nops);
     double *tile = reinterpret_cast<double *>(sec_smem);
-    double2 *cs = reinterpret_cast<double2 *>(tile + ((tile_cap + 1u) & ~1u));
-    SecOpLds *lop = reinterpret_cast<SecOpLds *>(cs + nrot);
-    uint32_t *wbuf = reinterpret_cast<uint32_t *>(lop + nops + 2);
+    double2 *cs = reinterpret_cast<double2 *>(sec_smem + L.cs);
+    SecOpLds *lop = reinterpret_cast<SecOpLds *>(sec_smem + L.ops);
+    uint32_t *wbuf = reinterpret_cast<uint32_t *>(sec_smem + L.wbuf);
     // Order of the prologue: everything that depends only on the tile number first (op table, cos/sin, tile bounds), then
     // — one round trip later — the first chunk of pair words AND the gather indices together, then the gather itself; the
     // pair words used to wait for the gather (one more dependent trip to memory per sweep).
@@ -672,6 +695,19 @@ __global__ __launch_bounds__(256) void k_sec_widen(const uint32_t *__restrict__ 
         for (uint32_t c = cur_chunk + 1u; c < maxchunks; ++c) rounds[(size_t)t * maxchunks + c] = 0;
     }
 }
+// The second and third forms pad the tile to (cap + 2) & ~1: one spare slot behind it takes the orphan words.  dst_lds = false
+// (batches: three workgroups per CU instead of two): the scatter indices are read from memory when the tile is written.  The third
+// form (k_sector_sweep3) has no round counts: maxchunks = 0.  (It takes its offsets from the two functions, not from the struct:
+// with the struct the compiler gives k_sector_sweep3<1024> 82 registers instead of 80, one wave per SIMD less on paper.)
+__host__ __device__ inline size_t sec_sweep2_cs_off(uint32_t tile_cap) { return (size_t)((tile_cap + 2u) & ~1u) * sizeof(double); }
+__host__ __device__ inline size_t sec_sweep2_dst_off(uint32_t tile_cap, int nrot) { return sec_sweep2_cs_off(tile_cap) + (size_t)nrot * sizeof(double2); }
+struct SecSweep2Lds { size_t cs, dst, nround, bytes; };   // the tile is at 0
+__host__ __device__ inline SecSweep2Lds sec_sweep2_lds(uint32_t tile_cap, int nrot, bool dst_lds, uint32_t maxchunks) {
+    const size_t cs = sec_sweep2_cs_off(tile_cap);                                     // [nrot] cos/sin
+    const size_t dst = sec_sweep2_dst_off(tile_cap, nrot);                             // [tile_cap] scatter indices, if dst_lds
+    const size_t nround = dst + (dst_lds ? (size_t)tile_cap * sizeof(uint32_t) : 0);   // [maxchunks]
+    return {cs, dst, nround, nround + (size_t)maxchunks * sizeof(uint32_t)};
+}
 template <int NT, int WPT>
 __global__ __launch_bounds__(NT) void k_sector_sweep2(const double *__restrict__ in, double *__restrict__ out, size_t in_stride,
                                                       size_t out_stride, const uint32_t *__restrict__ dstpad,
@@ -682,12 +718,12 @@ __global__ __launch_bounds__(NT) void k_sector_sweep2(const double *__restrict__
                                                       const uint32_t *__restrict__ torder) {
     constexpr uint32_t CH = (uint32_t)NT * WPT;   // = the chunk size the tables were built for (host checks)
     extern __shared__ __attribute__((aligned(16))) unsigned char sec_smem[];
+    const SecSweep2Lds L = sec_sweep2_lds(tile_cap, nrot, dst_lds != 0, (uint32_t)maxchunks);
     double *tile = reinterpret_cast<double *>(sec_smem);
     const uint32_t spare = tile_cap;     // one slot behind the tile (see the orphan words below); tile_cap < 0xffff
-    double2 *cs = reinterpret_cast<double2 *>(tile + ((tile_cap + 2u) & ~1u));
-    uint32_t *dst = reinterpret_cast<uint32_t *>(cs + nrot);
-    uint32_t *nround = dst + (dst_lds ? tile_cap : 0u);   // [maxchunks]; dst_lds = 0 (batches: three workgroups per CU instead of two): the
-                                                            // scatter indices are read from memory when the tile is written
+    double2 *cs = reinterpret_cast<double2 *>(sec_smem + L.cs);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(sec_smem + L.dst);
+    uint32_t *nround = reinterpret_cast<uint32_t *>(sec_smem + L.nround);
     // bfast: the grid of a BATCH has the state as its fastest index: the workgroups that
     // apply the same tile's pair words to different states run side by side and share the words through the caches
     const uint32_t tq = bfast ? blockIdx.y : blockIdx.x, b = bfast ? blockIdx.x : blockIdx.y;
@@ -811,6 +847,14 @@ __global__ __launch_bounds__(NT) void k_sector_sweep2(const double *__restrict__
 constexpr int SEC_STREAM_WAVES = 16;     // waves per workgroup the streams are planned for (k_sector_sweep3<1024>)
 constexpr int SEC_STREAM_G = 8;          // rows per batch
 constexpr int SEC_STREAM_CLASS_BITS = 6; // at most 64 slot classes per run
+struct SecWavePlanLds { size_t lpo, wcnt, wflag, own, bytes; };   // bas ([cap] basis index of every slot) is at 0; cap: a multiple of 4
+__host__ __device__ inline SecWavePlanLds sec_wave_plan_lds(uint32_t cap, int nops, int nw) {
+    const size_t lpo = (size_t)cap * sizeof(uint32_t);                  // [nops + 1] the tile's pair offsets
+    const size_t wcnt = lpo + ((size_t)nops + 1) * sizeof(uint32_t);    // [nops][nw] pair words of (op, wave)
+    const size_t wflag = wcnt + (size_t)nops * nw * sizeof(uint32_t);   // [nops][nw] bit 31: a word without partner; bits 0..30: patterns seen (30: that or beyond)
+    const size_t own = wflag + (size_t)nops * nw * sizeof(uint32_t);    // [cap] bytes: class, then wave, of every slot
+    return {lpo, wcnt, wflag, own, own + cap + 16};
+}
 // (SecWaveRun and the host side of the plan: sv_regular_host.hpp)
 // plan (FILL = false: rows per (tile, wave, op) and the class -> wave map) and fill (FILL = true: words and row headers) of the streams;
 // one workgroup per tile
@@ -825,11 +869,12 @@ __global__ __launch_bounds__(256) void k_sec_wave_plan(const uint32_t *__restric
     static_assert(NC == 64, "the classes are dealt to the waves by the 64 lanes of one wave");
     extern __shared__ __attribute__((aligned(16))) unsigned char sec_smem[];
     const int NW = nw;           // waves that work on the rows (a power of two up to SEC_STREAM_WAVES)
-    uint32_t *bas = reinterpret_cast<uint32_t *>(sec_smem);   // [cap] basis index of every slot
-    uint32_t *lpo = bas + cap;                                 // [nops + 1] the tile's pair offsets
-    uint32_t *wcnt = lpo + nops + 1;                           // [nops][NW] pair words of (op, wave)
-    uint32_t *wflag = wcnt + (size_t)nops * NW;                // [nops][NW] bit 31: a word without partner; bits 0..30: patterns seen (30: that or beyond)
-    uint8_t *own = reinterpret_cast<uint8_t *>(wflag + (size_t)nops * NW);   // [cap] class, then wave, of every slot
+    const SecWavePlanLds L = sec_wave_plan_lds(cap, nops, NW);
+    uint32_t *bas = reinterpret_cast<uint32_t *>(sec_smem);
+    uint32_t *lpo = reinterpret_cast<uint32_t *>(sec_smem + L.lpo);
+    uint32_t *wcnt = reinterpret_cast<uint32_t *>(sec_smem + L.wcnt);
+    uint32_t *wflag = reinterpret_cast<uint32_t *>(sec_smem + L.wflag);
+    uint8_t *own = sec_smem + L.own;
     __shared__ uint32_t ccount[NC];
     __shared__ uint8_t wofc[NC];
     const uint32_t t = blockIdx.x, e0 = off[t], n = off[t + 1] - e0;
@@ -973,8 +1018,8 @@ __global__ __launch_bounds__(NT) void k_sector_sweep3(const double *__restrict__
     extern __shared__ __attribute__((aligned(16))) unsigned char sec_smem[];
     double *tile = reinterpret_cast<double *>(sec_smem);
     const uint32_t spare = tile_cap;     // one slot behind the tile: partner of the words whose partner is outside the support
-    double2 *cs = reinterpret_cast<double2 *>(tile + ((tile_cap + 2u) & ~1u));
-    uint32_t *dst = reinterpret_cast<uint32_t *>(cs + nrot);
+    double2 *cs = reinterpret_cast<double2 *>(sec_smem + sec_sweep2_cs_off(tile_cap));
+    uint32_t *dst = reinterpret_cast<uint32_t *>(sec_smem + sec_sweep2_dst_off(tile_cap, nrot));
     const uint32_t tq = bfast ? blockIdx.y : blockIdx.x, b = bfast ? blockIdx.x : blockIdx.y;
     const uint32_t t = torder ? torder[tq] : tq;
     const uint32_t e0 = off[t];
@@ -1138,6 +1183,13 @@ struct SecTermL {
     uint32_t z, pad;
     double c;
 };
+// staged form: the group and term records (16 bytes each) behind the key map
+struct SecHbuildLds { size_t groups, terms, bytes; };   // the key map is at 0
+__host__ __device__ inline SecHbuildLds sec_hbuild_lds(size_t map_bytes, int ngroups, int nterms, bool staged) {
+    const size_t groups = map_bytes;
+    const size_t terms = groups + (size_t)ngroups * sizeof(uint4);
+    return {groups, terms, staged ? terms + (size_t)nterms * sizeof(uint4) : map_bytes};
+}
 template <bool FILL, int NT, bool DENSE>
 __global__ __launch_bounds__(NT) void k_sec_hbuild(const uint32_t *__restrict__ sup, const uint32_t *__restrict__ keys,
                                                    const uint32_t *__restrict__ cid, const uint32_t *__restrict__ off, int M,
@@ -1158,8 +1210,9 @@ __global__ __launch_bounds__(NT) void k_sec_hbuild(const uint32_t *__restrict__ 
     const SecGroupL *groups = groups_g;
     const SecTermL *terms = terms_g;
     if (staged) {
-        uint4 *lg = reinterpret_cast<uint4 *>(reinterpret_cast<unsigned char *>(sec_lk) + map_bytes);
-        uint4 *lt = lg + ngroups;
+        const SecHbuildLds L = sec_hbuild_lds(map_bytes, ngroups, nterms, true);
+        uint4 *lg = reinterpret_cast<uint4 *>(reinterpret_cast<unsigned char *>(sec_lk) + L.groups);
+        uint4 *lt = reinterpret_cast<uint4 *>(reinterpret_cast<unsigned char *>(sec_lk) + L.terms);
         for (int k = threadIdx.x; k < ngroups; k += NT) lg[k] = reinterpret_cast<const uint4 *>(groups_g)[k];
         for (int k = threadIdx.x; k < nterms; k += NT) lt[k] = reinterpret_cast<const uint4 *>(terms_g)[k];
         groups = reinterpret_cast<const SecGroupL *>(lg);
@@ -1355,7 +1408,7 @@ __device__ __forceinline__ double sec_row_sum(const SecHSweep &sw, const SecSlic
                                               const double *tile, const double *dict, double *lam) {
     constexpr int NFL = APPLY ? SEC_H_INFLIGHT_APPLY : SEC_H_INFLIGHT;   // 16-byte (packed: 12-byte) loads in flight per lane
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    double *dummy = const_cast<double *>(dict) + sw.ndict + 2 + lane;   // APPLY only: 64 doubles behind the dictionary (sector_h_smem)
+    double *dummy = const_cast<double *>(dict) + sw.ndict + 2 + lane;   // APPLY only: 64 doubles behind the dictionary (sec_h_lds_bytes)
     const double hai = 0.5 * ai;
     {
         const uint32_t L = mt.clen;   // a multiple of 4
@@ -1472,6 +1525,20 @@ __device__ __forceinline__ void sec_load_tile(double *__restrict__ tile, const d
         }
     }
 }
+// Dynamic LDS of the <H> kernels: `tiles` tiles of (tile_cap + 1) & ~1 doubles (k_sector_expect: the state's; k_sector_expect_batch:
+// one per state of the group, interleaved; k_sector_apply: the state's, then lambda's), behind them the sweep's dictionary and its
+// null element.  The kernels know the tile capacity, the host also the largest dictionary: it sizes the block with the two totals.
+__host__ __device__ inline size_t sec_h_dict_off(uint32_t tile_cap, int tiles) { return (size_t)tiles * ((tile_cap + 1u) & ~1u) * sizeof(double); }
+// k_sector_expect_batch (tiles = NB) and k_sector_apply (tiles = 2); + 64: the dummy slots of k_sector_apply
+__host__ __device__ inline size_t sec_h_lds_bytes(uint32_t tile_cap, int tiles, uint32_t max_dict) {
+    return sec_h_dict_off(tile_cap, tiles) + ((size_t)max_dict + 2 + 64) * sizeof(double);
+}
+// k_sector_expect: tile + dictionary + its null element, nothing else (at 24 qubits 54 272 bytes: three workgroups per CU); at least
+// 512 bytes: the workgroup's reduction scratch lives in the same block
+__host__ __device__ inline size_t sec_expect_lds_bytes(uint32_t tile_cap, uint32_t max_dict) {
+    const size_t b = sec_h_dict_off(tile_cap, 1) + ((size_t)max_dict + 1) * sizeof(double);
+    return b > 512 ? b : 512;
+}
 // E = sum over the sweeps and tiles of sum_rows a_i (sum_e value_e a_j): blockIdx.y = sweep; the workgroups of a sweep
 // share its tiles round robin; one wave per slice of a tile
 template <int NT>
@@ -1480,7 +1547,7 @@ __global__ __launch_bounds__(NT) void k_sector_expect(const double *__restrict__
     constexpr int NW = NT / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char sec_smem[];
     double *tile = reinterpret_cast<double *>(sec_smem);
-    double *dict = tile + ((tile_cap + 1u) & ~1u);
+    double *dict = reinterpret_cast<double *>(sec_smem + sec_h_dict_off(tile_cap, 1));
     const SecHSweep sw = sweeps[blockIdx.y];
     const size_t slot = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
     for (int k = threadIdx.x; k < sw.ndict; k += NT) dict[k] = sw.dict[k];
@@ -1554,7 +1621,7 @@ __global__ __launch_bounds__(NT) void k_sector_expect_batch(const double *__rest
     constexpr int NW = NT / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char sec_smem[];
     double *tile = reinterpret_cast<double *>(sec_smem);
-    double *dict = tile + (size_t)NB * ((tile_cap + 1u) & ~1u);
+    double *dict = reinterpret_cast<double *>(sec_smem + sec_h_dict_off(tile_cap, NB));
     __shared__ double2 red[NW];
     // zfast: the state group is the FASTEST grid index — the workgroups that walk the same tile's elements for different states run
     // side by side and share them through L2 / the Infinity Cache (cached loads) instead of streaming the table once per group
@@ -1686,8 +1753,8 @@ __global__ __launch_bounds__(NT) void k_sector_apply(const double *__restrict__ 
     constexpr int NW = NT / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char sec_smem[];
     double *tile = reinterpret_cast<double *>(sec_smem);
-    double *lam = tile + ((tile_cap + 1u) & ~1u);
-    double *dict = lam + ((tile_cap + 1u) & ~1u);
+    double *lam = reinterpret_cast<double *>(sec_smem + sec_h_dict_off(tile_cap, 1));   // (behind one tile)
+    double *dict = reinterpret_cast<double *>(sec_smem + sec_h_dict_off(tile_cap, 2));
     const SecHSweep sw = sweeps[sweep0 + blockIdx.y];
     for (int k = threadIdx.x; k < sw.ndict; k += NT) dict[k] = sw.dict[k];
     if (threadIdx.x == 0) dict[sw.ndict] = 0.0;
@@ -1738,6 +1805,15 @@ __global__ __launch_bounds__(256) void k_sec_dot(const double *__restrict__ a, c
     if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
 
+struct SecAdjointLds { size_t tl, cs, wacc, ops, wbuf, bytes; };   // psi's tile is at 0
+__host__ __device__ inline SecAdjointLds sec_adjoint_lds(uint32_t tile_cap, int nrot, int nops, int nw) {
+    const size_t tl = (size_t)((tile_cap + 1u) & ~1u) * sizeof(double);   // lambda's tile
+    const size_t cs = 2 * tl;                                             // [nrot] cos/sin
+    const size_t wacc = cs + (size_t)nrot * sizeof(double2);              // [nw][nrot] partial sums
+    const size_t ops = wacc + (size_t)nw * nrot * sizeof(double);         // [nops + 2] SecOpLds
+    const size_t wbuf = ops + ((size_t)nops + 2) * sizeof(SecOpLds);      // two staging buffers of pair words
+    return {tl, cs, wacc, ops, wbuf, wbuf + 2 * (size_t)SEC_STAGE_WORDS * sizeof(uint32_t)};
+}
 // One sweep of the circuit BACKWARDS on psi and lambda together (both in this sweep's order): for every op, last to
 // first, w[entry] += sum over its pairs of sigma (lambda_i psi_j - lambda_j psi_i) on the states after the op (dE/dtheta =
 // 2 coeff w), then both states are rotated back.  Output in the PREVIOUS sweep's order (scatter through src; the first
@@ -1753,13 +1829,13 @@ __global__ __launch_bounds__(NT) void k_sector_adjoint(const double *__restrict_
                                                        double *__restrict__ wpart, int wstride, int sb) {
     constexpr int NW = NT / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char sec_smem[];
-    const uint32_t capp = (tile_cap + 1u) & ~1u;
+    const SecAdjointLds L = sec_adjoint_lds(tile_cap, nrot, nops, NW);
     double *tp = reinterpret_cast<double *>(sec_smem);
-    double *tl = tp + capp;
-    double2 *cs = reinterpret_cast<double2 *>(tl + capp);
-    double *wacc = reinterpret_cast<double *>(cs + nrot);          // [NW][nrot]
-    SecOpLds *lop = reinterpret_cast<SecOpLds *>(wacc + (size_t)NW * nrot);
-    uint32_t *wbuf = reinterpret_cast<uint32_t *>(lop + nops + 2);
+    double *tl = reinterpret_cast<double *>(sec_smem + L.tl);
+    double2 *cs = reinterpret_cast<double2 *>(sec_smem + L.cs);
+    double *wacc = reinterpret_cast<double *>(sec_smem + L.wacc);
+    SecOpLds *lop = reinterpret_cast<SecOpLds *>(sec_smem + L.ops);
+    uint32_t *wbuf = reinterpret_cast<uint32_t *>(sec_smem + L.wbuf);
     const uint32_t t = blockIdx.x, e0 = off[t];
     const int n = (int)(off[t + 1] - e0);
     double *wp = wpart + (size_t)t * wstride + rot0;   // [tile][table entry], zeroed by the host
@@ -1884,6 +1960,18 @@ __global__ __launch_bounds__(NT) void k_sector_adjoint(const double *__restrict_
         }
     }
 }
+// Second and third form of the adjoint: tiles padded as in sec_sweep2_lds (the spare slot), one row of partial sums per wave that
+// works on the tile (k_sector_adjoint2: NT / 64; k_sector_adjoint3: the waves the streams were planned for), the scatter indices,
+// and the round counts (k_sector_adjoint3 has none: maxchunks = 0).
+struct SecAdjoint2Lds { size_t tl, cs, wacc, dst, nround, bytes; };   // psi's tile is at 0
+__host__ __device__ inline SecAdjoint2Lds sec_adjoint2_lds(uint32_t tile_cap, int nrot, int nw, uint32_t maxchunks) {
+    const size_t tl = (size_t)((tile_cap + 2u) & ~1u) * sizeof(double);   // lambda's tile
+    const size_t cs = 2 * tl;                                             // [nrot] cos/sin
+    const size_t wacc = cs + (size_t)nrot * sizeof(double2);              // [nw][nrot] partial sums
+    const size_t dst = wacc + (size_t)nw * nrot * sizeof(double);         // [tile_cap] scatter indices
+    const size_t nround = dst + (size_t)tile_cap * sizeof(uint32_t);      // [maxchunks]
+    return {tl, cs, wacc, dst, nround, nround + (size_t)maxchunks * sizeof(uint32_t)};
+}
 // Second form of the backward sweep, on the tables of k_sector_sweep2 (64-bit words in registers, rounds numbered at build
 // time, walked from the last chunk / round to the first): a word is applied exactly once, so its gradient term
 // sigma (lambda_i psi_j - lambda_j psi_i) stays in a register until its chunk is done and the chunk's terms are then summed
@@ -1902,13 +1990,13 @@ __global__ __launch_bounds__(NT) void k_sector_adjoint2(const double *__restrict
     constexpr uint32_t CH = (uint32_t)NT * WPT;
     constexpr int NW = NT / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char sec_smem[];
-    const uint32_t capp = (tile_cap + 2u) & ~1u;
+    const SecAdjoint2Lds L = sec_adjoint2_lds(tile_cap, nrot, NW, maxchunks);
     double *tp = reinterpret_cast<double *>(sec_smem);
-    double *tl = tp + capp;
-    double2 *cs = reinterpret_cast<double2 *>(tl + capp);
-    double *wacc = reinterpret_cast<double *>(cs + nrot);   // [NW][nrot]
-    uint32_t *dst = reinterpret_cast<uint32_t *>(wacc + (size_t)NW * nrot);
-    uint32_t *nround = dst + tile_cap;   // [maxchunks]
+    double *tl = reinterpret_cast<double *>(sec_smem + L.tl);
+    double2 *cs = reinterpret_cast<double2 *>(sec_smem + L.cs);
+    double *wacc = reinterpret_cast<double *>(sec_smem + L.wacc);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(sec_smem + L.dst);
+    uint32_t *nround = reinterpret_cast<uint32_t *>(sec_smem + L.nround);
     const uint32_t t = blockIdx.x;
     const uint32_t e0 = off[t];
     const uint32_t n = off[t + 1] - e0;
@@ -2314,6 +2402,17 @@ __device__ __forceinline__ void sec_reg_apply_pair(double *__restrict__ tile, co
     }
 }
 
+constexpr int SEC_REG_WROWS = 4;   // rows of 16 lanes per wave: each stores its own eight totals (summed over rows and waves at the flush)
+// Regular support: every tile has 2^mbits slots.  `tiles` tiles (k_sector_sweep_reg: the state's; k_sector_adjoint_reg: psi's, then
+// lambda's), the sweep's (c, s) table, and for the adjoint the waves' rows of partial sums: two banks of `runcap` units x two ops
+// of a block x nw waves x SEC_REG_WROWS rows of lanes x eight sums.
+struct SecRegLds { size_t tile2, cs, wrow, bytes; };   // the first tile is at 0
+__host__ __device__ inline SecRegLds sec_reg_lds(int mbits, int tiles, int nops, int nw, int runcap) {
+    const size_t tile2 = (size_t)sizeof(double) << mbits;
+    const size_t cs = (size_t)tiles * tile2;                                         // [nops][SEC_REG_TSTRIDE]
+    const size_t wrow = cs + (size_t)nops * SEC_REG_TSTRIDE * sizeof(double2);       // [2][runcap][2][nw][SEC_REG_WROWS][8]
+    return {tile2, cs, wrow, wrow + (size_t)2 * runcap * 2 * nw * SEC_REG_WROWS * 8 * sizeof(double)};
+}
 // one sweep: gather the tile from the previous sweep's order (srcpad: tile-padded gather indices; nullptr: |hf> at hf_pos),
 // apply the sweep's ops group by group, write the tile back contiguously (tile t = positions [t 2^m, (t + 1) 2^m) of this
 // sweep's order).  tg = the sweep's part of the (c, s) table (k_sec_reg_angles: 8 entries per op), staged in LDS behind the
@@ -2329,7 +2428,7 @@ __global__ __launch_bounds__(NT) void k_sector_sweep_reg(const double *__restric
     extern __shared__ __attribute__((aligned(16))) unsigned char sec_smem[];
     const uint32_t nslots = 1u << mbits, t = blockIdx.x;
     double *tile = reinterpret_cast<double *>(sec_smem);
-    double2 *cs = reinterpret_cast<double2 *>(tile + nslots);   // [nops][8]
+    double2 *cs = reinterpret_cast<double2 *>(sec_smem + sec_reg_lds(mbits, 1, nops, 0, 0).cs);
     const uint32_t flagmask = sync_all ? 0u : (1u << 27);        // w_nsel bit 27: the next unit follows without a barrier (sv_regular_host.hpp)
     const size_t e0 = (size_t)t * nslots;
     if (srcpad) {
@@ -2463,12 +2562,12 @@ __global__ __launch_bounds__(NT) void k_sector_adjoint3(const double *__restrict
     constexpr int G = SEC_STREAM_G;
     static_assert(G == 8, "the batch's gradient terms are reduced eight rows at a time");
     extern __shared__ __attribute__((aligned(16))) unsigned char sec_smem[];
-    const uint32_t capp = (tile_cap + 2u) & ~1u;
+    const SecAdjoint2Lds L = sec_adjoint2_lds(tile_cap, nrot, nwave, 0u);
     double *tp = reinterpret_cast<double *>(sec_smem);
-    double *tl = tp + capp;
-    double2 *cs = reinterpret_cast<double2 *>(tl + capp);
-    double *wacc = reinterpret_cast<double *>(cs + nrot);   // [nwave][nrot]
-    uint32_t *dst = reinterpret_cast<uint32_t *>(wacc + (size_t)nwave * nrot);
+    double *tl = reinterpret_cast<double *>(sec_smem + L.tl);
+    double2 *cs = reinterpret_cast<double2 *>(sec_smem + L.cs);
+    double *wacc = reinterpret_cast<double *>(sec_smem + L.wacc);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(sec_smem + L.dst);
     const uint32_t t = blockIdx.x;
     const uint32_t e0 = off[t];
     const uint32_t n = off[t + 1] - e0;
@@ -2515,7 +2614,7 @@ __global__ __launch_bounds__(NT) void k_sector_adjoint3(const double *__restrict
     double *mine = wacc + (size_t)min(wv, (uint32_t)nwave - 1u) * nrot;
     const uint32_t mask = (1u << sb) - 1u, pshift = 2u * (uint32_t)sb;
     unsigned char *const pb = reinterpret_cast<unsigned char *>(tp);
-    const uint32_t loff = capp * (uint32_t)sizeof(double);   // lambda's tile behind psi's
+    const uint32_t loff = (uint32_t)L.tl;   // lambda's tile behind psi's
     int rb = nruns - 1;      // next run boundary below this wave's current row
     uint32_t bnd = __builtin_amdgcn_readlane(myb, max(rb, 0));
     for (int b = nb - 1; b >= 0; --b) {
@@ -2612,7 +2711,6 @@ __global__ __launch_bounds__(NT) void k_sector_adjoint3(const double *__restrict
         }
     }
 }
-constexpr int SEC_REG_WROWS = 4;   // rows of 16 lanes per wave: each stores its own eight totals (summed over rows and waves at the flush)
 __device__ __forceinline__ void sec_reg_wstore(double *__restrict__ wslot, const double (&acc)[8]) {   // this wave's 4 x 8 totals
     const double tot = sec_reduce8(acc);
     const int lane = threadIdx.x & 63;
@@ -2754,9 +2852,10 @@ __global__ __launch_bounds__(NT) void k_sector_adjoint_reg(const double *__restr
     extern __shared__ __attribute__((aligned(16))) unsigned char sec_smem[];
     constexpr int NW = NT / 64;
     const uint32_t nslots = 1u << mbits, t = blockIdx.x;
-    double *psi = reinterpret_cast<double *>(sec_smem), *lam = psi + nslots;
-    double2 *cs = reinterpret_cast<double2 *>(lam + nslots);                       // [nops][8]
-    double *wrow = reinterpret_cast<double *>(cs + (size_t)nops * SEC_REG_TSTRIDE);   // [2 banks][runcap units][2 ops of a block][NW][4 rows of lanes][8]
+    const SecRegLds L = sec_reg_lds(mbits, 2, nops, NW, runcap);
+    double *psi = reinterpret_cast<double *>(sec_smem), *lam = reinterpret_cast<double *>(sec_smem + L.tile2);
+    double2 *cs = reinterpret_cast<double2 *>(sec_smem + L.cs);
+    double *wrow = reinterpret_cast<double *>(sec_smem + L.wrow);
     const size_t e0 = (size_t)t * nslots;
     for (uint32_t j = threadIdx.x; j < nslots; j += NT) {
         const uint32_t k = sec_reg_swz(oslot ? (uint32_t)oslot[j] : j);

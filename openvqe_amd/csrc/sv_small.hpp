@@ -450,6 +450,14 @@ __device__ __forceinline__ double small_expectation(const A *st, int n, const Ex
     return acc;
 }
 
+// LDS layout: [state (lds_state)] [rotation table] [ops of the current segment] [reduction scratch]
+struct SmallLds { size_t tab, ops, red, bytes; };   // the state, if it lives in LDS, is at 0
+__host__ __device__ inline SmallLds small_lds(bool real, bool lds_state, int n, int cs_capacity) {
+    const size_t tab = lds_state ? (real ? sizeof(double) : sizeof(amp_t)) << n : 0;   // [cs_capacity] RotLds
+    const size_t ops = tab + (size_t)cs_capacity * sizeof(RotLds);                     // [SMALL_OPS_CAP] SmallOp
+    const size_t red = ops + SMALL_OPS_CAP * sizeof(SmallOp);                          // [16]
+    return {tab, ops, red, red + 16 * sizeof(double2)};
+}
 template <bool REAL, bool LDS_STATE, int NT, int LBITS>
 __global__ __launch_bounds__(NT) void k_small_vqe(SmallArgs A, const double *__restrict__ theta,
                                                   const SmallOp *__restrict__ ops, const SmallRot *__restrict__ rots,
@@ -463,11 +471,11 @@ __global__ __launch_bounds__(NT) void k_small_vqe(SmallArgs A, const double *__r
     typedef typename Amp<REAL>::T amp;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t namps = 1u << A.n;
-    // LDS layout: [state (LDS_STATE)] [rotation table] [reduction scratch]
+    const SmallLds L = small_lds(REAL, LDS_STATE, A.n, A.cs_capacity);
     amp *st = LDS_STATE ? reinterpret_cast<amp *>(smem) : reinterpret_cast<amp *>(workspace) + (size_t)blockIdx.x * namps;
-    RotLds *tab = reinterpret_cast<RotLds *>(smem + (LDS_STATE ? (size_t)namps * sizeof(amp) : 0));
-    SmallOp *lops = reinterpret_cast<SmallOp *>(tab + A.cs_capacity);  // ops of the current segment
-    double2 *red = reinterpret_cast<double2 *>(lops + SMALL_OPS_CAP);
+    RotLds *tab = reinterpret_cast<RotLds *>(smem + L.tab);
+    SmallOp *lops = reinterpret_cast<SmallOp *>(smem + L.ops);
+    double2 *red = reinterpret_cast<double2 *>(smem + L.red);
 
     for (int64_t b = blockIdx.x; b < A.B; b += gridDim.x) {
         const double *th = theta + b * A.K;

@@ -47,6 +47,14 @@ struct SparseArgs {
     int dbg = 0;  // measurements ("sparse_dbg"; the rows kernels take it as a template argument): 1 no sincos, 2 no circuit rows, 3 no Hamiltonian entries
 };
 
+struct SpVqeLds { size_t cs, ops, pairs, bytes; };   // the spw states ([spw][mpad]) are at 0
+__host__ __device__ inline SpVqeLds sp_vqe_lds(const SparseArgs &A, int spw, bool stage) {
+    static_assert(sizeof(double2) == 16 && sizeof(SpOp) == 16, "16-byte records behind an even number of doubles");
+    const size_t cs = (size_t)spw * A.mpad * sizeof(double);          // [spw][ntab], 16-byte aligned
+    const size_t ops = cs + (size_t)spw * A.ntab * sizeof(double2);   // [nops]   (stage)
+    const size_t pairs = ops + (size_t)A.nops * sizeof(SpOp);         // [npairs] (stage)
+    return {cs, ops, pairs, stage ? pairs + (size_t)A.npairs * sizeof(uint32_t) : ops};
+}
 // STAGE = true (small batches, the latency path of one-evaluation-per-call optimisers): the op table and the pair
 // words are copied to LDS at kernel start, so the chain op -> pair word -> amplitudes never waits for global memory.
 template <int SPW, bool STAGE>
@@ -56,11 +64,12 @@ __global__ __launch_bounds__(64) void k_sparse_vqe(SparseArgs A, const double *_
                                                    const SpEntry *__restrict__ entries,
                                                    double *__restrict__ energies) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *st = reinterpret_cast<double *>(smem);                          // [SPW][mpad]
-    double2 *cs = reinterpret_cast<double2 *>(st + (size_t)SPW * A.mpad);   // [SPW][ntab], 16-byte aligned
+    const SpVqeLds L = sp_vqe_lds(A, SPW, STAGE);
+    double *st = reinterpret_cast<double *>(smem);
+    double2 *cs = reinterpret_cast<double2 *>(smem + L.cs);
     const int lane = threadIdx.x;
-    SpOp *lops = reinterpret_cast<SpOp *>(cs + (size_t)SPW * A.ntab);     // [nops]   (STAGE)
-    uint32_t *lpairs = reinterpret_cast<uint32_t *>(lops + A.nops);       // [npairs] (STAGE)
+    SpOp *lops = reinterpret_cast<SpOp *>(smem + L.ops);
+    uint32_t *lpairs = reinterpret_cast<uint32_t *>(smem + L.pairs);
     if constexpr (STAGE) {
         for (int i = lane; i < A.nops; i += 64) lops[i] = ops[i];
         for (int i = lane; i < A.npairs; i += 64) lpairs[i] = pairs[i];
@@ -152,6 +161,14 @@ __global__ __launch_bounds__(64) void k_sparse_vqe(SparseArgs A, const double *_
     }
 }
 
+// k_sparse_vqe_rows (spw = 2; mpad = support + 64 spare slots) and k_sparse_vqe_wg (spw = 1; + 128): the states, then one cos/sin
+// table of ntab + 1 entries each — the last entry is the identity
+struct SpRowsLds { size_t cs, bytes; };   // the states ([spw][mpad]) are at 0
+__host__ __device__ inline SpRowsLds sp_rows_lds(const SparseArgs &A, int spw) {
+    const size_t cs = (size_t)spw * A.mpad * sizeof(double);
+    return {cs, cs + (size_t)spw * (A.ntab + 1) * sizeof(double2)};
+}
+
 // ---- throughput form of the circuit (round 3): rows of 32 padded 64-bit words ------------------------------------------------
 // rocprofv3 counters of k_sparse_vqe<2> on the H2O workload: the LDS pipe is active 6 % of the wave cycles and bank-conflict
 // cycles can be cut by a third without any change in run time; 39 % of the wave cycles are instruction issue — about 60
@@ -169,14 +186,15 @@ __global__ __launch_bounds__(64) void k_sparse_vqe_rows(SparseArgs A, const doub
                                                         double *__restrict__ energies) {
     static_assert(SPW == 2, "rows are built for two evaluations per wave (32 lanes each)");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *st = reinterpret_cast<double *>(smem);                          // [SPW][mpad], mpad = support + 64 spare slots
-    double2 *cs = reinterpret_cast<double2 *>(st + (size_t)SPW * A.mpad);   // [SPW][ntab + 1]: the last entry is the identity
+    const SpRowsLds L = sp_rows_lds(A, SPW);
+    double *st = reinterpret_cast<double *>(smem);
+    double2 *cs = reinterpret_cast<double2 *>(smem + L.cs);
     const int lane = threadIdx.x;
     constexpr int LPS = 64 / SPW;
     const int s = lane / LPS, l = lane % LPS;
     const int ntab1 = A.ntab + 1;
     unsigned char *sbase = smem + (size_t)s * A.mpad * sizeof(double);
-    unsigned char *cbase = smem + (size_t)SPW * A.mpad * sizeof(double) + (size_t)s * ntab1 * sizeof(double2);
+    unsigned char *cbase = smem + L.cs + (size_t)s * ntab1 * sizeof(double2);
     const int64_t nwork = (A.B + SPW - 1) / SPW;
     const uint64_t *rp = rows + l;
     for (int64_t w = blockIdx.x; w < nwork; w += gridDim.x) {
@@ -253,6 +271,15 @@ __global__ __launch_bounds__(64) void k_sparse_vqe_rows(SparseArgs A, const doub
     }
 }
 
+struct SpRowsSharedLds { size_t cs, red, bytes; };   // the 2 NW states, SSTRIDE bytes apart, are at 0
+template <int NW, int SSTRIDE>
+__host__ __device__ constexpr SpRowsSharedLds sp_rows_shared_lds(int ntab) {
+    constexpr size_t NS = 2 * NW;
+    const size_t cs = NS * SSTRIDE;                                          // [NS][ntab + 1]: the last entry is the identity
+    const size_t red = cs + NS * (size_t)(ntab + 1) * sizeof(double2);     // [NW][NS] partial sums
+    return {cs, red, red + (size_t)NW * NS * sizeof(double)};
+}
+
 // ---- throughput form, workgroup geometry: the restricted Hamiltonian in REGISTERS ----------------------------------------------------
 // Half of k_sparse_vqe_rows<2> on the H2O workload is its entry loop: every wave streams the whole entry table from L2 (151 KB)
 // for every pair of evaluations, one 16-byte load + unpacking + two address computations per entry, lane and state.  Here NW
@@ -282,8 +309,9 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_vqe_rows_shared(SparseArgs A
                   "state offsets are DS instruction immediates; a stride the ds_read2 forms cannot encode (see above)");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int ntab1 = A.ntab + 1;
-    double2 *cs = reinterpret_cast<double2 *>(smem + (size_t)NS * SSTRIDE);   // [NS][ntab + 1]: the last entry is the identity
-    double *red = reinterpret_cast<double *>(cs + (size_t)NS * ntab1);        // [NW][NS] partial sums
+    const SpRowsSharedLds L = sp_rows_shared_lds<NW, SSTRIDE>(A.ntab);
+    double2 *cs = reinterpret_cast<double2 *>(smem + L.cs);
+    double *red = reinterpret_cast<double *>(smem + L.red);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s = lane >> 5, l = lane & 31, my = 2 * wave + s;                // my: this half-wave's state of the workgroup
     unsigned char *sbase = smem + (size_t)my * SSTRIDE;
@@ -392,8 +420,8 @@ __global__ __launch_bounds__(NT) void k_sparse_vqe_wg(SparseArgs A, const double
                                                       int nrows8, const SpEntry *__restrict__ entries,
                                                       double *__restrict__ energies) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *st = reinterpret_cast<double *>(smem);                 // [mpad] = support + 128 spare slots
-    double2 *cs = reinterpret_cast<double2 *>(st + A.mpad);        // [ntab + 1]: the last entry is the identity
+    double *st = reinterpret_cast<double *>(smem);
+    double2 *cs = reinterpret_cast<double2 *>(smem + sp_rows_lds(A, 1).cs);
     __shared__ double2 red[NT / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #ifdef OVQE_TESTING
@@ -472,6 +500,17 @@ __global__ __launch_bounds__(NT) void k_sparse_vqe_wg(SparseArgs A, const double
 #undef OVQE_STAMP
 }
 
+struct SpGradLds { size_t lam, cs, w, gk, ops, pairs, bytes; };   // psi ([mpad]) is at 0
+__host__ __device__ inline SpGradLds sp_grad_lds(const SparseArgs &A, bool stage) {
+    const size_t lam = (size_t)A.mpad * sizeof(double);                  // [mpad]
+    const size_t cs = 2 * lam;                                           // [ntab]
+    const size_t w = cs + (size_t)A.ntab * sizeof(double2);              // [ntab]
+    const size_t gk = w + (size_t)A.ntab * sizeof(double);               // [K]
+    const size_t ops = gk + (size_t)((A.K + 1) & ~1) * sizeof(double);   // [nops]   (stage)
+    const size_t pairs = ops + (size_t)A.nops * sizeof(SpOp);            // [npairs] (stage)
+    return {lam, cs, w, gk, ops, pairs, stage ? pairs + (size_t)A.npairs * sizeof(uint32_t) : ops};
+}
+
 // ---- exact gradient on the compact support (round 3) ---------------------------------------------------------------------
 // E(theta) and dE/dtheta_k for ALL K parameters of one parameter vector per wave, in ONE launch: forward circuit as above,
 // lambda = H psi from the restricted Hamiltonian's entries (f64 LDS atomics: lambda_i += H_ij a_j, lambda_j += H_ij a_i),
@@ -486,13 +525,14 @@ __global__ __launch_bounds__(64) void k_sparse_grad(SparseArgs A, const double *
                                                     const SpEntry *__restrict__ entries, double *__restrict__ energies,
                                                     double *__restrict__ grads) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *psi = reinterpret_cast<double *>(smem);                 // [mpad]
-    double *lam = psi + A.mpad;                                     // [mpad]
-    double2 *cs = reinterpret_cast<double2 *>(lam + A.mpad);        // [ntab]
-    double *w = reinterpret_cast<double *>(cs + A.ntab);            // [ntab]
-    double *gk = w + A.ntab;                                        // [K]
-    SpOp *lops = reinterpret_cast<SpOp *>(gk + ((A.K + 1) & ~1));   // [nops]   (STAGE)
-    uint32_t *lpairs = reinterpret_cast<uint32_t *>(lops + A.nops); // [npairs] (STAGE)
+    const SpGradLds L = sp_grad_lds(A, STAGE);
+    double *psi = reinterpret_cast<double *>(smem);
+    double *lam = reinterpret_cast<double *>(smem + L.lam);
+    double2 *cs = reinterpret_cast<double2 *>(smem + L.cs);
+    double *w = reinterpret_cast<double *>(smem + L.w);
+    double *gk = reinterpret_cast<double *>(smem + L.gk);
+    SpOp *lops = reinterpret_cast<SpOp *>(smem + L.ops);
+    uint32_t *lpairs = reinterpret_cast<uint32_t *>(smem + L.pairs);
     const int lane = threadIdx.x;
     if constexpr (STAGE) {
         for (int i = lane; i < A.nops; i += 64) lops[i] = ops[i];
@@ -584,6 +624,14 @@ __global__ __launch_bounds__(64) void k_sparse_grad(SparseArgs A, const double *
     }
 }
 
+struct SpGradWgLds { size_t lam, cs, w, gk, bytes; };   // psi ([mpad] = support + 128 spare slots) is at 0
+__host__ __device__ inline SpGradWgLds sp_grad_wg_lds(const SparseArgs &A) {
+    const size_t lam = (size_t)A.mpad * sizeof(double);                   // [mpad]
+    const size_t cs = 2 * lam;                                            // [ntab + 1]
+    const size_t w = cs + (size_t)(A.ntab + 1) * sizeof(double2);         // [ntab + 1], an even number of slots
+    const size_t gk = w + (size_t)((A.ntab + 2) & ~1) * sizeof(double);   // [K]
+    return {lam, cs, w, gk, gk + (size_t)((A.K + 1) & ~1) * sizeof(double)};
+}
 // ... and with ONE parameter vector per workgroup (latency form, as k_sparse_vqe_wg): all threads prepare and hold the restricted
 // Hamiltonian's entries in registers, wave 0 runs the circuit forwards over rows of 64 padded words, all waves form
 // E = <psi|H|psi> and lambda = H psi (f64 LDS atomics), wave 0 walks the rows BACKWARDS on psi and lambda — per row
@@ -594,14 +642,15 @@ __global__ __launch_bounds__(NT) void k_sparse_grad_wg(SparseArgs A, const doubl
                                                        const uint64_t *__restrict__ rows, int nrows8, const SpEntry *__restrict__ entries,
                                                        double *__restrict__ energies, double *__restrict__ grads) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *psi = reinterpret_cast<double *>(smem);                 // [mpad]
-    double *lam = psi + A.mpad;                                     // [mpad]
-    double2 *cs = reinterpret_cast<double2 *>(lam + A.mpad);        // [ntab + 1]
-    double *w = reinterpret_cast<double *>(cs + A.ntab + 1);        // [ntab + 1]
-    double *gk = w + ((A.ntab + 2) & ~1);                           // [K]
+    const SpGradWgLds L = sp_grad_wg_lds(A);
+    double *psi = reinterpret_cast<double *>(smem);
+    double *lam = reinterpret_cast<double *>(smem + L.lam);
+    double2 *cs = reinterpret_cast<double2 *>(smem + L.cs);
+    double *w = reinterpret_cast<double *>(smem + L.w);
+    double *gk = reinterpret_cast<double *>(smem + L.gk);
     __shared__ double2 red[NT / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t lam_off = (uint32_t)A.mpad * (uint32_t)sizeof(double);
+    const uint32_t lam_off = (uint32_t)L.lam;
     for (int64_t b = blockIdx.x; b < A.B; b += gridDim.x) {
         const double *th = theta + b * A.K;
         SpEntry ent[EPT];

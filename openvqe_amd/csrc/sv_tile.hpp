@@ -76,6 +76,12 @@ __device__ __forceinline__ uint64_t spread_bits(uint32_t v, uint64_t mask) {
 // a basis state, keeps the amplitudes real): the same code moves 16-byte elements = PAIRS of amplitudes, i.e. the
 // segment's masks live in the index space of the pairs (amplitude index >> 1, bit 0 always inside the tile), and the
 // tile holds 2^M doubles — twice the amplitudes per LDS byte, so one more mixing bit per sweep at half the HBM bytes.
+struct TileSweepLds { size_t tab, bytes; };   // the tile (2^M amplitudes) is at 0
+template <int M, bool REAL>
+__host__ __device__ constexpr TileSweepLds tile_sweep_lds() {
+    const size_t tab = (size_t)(REAL ? 8 : 16) << M;   // [TILE_ROT_CAP] RotLds
+    return {tab, tab + TILE_ROT_CAP * sizeof(RotLds)};
+}
 template <int M, int NT, bool NTL, bool REAL>
 __global__ __launch_bounds__(NT) void k_tile_sweep(void *__restrict__ st, uint64_t base, TileSeg seg,
                                                    const TileOp *__restrict__ ops, const TileRot *__restrict__ trot,
@@ -88,7 +94,7 @@ __global__ __launch_bounds__(NT) void k_tile_sweep(void *__restrict__ st, uint64
     constexpr int U = (NEL / 2 / NT) >= 4 ? 4 : ((NEL / 2 / NT) >= 2 ? 2 : 1);
     const TileView<REAL> tile{reinterpret_cast<amp *>(smem)};  // bank-swizzled (see tile_swz)
     double2 *tilev = reinterpret_cast<double2 *>(smem);
-    RotLds *tab = reinterpret_cast<RotLds *>(smem + (size_t)NELV * sizeof(double2));
+    RotLds *tab = reinterpret_cast<RotLds *>(smem + tile_sweep_lds<M, REAL>().tab);
     v2d *p = reinterpret_cast<v2d *>(st);
 
     // tile base: the block index spread over the index bits NOT in the tile
@@ -177,6 +183,14 @@ constexpr int TILE_ADJ_LOG_NT = 9;
 // rotations per backward segment: two 2^11 tiles + the tables of 128 rotations are 76 KiB (two workgroups per CU), two 2^12
 // tiles + the tables of 256 are 152 KiB of the 160 KiB (one)
 constexpr int tile_adj_rot_cap(int m) { return m >= 12 ? TILE_ROT_CAP : TILE_ROT_CAP / 2; }
+struct TileAdjointLds { size_t tl, tab, wacc, bytes; };   // psi's tile (element e at tile_swz_v(e)) is at 0
+template <int M, int NT>
+__host__ __device__ constexpr TileAdjointLds tile_adjoint_lds() {
+    const size_t tl = (size_t)16 << M;                                // lambda's tile
+    const size_t tab = 2 * tl;                                        // [CAP] RotLds
+    const size_t wacc = tab + tile_adj_rot_cap(M) * sizeof(RotLds);   // [NT / 64][CAP]
+    return {tl, tab, wacc, wacc + (size_t)(NT / 64) * tile_adj_rot_cap(M) * sizeof(double)};
+}
 
 template <int M, int NT, bool NTL>
 __global__ __launch_bounds__(NT) void k_tile_adjoint(amp_t *__restrict__ psi, amp_t *__restrict__ lam, uint64_t base,
@@ -189,10 +203,11 @@ __global__ __launch_bounds__(NT) void k_tile_adjoint(amp_t *__restrict__ psi, am
     constexpr int PP = NEL / 2 / NT;      // pairs per thread
     constexpr int NW = NT / 64;
     constexpr int CAP = tile_adj_rot_cap(M);
-    double2 *tp = reinterpret_cast<double2 *>(smem);   // psi tile, element e at tile_swz_v(e)
-    double2 *tl = tp + NEL;                            // lam tile
-    RotLds *tab = reinterpret_cast<RotLds *>(tl + NEL);
-    double *wacc = reinterpret_cast<double *>(tab + CAP);   // [NW][CAP]
+    constexpr TileAdjointLds L = tile_adjoint_lds<M, NT>();
+    double2 *tp = reinterpret_cast<double2 *>(smem);
+    double2 *tl = reinterpret_cast<double2 *>(smem + L.tl);
+    RotLds *tab = reinterpret_cast<RotLds *>(smem + L.tab);
+    double *wacc = reinterpret_cast<double *>(smem + L.wacc);
     v2d *gp = reinterpret_cast<v2d *>(psi), *gl = reinterpret_cast<v2d *>(lam);
     const int nrot = seg.rot1 - seg.rot0;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -555,6 +570,22 @@ __device__ __forceinline__ double tile_entry_pairs(const typename Amp<REAL>::T *
     return part;
 }
 
+// k_tile_expect: [tile][dense path: term table | sparse path: staged terms + pieces (same bytes)][reduction][scan][non-zero list].
+// dense = true (the kernel's sparse_den < 0, launch_tile_expect's dense_only): the launch leaves out what only the sparse-tile path
+// needs — the staging area beyond the term table of one chunk (TILE_TERM_CAP entries at its start), the pieces, the non-zero list:
+// [tile][term table of one chunk][reduction][scan].  The reduction and scan slots move up with the area's end; both totals are totals
+// of this one layout.
+struct TileExpectLds { size_t terms, groups, red, scan, nz, bytes; };   // the tile is at 0
+template <int M, int NT, bool REAL>
+__host__ __device__ constexpr TileExpectLds tile_expect_lds(bool dense) {
+    static_assert(TILE_SPARSE_TERMS >= TILE_TERM_CAP, "the dense term table lives in the sparse staging bytes");
+    const size_t terms = (size_t)(REAL ? 8 : 16) << M;                                               // dense: term table; sparse: staged terms ...
+    const size_t groups = terms + (dense ? TILE_TERM_CAP : TILE_SPARSE_TERMS) * sizeof(ExTermLds);   // ... and pieces of a pass
+    const size_t red = groups + (dense ? 0 : TILE_SPARSE_GROUPS) * sizeof(ExAGroupT);                // [NT / 64]
+    const size_t scan = red + (NT / 64) * sizeof(double2);                                           // NT / 64 wave totals + the tile's count
+    const size_t nz = scan + (NT / 64 + 2) * sizeof(int);                                            // tile-local indices of the non-zero amplitudes
+    return {terms, groups, red, scan, nz, dense ? nz : nz + ((size_t)2 << M)};
+}
 template <int M, int NT, bool NTL, bool REAL>
 __global__ __launch_bounds__(NT) void k_tile_expect(const void *__restrict__ st, uint64_t base, ExSweep sw,
                                                     const ExChunkT *__restrict__ chunks,
@@ -574,18 +605,14 @@ __global__ __launch_bounds__(NT) void k_tile_expect(const void *__restrict__ st,
     constexpr int PP = TILE_ENTRY_PAIRS / 64;  // pairs per lane
     const amp *tile = reinterpret_cast<const amp *>(smem);
     double2 *tilev = reinterpret_cast<double2 *>(smem);
-    // [tile][dense path: term table | sparse path: staged terms + pieces (same bytes)][reduction][scan][non-zero list]
-    // sparse_den < 0: DENSE layout — the launch left the sparse path's staging area and non-zero list out (launch_tile_expect):
-    // [tile][term table of one chunk][reduction]
-    const bool dense_layout = sparse_den < 0;
+    const TileExpectLds L = tile_expect_lds<M, NT, REAL>(sparse_den < 0);
     const bool skip_diag = sparse_den == -2;   // the diagonal group is evaluated by k_tile_diag (dense registers, run_expectation_tiled)
-    ExTermLds *lt = reinterpret_cast<ExTermLds *>(smem + (size_t)NELV * sizeof(double2));
-    ExTermLds *spt = lt;                                             // sparse path: staged terms ...
-    ExAGroupT *spg = reinterpret_cast<ExAGroupT *>(spt + (dense_layout ? TILE_TERM_CAP : TILE_SPARSE_TERMS));  // ... and pieces of a pass
-    double2 *red = reinterpret_cast<double2 *>(spg + (dense_layout ? 0 : TILE_SPARSE_GROUPS));
-    int *scan = reinterpret_cast<int *>(red + NT / 64);             // NT / 64 wave totals + the tile's count
-    uint16_t *nz = reinterpret_cast<uint16_t *>(scan + NT / 64 + 2);  // tile-local indices of the non-zero amplitudes
-    static_assert(TILE_SPARSE_TERMS >= TILE_TERM_CAP, "the dense term table lives in the sparse staging bytes");
+    ExTermLds *lt = reinterpret_cast<ExTermLds *>(smem + L.terms);
+    ExTermLds *spt = lt;
+    ExAGroupT *spg = reinterpret_cast<ExAGroupT *>(smem + L.groups);
+    double2 *red = reinterpret_cast<double2 *>(smem + L.red);
+    int *scan = reinterpret_cast<int *>(smem + L.scan);
+    uint16_t *nz = reinterpret_cast<uint16_t *>(smem + L.nz);
     const v2d *p = reinterpret_cast<const v2d *>(st);
 
     uint64_t tb = blockIdx.x;
@@ -840,6 +867,12 @@ struct DiagTermT {
     uint64_t zout;   // z above the tile bits
     double c;
 };
+struct TileDiagLds { size_t red, bytes; };   // W ([2^M] doubles) is at 0
+template <int M, int NT>
+__host__ __device__ constexpr TileDiagLds tile_diag_lds() {
+    const size_t red = (size_t)8 << M;   // [NT / 64]
+    return {red, red + (NT / 64) * sizeof(double2)};
+}
 template <int M, int NT, bool NTL, bool REAL>
 __global__ __launch_bounds__(NT) void k_tile_diag(const void *__restrict__ st, uint64_t base, const uint32_t *__restrict__ uzin,
                                                   const int32_t *__restrict__ uoff, const DiagTermT *__restrict__ dterms, int nu,
@@ -848,7 +881,7 @@ __global__ __launch_bounds__(NT) void k_tile_diag(const void *__restrict__ st, u
     constexpr uint32_t NEL = 1u << M;
     constexpr int K = NEL / NT;          // amplitudes per thread
     double *W = reinterpret_cast<double *>(smem);
-    double2 *red = reinterpret_cast<double2 *>(W + NEL);
+    double2 *red = reinterpret_cast<double2 *>(smem + tile_diag_lds<M, NT>().red);
     const uint64_t gbase = base | ((uint64_t)blockIdx.x << M);
     double w2[K];
     bool any = false;
@@ -957,6 +990,15 @@ __global__ __launch_bounds__(256) void k_compact_permute(const typename Amp<REAL
         vals[k] = psic[cid[k]];
 }
 
+struct TileCompactLds { size_t terms, groups, red, nz, bytes; };   // the tile (natural order, no bank swizzle) is at 0
+template <int M, int NT, bool REAL>
+__host__ __device__ constexpr TileCompactLds tile_compact_lds(int term_cap, int group_cap, uint32_t max_nnz) {
+    const size_t terms = (size_t)(REAL ? 8 : 16) << M;                    // [term_cap] ExTermLds
+    const size_t groups = terms + (size_t)term_cap * sizeof(ExTermLds);   // [group_cap] ExAGroupT
+    const size_t red = groups + (size_t)group_cap * sizeof(ExAGroupT);    // [NT / 64]
+    const size_t nz = red + (NT / 64) * sizeof(double2);                  // [max_nnz] 16-bit indices, rounded up to 16 bytes
+    return {terms, groups, red, nz, nz + (((size_t)max_nnz * 2 + 15) & ~(size_t)15)};
+}
 template <int M, int NT, bool REAL>
 __global__ __launch_bounds__(NT) void k_tile_expect_compact(const typename Amp<REAL>::T *__restrict__ vals,
                                                             const uint16_t *__restrict__ loc,
@@ -977,11 +1019,12 @@ __global__ __launch_bounds__(NT) void k_tile_expect_compact(const typename Amp<R
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     typedef typename Amp<REAL>::T amp;
     constexpr uint32_t NEL = 1u << M;
-    amp *tile = reinterpret_cast<amp *>(smem);                                   // natural order (no bank swizzle)
-    ExTermLds *spt = reinterpret_cast<ExTermLds *>(smem + (size_t)NEL * sizeof(amp));
-    ExAGroupT *spg = reinterpret_cast<ExAGroupT *>(spt + term_cap);
-    double2 *red = reinterpret_cast<double2 *>(spg + group_cap);
-    uint16_t *nz = reinterpret_cast<uint16_t *>(red + NT / 64);
+    const TileCompactLds L = tile_compact_lds<M, NT, REAL>(term_cap, group_cap, 0u);
+    amp *tile = reinterpret_cast<amp *>(smem);
+    ExTermLds *spt = reinterpret_cast<ExTermLds *>(smem + L.terms);
+    ExAGroupT *spg = reinterpret_cast<ExAGroupT *>(smem + L.groups);
+    double2 *red = reinterpret_cast<double2 *>(smem + L.red);
+    uint16_t *nz = reinterpret_cast<uint16_t *>(smem + L.nz);
     const uint32_t n0 = off[blockIdx.x], nnz = off[blockIdx.x + 1] - n0;
     const size_t slot = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
     if (nnz == 0) {   // no support in this tile (uniform): contributes nothing
@@ -1092,6 +1135,16 @@ __global__ __launch_bounds__(256) void k_tile_lists(const uint64_t *__restrict__
 // moves 48 bytes per amplitude where the gather kernel k_apply_sum re-reads the input once per x-group.  VALU-bound
 // (every term of every group is evaluated for every amplitude): about twice as fast as the gather kernel at 24 qubits.
 
+// k_tile_apply, and with `red` reduction slots behind it k_tile_cross / k_tile_cross_real (sv_cross.hpp): a tile of 2^M elements of
+// `elem` bytes, the term table and the x-groups of one chunk
+struct TileApplyLds { size_t terms, groups, red, bytes; };   // the tile is at 0
+template <int M>
+__host__ __device__ constexpr TileApplyLds tile_apply_lds(size_t elem, int nred) {
+    const size_t terms = elem << M;                                      // [TILE_TERM_CAP] ExTermLds
+    const size_t groups = terms + TILE_TERM_CAP * sizeof(ExTermLds);     // [TILE_APPLY_GROUPS] ExAGroupT
+    const size_t red = groups + TILE_APPLY_GROUPS * sizeof(ExAGroupT);   // [red]
+    return {terms, groups, red, red + (size_t)nred * sizeof(double2)};
+}
 template <int M, int NT, bool NTL>
 __global__ __launch_bounds__(NT) void k_tile_apply(const amp_t *__restrict__ in, amp_t *__restrict__ out, uint64_t base,
                                                    ExSweep sw, const ExChunkT *__restrict__ chunks,
@@ -1103,8 +1156,9 @@ __global__ __launch_bounds__(NT) void k_tile_apply(const amp_t *__restrict__ in,
     constexpr uint32_t NEL = 1u << M;
     constexpr int TRIPS = NEL / NT;
     double2 *tile = reinterpret_cast<double2 *>(smem);
-    ExTermLds *lt = reinterpret_cast<ExTermLds *>(smem + (size_t)NEL * sizeof(double2));
-    ExAGroupT *lg = reinterpret_cast<ExAGroupT *>(lt + TILE_TERM_CAP);
+    constexpr TileApplyLds L = tile_apply_lds<M>(sizeof(double2), 0);
+    ExTermLds *lt = reinterpret_cast<ExTermLds *>(smem + L.terms);
+    ExAGroupT *lg = reinterpret_cast<ExAGroupT *>(smem + L.groups);
     const v2d *p = reinterpret_cast<const v2d *>(in);
     v2d *q = reinterpret_cast<v2d *>(out);
 

@@ -363,27 +363,13 @@ int launch_tile_expect(ovqe_handle h, const HamDev &H, const ExSweep &sw, double
                        hipStream_t stream, bool dense_only = false, int *census = nullptr, bool skip_diag = false) {
     constexpr int NT = 1 << TILE_EXPECT_LOG_NT;
     static_assert(TILE_SPARSE_TERMS >= 2 * TILE_TERM_CAP && TILE_SPARSE_GROUPS >= 2 * TILE_APPLY_GROUPS, "two host chunks per pass");
-    const size_t smem_full = ((size_t)(REAL ? 8 : 16) << M) + TILE_SPARSE_TERMS * sizeof(ExTermLds) +
-                             TILE_SPARSE_GROUPS * sizeof(ExAGroupT) + (NT / 64) * sizeof(double2) + (NT / 64 + 2) * sizeof(int) +
-                             ((size_t)2 << M);
-    // (dense path: the term table of a chunk, TILE_TERM_CAP entries, lives at the start of the staging bytes; the reduction slots
-    // sit behind the whole staging area in the kernel's layout, so the dense launch keeps the area's address range up to them)
-    const size_t smem_dense = ((size_t)(REAL ? 8 : 16) << M) + TILE_TERM_CAP * sizeof(ExTermLds) + (NT / 64) * sizeof(double2) +
-                              (NT / 64 + 2) * sizeof(int);
+    constexpr size_t smem_full = tile_expect_lds<M, NT, REAL>(false).bytes, smem_dense = tile_expect_lds<M, NT, REAL>(true).bytes;
     const size_t smem = dense_only ? smem_dense : smem_full;
     const dim3 grid((unsigned)(h->namps >> M), (unsigned)expect_ysplit(h, M));
     // a tile with at most 1/SPARSE_DEN of its amplitudes non-zero is evaluated over the compacted list of those amplitudes
     constexpr int SPARSE_DEN = 4;
     const int sparse_den = dense_only ? (skip_diag ? -2 : -1) : ((H.d_agroups.p && sw.a1 > sw.a0) ? SPARSE_DEN : 0);
-    static bool attr_done_dev[64] = {};  // function attributes are per device
-    bool &attr_done = attr_done_dev[h->device & 63];
-    if (!attr_done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_expect<M, NT, true, REAL>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_full));
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_expect<M, NT, false, REAL>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_full));
-        attr_done = true;
-    }
+    if (int rc = lds_opt_in<&k_tile_expect<M, NT, true, REAL>, &k_tile_expect<M, NT, false, REAL>>(h, smem_full)) return rc;
     if (h->n_local >= 25) {
         hipLaunchKernelGGL((k_tile_expect<M, NT, true, REAL>), grid, dim3(NT), smem, stream, (const void *)h->state, h->base, sw,
                            (const ExChunkT *)H.d_tchunks.p, (const ExEntryT *)H.d_tgroups.p,
@@ -503,7 +489,7 @@ int run_expectation_tiled(ovqe_handle h, HamDev &H, double2 *out, bool *used, bo
     int64_t count = ntiles * nparts;
     if (diag_wht) {   // the diagonal group: one pass over contiguous tiles, Walsh-Hadamard form (sv_tile.hpp k_tile_diag)
         constexpr int DM = 12, DNT = 512;
-        const size_t dsm = ((size_t)8 << DM) + (DNT / 64) * sizeof(double2);
+        constexpr size_t dsm = tile_diag_lds<DM, DNT>().bytes;
         const bool ntl = h->n_local >= 25;
         if (real) {
             if (ntl) hipLaunchKernelGGL((k_tile_diag<DM, DNT, true, true>), dim3((unsigned)ndiag), dim3(DNT), dsm, h->stream, (const void *)h->state, h->base,
@@ -645,15 +631,8 @@ int launch_tile_expect_compact(ovqe_handle h, const HamDev &H, double2 *partials
     const CompactCover &C = h->cc;
     constexpr int cpp = 1;   // host chunks (512 terms each) staged in LDS per pass
     const int term_cap = cpp * TILE_TERM_CAP, group_cap = cpp * TILE_APPLY_GROUPS;
-    const size_t smem = ((size_t)8 << M) + (size_t)term_cap * sizeof(ExTermLds) + (size_t)group_cap * sizeof(ExAGroupT) +
-                        (NT / 64) * sizeof(double2) + (((size_t)C.max_nnz * 2 + 15) & ~(size_t)15);
-    static bool attr_done_dev[64] = {};
-    bool &attr_done = attr_done_dev[h->device & 63];
-    if (!attr_done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_expect_compact<M, NT, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
-        attr_done = true;
-    }
+    const size_t smem = tile_compact_lds<M, NT, true>(term_cap, group_cap, (uint32_t)C.max_nnz).bytes;
+    if (int rc = lds_opt_in<&k_tile_expect_compact<M, NT, true>>(h, 120 * 1024)) return rc;
     hipLaunchKernelGGL((k_tile_expect_compact<M, NT, true>), dim3((unsigned)C.ntiles, (unsigned)H.tsweeps.size()), dim3(NT),
                        smem, h->stream, (const double *)C.d_psic.p + C.K, (const uint16_t *)C.d_loc.p, (const uint32_t *)C.d_off.p,
                        h->base, (const ExSweep *)C.d_sweeps.p, C.K, (const ExChunkT *)H.d_achunks.p,
@@ -708,16 +687,8 @@ int launch_tile_apply(ovqe_handle h, const HamDev &H, const ExSweep &sw, const a
                       double ident, const uint32_t *tile_list = nullptr, const uint32_t *tile_count = nullptr,
                       unsigned listed_grid = 0) {
     constexpr int NT = 1 << TILE_EXPECT_LOG_NT;  // the sweeps' thread / trip masks are laid out for this group size
-    const size_t smem = ((size_t)16 << M) + TILE_TERM_CAP * sizeof(ExTermLds) + TILE_APPLY_GROUPS * sizeof(ExAGroupT);
-    static bool attr_done_dev[64] = {};  // function attributes are per device
-    bool &attr_done = attr_done_dev[h->device & 63];
-    if (!attr_done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_apply<M, NT, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_apply<M, NT, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_done = true;
-    }
+    constexpr size_t smem = tile_apply_lds<M>(sizeof(double2), 0).bytes;
+    if (int rc = lds_opt_in<&k_tile_apply<M, NT, true>, &k_tile_apply<M, NT, false>>(h, smem)) return rc;
     const unsigned grid = tile_list ? listed_grid : (unsigned)(h->namps >> M);
     if (h->n_local >= 25) {
         hipLaunchKernelGGL((k_tile_apply<M, NT, true>), dim3(grid), dim3(NT), smem, h->stream, in, out, h->base, sw,
@@ -799,18 +770,10 @@ int init_basis(ovqe_handle h, uint64_t index, double2 one = make_double2(1.0, 0.
 template <int M, bool REAL>
 int launch_tile(ovqe_handle h, const TilePlan &tp, const TileSeg &sg) {
     constexpr int NT = 1 << TILE_SWEEP_LOG_NT;
-    const size_t smem = ((size_t)(REAL ? 8 : 16) << M) + TILE_ROT_CAP * sizeof(RotLds);
+    constexpr size_t smem = tile_sweep_lds<M, REAL>().bytes;
     const unsigned grid = (unsigned)(h->namps >> M);
     const bool ntl = h->n_local >= 25;
-    static bool attr_done_dev[64] = {};  // function attributes are per device
-    bool &attr_done = attr_done_dev[h->device & 63];
-    if (!attr_done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_sweep<M, NT, true, REAL>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_sweep<M, NT, false, REAL>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_done = true;
-    }
+    if (int rc = lds_opt_in<&k_tile_sweep<M, NT, true, REAL>, &k_tile_sweep<M, NT, false, REAL>>(h, smem)) return rc;
     if (ntl) {
         hipLaunchKernelGGL((k_tile_sweep<M, NT, true, REAL>), dim3(grid), dim3(NT), smem, h->stream, (void *)h->state,
                            h->base, sg, (const TileOp *)tp.d_tops.p, (const TileRot *)tp.d_trots.p,
@@ -861,17 +824,9 @@ template <int M>
 int launch_tile_adjoint_m(ovqe_handle h, amp_t *lam, const TilePlan &tp, const TileSeg &sg, double *partials, int grid) {
     constexpr int NT = 1 << TILE_ADJ_LOG_NT;
     constexpr int CAP = tile_adj_rot_cap(M);
-    const size_t smem = ((size_t)32 << M) + CAP * sizeof(RotLds) + (size_t)(NT / 64) * CAP * sizeof(double);
+    constexpr size_t smem = tile_adjoint_lds<M, NT>().bytes;
     const bool ntl = h->n_local >= 25;
-    static bool attr_done_dev[64] = {};  // function attributes are per device
-    bool &attr_done = attr_done_dev[h->device & 63];
-    if (!attr_done) {
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_adjoint<M, NT, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_adjoint<M, NT, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_done = true;
-    }
+    if (int rc = lds_opt_in<&k_tile_adjoint<M, NT, true>, &k_tile_adjoint<M, NT, false>>(h, smem)) return rc;
     const uint32_t ntiles = (uint32_t)(h->namps >> M);
     if (ntl) {
         hipLaunchKernelGGL((k_tile_adjoint<M, NT, true>), dim3((unsigned)grid), dim3(NT), smem, h->stream, h->state, lam, h->base,
