@@ -147,7 +147,8 @@ int ovqe_set_stream(ovqe_handle h, void *hip_stream);
  *   "fault_inject" (1: the next term-list build throws std::bad_alloc: the exception barrier's test), "sector_debug" (2: say on stderr why a
  *   program was left to the dense kernels; 4: wall time of the build's phases), "sector_sweep_dbg" / "sector_h_dbg" / "sparse_dbg" (kernels
  *   truncated after a given phase), and the launch geometries and superseded forms kept for comparison: "sparse_rows", "sparse_wg",
- *   "sparse_shared" (0: large batches of the rows form on one wave per pair of evaluations instead of the workgroup geometry, 2: that geometry below its batch threshold too), "sparse_spw", "sector_sweep" (circuit sweeps on an irregular support: 3 pair words in per-wave streams with barriers at
+ *   "sparse_shared" (0: large batches of the rows form on one wave per pair of evaluations instead of the workgroup geometry, 2: that geometry below its batch threshold too),
+ *   "sparse_pack" (0: the restricted Hamiltonian counts as one that does not pack into the workgroup geometry's owner pieces: the selection's fall-back), "sparse_spw", "sector_sweep" (circuit sweeps on an irregular support: 3 pair words in per-wave streams with barriers at
  *   run boundaries only — built on top of the tables of 2 —, 2 64-bit pair words in registers with a barrier per round, 1 first form; 2 on a
  *   handle built under 3 runs the second form on the same tables; 4: the streams for the states of a batch too — the product gives
  *   batches the second form: their workgroups hide each other's barriers and the streams gain them nothing), "sector_stream_waves" (0: waves that share a tile's rows from the pairs per
@@ -408,7 +409,9 @@ int ovqe_last_support(ovqe_handle h, int32_t which, int64_t *support);
  *   rotations) with the support numbered in discovery order, and with the numbering in use (option "sparse_renumber")
  *   [28..29] sector path on a REGULAR support (the full coset of the program's Z2 symmetries, e.g. the spin-parity quarter of
  *   the register that the reference's QUCCSD templates populate; option "sector_regular", default 1): slot bits of a circuit
- *   tile — the sweeps then run from bit arithmetic, without pair words — and the number of free (dependent) index bits; 0 else */
+ *   tile — the sweeps then run from bit arithmetic, without pair words — and the number of free (dependent) index bits; 0 else
+ *   [30..32] support-compacted program, batched workgroup kernel (0 when no instance of it holds the program): owner pieces of the
+ *   restricted Hamiltonian that hold entries, entry slots per thread, LDS reads per thread and state of the <H> contraction */
 int ovqe_program_info(ovqe_handle h, int64_t *info, int count);
 /* The stored program as its sequence of Pauli rotations exp(-i (coeff[r] theta[pidx[r]] + phi0[r]) P_r), P_r = (x[r], z[r]) in
  * index-bit space, in execution order (pidx < 0: a constant angle) — for a gate program in Clifford-frame form

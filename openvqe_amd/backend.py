@@ -417,7 +417,9 @@ class Statevector:
     def sparse_geometries(self):
         """launch geometries that served the "rows2" form on this handle since its program was set: "per_wave" (k_sparse_vqe_rows<2>,
         one wave per pair of evaluations) or an instance of the workgroup geometry with the Hamiltonian's entries in registers
-        (k_sparse_vqe_rows_shared: entries per thread, bytes between the states in LDS)"""
+        (k_sparse_vqe_rows_shared).  A name identifies the instance — "e37": it takes programs of up to 37 entries per thread,
+        "s4104": bytes between the states in LDS — not the layout of the entries in the registers (owner pieces:
+        ``program_info()["sp_h_slots"]``, ``["sp_h_reads_per_state"]``)"""
         out = ctypes.c_int64()
         self._ck(self._L.ovqe_last_support(self._h, 7, ctypes.byref(out)))
         return {name for bit, name in enumerate(self.SPARSE_GEOMETRIES) if (out.value >> (10 + bit)) & 1}
@@ -459,14 +461,15 @@ class Statevector:
     def program_info(self):
         """shape of the compiled program: ops, rotations, literal gates, sweeps per evaluation, tiled sweeps,
         fused-kernel ops, support size (-1 = not analysed yet)"""
-        out = (ctypes.c_int64 * 30)()
-        self._ck(self._L.ovqe_program_info(self._h, out, 30))
+        out = (ctypes.c_int64 * 33)()
+        self._ck(self._L.ovqe_program_info(self._h, out, 33))
         keys = ("ops", "rotations", "literal_gates", "sweeps", "tiled_sweeps", "fused_ops", "support",
                 "h_tile_sweeps", "h_untiled_groups", "h_entries", "h_merged_terms", "h_pair_terms_per_tile",
                 "real_stream", "sp_ops", "sp_pairs", "sp_h_entries",
                 "sector_support", "sector_sweeps", "sector_pairs", "sector_h_sweeps", "sector_h_elements", "sector_bytes",
                 "sector_circuit_us", "sector_expect_us", "sector_h_stream_bytes", "sector_fci_block",
-                "sp_conflicts_discovery_order", "sp_conflicts", "sector_regular_slot_bits", "sector_free_bits")
+                "sp_conflicts_discovery_order", "sp_conflicts", "sector_regular_slot_bits", "sector_free_bits",
+                "sp_h_pieces", "sp_h_slots", "sp_h_reads_per_state")
         return dict(zip(keys, [int(v) for v in out]))
 
     def rotation_program(self):

@@ -32,6 +32,7 @@
 #include "sv_kernels.hpp"
 #include "sv_small.hpp"
 #include "sv_sparse.hpp"
+#include "sparse_pack.hpp"
 #include "sv_tile.hpp"
 #include "sv_sector.hpp"
 #include "sv_cross.hpp"
@@ -324,6 +325,10 @@ struct ovqe_sv {
     int64_t sp_conflicts_before = 0, sp_conflicts_after = 0;   // colliding lane pairs per evaluation, discovery order / renumbered
     int64_t sp_npairs = 0;
     DevBuf d_sp_ops, d_sp_pairs, d_sp_entries;
+    // the entries as owner pieces for k_sparse_vqe_rows_shared (sparse_pack.hpp): the instance they were packed for (index into
+    // SHARED_INSTANCES, -1: none holds the program), rows' pieces in use, pieces per thread, slots per piece
+    int sp_pack_inst = -1, sp_h_pieces = 0, sp_h_rpt = 0, sp_h_epr = 0;
+    DevBuf d_sp_hpack;
     // device copy of the ADAPT pool of the last ovqe_pool_gradients call (+ its host image for the change test)
     DevBuf d_pg_off, d_pg_xs, d_pg_terms, d_pg_out, d_pg_part;
     DevBuf d_pg_runs, d_pg_tabs;   // pattern tables of the pool's same-x runs (PoolRun, k_pool_grad_nz)
@@ -361,6 +366,7 @@ struct ovqe_sv {
     bool pg_valid = false;
     int opt_sparse = 1;           // allow the support-compacted path
     int opt_sparse_spw = 0;       // evaluations per wave (0 = automatic)
+    int opt_sparse_pack = 1;      // test of the selection: 0 = the owner pieces of the restricted Hamiltonian count as "do not fit" (sparse_pack.hpp)
     int opt_sparse_dbg = 0;       // measurement: k_sparse_vqe_rows / k_sparse_vqe_rows_shared without one of their phases (SparseArgs::dbg)
     int opt_clifford_phase_host = 1;   // global phase of a closed Clifford frame from a sparse host simulation (0: the gates run on the device)
     int opt_sparse_renumber = 1;  // number the compact support against LDS bank conflicts of the circuit's pairs
@@ -1178,7 +1184,7 @@ int ovqe_destroy(ovqe_handle h) try {
     std::vector<DevBuf *> bufs = {&h->d_tile_cnt, &h->d_partials, &h->d_result, &h->d_rp, &h->d_ops, &h->d_rots, &h->d_rots_seq, &h->d_segs,
                                   &h->d_stream,
                                   &h->d_theta, &h->d_energies, &h->d_workspace, &h->d_egroups, &h->d_eterms, &h->d_echunks,
-                                  &h->d_eflat, &h->d_sp_ops, &h->d_sp_rows, &h->d_sp_rows64, &h->d_sp_prim, &h->d_sp_pairs, &h->d_sp_entries, &h->d_pg_off, &h->d_pg_xs, &h->d_pg_terms, &h->d_pg_runs, &h->d_pg_tabs,
+                                  &h->d_eflat, &h->d_sp_ops, &h->d_sp_rows, &h->d_sp_rows64, &h->d_sp_prim, &h->d_sp_pairs, &h->d_sp_entries, &h->d_sp_hpack, &h->d_pg_off, &h->d_pg_xs, &h->d_pg_terms, &h->d_pg_runs, &h->d_pg_tabs,
                                   &h->d_pg_out, &h->d_pg_part, &h->d_nz_cnt, &h->d_nz_start, &h->d_nz_idx, &h->d_nz_val, &h->d_nz_bitmap, &h->d_exp_groups, &h->d_exp_terms, &h->d_tile_smasks, &h->d_tile_lists, &h->d_tile_counts, &h->cc.d_sup, &h->cc.d_psic, &h->cc.d_loc, &h->cc.d_cid, &h->cc.d_off, &h->cc.d_sweeps};
     for (TilePlan *tp : {&h->tp, &h->tp_adhoc, &h->tp_real, &h->tp_adjoint}) bufs.insert(bufs.end(), {&tp->d_tops, &tp->d_trots});
     for (HamDev *H : {&h->ham, &h->ham_adhoc, &h->ham_real, &h->ham_conj})
@@ -1247,6 +1253,10 @@ int ovqe_set_option(ovqe_handle h, const char *name, int64_t value) try {
 #ifdef OVQE_TESTING
     else if (k == "sparse_spw") h->opt_sparse_spw = (int)value;
     else if (k == "sparse_dbg") h->opt_sparse_dbg = (int)value;
+    else if (k == "sparse_pack") {
+        h->opt_sparse_pack = value ? 1 : 0;
+        h->sp_tried = false;
+    }
 #endif
     else if (k == "clifford_phase_host") h->opt_clifford_phase_host = (int)value;
     else if (k == "index_streams") {
@@ -1537,6 +1547,10 @@ int ovqe_program_info(ovqe_handle h, int64_t *info, int count) try {
                             (E.valid && E.regular && h->opt_sector_regular) ? (int64_t)E.reg_m : 0,
                             (E.valid && E.regular) ? (int64_t)__builtin_popcount(E.freemask) : 0};
     for (int i = 16; i < count && i < 30; ++i) info[i] = sv[i - 16];
+    const bool packed = h->sp_valid && h->sp_pack_inst >= 0;
+    const int64_t pv[3] = {packed ? (int64_t)h->sp_h_pieces : 0, packed ? (int64_t)h->sp_h_rpt * h->sp_h_epr : 0,
+                           packed ? (int64_t)h->sp_h_rpt * (h->sp_h_epr + 1) : 0};
+    for (int i = 30; i < count && i < 33; ++i) info[i] = pv[i - 30];
     return OVQE_OK;
 } OVQE_CATCH(h)
 

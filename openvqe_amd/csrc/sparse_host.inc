@@ -1,6 +1,15 @@
 // sparse_host.inc — the support-compacted path (states whose program reaches few basis states): table build and launches
 // (kernels: sv_sparse.hpp).  Included by ovqe_sv.hip inside its anonymous namespace.
 
+// Instances of the workgroup geometry of the rows form (k_sparse_vqe_rows_shared<NW, RPT, EPR, SSTRIDE>), smaller first.  An instance
+// holds a program when its entries are at most 64 NW x EPT (the capacity criterion its name carries), its state fits the stride, its
+// LDS fits half a CU (launch_rows_shared) AND the entries pack into 64 NW x RPT owner pieces of EPR slots (sparse_pack.hpp).  The
+// shapes RPT x EPR are the measured ones of profiles/owner_rows/README.md.
+struct SharedInstance { int nw, ept, sstride, rpt, epr; };
+constexpr SharedInstance SHARED_13 = {4, 13, 2568, 1, 17};   // LiH: 225 states, 3243 entries: 18 LDS reads per thread and state
+constexpr SharedInstance SHARED_37 = {4, 37, 4104, 4, 10};   // H2O: 441 states, 9443 entries: 44
+constexpr SharedInstance SHARED_INSTANCES[2] = {SHARED_13, SHARED_37};
+
 // ---- support-compacted path (sv_sparse.hpp) -------------------------------------------------------------------
 // Propagate the reachable support of |hf> through the OP_TAB ops and restate program and Hamiltonian on compact
 // indices.  Returns with h->sp_valid = false when the structure is absent (then the dense kernels run).
@@ -387,7 +396,37 @@ int build_sparse_program(ovqe_handle h) {
             for (int lane = 0; lane < 64; ++lane) rows64.push_back(pad_word(lane));
         h->sp_nrows8 = nrows8;
     }
+    // owner pieces of the restricted Hamiltonian for the first instance of the workgroup geometry that holds the program
+    h->sp_pack_inst = -1;
+    h->sp_h_pieces = h->sp_h_rpt = h->sp_h_epr = 0;
+    std::vector<unsigned char> hpack;
+    if (h->sp_nrows4 && !entries.empty() && h->opt_sparse_pack) {
+        std::vector<uint32_t> ei(entries.size()), ej(entries.size());
+        std::vector<double> ec(entries.size());
+        for (size_t e = 0; e < entries.size(); ++e) {
+            ei[e] = entries[e].ij & 0xfffu;
+            ej[e] = (entries[e].ij >> 12) & 0xfffu;
+            ec[e] = entries[e].c;
+        }
+        const size_t state_bytes = (size_t)((mp + 64 + 1) & ~1) * sizeof(double);   // run_sparse: the rows form's state + spare slots
+        for (int k = 0; k < 2 && h->sp_pack_inst < 0; ++k) {
+            const SharedInstance &I = SHARED_INSTANCES[k];
+            const int nt = 64 * I.nw;
+            if (entries.size() > (size_t)nt * I.ept || state_bytes > (size_t)I.sstride) continue;
+            OwnerPack P;
+            if (!pack_owner_pieces(ei, ej, ec, mp, nt, I.rpt, I.epr, &P)) continue;
+            hpack.resize(P.c.size() * sizeof(double) + (P.oj.size() + P.oi.size()) * sizeof(uint16_t));
+            std::memcpy(hpack.data(), P.c.data(), P.c.size() * sizeof(double));
+            std::memcpy(hpack.data() + P.c.size() * sizeof(double), P.oj.data(), P.oj.size() * sizeof(uint16_t));
+            std::memcpy(hpack.data() + P.c.size() * sizeof(double) + P.oj.size() * sizeof(uint16_t), P.oi.data(), P.oi.size() * sizeof(uint16_t));
+            h->sp_pack_inst = k;
+            h->sp_h_pieces = P.pieces;
+            h->sp_h_rpt = I.rpt;
+            h->sp_h_epr = I.epr;
+        }
+    }
     int rc = upload(h, h->d_sp_ops, ops.data(), ops.size() * sizeof(SpOp));
+    if (!rc && h->sp_pack_inst >= 0) rc = upload(h, h->d_sp_hpack, hpack.data(), hpack.size());
     if (!rc && h->sp_nrows4) rc = upload(h, h->d_sp_rows, rows.data(), rows.size() * sizeof(uint64_t));
     if (!rc && (h->sp_nrows4 || h->sp_nrows8)) rc = upload(h, h->d_sp_prim, prim.data(), prim.size() * sizeof(SmallRot));
     if (!rc && h->sp_nrows8) rc = upload(h, h->d_sp_rows64, rows64.data(), rows64.size() * sizeof(uint64_t));
@@ -428,21 +467,27 @@ enum : uint32_t {
     SPF_DECLINED = 1u << 9,      // a call wanted the compact path and no form of it fits: the other paths served it
     // launch geometry of SPF_ROWS2 (bits the form names do not reach: Statevector.sparse_geometries())
     SPG_PER_WAVE = 1u << 10,     // k_sparse_vqe_rows<2>: one wave per pair of evaluations, the Hamiltonian's entries streamed from L2
-    SPG_SHARED_37 = 1u << 11,    // k_sparse_vqe_rows_shared<4, 37, 4104>: entries in registers (H2O: 441 states, 9443 entries)
-    SPG_SHARED_13 = 1u << 12,    // k_sparse_vqe_rows_shared<4, 13, 2568>  (LiH: 225 states)
+    // ... the instances of k_sparse_vqe_rows_shared (entries in registers as owner pieces).  The names ("shared_e37_s4104",
+    // "shared_e13_s2568" in backend.py) identify the INSTANCE — its capacity criterion, 37 / 13 entries per thread, and its stride —
+    // not the slot layout of the pieces (SHARED_37 / SHARED_13 above)
+    SPG_SHARED_37 = 1u << 11,    // k_sparse_vqe_rows_shared<4, 4, 10, 4104>  (H2O: 441 states, 9443 entries)
+    SPG_SHARED_13 = 1u << 12,    // k_sparse_vqe_rows_shared<4, 1, 17, 2568>  (LiH: 225 states)
 };
 
 // the workgroup geometry of the rows form: batches from SHARED_MIN_B on — measured (tools/exp_shared_sweep.py, profiles/shared_rows): it
 // wins beyond the spread at every batch size the rows form takes, 2048 included (H2O: 35.6 against 40.3 us)
 constexpr int64_t SHARED_MIN_B = 2048;
 
-template <int NW, int EPT, int SSTRIDE, int DBG>
+template <int NW, int RPT, int EPR, int SSTRIDE, int DBG>
 int launch_rows_shared_dbg(ovqe_handle h, const SparseArgs &R, size_t smem) {
     constexpr int NS = 2 * NW;
     // workgroups one CU holds at once at this much LDS, cached per device: both in ONE word (smem << 8 | per_cu; smem <= 80 KiB,
     // per_cu <= 32), so that two threads with a handle each never see one without the other
     static std::atomic<uint32_t> per_dev[64];
-    constexpr auto kern = &k_sparse_vqe_rows_shared<NW, EPT, SSTRIDE, DBG>;
+    constexpr auto kern = &k_sparse_vqe_rows_shared<NW, RPT, EPR, SSTRIDE, DBG>;
+    constexpr size_t slots = (size_t)RPT * EPR * NW * 64;   // the packed tables: coefficients, then 16-bit offsets (sparse_pack.hpp)
+    const double *hc = (const double *)h->d_sp_hpack.p;
+    const uint16_t *ho = (const uint16_t *)(hc + slots);
     if (int rc = lds_opt_in<kern>(h, LDS_WG_MAX)) return rc;
     uint32_t pd = per_dev[h->device & 63].load(std::memory_order_relaxed);
     if ((pd >> 8) != smem) {
@@ -460,28 +505,31 @@ int launch_rows_shared_dbg(ovqe_handle h, const SparseArgs &R, size_t smem) {
     // persistent: as many workgroups as the chip holds at once, each walks work items of 2 NW evaluations
     const int grid = (int)std::min<int64_t>((R.B + NS - 1) / NS, (int64_t)h->num_cus * per_cu);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), smem, h->stream, R, h->cur_theta, (const SmallRot *)h->d_sp_prim.p,
-                       (const uint64_t *)h->d_sp_rows.p, h->sp_nrows4, (const SpEntry *)h->d_sp_entries.p, h->cur_energies);
+                       (const uint64_t *)h->d_sp_rows.p, h->sp_nrows4, hc, ho, h->cur_energies);
     HIPC(h, hipGetLastError());
     return OVQE_OK;
 }
 
-// One instance of the workgroup geometry.  *taken = false: it does not hold this program (nothing launched): more entries than
-// its threads keep in registers, a support beyond its stride, or states + cos/sin tables beyond the LDS of half a CU.
-template <int NW, int EPT, int SSTRIDE>
+// Instance K of the workgroup geometry.  *taken = false: it does not hold this program (nothing launched): more entries than
+// its capacity criterion, a support beyond its stride, entries that do not pack into its pieces (all three decided with the
+// tables: build_sparse_program packed for instance sp_pack_inst), or states + cos/sin tables beyond the LDS of half a CU.
+template <int K>
 int launch_rows_shared(ovqe_handle h, const SparseArgs &R, bool *taken) {
-    constexpr int NS = 2 * NW;
+    constexpr SharedInstance I = SHARED_INSTANCES[K];
+    constexpr int NW = I.nw, RPT = I.rpt, EPR = I.epr, SSTRIDE = I.sstride;
     const size_t smem = sp_rows_shared_lds<NW, SSTRIDE>(R.ntab).bytes;
-    *taken = R.nent >= 1 && R.nent <= NW * 64 * EPT && (size_t)R.mpad * sizeof(double) <= (size_t)SSTRIDE && smem <= LDS_TWO_PER_CU;
+    *taken = h->sp_pack_inst == K && R.nent >= 1 && R.nent <= NW * 64 * I.ept && (size_t)R.mpad * sizeof(double) <= (size_t)SSTRIDE &&
+             smem <= LDS_TWO_PER_CU;
     if (!*taken) return OVQE_OK;
 #ifdef OVQE_TESTING
     switch (h->opt_sparse_dbg) {
-    case 1: return launch_rows_shared_dbg<NW, EPT, SSTRIDE, 1>(h, R, smem);
-    case 2: return launch_rows_shared_dbg<NW, EPT, SSTRIDE, 2>(h, R, smem);
-    case 3: return launch_rows_shared_dbg<NW, EPT, SSTRIDE, 3>(h, R, smem);
+    case 1: return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, 1>(h, R, smem);
+    case 2: return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, 2>(h, R, smem);
+    case 3: return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, 3>(h, R, smem);
     default: break;
     }
 #endif
-    return launch_rows_shared_dbg<NW, EPT, SSTRIDE, 0>(h, R, smem);
+    return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, 0>(h, R, smem);
 }
 
 // on_device: theta / energies are device pointers (inputs already resident in HBM, results left there).  *done = false: no compact
@@ -568,11 +616,11 @@ int run_sparse(ovqe_handle h, int64_t B, const double *theta, double *energies, 
         bool shared = false;
         if ((B >= SHARED_MIN_B && h->opt_sparse_shared) || h->opt_sparse_shared >= 2) {   // (2: the threshold sweep)
             if (!rc && !shared) {
-                rc = launch_rows_shared<4, 13, 2568>(h, R, &shared);
+                rc = launch_rows_shared<0>(h, R, &shared);
                 if (shared) h->sp_forms |= SPG_SHARED_13;
             }
             if (!rc && !shared) {
-                rc = launch_rows_shared<4, 37, 4104>(h, R, &shared);
+                rc = launch_rows_shared<1>(h, R, &shared);
                 if (shared) h->sp_forms |= SPG_SHARED_37;
             }
             if (rc) return rc;

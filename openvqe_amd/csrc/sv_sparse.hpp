@@ -249,7 +249,8 @@ __global__ __launch_bounds__(64) void k_sparse_vqe_rows(SparseArgs A, const doub
         // with nine waves per CU the kernel is bound by LDS instructions, ~5 per pair and 2 per entry and state at ~3 ns each per CU,
         // tools/micro/lds_atomic.hip, not by this loop's latency.  Also measured and dropped: the restricted Hamiltonian in row format
         // (lane = row, a_i once per slice of 64 rows, ONE amplitude read per entry and state instead of two, entries ordered
-        // against bank conflicts): 0.673 ms against 0.675 — the entry loop's LDS reads are not what bounds the kernel either;
+        // against bank conflicts): 0.673 ms against 0.675 — the entry loop's LDS reads are not what bounds THIS kernel either
+        // (it streams the entries from L2; with the entries in registers they are: k_sparse_vqe_rows_shared below reads a_i once);
         // per wave and pair of evaluations ~6600 VALU, 3700 SALU, 1400 LDS instructions at 2.25 waves per SIMD.)
         // (Round 4, measured and dropped: the two states copied side by side behind the circuit (slot -> double2) so that ONE 16-byte
         // LDS read per amplitude serves both states and one address is computed instead of two — bit-identical energies, 0.885 ms
@@ -280,29 +281,36 @@ __host__ __device__ constexpr SpRowsSharedLds sp_rows_shared_lds(int ntab) {
     return {cs, red, red + (size_t)NW * NS * sizeof(double)};
 }
 
-// ---- throughput form, workgroup geometry: the restricted Hamiltonian in REGISTERS ----------------------------------------------------
+// ---- throughput form, workgroup geometry: the restricted Hamiltonian in REGISTERS, as owner pieces ---------------------------------
 // Half of k_sparse_vqe_rows<2> on the H2O workload is its entry loop: every wave streams the whole entry table from L2 (151 KB)
 // for every pair of evaluations, one 16-byte load + unpacking + two address computations per entry, lane and state.  Here NW
 // waves share a workgroup.  Each wave runs the circuit of ITS two evaluations exactly as above (same row table, rows four ahead,
 // no barrier between rows); the 2 NW states lie side by side in LDS at the compile-time stride SSTRIDE (bytes), the cos/sin
-// tables behind them.  Thread t holds entries t, t + NT, ... (EPT of them, the tail padded with coefficient 0) in registers
-// for the whole launch — both byte offsets in one VGPR, the coefficient in two — and after ONE barrier every wave contracts
-// its entries against ALL 2 NW states: the addresses are offset + q * SSTRIDE, instruction immediates (two states per
-// ds_read_b64), no global traffic, no address arithmetic.  Partial sums of the NW waves go through LDS and are added in
-// wave order (no floating-point atomics: the energy of a parameter vector depends neither on its position in the batch nor on
-// the run).  The second barrier also frees the states for the next work item of the persistent loop.
-// Two things the compiler needs: the stride at compile time (with a run-time stride it hoists all 2 NW x EPT x 2 addresses out of
-// the work loop and spills), and the accumulators pinned after each entry (otherwise it finishes state 0 over all entries first
-// and parks every other state's loads in scratch).  SSTRIDE is the state rounded up to 512 bytes PLUS 8: at a multiple of 512
-// the compiler pairs the reads of two states into ds_read2st64_b64, which the LDS serves at half the rate of two ds_read_b64
-// (8 against 2 x 2 cycles per wave) and in groups of 16 lanes against 32 banks, where the host's arrangement of the entries
-// (conflict-free inside aligned groups of 32 against 64 banks) does not hold — measured on the H2O workload: 0.73 ms per
-// 65 536 evaluations with a stride of 4096 (no gain over the per-wave geometry).  With + 8 every state is shifted by one slot against its neighbour: the same
-// shift for all lanes of an instruction, the arrangement keeps its meaning.  DBG as k_sparse_vqe_rows.
-template <int NW, int EPT, int SSTRIDE, int DBG = 0>
+// tables behind them.  The entries are a symmetric quadratic form, E = sum_i a_i (sum_{j in row i} c_ij a_j): the host packs them
+// into OWNER PIECES (sparse_pack.hpp: up to EPR entries that share their first amplitude, either endpoint of an off-diagonal entry
+// may own it, rows above EPR entries are split, tails padded with coefficient 0).  Thread t holds RPT pieces in registers for the
+// whole launch — per piece the owner's byte offset, per slot the coefficient in two VGPRs and the other amplitude's byte offset,
+// two to a VGPR — and after ONE barrier every wave contracts its pieces against ALL 2 NW states: per piece and state the owner's
+// amplitude is read ONCE, then one ds_read_b64 and one fma per slot, t += c a_j, and acc += a_i t.  RPT (EPR + 1) reads per
+// thread and state against 2 entries-per-thread before (H2O: 44 against 74, LiH: 18 against 26; profiles/owner_rows/README.md);
+// the f64 operations per entry halve.  The addresses are offset + q * SSTRIDE, instruction immediates, no global traffic, no
+// address arithmetic.  Partial sums of the NW waves go through LDS and are added in wave order (no floating-point atomics: the
+// energy of a parameter vector depends neither on its position in the batch nor on the run).  The second barrier also frees the
+// states for the next work item of the persistent loop.
+// Two things the compiler needs: the stride at compile time (with a run-time stride it hoists all the addresses out of the work
+// loop and spills), and the sums pinned after each slot (otherwise it finishes state 0 over all slots first and parks every
+// other state's loads in scratch).  SSTRIDE is the state rounded up to 512 bytes PLUS 8: at a multiple of 512 the compiler pairs
+// the reads of two states into ds_read2st64_b64, which the LDS serves at half the rate of two ds_read_b64 (8 against 2 x 2 cycles
+// per wave) and in groups of 16 lanes against 32 banks, where the host's arrangement of the pieces (owners and slots that differ
+// mod 32 inside aligned groups of 32 lanes) does not hold — measured on the H2O workload: 0.73 ms per 65 536 evaluations with a
+// stride of 4096 (no gain over the per-wave geometry).  With + 8 every state is shifted by one slot against its neighbour: the
+// same shift for all lanes of an instruction, the arrangement keeps its meaning.  DBG as k_sparse_vqe_rows.
+// hc / ho: the packed tables of sparse_pack.hpp for NT = 64 NW threads — coefficients [RPT * EPR][NT]; 16-bit byte offsets
+// [RPT * EPR][NT] of the slots, then [RPT][NT] of the owners.
+template <int NW, int RPT, int EPR, int SSTRIDE, int DBG = 0>
 __global__ __launch_bounds__(NW * 64) void k_sparse_vqe_rows_shared(SparseArgs A, const double *__restrict__ theta,
                                                                     const SmallRot *__restrict__ tabrots, const uint64_t *__restrict__ rows,
-                                                                    int nrows4, const SpEntry *__restrict__ entries,
+                                                                    int nrows4, const double *__restrict__ hc, const uint16_t *__restrict__ ho,
                                                                     double *__restrict__ energies) {
     constexpr int NT = NW * 64, NS = 2 * NW, SD = SSTRIDE / 8;
     static_assert(SSTRIDE % 8 == 0 && SSTRIDE % 512 != 0 && NS * SSTRIDE <= 65536 && (NS * SSTRIDE) % 16 == 0,
@@ -318,15 +326,21 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_vqe_rows_shared(SparseArgs A
     double *sst = reinterpret_cast<double *>(sbase);
     double2 *csm = cs + (size_t)my * ntab1;
     unsigned char *cbase = reinterpret_cast<unsigned char *>(csm);
-    // this thread's entries: loaded once per launch
-    uint32_t oij[EPT];
-    double ec[EPT];
+    // this thread's pieces: loaded once per launch
+    constexpr int OPP = (EPR + 1) / 2;   // VGPRs of a piece's slot offsets
+    uint32_t oi[RPT], ojj[RPT][OPP];
+    double ec[RPT][EPR];
 #pragma unroll
-    for (int k = 0; k < EPT; ++k) {
-        const int e = tid + k * NT;
-        const SpEntry en = entries[min(e, A.nent - 1)];
-        oij[k] = ((en.ij & 0xfffu) * 8u) | ((((en.ij >> 12) & 0xfffu) * 8u) << 16);
-        ec[k] = e < A.nent ? en.c : 0.0;
+    for (int r = 0; r < RPT; ++r) {
+        oi[r] = ho[(size_t)(RPT * EPR + r) * NT + tid];
+#pragma unroll
+        for (int k = 0; k < EPR; ++k) ec[r][k] = hc[(size_t)(r * EPR + k) * NT + tid];
+#pragma unroll
+        for (int k = 0; k < OPP; ++k) {
+            const uint32_t lo = ho[(size_t)(r * EPR + 2 * k) * NT + tid];
+            const uint32_t hi = 2 * k + 1 < EPR ? ho[(size_t)(r * EPR + 2 * k + 1) * NT + tid] : 0u;
+            ojj[r][k] = lo | (hi << 16);
+        }
     }
     const int64_t nwork = (A.B + NS - 1) / NS;
     const uint64_t *rp = rows + l;
@@ -379,16 +393,25 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_vqe_rows_shared(SparseArgs A
         for (int q = 0; q < NS; ++q) acc[q] = 0.0;
         if (DBG != 3) {
 #pragma unroll
-            for (int k = 0; k < EPT; ++k) {
-                uint32_t pk = oij[k];
-                asm volatile("" : "+v"(pk));   // (keeps the unpacking inside the loop: 2 EPT registers less)
-                const uint32_t oi = pk & 0xffffu, oj = pk >> 16;
+            for (int r = 0; r < RPT; ++r) {
+                uint32_t po = oi[r];
+                asm volatile("" : "+v"(po));   // (keeps the address arithmetic inside the loop)
+                double t[NS];
 #pragma unroll
-                for (int q = 0; q < NS; ++q) {
-                    const double ai = *reinterpret_cast<const double *>(smem + oi + q * SSTRIDE);
-                    const double aj = *reinterpret_cast<const double *>(smem + oj + q * SSTRIDE);
-                    acc[q] += ec[k] * ai * aj;
+                for (int k = 0; k < EPR; ++k) {
+                    uint32_t pk = ojj[r][k / 2];
+                    asm volatile("" : "+v"(pk));   // (keeps the unpacking inside the loop: EPR registers less per piece)
+                    const uint32_t oj = (k & 1) ? pk >> 16 : pk & 0xffffu;
+#pragma unroll
+                    for (int q = 0; q < NS; ++q) {
+                        const double aj = *reinterpret_cast<const double *>(smem + oj + q * SSTRIDE);
+                        t[q] = k ? fma(ec[r][k], aj, t[q]) : ec[r][k] * aj;
+                    }
+#pragma unroll
+                    for (int q = 0; q < NS; ++q) asm volatile("" : "+v"(t[q]));
                 }
+#pragma unroll
+                for (int q = 0; q < NS; ++q) acc[q] = fma(*reinterpret_cast<const double *>(smem + po + q * SSTRIDE), t[q], acc[q]);
 #pragma unroll
                 for (int q = 0; q < NS; ++q) asm volatile("" : "+v"(acc[q]));
             }
