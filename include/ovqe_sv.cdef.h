@@ -56,6 +56,11 @@ int ovqe_xsum_expect_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chun
 int ovqe_xsum_expect_finish(ovqe_handle h, int32_t id, double *out_re_im);
 int ovqe_xsum_apply_local(ovqe_handle h, int32_t id, void *out_dev, double ident);
 int ovqe_xsum_apply_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chunk, const void *ket_chunk, void *out_dev);
+int ovqe_vec_dot(ovqe_handle h, const void *a_dev, const void *b_dev, double *out_re_im);
+int ovqe_vec_lanczos_update(ovqe_handle h, void *w_dev, const void *v_dev, const void *vprev_dev, double alpha, double beta,
+                            double *norm2_out);
+int ovqe_vec_scale(ovqe_handle h, void *v_dev, double s);
+int ovqe_vec_axpy(ovqe_handle h, void *y_dev, const void *x_dev, double s, int overwrite);
 int ovqe_shard_pack(ovqe_handle h, uint64_t local_bit_mask, uint64_t block, int64_t first, int64_t count, void *dst,
                     int real_parts_only);
 int ovqe_shard_unpack(ovqe_handle h, uint64_t local_bit_mask, uint64_t block, int64_t first, int64_t count, const void *src,

@@ -125,6 +125,13 @@ int ovqe_set_stream(ovqe_handle h, void *hip_stream);
  *   "lanczos_keep_gb" (160) ovqe_ground_state keeps its Lanczos vectors in HBM up to this many GB (and 60 % of the free memory): one pass of
  *                     the recurrence gives the Ritz vector; 0 or vectors that do not fit: the recurrence runs twice
  *
+ *   "real_state" (0)  the state buffer holds 2^n_local DOUBLES (8 bytes per amplitude: a shard of the partitioned register while its
+ *                     amplitudes are real).  BUFFER-SIZE CONTRACT: while it is set, the state and every shard-sized operand of
+ *                     ovqe_init_basis, ovqe_randomize, ovqe_norm2, ovqe_apply_pauli_rotations (odd-Y strings only), ovqe_shard_pack / _unpack,
+ *                     ovqe_xsum_expect_*, ovqe_xsum_apply_* (out_dev; ket_chunk = 2^chunk_bits doubles) and ovqe_vec_* is 2^n_local
+ *                     doubles; the caller sets it together with ovqe_adopt_state of a buffer of that size.  Every other entry
+ *                     point keeps reading 16-byte amplitudes: clear the option and widen the buffer before calling one.
+ *
  * (B) GEOMETRY — defaults are the measured optimum on MI355X
  *   streaming path: "tile_bits" (-1 automatic: 12 for n >= 25, else 11; 0 = one sweep per op), "tile_low" (4), "apply_min_tiles" (256),
  *                     "index_streams"; "adjoint_tile_bits" (-1 automatic: 12 for n >= 25, else 11; 0 = one backward pass per run) of ovqe_adjoint_rotations
@@ -183,7 +190,8 @@ int ovqe_get_amplitudes(ovqe_handle h, int64_t count, const uint64_t *local_indi
 /* deterministic synthetic state: amp(i) = scale * (u1(i), u2(i)), u in [-1,1) from a counter-based
  * integer hash of (seed, global index) (bit-reproducible on the host, see openvqe_amd/synth.py);
  * scale normalises the FULL state when norm2_total > 0 is given, else this shard alone.
- * Returns the scale used. */
+ * Returns the scale used.  Under option "real_state" the 2^n_local doubles take the REAL parts of that fill (amp(i) = scale * u1(i)
+ * at the same global index: independent of the partition) and the shard's own norm counts those alone. */
 int ovqe_randomize(ovqe_handle h, uint64_t seed, double norm2_total, double *scale_out);
 int ovqe_norm2(ovqe_handle h, double *out); /* sum |a_i|^2 over this shard */
 
@@ -244,10 +252,28 @@ int ovqe_xsum_expect_local(ovqe_handle h, int32_t id, double *out);
 int ovqe_xsum_expect_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chunk, const void *ket_chunk);
 /* the accumulated remote contractions (re, im) since the last finish; resets the accumulator */
 int ovqe_xsum_expect_finish(ovqe_handle h, int32_t id, double *out_re_im);
-/* out = ident * psi + H_0 psi on this shard's state (out: 2^n_local amplitudes, != the state) */
+/* out = ident * psi + H_0 psi on this shard's state (out: 2^n_local amplitudes, != the state).  Under option "real_state" out holds
+ * 2^n_local doubles and must not overlap the state; a sum that does not map real vectors to real vectors (a string with an odd
+ * number of Y, a coefficient with an imaginary part) is refused with OVQE_ERR_STATE, here and in ovqe_xsum_apply_remote */
 int ovqe_xsum_apply_local(ovqe_handle h, int32_t id, void *out_dev, double ident);
-/* out += H_d ket for one received chunk (out: the 2^n_local-amplitude buffer being accumulated) */
+/* out += H_d ket for one received chunk (out: the 2^n_local-amplitude buffer being accumulated; under "real_state" ket_chunk is
+ * 2^chunk_bits doubles and out 2^n_local doubles) */
 int ovqe_xsum_apply_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chunk, const void *ket_chunk, void *out_dev);
+
+/* ---- Lanczos vector operations on caller-held device buffers of the handle's storage (2^n_local amplitudes of 16 bytes, or 2^n_local
+ * doubles under option "real_state"): the steps of ovqe_ground_state for a host layer that runs the recurrence over a partitioned
+ * register (openvqe_amd/distributed.py ground_state; ref:openvqe/adapt/fermionic_adapt_vqe.py:419 takes the same eigenpair from a
+ * sparse matrix on one host).  Each returns the partial of THIS shard — the library never communicates.  dot and lanczos_update
+ * synchronise the handle's stream; scale and axpy only enqueue on it. */
+/* sum_i conj(a_i) b_i -> (re, im); im = 0 under "real_state" */
+int ovqe_vec_dot(ovqe_handle h, const void *a_dev, const void *b_dev, double *out_re_im);
+/* w <- w - alpha v - beta v_prev (v_prev may be NULL), *norm2_out = sum_i |w_i|^2 of the result */
+int ovqe_vec_lanczos_update(ovqe_handle h, void *w_dev, const void *v_dev, const void *vprev_dev, double alpha, double beta,
+                            double *norm2_out);
+/* v <- s v */
+int ovqe_vec_scale(ovqe_handle h, void *v_dev, double s);
+/* y <- y + s x, or y <- s x when overwrite != 0 */
+int ovqe_vec_axpy(ovqe_handle h, void *y_dev, const void *x_dev, double s, int overwrite);
 
 /* ---- k-bit shard exchange of a partitioned register (openvqe_amd/distributed.py: k global index bits traded for k local ones in one
  * all-to-all among the 2^k ranks of a sub-cube; the many-device form of the state that qpu.submit keeps on one host,

@@ -67,6 +67,10 @@ SIGNATURES = {
     "ovqe_xsum_expect_finish": (_int, [_H, ctypes.c_int32, _f64p]),
     "ovqe_xsum_apply_local": (_int, [_H, ctypes.c_int32, _vp, _dbl]),
     "ovqe_xsum_apply_remote": (_int, [_H, ctypes.c_int32, _u64, _u64, _vp, _vp]),
+    "ovqe_vec_dot": (_int, [_H, _vp, _vp, _f64p]),
+    "ovqe_vec_lanczos_update": (_int, [_H, _vp, _vp, _vp, _dbl, _dbl, ctypes.POINTER(_dbl)]),
+    "ovqe_vec_scale": (_int, [_H, _vp, _dbl]),
+    "ovqe_vec_axpy": (_int, [_H, _vp, _vp, _dbl, _int]),
     "ovqe_shard_pack": (_int, [_H, _u64, _u64, _i64, _i64, _vp, _int]),
     "ovqe_shard_unpack": (_int, [_H, _u64, _u64, _i64, _i64, _vp, _int]),
     "ovqe_set_hamiltonian": (_int, [_H, _i64, _u64p, _u64p, _f64p, _dbl]),

@@ -269,6 +269,25 @@ class Statevector:
     def xsum_apply_local(self, sid, out_ptr, ident=0.0):
         self._ck(self._L.ovqe_xsum_apply_local(self._h, int(sid), ctypes.c_void_p(out_ptr), float(ident)))
 
+    # -- Lanczos vector operations on device buffers of the handle's storage (shard-local partials; ovqe_vec_*)
+    def vec_dot(self, a_ptr, b_ptr):
+        out = np.zeros(2, np.float64)
+        self._ck(self._L.ovqe_vec_dot(self._h, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr), out))
+        return complex(out[0], out[1])
+
+    def vec_lanczos_update(self, w_ptr, v_ptr, vprev_ptr, alpha, beta):
+        out = ctypes.c_double()
+        self._ck(self._L.ovqe_vec_lanczos_update(self._h, ctypes.c_void_p(w_ptr), ctypes.c_void_p(v_ptr),
+                                                 None if vprev_ptr is None else ctypes.c_void_p(vprev_ptr), float(alpha), float(beta),
+                                                 ctypes.byref(out)))
+        return out.value
+
+    def vec_scale(self, v_ptr, s):
+        self._ck(self._L.ovqe_vec_scale(self._h, ctypes.c_void_p(v_ptr), float(s)))
+
+    def vec_axpy(self, y_ptr, x_ptr, s, overwrite=False):
+        self._ck(self._L.ovqe_vec_axpy(self._h, ctypes.c_void_p(y_ptr), ctypes.c_void_p(x_ptr), float(s), 1 if overwrite else 0))
+
     def xsum_apply_remote(self, sid, d, chunk, ket_ptr, out_ptr):
         self._ck(self._L.ovqe_xsum_apply_remote(self._h, int(sid), int(d), int(chunk), ctypes.c_void_p(ket_ptr),
                                                 ctypes.c_void_p(out_ptr)))

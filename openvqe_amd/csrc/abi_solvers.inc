@@ -222,6 +222,76 @@ extern "C" int ovqe_ground_state(ovqe_handle h, double tol, int max_iter, uint64
     return OVQE_OK;
 } OVQE_CATCH(h)
 
+// ---- Lanczos vector operations on caller-held shard buffers ----------------------------------------------------------------------
+// What struct Lanczos does inside ovqe_ground_state, for a host layer that runs the recurrence over a partitioned register
+// (openvqe_amd/distributed.py: ShardedStatevector.ground_state).  Operands are device buffers of the handle's storage: 2^n_local
+// amp_t, or 2^n_local doubles under "real_state" — the kernels read a buffer as double2 elements, and a real buffer is half as many
+// elements with the same sums.  Every value returned is the partial of THIS shard: the caller reduces over the ranks.
+namespace {
+inline uint64_t vec_elements(ovqe_handle h) { return h->opt_real_state ? std::max<uint64_t>(h->namps >> 1, 1) : h->namps; }
+int vec_reduce_prepare(ovqe_handle h, int nb) {
+    int rc = ensure(h, h->d_partials, (size_t)nb * sizeof(double2));
+    if (!rc) rc = ensure(h, h->d_result, 64 * sizeof(double2));
+    return rc;
+}
+int vec_reduce_to_host(ovqe_handle h, int nb, double2 *out) {
+    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, h->stream, (const double2 *)h->d_partials.p, (int64_t)nb, (double2 *)h->d_result.p, 0);
+    HIPC(h, hipGetLastError());
+    HIPC(h, hipMemcpyAsync(h->h_result, h->d_result.p, sizeof(double2), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    *out = h->h_result[0];
+    return OVQE_OK;
+}
+}  // namespace
+
+extern "C" int ovqe_vec_dot(ovqe_handle h, const void *a_dev, const void *b_dev, double *out_re_im) try {
+    OVQE_ENTER(h);
+    if (!h || !a_dev || !b_dev || !out_re_im) return OVQE_ERR_INVALID;
+    const uint64_t nel = vec_elements(h);
+    const int nb = reduce_blocks(nel);
+    if (int rc = vec_reduce_prepare(h, nb)) return rc;
+    hipLaunchKernelGGL(k_dot, dim3(nb), dim3(256), 0, h->stream, (const amp_t *)a_dev, (const amp_t *)b_dev, nel, (double2 *)h->d_partials.p);
+    double2 r;
+    if (int rc = vec_reduce_to_host(h, nb, &r)) return rc;
+    out_re_im[0] = r.x;
+    out_re_im[1] = h->opt_real_state ? 0.0 : r.y;   // (the y sum of doubles read as pairs means nothing)
+    return OVQE_OK;
+} OVQE_CATCH(h)
+
+extern "C" int ovqe_vec_lanczos_update(ovqe_handle h, void *w_dev, const void *v_dev, const void *vprev_dev, double alpha, double beta,
+                                       double *norm2_out) try {
+    OVQE_ENTER(h);
+    if (!h || !w_dev || !v_dev || !norm2_out) return OVQE_ERR_INVALID;
+    if (w_dev == v_dev || w_dev == vprev_dev) return fail(h, OVQE_ERR_INVALID, "ovqe_vec_lanczos_update: w must differ from v and v_prev");
+    const uint64_t nel = vec_elements(h);
+    const int nb = reduce_blocks(nel);
+    if (int rc = vec_reduce_prepare(h, nb)) return rc;
+    hipLaunchKernelGGL(k_lanczos_update, dim3(nb), dim3(256), 0, h->stream, (amp_t *)w_dev, (const amp_t *)v_dev, (const amp_t *)vprev_dev, alpha, beta,
+                       nel, (double2 *)h->d_partials.p);
+    double2 r;
+    if (int rc = vec_reduce_to_host(h, nb, &r)) return rc;
+    *norm2_out = r.x;
+    return OVQE_OK;
+} OVQE_CATCH(h)
+
+extern "C" int ovqe_vec_scale(ovqe_handle h, void *v_dev, double s) try {
+    OVQE_ENTER(h);
+    if (!h || !v_dev) return OVQE_ERR_INVALID;
+    const uint64_t nel = vec_elements(h);
+    hipLaunchKernelGGL(k_scale, dim3(reduce_blocks(nel)), dim3(256), 0, h->stream, (amp_t *)v_dev, nel, s);
+    HIPC(h, hipGetLastError());
+    return OVQE_OK;
+} OVQE_CATCH(h)
+
+extern "C" int ovqe_vec_axpy(ovqe_handle h, void *y_dev, const void *x_dev, double s, int overwrite) try {
+    OVQE_ENTER(h);
+    if (!h || !y_dev || !x_dev) return OVQE_ERR_INVALID;
+    const uint64_t nel = vec_elements(h);
+    hipLaunchKernelGGL(k_axpy_real, dim3(reduce_blocks(nel)), dim3(256), 0, h->stream, (amp_t *)y_dev, (const amp_t *)x_dev, s, nel, overwrite ? 1 : 0);
+    HIPC(h, hipGetLastError());
+    return OVQE_OK;
+} OVQE_CATCH(h)
+
 // ---- lowest eigenpair inside the support of the stored program (sector tables) ------------------------------------
 extern "C" int ovqe_sector_ground_state(ovqe_handle h, double tol, int max_iter, uint64_t seed, double *energy, double *residual,
                                         int *iterations) try {

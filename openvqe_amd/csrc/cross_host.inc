@@ -163,33 +163,36 @@ int launch_tile_cross(ovqe_handle h, const CrossCover &C, const CrossPass &ps, c
     return OVQE_OK;
 }
 
-template <int M>
-int launch_tile_cross_real(ovqe_handle h, const CrossCover &C, const CrossPass &ps, const double *ket, const double *bra, uint64_t ket_gbase,
+template <int M, bool DOT>
+int launch_tile_cross_real(ovqe_handle h, const CrossCover &C, const CrossPass &ps, const double *ket, double *other, uint64_t ket_gbase,
                            uint64_t chunk_off, unsigned grid, double2 *partials) {
     constexpr int NT = 1 << TILE_EXPECT_LOG_NT;
     constexpr size_t smem = tile_apply_lds<M>(sizeof(double), NT / 64).bytes;
-    if (int rc = lds_opt_in<&k_tile_cross_real<M, NT, true>, &k_tile_cross_real<M, NT, false>>(h, smem)) return rc;
+    if (int rc = lds_opt_in<&k_tile_cross_real<M, NT, true, DOT>, &k_tile_cross_real<M, NT, false, DOT>>(h, smem)) return rc;
     if (h->n_local >= 26)
-        hipLaunchKernelGGL((k_tile_cross_real<M, NT, true>), dim3(grid), dim3(NT), smem, h->stream, ket, bra, ket_gbase, chunk_off, ps,
+        hipLaunchKernelGGL((k_tile_cross_real<M, NT, true, DOT>), dim3(grid), dim3(NT), smem, h->stream, ket, other, ket_gbase, chunk_off, ps,
                            (const ExChunkT *)C.d_achunks.p, (const ExAGroupT *)C.d_agroups.p, (const ExTermT *)C.d_aterms.p, partials);
     else
-        hipLaunchKernelGGL((k_tile_cross_real<M, NT, false>), dim3(grid), dim3(NT), smem, h->stream, ket, bra, ket_gbase, chunk_off, ps,
+        hipLaunchKernelGGL((k_tile_cross_real<M, NT, false, DOT>), dim3(grid), dim3(NT), smem, h->stream, ket, other, ket_gbase, chunk_off, ps,
                            (const ExChunkT *)C.d_achunks.p, (const ExAGroupT *)C.d_agroups.p, (const ExTermT *)C.d_aterms.p, partials);
     HIPC(h, hipGetLastError());
     return OVQE_OK;
 }
 
-// the passes of partner cover C (real flavour) over one received chunk of doubles: partials += bra . (H_d ket)
-int run_cross_chunk_real(ovqe_handle h, CrossSum &X, const CrossCover &C, uint64_t chunk, const double *ket, const double *bra) {
-    const int m = X.chunk_bits;
+// the passes of cover C (real flavour) over one chunk of 2^m doubles; DOT: partials += other . (H_d ket), else other += H_d ket.
+// A partner's cover takes the received chunks (m = the plan's chunk_bits); the d = 0 cover of sigma = H psi takes the shard itself
+// as its one chunk (m = n_local, xsum_build_local).
+template <bool DOT>
+int run_cross_chunk_real(ovqe_handle h, CrossSum &X, const CrossCover &C, int m, uint64_t chunk, const double *ket, double *other) {
     const uint64_t csize = 1ull << m;
     const uint64_t ket_gbase = ((h->shard ^ C.d) << h->n_local) | (chunk << m);
     double2 *partials = (double2 *)X.d_part.p;
     if (C.small) {
-        const int nb = (int)std::min<uint64_t>(X.part_slots, std::max<uint64_t>(1, (csize + 255) / 256));
+        const int nb = (int)std::min<uint64_t>(DOT ? X.part_slots : 2048, std::max<uint64_t>(1, (csize + 255) / 256));
         for (size_t k = 0; k < C.class_h.size(); ++k)
-            hipLaunchKernelGGL(k_cross_small_real, dim3(nb), dim3(256), 0, h->stream, ket, bra + ((chunk ^ C.class_h[k]) << m), csize, ket_gbase,
-                               (const HGroup *)C.d_groups.p, C.class_groups[k].first, C.class_groups[k].second, (const HTerm *)C.d_terms.p, partials);
+            hipLaunchKernelGGL((k_cross_small_real<DOT>), dim3(nb), dim3(256), 0, h->stream, ket, other + ((chunk ^ C.class_h[k]) << m), csize,
+                               ket_gbase, (const HGroup *)C.d_groups.p, C.class_groups[k].first, C.class_groups[k].second,
+                               (const HTerm *)C.d_terms.p, partials);
         HIPC(h, hipGetLastError());
         return OVQE_OK;
     }
@@ -197,9 +200,9 @@ int run_cross_chunk_real(ovqe_handle h, CrossSum &X, const CrossCover &C, uint64
     for (const CrossPass &ps : C.passes) {
         int rc;
         switch (C.M) {
-        case 11: rc = launch_tile_cross_real<11>(h, C, ps, ket, bra, ket_gbase, chunk << m, grid, partials); break;
-        case 12: rc = launch_tile_cross_real<12>(h, C, ps, ket, bra, ket_gbase, chunk << m, grid, partials); break;
-        default: rc = launch_tile_cross_real<13>(h, C, ps, ket, bra, ket_gbase, chunk << m, grid, partials); break;
+        case 11: rc = launch_tile_cross_real<11, DOT>(h, C, ps, ket, other, ket_gbase, chunk << m, grid, partials); break;
+        case 12: rc = launch_tile_cross_real<12, DOT>(h, C, ps, ket, other, ket_gbase, chunk << m, grid, partials); break;
+        default: rc = launch_tile_cross_real<13, DOT>(h, C, ps, ket, other, ket_gbase, chunk << m, grid, partials); break;
         }
         if (rc) return rc;
     }
@@ -283,6 +286,29 @@ const CrossCover *xsum_partner(ovqe_handle h, CrossSum &X, uint64_t d, uint64_t 
     return nullptr;
 }
 
+// sigma = H psi on real amplitudes: the d = 0 groups as one more cover, the shard being its own "partner" and its one chunk
+// (m = n_local: no x bits above the chunk, so one class / no displacement above it), built at the first real apply
+int xsum_build_local(ovqe_handle h, CrossSum &X) {
+    if (X.local_built) return OVQE_OK;
+    X.local_cover.d = 0;
+    int rc = build_cross_cover(h, X.local_cover, X.raw_local, h->n_local, true);
+    if (rc) return rc;
+    X.local_built = true;
+    return OVQE_OK;
+}
+
+// real storage holds sigma only when the sum maps real vectors to real vectors
+int xsum_real_apply_ok(ovqe_handle h, const CrossSum &X, const char *who, const void *out_dev) {
+    if (!X.real_map)
+        return fail(h, OVQE_ERR_STATE, std::string(who) + ": under real_state sigma = H psi needs a real-symmetric sum (every string an even number of Y, "
+                                       "every coefficient real); this one would leave the real vectors: clear real_state and widen the buffers");
+    const char *s0 = (const char *)h->state, *o0 = (const char *)out_dev;
+    const size_t bytes = (size_t)h->namps * sizeof(double);
+    if (o0 < s0 + bytes && s0 < o0 + bytes)
+        return fail(h, OVQE_ERR_STATE, std::string(who) + ": out overlaps the state buffer (under real_state both hold 2^n_local doubles, not complex amplitudes)");
+    return OVQE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -301,18 +327,14 @@ int ovqe_xsum_create(ovqe_handle h, int64_t T, const uint64_t *x, const uint64_t
     std::vector<uint64_t> lx, lz;
     std::vector<double> lr, li;
     std::map<uint64_t, std::map<uint64_t, CrossRawGroup>> remote;   // d -> local x -> group (ascending: the same plan on every rank)
+    std::map<uint64_t, CrossRawGroup> local_raw;                    // the d = 0 groups once more, for sigma = H psi on real amplitudes
+    X->real_map = true;
     for (int64_t t = 0; t < T; ++t) {
         if ((x[t] | z[t]) & ~allmask) return fail(h, OVQE_ERR_INVALID, "Pauli mask has bits beyond the register");
         const double a = coeff_re[t], b = coeff_im ? coeff_im[t] : 0.0;
         if (b != 0.0) X->hermitian = false;
+        if (b != 0.0 || (__builtin_popcountll(x[t] & z[t]) & 1)) X->real_map = false;
         const uint64_t d = x[t] >> h->n_local;
-        if (d == 0) {
-            lx.push_back(x[t]);
-            lz.push_back(z[t]);
-            lr.push_back(a);
-            li.push_back(b);
-            continue;
-        }
         HTerm ht;
         ht.z = z[t];
         switch (__builtin_popcountll(x[t] & z[t]) & 3) {  // (a + ib) * i^ny
@@ -320,6 +342,16 @@ int ovqe_xsum_create(ovqe_handle h, int64_t T, const uint64_t *x, const uint64_t
         case 1: ht.cr = -b; ht.ci = a; break;
         case 2: ht.cr = -a; ht.ci = -b; break;
         default: ht.cr = b; ht.ci = -a; break;
+        }
+        if (d == 0) {
+            lx.push_back(x[t]);
+            lz.push_back(z[t]);
+            lr.push_back(a);
+            li.push_back(b);
+            CrossRawGroup &g = local_raw[x[t]];
+            g.x = x[t];
+            g.terms.push_back(ht);
+            continue;
         }
         CrossRawGroup &g = remote[d][x[t] & lmask];
         g.x = x[t] & lmask;
@@ -336,6 +368,7 @@ int ovqe_xsum_create(ovqe_handle h, int64_t T, const uint64_t *x, const uint64_t
         H.version = ++h->ham_versions;
         X->has_local = true;
     }
+    for (auto &g : local_raw) X->raw_local.push_back(std::move(g.second));
     for (auto &kv : remote) {
         std::vector<CrossRawGroup> groups;
         for (auto &g : kv.second) groups.push_back(std::move(g.second));
@@ -446,7 +479,7 @@ int ovqe_xsum_expect_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chun
     if (!C) return OVQE_ERR_INVALID;
     h->last_passes = C->small ? (int64_t)C->class_h.size() : (int64_t)C->passes.size();
     h->last_pass_bytes = (int64_t)((real ? 16.0 : 32.0) * (double)(1ull << X->chunk_bits) * (double)h->last_passes);
-    if (real) return run_cross_chunk_real(h, *X, *C, chunk, (const double *)ket_chunk, (const double *)h->state);
+    if (real) return run_cross_chunk_real<true>(h, *X, *C, X->chunk_bits, chunk, (const double *)ket_chunk, (double *)h->state);
     return run_cross_chunk<true>(h, *X, *C, chunk, (const amp_t *)ket_chunk, h->state);
 } OVQE_CATCH(h)
 
@@ -470,8 +503,20 @@ int ovqe_xsum_apply_local(ovqe_handle h, int32_t id, void *out_dev, double ident
     OVQE_ENTER(h);
     CrossSum *X = xsum_of(h, id);
     if (!X || !out_dev) return OVQE_ERR_INVALID;
+    if (h->opt_real_state) {   // 2^n_local doubles: out = ident * psi, then the d = 0 cover with the shard as its own ket chunk
+        int rc = xsum_real_apply_ok(h, *X, "ovqe_xsum_apply_local", out_dev);
+        if (!rc && X->has_local) rc = xsum_build_local(h, *X);
+        if (rc) return rc;
+        const uint64_t nel = std::max<uint64_t>(h->namps >> 1, 1);   // (the doubles as double2 elements, as ovqe_norm2 reads them)
+        hipLaunchKernelGGL(k_axpy_real, dim3(reduce_blocks(nel)), dim3(256), 0, h->stream, (amp_t *)out_dev, (const amp_t *)h->state, ident, nel, 1);
+        HIPC(h, hipGetLastError());
+        if (!X->has_local) return OVQE_OK;
+        const CrossCover &C = X->local_cover;
+        h->last_passes = C.small ? (int64_t)C.class_h.size() : (int64_t)C.passes.size();
+        h->last_pass_bytes = (int64_t)(24.0 * (double)h->namps * (double)h->last_passes);   // ket read, out read and written
+        return run_cross_chunk_real<false>(h, *X, C, h->n_local, 0, (const double *)h->state, (double *)out_dev);
+    }
     if (out_dev == (void *)h->state) return fail(h, OVQE_ERR_INVALID, "ovqe_xsum_apply_local: out must differ from the state");
-    if (h->opt_real_state) return fail(h, OVQE_ERR_STATE, "sigma = H psi works on complex amplitudes: clear option real_state and widen the buffer");
     if (!X->has_local) {   // out = ident * psi
         hipLaunchKernelGGL(k_apply_sum, dim3(reduce_blocks(h->namps)), dim3(256), 0, h->stream, (amp_t *)out_dev, (const amp_t *)h->state,
                            (amp_t *)nullptr, h->namps, h->base, (const HGroup *)nullptr, 0, (const HTerm *)nullptr, 1.0, 0.0, ident, 0.0);
@@ -485,7 +530,14 @@ int ovqe_xsum_apply_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chunk
     OVQE_ENTER(h);
     CrossSum *X = xsum_of(h, id);
     if (!X || !ket_chunk || !out_dev) return OVQE_ERR_INVALID;
-    if (h->opt_real_state) return fail(h, OVQE_ERR_STATE, "sigma = H psi works on complex amplitudes: clear option real_state and widen the buffer");
+    if (h->opt_real_state) {
+        if (int rc = xsum_real_apply_ok(h, *X, "ovqe_xsum_apply_remote", out_dev)) return rc;
+        const CrossCover *C = xsum_partner(h, *X, d, chunk, 1);
+        if (!C) return OVQE_ERR_INVALID;
+        h->last_passes = C->small ? (int64_t)C->class_h.size() : (int64_t)C->passes.size();
+        h->last_pass_bytes = (int64_t)(24.0 * (double)(1ull << X->chunk_bits) * (double)h->last_passes);
+        return run_cross_chunk_real<false>(h, *X, *C, X->chunk_bits, chunk, (const double *)ket_chunk, (double *)out_dev);
+    }
     const CrossCover *C = xsum_partner(h, *X, d, chunk, 0);
     if (!C) return OVQE_ERR_INVALID;
     return run_cross_chunk<false>(h, *X, *C, chunk, (const amp_t *)ket_chunk, (amp_t *)out_dev);

@@ -161,6 +161,10 @@ struct CrossSum {
     std::vector<std::pair<uint64_t, std::vector<CrossRawGroup>>> raw;   // the terms of every rank difference d != 0, ascending
     std::vector<CrossCover> partners[2];   // their pass lists: [0] complex amplitudes, [1] real amplitudes (option "real_state"); built at first use
     bool built[2] = {false, false};
+    bool real_map = false;   // every string an even number of Y and every coefficient real: the sum maps real vectors to real vectors
+    std::vector<CrossRawGroup> raw_local;   // the d = 0 terms in the form of `raw`, and their cover for sigma = H psi on real amplitudes
+    CrossCover local_cover;                 // (k_tile_cross_real APPLY with the shard as its own partner), built at the first real apply
+    bool local_built = false;
     DevBuf d_part;           // per-workgroup partial sums of the remote contractions of one expectation value
     size_t part_slots = 0;
 };
@@ -549,6 +553,8 @@ void free_hamdev(HamDev &H) {
 void free_cross_sum(CrossSum *X) {
     if (!X) return;
     free_hamdev(X->local);
+    for (DevBuf *b : {&X->local_cover.d_achunks, &X->local_cover.d_agroups, &X->local_cover.d_aterms, &X->local_cover.d_groups, &X->local_cover.d_terms})
+        if (b->p) (void)hipFree(b->p);
     for (int f = 0; f < 2; ++f)
         for (CrossCover &C : X->partners[f])
             for (DevBuf *b : {&C.d_achunks, &C.d_agroups, &C.d_aterms, &C.d_groups, &C.d_terms})
@@ -1454,8 +1460,12 @@ int ovqe_randomize(ovqe_handle h, uint64_t seed, double norm2_total, double *sca
     int rc = ensure(h, h->d_partials, (size_t)nb * sizeof(double2));
     if (!rc) rc = ensure(h, h->d_result, 64 * sizeof(double2));
     if (rc) return rc;
-    hipLaunchKernelGGL(k_randomize, dim3(nb), dim3(256), 0, h->stream, h->state, h->namps, h->base, seed, 1.0,
-                       (double2 *)h->d_partials.p);
+    if (h->opt_real_state)   // 2^n_local doubles: the real parts of the complex fill
+        hipLaunchKernelGGL(k_randomize_real, dim3(nb), dim3(256), 0, h->stream, (double *)h->state, h->namps, h->base, seed, 1.0,
+                           (double2 *)h->d_partials.p);
+    else
+        hipLaunchKernelGGL(k_randomize, dim3(nb), dim3(256), 0, h->stream, h->state, h->namps, h->base, seed, 1.0,
+                           (double2 *)h->d_partials.p);
     hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, h->stream, (const double2 *)h->d_partials.p, (int64_t)nb,
                        (double2 *)h->d_result.p, 0);
     HIPC(h, hipGetLastError());
@@ -1463,7 +1473,7 @@ int ovqe_randomize(ovqe_handle h, uint64_t seed, double norm2_total, double *sca
     HIPC(h, hipStreamSynchronize(h->stream));
     const double n2 = norm2_total > 0.0 ? norm2_total : h->h_result[0].x;
     const double scale = 1.0 / std::sqrt(n2);
-    hipLaunchKernelGGL(k_scale, dim3(nb), dim3(256), 0, h->stream, h->state, h->namps, scale);
+    hipLaunchKernelGGL(k_scale, dim3(nb), dim3(256), 0, h->stream, h->state, h->opt_real_state ? std::max<uint64_t>(h->namps >> 1, 1) : h->namps, scale);
     HIPC(h, hipGetLastError());
     HIPC(h, hipStreamSynchronize(h->stream));
     if (scale_out) *scale_out = scale;

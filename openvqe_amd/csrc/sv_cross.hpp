@@ -161,8 +161,13 @@ __global__ __launch_bounds__(NT) void k_tile_cross(const amp_t *__restrict__ ket
 // the pass's masks live in the index space of the pairs (index bit 0 is always inside the tile, d_out never has it); the tile holds
 // 2^M doubles (M <= 13: the same 64 KB).  Terms with an imaginary folded coefficient (odd number of Y) vanish between real vectors
 // and are left out by the host; partials take the real part only.
-template <int M, int NT, bool NTL>
-__global__ __launch_bounds__(NT) void k_tile_cross_real(const double *__restrict__ ket, const double *__restrict__ bra, uint64_t ket_gbase,
+// APPLY (DOT = false): other_i += s_i, sigma = H psi of a real-symmetric sum on real amplitudes (the host refuses any other sum: a
+// dropped term would be a wrong sigma).  The output tile is read, added to and written back as 16-byte amplitude pairs.  Within a
+// pass the map ket tile -> output tile (tile ^ d_out, d_out outside the tile bits) is a bijection and a workgroup owns one ket tile:
+// every (pass, ket tile) writes its own output tile, so a pass needs no atomics; passes, chunks and partners follow each other on
+// one stream.  (The same invariant carries the APPLY form of k_tile_cross.)  A ket tile of zeros adds nothing: the early exit stays.
+template <int M, int NT, bool NTL, bool DOT>
+__global__ __launch_bounds__(NT) void k_tile_cross_real(const double *__restrict__ ket, double *__restrict__ other, uint64_t ket_gbase,
                                                         uint64_t chunk_off, CrossPass ps, const ExChunkT *__restrict__ chunks,
                                                         const ExAGroupT *__restrict__ groups, const ExTermT *__restrict__ terms,
                                                         double2 *__restrict__ partials) {
@@ -177,7 +182,7 @@ __global__ __launch_bounds__(NT) void k_tile_cross_real(const double *__restrict
     ExAGroupT *lg = reinterpret_cast<ExAGroupT *>(smem + L.groups);
     double2 *red = reinterpret_cast<double2 *>(smem + L.red);
     const v2d *p = reinterpret_cast<const v2d *>(ket);
-    const v2d *q = reinterpret_cast<const v2d *>(bra);
+    v2d *q = reinterpret_cast<v2d *>(other);
 
     uint64_t tb = blockIdx.x;   // pair-index space
     for (uint64_t mk = ps.smask; mk; mk &= mk - 1ull) tb = insert_zero(tb, __ffsll((long long)mk) - 1);
@@ -246,26 +251,39 @@ __global__ __launch_bounds__(NT) void k_tile_cross_real(const double *__restrict
             }
         }
     }
-    v2d breg[TRIPS];     // (the bra tile behind the groups: fewer registers while they run)
+    if constexpr (DOT) {
+        v2d breg[TRIPS];     // (the bra tile behind the groups: fewer registers while they run)
 #pragma unroll
-    for (int j = 0; j < TRIPS; ++j) breg[j] = NTL ? __builtin_nontemporal_load(&q[ob | glow | spread_bits((uint32_t)j, ps.mask_hi)])
-                                                  : q[ob | glow | spread_bits((uint32_t)j, ps.mask_hi)];
-    double part = 0.0;
+        for (int j = 0; j < TRIPS; ++j) breg[j] = NTL ? __builtin_nontemporal_load(&q[ob | glow | spread_bits((uint32_t)j, ps.mask_hi)])
+                                                      : q[ob | glow | spread_bits((uint32_t)j, ps.mask_hi)];
+        double part = 0.0;
 #pragma unroll
-    for (int j = 0; j < TRIPS; ++j) part += breg[j].x * acc0[j] + breg[j].y * acc1[j];
-    __syncthreads();
-    const double2 t = block_sum<NT>(make_double2(part, 0.0), red);
-    if (threadIdx.x == 0) {
-        const double2 o = partials[blockIdx.x];
-        partials[blockIdx.x] = make_double2(o.x + t.x, o.y);
+        for (int j = 0; j < TRIPS; ++j) part += breg[j].x * acc0[j] + breg[j].y * acc1[j];
+        __syncthreads();
+        const double2 t = block_sum<NT>(make_double2(part, 0.0), red);
+        if (threadIdx.x == 0) {
+            const double2 o = partials[blockIdx.x];
+            partials[blockIdx.x] = make_double2(o.x + t.x, o.y);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < TRIPS; ++j) {
+            const uint64_t g = ob | glow | spread_bits((uint32_t)j, ps.mask_hi);
+            const v2d o = q[g];
+            v2d r;
+            r.x = o.x + acc0[j];
+            r.y = o.y + acc1[j];
+            q[g] = r;
+        }
     }
 }
 
 // Registers below the tile sizes.  Groups [g0, g1) share the part of their x mask above the chunk bits (the host launches one
 // class at a time), so output amplitude i of the class's output chunk `other` takes ket_{i ^ x_low} of the received chunk from
 // every group; a thread owns its outputs.  HGroup::x = the x mask on the chunk bits, HTerm::z = the full z mask (the sign is read
-// off the ket's GLOBAL index ket_gbase | j).
-__global__ __launch_bounds__(256) void k_cross_small_real(const double *__restrict__ ket, const double *__restrict__ bra, uint64_t csize,
+// off the ket's GLOBAL index ket_gbase | j).  DOT: partials += other . s; APPLY: other_i += s_i (a thread owns its outputs).
+template <bool DOT>
+__global__ __launch_bounds__(256) void k_cross_small_real(const double *__restrict__ ket, double *__restrict__ other, uint64_t csize,
                                                           uint64_t ket_gbase, const HGroup *__restrict__ groups, int g0, int g1,
                                                           const HTerm *__restrict__ terms, double2 *__restrict__ partials) {
     __shared__ double2 red[4];
@@ -283,12 +301,15 @@ __global__ __launch_bounds__(256) void k_cross_small_real(const double *__restri
             }
             s = fma(dr, ket[j], s);
         }
-        part = fma(bra[i], s, part);
+        if constexpr (DOT) part = fma(other[i], s, part);
+        else other[i] += s;
     }
-    const double2 t = block_sum<256>(make_double2(part, 0.0), red);
-    if (threadIdx.x == 0) {
-        const double2 o = partials[blockIdx.x];
-        partials[blockIdx.x] = make_double2(o.x + t.x, o.y);
+    if constexpr (DOT) {
+        const double2 t = block_sum<256>(make_double2(part, 0.0), red);
+        if (threadIdx.x == 0) {
+            const double2 o = partials[blockIdx.x];
+            partials[blockIdx.x] = make_double2(o.x + t.x, o.y);
+        }
     }
 }
 

@@ -771,6 +771,22 @@ __global__ __launch_bounds__(256) void k_randomize(amp_t *__restrict__ st, uint6
     if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
 
+// the fill of a real shard (option "real_state"): amplitude i = the real part of k_randomize's amplitude at the same global index
+__global__ __launch_bounds__(256) void k_randomize_real(double *__restrict__ st, uint64_t namps, uint64_t base, uint64_t seed,
+                                                        double scale, double2 *__restrict__ partials) {
+    __shared__ double2 red[4];
+    double acc = 0.0;
+    const uint64_t stride = (uint64_t)gridDim.x * 256u;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < namps; i += stride) {
+        const uint64_t h = mix64(seed ^ mix64(base | i));
+        const double a = unit_pm1(mix64(h ^ 0x1234567ull)) * scale;
+        st[i] = a;
+        acc += a * a;
+    }
+    const double2 t = block_sum<256>(make_double2(acc, 0.0), red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+
 __global__ __launch_bounds__(256) void k_scale(amp_t *__restrict__ st, uint64_t namps, double scale) {
     const uint64_t stride = (uint64_t)gridDim.x * 256u;
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < namps; i += stride) {

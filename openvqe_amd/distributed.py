@@ -198,10 +198,11 @@ class HipShardEngine:
         return w
 
     def set_tensor(self, tensor):
-        """make another shard-sized complex buffer the shard the handle works on (the exchange of lambda in the backward pass:
-        pack / unpack read and write the handle's state); the previous buffer stays with the caller"""
-        if tensor.dtype != torch.complex128 or tensor.numel() != self.tensor.numel() or self.is_real:
-            raise ValueError("set_tensor: a complex buffer of the shard's size on a complex shard")
+        """make another shard-sized buffer of the shard's storage the shard the handle works on (the exchange of lambda in the backward
+        pass: pack / unpack read and write the handle's state; the rotating vectors of the Lanczos recurrence: sigma = H psi reads
+        the handle's state); the previous buffer stays with the caller"""
+        if tensor.dtype != self.tensor.dtype or tensor.numel() != self.tensor.numel():
+            raise ValueError("set_tensor: a buffer of the shard's size in the shard's storage (complex128, or float64 on a real shard)")
         self.sync()
         self.tensor = tensor
         self.sv.adopt_state(tensor.data_ptr())
@@ -249,6 +250,21 @@ class HipShardEngine:
 
     def sum_apply_remote(self, sid, d, chunk, ket, out):
         self.sv.xsum_apply_remote(sid, d, chunk, ket.data_ptr(), out.data_ptr())
+
+    # -- Lanczos vector operations on shard-sized buffers of the shard's storage (ovqe_vec_*): this shard's partial sums; dot and
+    # update synchronise, scale and axpy only enqueue on the engine's stream
+    def vec_dot(self, a, b):
+        return self.sv.vec_dot(a.data_ptr(), b.data_ptr())
+
+    def vec_update(self, w, v, vprev, alpha, beta):
+        """w <- w - alpha v - beta vprev (vprev may be None) -> sum |w_i|^2 over this shard"""
+        return self.sv.vec_lanczos_update(w.data_ptr(), v.data_ptr(), None if vprev is None else vprev.data_ptr(), alpha, beta)
+
+    def vec_scale(self, v, s):
+        self.sv.vec_scale(v.data_ptr(), s)
+
+    def vec_axpy(self, y, x, s, overwrite=False):
+        self.sv.vec_axpy(y.data_ptr(), x.data_ptr(), s, overwrite)
 
     # -- the pool contraction on CHUNKS: 2^m consecutive amplitudes of a shard-sized buffer against a received chunk of the
     # partner's shard; masks live on the m low bits (the host layer folds everything above them into the coefficients)
@@ -996,15 +1012,154 @@ class ShardedStatevector:
         plan = plan if plan is not None else self._plan_for(xs, zs, coeffs, constant)
         if plan["perm"] != tuple(self.perm):
             raise ValueError("the Hamiltonian was planned under another qubit permutation")
+        return self._apply_planned(plan, sigma, float(np.real(constant)))
+
+    def _apply_planned(self, plan, sigma, ident):
+        """sigma <- (H + ident) psi with the planned "apply" sum, psi = the engine's state buffer in its current storage (on float64
+        shards the partner chunks travel as doubles and the engine contracts them as such)"""
         sid = self._plan_sum(plan, "apply")
         with self._compute("apply"):
-            self.engine.sum_apply_local(sid, sigma, float(np.real(constant)))
+            self.engine.sum_apply_local(sid, sigma, ident)
         for c, chunks in self._partner_chunks(plan["partners"]):
             with self._compute("apply"):
                 for d, ket in zip(plan["partners"], chunks):
                     self.engine.sum_apply_remote(sid, d, c, ket, sigma)
         self.engine.sync()
         return sigma
+
+    # -- lowest eigenpair of a Hermitian Pauli sum: Lanczos over the shards ---------------------------------------------------------
+    def _all_sum(self, *values):
+        """the sums over the ranks of a few local scalars (one all-reduce)"""
+        buf = torch.tensor([float(v) for v in values], dtype=torch.float64, device=self.engine.tensor.device)
+        if self._dist:
+            dist.all_reduce(buf, group=self.group)
+        return [float(v) for v in buf.cpu()]
+
+    def _vec_dot(self, a, b):
+        if hasattr(self.engine, "vec_dot"):
+            return complex(self.engine.vec_dot(a, b))
+        return complex(torch.vdot(a, b).item())
+
+    def _vec_update(self, w, v, vprev, alpha, beta):
+        if hasattr(self.engine, "vec_update"):
+            return float(self.engine.vec_update(w, v, vprev, alpha, beta))
+        w.add_(v, alpha=-alpha)
+        if vprev is not None:
+            w.add_(vprev, alpha=-beta)
+        return float(torch.vdot(w, w).real.item())
+
+    def _vec_scale(self, v, s):
+        if hasattr(self.engine, "vec_scale"):
+            self.engine.vec_scale(v, s)
+        else:
+            v.mul_(s)
+
+    def _vec_axpy(self, y, x, s, overwrite=False):
+        if hasattr(self.engine, "vec_axpy"):
+            self.engine.vec_axpy(y, x, s, overwrite)
+        elif overwrite:
+            torch.mul(x, s, out=y)
+        else:
+            y.add_(x, alpha=s)
+
+    def ground_state(self, xs, zs, coeffs, constant=0.0, tol=1e-10, max_iter=3000, seed=20250227):
+        """Lowest eigenpair of H = constant + sum_t c_t P_t (real c_t, logical masks) by Lanczos on the partitioned register
+        -> (energy, residual |H y - E y|, steps), the same numbers on every rank; ``tol``, ``max_iter`` and ``seed`` mean what they
+        mean to ``backend.Statevector.ground_state``.  Afterwards the register holds the normalised eigenvector y under the
+        identity permutation.
+
+        Two passes of the three-term recurrence, as ``ovqe_ground_state`` runs it when its vectors do not fit: pass 1 builds the
+        tridiagonal matrix (stop test |beta_m s_m| < tol max(1, |lambda|) every fifth step), pass 2 repeats it from the same
+        seeded start and accumulates the Ritz vector; then the Rayleigh quotient and the true residual of y.  NO Lanczos vector is
+        kept at shard size — at the register sizes this path is for nothing is left to keep them in: a rank holds four
+        shard-sized vectors (v_{j-1}, v_j, w and y) and the double buffers of the partner chunks, whatever the step count.
+        alpha_j and beta_j are all-reduced before any use (two all-reduces per step), so every rank solves the identical
+        tridiagonal matrix on the host and stops at the same step.
+
+        Storage: float64 shards when every string has an even number of Y (a real-symmetric H: every Jordan-Wigner molecular
+        Hamiltonian; its Krylov vectors stay real) and the engine offers ``set_real`` — half the HBM bytes per vector and per
+        sigma = H psi pass and half the link bytes per partner chunk; complex128 otherwise."""
+        from scipy.linalg import eigh_tridiagonal
+        cs = np.asarray(coeffs, np.complex128).reshape(-1)
+        if np.any(cs.imag != 0.0):
+            raise ValueError("ground_state: a Hermitian sum has real coefficients")
+        if not hasattr(self.engine, "randomize"):
+            raise NotImplementedError("this shard engine has no randomize (the seeded start vector)")
+        xs = [int(v) for v in xs]
+        zs = [int(v) for v in zs]
+        size = 1 << self.n_local
+        self.perm = list(range(self.n))
+        real = bool(all(not (bin(x & z).count("1") & 1) for x, z in zip(xs, zs)) and hasattr(self.engine, "set_real")
+                    and self.real_storage and self.n_local >= 2)
+        if hasattr(self.engine, "set_real"):
+            self.engine.set_real(real, discard=True)
+        self._tmp = self._chunk_bufs = self._sigma = None
+        self.real = real          # (the partner chunks of a complex Krylov vector travel whole)
+        plan = self._plan_for(xs, zs, cs.real, 0.0)
+        bufs = [self.engine.tensor] + [self.engine.new_buffer(size) for _ in range(3)]
+        y = bufs[3]
+        max_iter = int(min(max(int(max_iter), 1), 1 << self.n))
+        alpha, beta = [], []
+        state = {"m": 0, "lam": 0.0, "s": None}
+
+        def lowest():
+            m = state["m"]
+            if m == 1:
+                return alpha[0], np.ones(1)
+            w, v = eigh_tridiagonal(np.array(alpha[:m]), np.array(beta[:m - 1]), select="i", select_range=(0, 0))
+            return float(w[0]), v[:, 0]
+
+        def start(B):
+            self._set_engine_tensor(B)
+            self.engine.randomize(seed, 1.0)
+            n2, = self._all_sum(self.engine.norm2())
+            self._vec_scale(B, 1.0 / n2 ** 0.5)
+
+        def recurrence(accumulate):
+            A, B, C = bufs[0], bufs[1], bufs[2]
+            start(B)
+            s = state["s"]
+            if accumulate:
+                self._vec_axpy(y, B, float(s[0]), overwrite=True)
+            steps = state["m"] - 1 if accumulate else max_iter
+            for j in range(steps):
+                _progress("Lanczos")
+                self._set_engine_tensor(B)
+                self._apply_planned(plan, C, 0.0)
+                if accumulate:
+                    self._vec_update(C, B, A if j else None, alpha[j], beta[j - 1] if j else 0.0)
+                    bj = beta[j]
+                else:
+                    a, = self._all_sum(self._vec_dot(B, C).real)
+                    alpha.append(a)
+                    b2, = self._all_sum(self._vec_update(C, B, A if j else None, a, beta[j - 1] if j else 0.0))
+                    bj = max(b2, 0.0) ** 0.5
+                    state["m"] = j + 1
+                    last = j + 1 == steps or bj < 1e-13 * max(1.0, abs(a))
+                    if last or (j >= 4 and j % 5 == 4):
+                        state["lam"], state["s"] = lowest()
+                        est = abs(bj * state["s"][-1])
+                        if last or est < tol * max(1.0, abs(state["lam"])):
+                            return
+                    beta.append(bj)
+                self._vec_scale(C, 1.0 / bj)
+                A, B, C = B, C, A
+                if accumulate:
+                    self._vec_axpy(y, B, float(s[j + 1]))
+
+        recurrence(False)     # pass 1: the tridiagonal matrix
+        recurrence(True)      # pass 2: the Ritz vector, same recurrence
+        _progress("Lanczos")
+        self._set_engine_tensor(y)
+        n2, = self._all_sum(self._vec_dot(y, y).real)
+        self._vec_scale(y, 1.0 / n2 ** 0.5)
+        sigma = bufs[0]
+        self._apply_planned(plan, sigma, 0.0)
+        lam, = self._all_sum(self._vec_dot(y, sigma).real)
+        r2, = self._all_sum(self._vec_update(sigma, y, None, lam, 0.0))
+        self.engine.sync()
+        _progress("local sweeps")
+        return lam + float(np.real(constant)), max(r2, 0.0) ** 0.5, state["m"]
 
     def pool_gradients(self, ham, pool, mode="fermionic"):
         """ADAPT screen over ``pool`` = [(xs, zs, coeffs) per operator] with H = (ham_xs, ham_zs, ham_coeffs, constant):

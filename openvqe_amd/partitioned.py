@@ -12,8 +12,11 @@ What maps to what:
   ``init_basis`` / ``apply_exp_pauli_sum``  (the ADAPT screen state)     ->  rotations when the operator's strings commute (every JW single /
                                                                              double excitation, every pool string), else a Taylor series of sigma = A psi
   ``pool_gradients``                                                     ->  ``ShardedStatevector.pool_gradients``
+  ``ground_state(tol, max_iter, seed)``                                  ->  ``ShardedStatevector.ground_state``: two-pass Lanczos over the shards
+                                                                             (float64 shards for a real-symmetric Hamiltonian), four shard-sized
+                                                                             vectors per rank
 Not offered on the partitioned register (each raises with a plain message): literal gate programs (the QUCCSD templates stop at 24
-qubits in every config), device Lanczos.
+qubits in every config), ``sector_ground_state`` (sector tables are a one-device structure).
 """
 from __future__ import annotations
 
@@ -213,12 +216,20 @@ class PartitionedStatevector:
             cache = self._pool_cache = (pool_ops, len(pool_ops), packed)
         return np.asarray(self.sharded.pool_gradients(self._ham, cache[2], "fermionic" if int(mode) == GRAD_FERMIONIC else "qubit"))
 
-    # -- one-device features ----------------------------------------------------------------------------------------------------
-    def ground_state(self, *args, **kwargs):
-        raise NotImplementedError("device Lanczos is a one-device path (ovqe_ground_state); the partitioned register offers energies, "
-                                  "states and gradient screens")
+    def ground_state(self, tol=1e-10, max_iter=3000, seed=20250227):
+        """lowest eigenpair of the stored Hamiltonian by Lanczos over the shards (``ShardedStatevector.ground_state``: signature and
+        meaning of ``backend.Statevector.ground_state``; the same numbers on every rank) -> (energy, residual, steps).  The
+        register then holds the normalised eigenvector under the identity permutation — on float64 shards when the Hamiltonian is
+        real-symmetric and the engine offers them — and ``expectation``, ``pool_gradients``, ``norm2`` and ``get_state`` work on it."""
+        if self._ham is None:
+            raise RuntimeError("no Hamiltonian set")
+        xs, zs, coeff, const = self._ham
+        return self.sharded.ground_state(xs, zs, coeff, const, tol=tol, max_iter=max_iter, seed=seed)
 
-    sector_ground_state = ground_state
+    # -- one-device features ----------------------------------------------------------------------------------------------------
+    def sector_ground_state(self, *args, **kwargs):
+        raise NotImplementedError("sector tables are a one-device structure (ovqe_sector_ground_state); on the partitioned register "
+                                  "ground_state() is the path: Lanczos over the whole register")
 
     def last_screen_support(self):
         return -1
