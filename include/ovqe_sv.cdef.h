@@ -56,6 +56,14 @@ int ovqe_xsum_expect_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chun
 int ovqe_xsum_expect_finish(ovqe_handle h, int32_t id, double *out_re_im);
 int ovqe_xsum_apply_local(ovqe_handle h, int32_t id, void *out_dev, double ident);
 int ovqe_xsum_apply_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chunk, const void *ket_chunk, void *out_dev);
+int ovqe_xpool_create(ovqe_handle h, int64_t n_ops, const int64_t *offsets, const uint64_t *x, const uint64_t *z, const double *coeff_re,
+                      const double *coeff_im, int chunk_bits, int32_t *id);
+int ovqe_xpool_destroy(ovqe_handle h, int32_t id);
+int ovqe_xpool_partners(ovqe_handle h, int32_t id, int64_t capacity, uint64_t *d, int64_t *passes, int64_t *count);
+int ovqe_xpool_info(ovqe_handle h, int32_t id, int64_t *info, int count);
+int ovqe_xpool_local(ovqe_handle h, int32_t id, const void *bra_dev);
+int ovqe_xpool_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chunk, const void *ket_chunk, const void *bra_dev);
+int ovqe_xpool_finish(ovqe_handle h, int32_t id, double *out_re_im);
 int ovqe_vec_dot(ovqe_handle h, const void *a_dev, const void *b_dev, double *out_re_im);
 int ovqe_vec_lanczos_update(ovqe_handle h, void *w_dev, const void *v_dev, const void *vprev_dev, double alpha, double beta,
                             double *norm2_out);

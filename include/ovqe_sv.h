@@ -260,6 +260,35 @@ int ovqe_xsum_apply_local(ovqe_handle h, int32_t id, void *out_dev, double ident
  * 2^chunk_bits doubles and out 2^n_local doubles) */
 int ovqe_xsum_apply_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chunk, const void *ket_chunk, void *out_dev);
 
+/* ---- The ADAPT pool screen planned once for a shard of the partitioned register: v_k = sum_t c_t <sigma| P_t |psi> for every pool
+ * operator k (g_k = 2 Re v_k, ref:openvqe/adapt/fermionic_adapt_vqe.py:41-122; g_k = 2 |v_k|, ref:openvqe/adapt/qubit_adapt_vqe.py:126-150)
+ * with sigma = H psi resident on this rank (ovqe_xsum_apply_*) and psi arriving chunk by chunk, as for the sums above.  Terms in CSR
+ * form (offsets[0..n_ops], never decreasing), masks in the PHYSICAL index-bit space of the whole register.  The plan — per rank
+ * difference d = x >> n_local a greedy cover of the distinct local x masks by LDS-tiled passes that evaluate EVERY operator of the
+ * pass from one staging of the ket tile (csrc/sv_pool_host.hpp, csrc/sv_pool.hpp; chunks below 2^10 complex / 2^11 real amplitudes
+ * stream) — is made once per (pool, permutation, chunk bits); a screen uploads nothing.  Partial sums: 512 rows x n_ops x 16 bytes
+ * whatever the shard, reduced in a fixed order (results are bit-identical from run to run).  Under option "real_state" bra and ket
+ * are doubles and both parts of v_k are kept: real folded coefficients c i^ny give Re v_k, imaginary ones Im v_k. */
+int ovqe_xpool_create(ovqe_handle h, int64_t n_ops, const int64_t *offsets, const uint64_t *x, const uint64_t *z, const double *coeff_re,
+                      const double *coeff_im, int chunk_bits, int32_t *id);
+int ovqe_xpool_destroy(ovqe_handle h, int32_t id);
+/* the rank differences d != 0 the pool has entries for (ascending) and the passes one chunk of each costs; *count = how many */
+int ovqe_xpool_partners(ovqe_handle h, int32_t id, int64_t capacity, uint64_t *d, int64_t *passes, int64_t *count);
+/* info[0..9): operators, (operator, local x) entries, distinct local x masks summed over the rank differences, partners, passes per
+ * chunk summed over the partners, passes of the d = 0 entries over the shard, tile bits of the passes, 1 when a chunk is too small
+ * to tile (streaming kernel), bytes of the partial sums */
+int ovqe_xpool_info(ovqe_handle h, int32_t id, int64_t *info, int count);
+/* accumulate the d = 0 entries: bra = bra_dev (the sigma shard: 2^n_local amplitudes, not overlapping the state), ket = the handle's
+ * state (ref:openvqe/adapt/fermionic_adapt_vqe.py:67-73).  Only enqueues on the handle's stream. */
+int ovqe_xpool_local(ovqe_handle h, int32_t id, const void *bra_dev);
+/* accumulate the entries of rank difference d for chunk `chunk` of the shard of (this shard's index ^ d): ket_chunk = 2^chunk_bits
+ * amplitudes on this device.  Only enqueues on the handle's stream; afterwards ovqe_last_support(4 / 5) = the passes over the chunk
+ * and the bytes they move by construction (32 B, or 16 B under "real_state", per amplitude and pass). */
+int ovqe_xpool_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chunk, const void *ket_chunk, const void *bra_dev);
+/* v_k as (re, im) pairs, 2 * n_ops doubles (ref:openvqe/adapt/qubit_adapt_vqe.py:147-150 takes |v_k|): the accumulated local and
+ * remote contractions since the last finish; resets the accumulators and synchronises */
+int ovqe_xpool_finish(ovqe_handle h, int32_t id, double *out_re_im);
+
 /* ---- Lanczos vector operations on caller-held device buffers of the handle's storage (2^n_local amplitudes of 16 bytes, or 2^n_local
  * doubles under option "real_state"): the steps of ovqe_ground_state for a host layer that runs the recurrence over a partitioned
  * register (openvqe_amd/distributed.py ground_state; ref:openvqe/adapt/fermionic_adapt_vqe.py:419 takes the same eigenpair from a

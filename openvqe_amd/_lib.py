@@ -67,6 +67,13 @@ SIGNATURES = {
     "ovqe_xsum_expect_finish": (_int, [_H, ctypes.c_int32, _f64p]),
     "ovqe_xsum_apply_local": (_int, [_H, ctypes.c_int32, _vp, _dbl]),
     "ovqe_xsum_apply_remote": (_int, [_H, ctypes.c_int32, _u64, _u64, _vp, _vp]),
+    "ovqe_xpool_create": (_int, [_H, _i64, _i64p, _u64p, _u64p, _f64p, _OptF64, _int, ctypes.POINTER(ctypes.c_int32)]),
+    "ovqe_xpool_destroy": (_int, [_H, ctypes.c_int32]),
+    "ovqe_xpool_partners": (_int, [_H, ctypes.c_int32, _i64, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(_i64)]),
+    "ovqe_xpool_info": (_int, [_H, ctypes.c_int32, ctypes.POINTER(_i64), _int]),
+    "ovqe_xpool_local": (_int, [_H, ctypes.c_int32, _vp]),
+    "ovqe_xpool_remote": (_int, [_H, ctypes.c_int32, _u64, _u64, _vp, _vp]),
+    "ovqe_xpool_finish": (_int, [_H, ctypes.c_int32, _f64p]),
     "ovqe_vec_dot": (_int, [_H, _vp, _vp, _f64p]),
     "ovqe_vec_lanczos_update": (_int, [_H, _vp, _vp, _vp, _dbl, _dbl, ctypes.POINTER(_dbl)]),
     "ovqe_vec_scale": (_int, [_H, _vp, _dbl]),

@@ -250,6 +250,54 @@ class Statevector:
     def xsum_expect_remote(self, sid, d, chunk, ket_ptr):
         self._ck(self._L.ovqe_xsum_expect_remote(self._h, int(sid), int(d), int(chunk), ctypes.c_void_p(ket_ptr)))
 
+    # -- the ADAPT pool planned once for a shard of the partitioned register (ovqe_xpool_*, csrc/pool_host.inc) ---------------------
+    def xpool_create(self, offsets, xs, zs, coeff, chunk_bits):
+        """plan of the pool operators A_k = sum_{t in [offsets[k], offsets[k + 1])} c_t P_t (physical masks of the WHOLE register) -> id"""
+        coeff = np.asarray(coeff, np.complex128).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        pid = ctypes.c_int32()
+        n = len(xs)
+        one = np.zeros(1)
+        self._ck(self._L.ovqe_xpool_create(self._h, len(offsets) - 1, offsets, np.ascontiguousarray(xs if n else [0], np.uint64),
+                                           np.ascontiguousarray(zs if n else [0], np.uint64),
+                                           np.ascontiguousarray(coeff.real) if n else one,
+                                           (np.ascontiguousarray(coeff.imag) if n else one) if np.any(coeff.imag != 0.0) else None,
+                                           int(chunk_bits), ctypes.byref(pid)))
+        self.__dict__.setdefault("_xpool_ops", {})[pid.value] = len(offsets) - 1
+        return pid.value
+
+    def xpool_destroy(self, pid):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._L.ovqe_xpool_destroy(self._h, int(pid))
+
+    def xpool_partners(self, pid):
+        """[(rank difference d, passes one chunk of that partner costs)]"""
+        n = ctypes.c_int64()
+        self._ck(self._L.ovqe_xpool_partners(self._h, int(pid), 0, None, None, ctypes.byref(n)))
+        d, p = np.zeros(max(n.value, 1), np.uint64), np.zeros(max(n.value, 1), np.int64)
+        self._ck(self._L.ovqe_xpool_partners(self._h, int(pid), n.value, d.ctypes.data, p.ctypes.data, ctypes.byref(n)))
+        return [(int(d[k]), int(p[k])) for k in range(n.value)]
+
+    def xpool_info(self, pid):
+        out = (ctypes.c_int64 * 9)()
+        self._ck(self._L.ovqe_xpool_info(self._h, int(pid), out, 9))
+        keys = ("operators", "entries", "x_masks", "partners", "remote_passes_per_chunk", "local_passes", "tile_bits",
+                "streaming_fallback", "partial_bytes")
+        return dict(zip(keys, [int(v) for v in out]))
+
+    def xpool_local(self, pid, bra_ptr):
+        self._ck(self._L.ovqe_xpool_local(self._h, int(pid), ctypes.c_void_p(bra_ptr)))
+
+    def xpool_remote(self, pid, d, chunk, ket_ptr, bra_ptr):
+        self._ck(self._L.ovqe_xpool_remote(self._h, int(pid), int(d), int(chunk), ctypes.c_void_p(ket_ptr), ctypes.c_void_p(bra_ptr)))
+
+    def xpool_finish(self, pid):
+        """v_k per operator (complex array) since the last finish; resets the accumulators"""
+        n_ops = self._xpool_ops[int(pid)]
+        out = np.zeros(2 * max(n_ops, 1), np.float64)
+        self._ck(self._L.ovqe_xpool_finish(self._h, int(pid), out))
+        return out[0:2 * n_ops:2] + 1j * out[1:2 * n_ops:2]
+
     # -- k-bit shard exchange: one block of the shard <-> a contiguous stream (ovqe_shard_pack / ovqe_shard_unpack; enqueue only) ----
     def shard_pack(self, local_bit_mask, block, first, count, dst_ptr, real_parts_only=False):
         """dst[j - first] = amplitude j of block ``block`` of the local bits ``local_bit_mask``, j in [first, first + count)"""

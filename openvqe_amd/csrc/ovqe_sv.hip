@@ -36,6 +36,7 @@
 #include "sv_tile.hpp"
 #include "sv_sector.hpp"
 #include "sv_cross.hpp"
+#include "sv_pool.hpp"
 #include "sv_frame_host.hpp"
 #include <hipcub/hipcub.hpp>
 #include <unordered_map>
@@ -167,6 +168,22 @@ struct CrossSum {
     bool local_built = false;
     DevBuf d_part;           // per-workgroup partial sums of the remote contractions of one expectation value
     size_t part_slots = 0;
+};
+
+// ADAPT pool planned ONCE for a shard of the partitioned register (sv_pool_host.hpp, sv_pool.hpp, pool_host.inc): the entries of every
+// rank difference (0: inside the shard) with their pass lists, and POOL_ROWS rows of per-operator partial sums
+struct PoolCoverDev {
+    pool::Cover c;
+    DevBuf d_chunks, d_entries, d_terms;
+};
+struct PoolPlan {
+    int chunk_bits = 0;
+    int64_t n_ops = 0;
+    std::vector<std::pair<uint64_t, std::vector<pool::RawEntry>>> raw;   // (operator, local x) entries per rank difference d, ascending
+    std::vector<PoolCoverDev> covers[2];   // [0] complex amplitudes, [1] real amplitudes (option "real_state"); built at first use
+    bool built[2] = {false, false};
+    DevBuf d_part, d_out;                  // pool::partial_bytes(n_ops); the reduced v_k
+    size_t part_bytes = 0;
 };
 
 // compact cover (sv_tile.hpp k_tile_expect_compact): the support of the program's states, sorted by tile for every sweep
@@ -464,6 +481,7 @@ struct ovqe_sv {
     int opt_adjoint_tile_bits = -1;  // -1: automatic (12 for n >= 25, else 11); 11 / 12: tile size of k_tile_adjoint; 0: k_adjoint_pairs / k_adjoint_diag only
     int num_cus = 0;              // compute units of the device (first use)
     std::vector<CrossSum *> xsums;   // ovqe_xsum_create (slots of destroyed sums are nullptr)
+    std::vector<PoolPlan *> xpools;  // ovqe_xpool_create (likewise)
 };
 
 namespace {
@@ -561,6 +579,17 @@ void free_cross_sum(CrossSum *X) {
                 if (b->p) (void)hipFree(b->p);
     if (X->d_part.p) (void)hipFree(X->d_part.p);
     delete X;
+}
+
+void free_pool_plan(PoolPlan *P) {
+    if (!P) return;
+    for (int f = 0; f < 2; ++f)
+        for (PoolCoverDev &D : P->covers[f])
+            for (DevBuf *b : {&D.d_chunks, &D.d_entries, &D.d_terms})
+                if (b->p) (void)hipFree(b->p);
+    for (DevBuf *b : {&P->d_part, &P->d_out})
+        if (b->p) (void)hipFree(b->p);
+    delete P;
 }
 
 void release_block(void *p, size_t cap) {
@@ -1201,6 +1230,7 @@ int ovqe_destroy(ovqe_handle h) try {
     free_sector(h->sec);
     free_sector(h->scr);
     for (CrossSum *X : h->xsums) free_cross_sum(X);
+    for (PoolPlan *P : h->xpools) free_pool_plan(P);
     h->kept_blocks.flush();
     if (h->h_rp) (void)hipHostFree(h->h_rp);
     if (h->h_result) (void)hipHostFree(h->h_result);
@@ -1606,3 +1636,4 @@ int ovqe_last_batch_ms(ovqe_handle h, double *ms) try {
 }  // extern "C"
 
 #include "cross_host.inc"
+#include "pool_host.inc"

@@ -1,0 +1,266 @@
+// pool_host.inc — the planned ADAPT pool screen on one shard of the partitioned register: the ovqe_xpool_* entry points (planner:
+// sv_pool_host.hpp; kernels: sv_pool.hpp; the multi-rank protocol above them: openvqe_amd/distributed.py pool_gradients).  Included
+// at the end of ovqe_sv.hip.  The plan is made once per (pool, permutation, chunk bits) — the same pool is screened at every ADAPT
+// macro-iteration (ref:openvqe/adapt/fermionic_adapt_vqe.py:41-122, ref:openvqe/adapt/qubit_adapt_vqe.py:126-150) — so a screen
+// uploads nothing and synchronises once, in ovqe_xpool_finish.
+
+namespace {
+
+PoolPlan *xpool_of(ovqe_handle h, int32_t id) {
+    if (!h || id < 0 || id >= (int32_t)h->xpools.size() || !h->xpools[id]) {
+        if (h) fail(h, OVQE_ERR_INVALID, "no such planned pool (ovqe_xpool_create)");
+        return nullptr;
+    }
+    return h->xpools[id];
+}
+
+// the covers of every rank difference for complex (0) or real (1) amplitudes, built and uploaded at the first use of that flavour
+int xpool_build(ovqe_handle h, PoolPlan &P, int real) {
+    if (P.built[real]) return OVQE_OK;
+    P.covers[real].clear();
+    P.covers[real].reserve(P.raw.size());
+    for (const auto &kv : P.raw) {
+        P.covers[real].emplace_back();
+        PoolCoverDev &D = P.covers[real].back();
+        D.c.d = kv.first;
+        pool::build_cover(D.c, kv.second, kv.first ? P.chunk_bits : h->n_local, real != 0);
+        int rc = upload(h, D.d_chunks, D.c.chunks.data(), D.c.chunks.size() * sizeof(PoolChunk));
+        if (!rc) rc = upload(h, D.d_entries, D.c.entries.data(), D.c.entries.size() * sizeof(PoolEntry));
+        if (!rc) rc = upload(h, D.d_terms, D.c.terms.data(), D.c.terms.size() * sizeof(PoolTerm));
+        if (rc) return rc;
+    }
+    P.built[real] = true;
+    return OVQE_OK;
+}
+
+const PoolCoverDev *xpool_cover(ovqe_handle h, PoolPlan &P, uint64_t d, int real) {
+    if (xpool_build(h, P, real)) return nullptr;
+    for (const PoolCoverDev &D : P.covers[real])
+        if (D.c.d == d) return &D;
+    return nullptr;
+}
+
+template <int M>
+int launch_tile_pool(ovqe_handle h, const PoolPlan &P, const PoolCoverDev &D, const PoolPass &ps, const amp_t *ket, const amp_t *bra,
+                     uint64_t ket_gbase, uint64_t chunk_off, uint32_t ntiles) {
+    constexpr int NT = 1 << pool::POOL_LOG_NT;
+    constexpr size_t smem = tile_pool_lds<M>(sizeof(double2), NT / 64).bytes;
+    static_assert(smem <= LDS_TWO_PER_CU, "two workgroups of the pool pass per CU");
+    if (int rc = lds_opt_in<&k_tile_pool<M, NT, true>, &k_tile_pool<M, NT, false>>(h, smem)) return rc;
+    const unsigned grid = std::min<uint32_t>(ntiles, pool::POOL_ROWS);
+    if (h->n_local >= 25)
+        hipLaunchKernelGGL((k_tile_pool<M, NT, true>), dim3(grid), dim3(NT), smem, h->stream, ket, bra, ket_gbase, chunk_off, ps, ntiles,
+                           (const PoolChunk *)D.d_chunks.p, (const PoolEntry *)D.d_entries.p, (const PoolTerm *)D.d_terms.p,
+                           (double2 *)P.d_part.p, (int)P.n_ops);
+    else
+        hipLaunchKernelGGL((k_tile_pool<M, NT, false>), dim3(grid), dim3(NT), smem, h->stream, ket, bra, ket_gbase, chunk_off, ps, ntiles,
+                           (const PoolChunk *)D.d_chunks.p, (const PoolEntry *)D.d_entries.p, (const PoolTerm *)D.d_terms.p,
+                           (double2 *)P.d_part.p, (int)P.n_ops);
+    HIPC(h, hipGetLastError());
+    return OVQE_OK;
+}
+
+template <int M>
+int launch_tile_pool_real(ovqe_handle h, const PoolPlan &P, const PoolCoverDev &D, const PoolPass &ps, const double *ket, const double *bra,
+                          uint64_t ket_gbase, uint64_t chunk_off, uint32_t ntiles) {
+    constexpr int NT = 1 << pool::POOL_LOG_NT;
+    constexpr size_t smem = tile_pool_lds<M>(sizeof(double), NT / 64).bytes;
+    static_assert(smem <= LDS_TWO_PER_CU, "two workgroups of the pool pass per CU");
+    if (int rc = lds_opt_in<&k_tile_pool_real<M, NT, true>, &k_tile_pool_real<M, NT, false>>(h, smem)) return rc;
+    const unsigned grid = std::min<uint32_t>(ntiles, pool::POOL_ROWS);
+    if (h->n_local >= 26)
+        hipLaunchKernelGGL((k_tile_pool_real<M, NT, true>), dim3(grid), dim3(NT), smem, h->stream, ket, bra, ket_gbase, chunk_off, ps, ntiles,
+                           (const PoolChunk *)D.d_chunks.p, (const PoolEntry *)D.d_entries.p, (const PoolTerm *)D.d_terms.p,
+                           (double2 *)P.d_part.p, (int)P.n_ops);
+    else
+        hipLaunchKernelGGL((k_tile_pool_real<M, NT, false>), dim3(grid), dim3(NT), smem, h->stream, ket, bra, ket_gbase, chunk_off, ps, ntiles,
+                           (const PoolChunk *)D.d_chunks.p, (const PoolEntry *)D.d_entries.p, (const PoolTerm *)D.d_terms.p,
+                           (double2 *)P.d_part.p, (int)P.n_ops);
+    HIPC(h, hipGetLastError());
+    return OVQE_OK;
+}
+
+// every pass of cover D over one ket chunk of 2^m amplitudes (m = the cover's chunk bits): partials += conj(bra) . (A_k ket) per entry
+int run_pool_chunk(ovqe_handle h, PoolPlan &P, const PoolCoverDev &D, uint64_t chunk, const void *ket, const void *bra, bool real) {
+    const pool::Cover &C = D.c;
+    const int m = C.m;
+    const uint64_t csize = 1ull << m;
+    const uint64_t ket_gbase = ((h->shard ^ C.d) << h->n_local) | (chunk << m);
+    const size_t ab = real ? sizeof(double) : sizeof(amp_t);
+    h->last_passes = C.n_passes();
+    h->last_pass_bytes = (int64_t)((real ? 16.0 : 32.0) * (double)csize * (double)h->last_passes);
+    if (C.small) {
+        const int nb = (int)std::min<uint64_t>(pool::POOL_SMALL_ROWS, std::max<uint64_t>(1, (csize + 255) / 256));
+        for (size_t k = 0; k < C.class_h.size(); ++k) {
+            const void *bc = (const char *)bra + ((chunk ^ C.class_h[k]) << m) * ab;
+            if (real)
+                hipLaunchKernelGGL((k_pool_small<true>), dim3(nb), dim3(256), 0, h->stream, ket, bc, csize, ket_gbase, (const PoolEntry *)D.d_entries.p,
+                                   C.class_entries[k].first, C.class_entries[k].second, (const PoolTerm *)D.d_terms.p, (double2 *)P.d_part.p, (int)P.n_ops);
+            else
+                hipLaunchKernelGGL((k_pool_small<false>), dim3(nb), dim3(256), 0, h->stream, ket, bc, csize, ket_gbase, (const PoolEntry *)D.d_entries.p,
+                                   C.class_entries[k].first, C.class_entries[k].second, (const PoolTerm *)D.d_terms.p, (double2 *)P.d_part.p, (int)P.n_ops);
+        }
+        HIPC(h, hipGetLastError());
+        return OVQE_OK;
+    }
+    const uint32_t ntiles = (uint32_t)(csize >> C.M);
+    for (const PoolPass &ps : C.passes) {
+        int rc;
+        if (real) {
+            switch (C.M) {
+            case 11: rc = launch_tile_pool_real<11>(h, P, D, ps, (const double *)ket, (const double *)bra, ket_gbase, chunk << m, ntiles); break;
+            case 12: rc = launch_tile_pool_real<12>(h, P, D, ps, (const double *)ket, (const double *)bra, ket_gbase, chunk << m, ntiles); break;
+            default: rc = launch_tile_pool_real<13>(h, P, D, ps, (const double *)ket, (const double *)bra, ket_gbase, chunk << m, ntiles); break;
+            }
+        } else {
+            switch (C.M) {
+            case 10: rc = launch_tile_pool<10>(h, P, D, ps, (const amp_t *)ket, (const amp_t *)bra, ket_gbase, chunk << m, ntiles); break;
+            case 11: rc = launch_tile_pool<11>(h, P, D, ps, (const amp_t *)ket, (const amp_t *)bra, ket_gbase, chunk << m, ntiles); break;
+            default: rc = launch_tile_pool<12>(h, P, D, ps, (const amp_t *)ket, (const amp_t *)bra, ket_gbase, chunk << m, ntiles); break;
+            }
+        }
+        if (rc) return rc;
+    }
+    return OVQE_OK;
+}
+
+int xpool_bra_ok(ovqe_handle h, const char *who, const void *bra_dev) {
+    const char *s0 = (const char *)h->state, *b0 = (const char *)bra_dev;
+    const size_t bytes = (size_t)h->namps * (h->opt_real_state ? sizeof(double) : sizeof(amp_t));
+    if (b0 < s0 + bytes && s0 < b0 + bytes)
+        return fail(h, OVQE_ERR_INVALID, std::string(who) + ": the bra overlaps the state buffer (sigma = H psi lives in a buffer of its own)");
+    return OVQE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ovqe_xpool_create(ovqe_handle h, int64_t n_ops, const int64_t *offsets, const uint64_t *x, const uint64_t *z, const double *coeff_re,
+                      const double *coeff_im, int chunk_bits, int32_t *id) try {
+    OVQE_ENTER(h);
+    if (!h || !id || n_ops < 0 || (n_ops && !offsets)) return OVQE_ERR_INVALID;
+    if (chunk_bits < 1 || chunk_bits > h->n_local) return fail(h, OVQE_ERR_INVALID, "chunk_bits must lie in 1 .. n_local");
+    if (n_ops > (int64_t)1 << 24) return fail(h, OVQE_ERR_INVALID, "ovqe_xpool_create: more than 2^24 operators");
+    if (n_ops && offsets[n_ops] > 0 && (!x || !z || !coeff_re)) return OVQE_ERR_INVALID;
+    std::unique_ptr<PoolPlan, void (*)(PoolPlan *)> P(new PoolPlan(), free_pool_plan);
+    P->chunk_bits = chunk_bits;
+    P->n_ops = n_ops;
+    std::map<uint64_t, std::vector<pool::RawEntry>> by_d;
+    const std::string err = pool::collect(h->n_local, h->n_local + h->n_global, n_ops, offsets, x, z, coeff_re, coeff_im, by_d);
+    if (!err.empty()) return fail(h, OVQE_ERR_INVALID, "ovqe_xpool_create: " + err);
+    for (auto &kv : by_d) P->raw.emplace_back(kv.first, std::move(kv.second));
+    P->part_bytes = pool::partial_bytes(n_ops);
+    int rc = ensure(h, P->d_part, P->part_bytes);
+    if (!rc) rc = ensure(h, P->d_out, (size_t)std::max<int64_t>(n_ops, 1) * sizeof(double2));
+    if (rc) return rc;
+    HIPC(h, hipMemsetAsync(P->d_part.p, 0, P->part_bytes, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    rc = xpool_build(h, *P, h->opt_real_state ? 1 : 0);
+    if (rc) return rc;
+    int32_t slot = -1;
+    for (size_t k = 0; k < h->xpools.size(); ++k)
+        if (!h->xpools[k]) slot = (int32_t)k;
+    if (slot < 0) {
+        h->xpools.push_back(nullptr);
+        slot = (int32_t)h->xpools.size() - 1;
+    }
+    h->xpools[slot] = P.release();
+    *id = slot;
+    return OVQE_OK;
+} OVQE_CATCH(h)
+
+int ovqe_xpool_destroy(ovqe_handle h, int32_t id) try {
+    OVQE_ENTER(h);
+    PoolPlan *P = xpool_of(h, id);
+    if (!P) return OVQE_ERR_INVALID;
+    HIPC(h, hipStreamSynchronize(h->stream));
+    free_pool_plan(P);
+    h->xpools[id] = nullptr;
+    return OVQE_OK;
+} OVQE_CATCH(h)
+
+int ovqe_xpool_partners(ovqe_handle h, int32_t id, int64_t capacity, uint64_t *d, int64_t *passes, int64_t *count) try {
+    OVQE_ENTER(h);
+    PoolPlan *P = xpool_of(h, id);
+    if (!P || !count || capacity < 0) return OVQE_ERR_INVALID;
+    const int f = h->opt_real_state ? 1 : 0;
+    if (int rc = xpool_build(h, *P, f)) return rc;
+    int64_t n = 0;
+    for (const PoolCoverDev &D : P->covers[f]) {
+        if (D.c.d == 0) continue;
+        if (n < capacity) {
+            if (d) d[n] = D.c.d;
+            if (passes) passes[n] = D.c.n_passes();
+        }
+        ++n;
+    }
+    *count = n;
+    return OVQE_OK;
+} OVQE_CATCH(h)
+
+int ovqe_xpool_info(ovqe_handle h, int32_t id, int64_t *info, int count) try {
+    OVQE_ENTER(h);
+    PoolPlan *P = xpool_of(h, id);
+    if (!P || !info || count < 0) return OVQE_ERR_INVALID;
+    const int f = h->opt_real_state ? 1 : 0;
+    if (int rc = xpool_build(h, *P, f)) return rc;
+    int64_t entries = 0, nx = 0, partners = 0, rp = 0, lp = 0, M = 0, small = 0;
+    for (const PoolCoverDev &D : P->covers[f]) {
+        entries += D.c.n_entries;
+        nx += D.c.n_x;
+        if (D.c.d) {
+            ++partners;
+            rp += D.c.n_passes();
+        } else {
+            lp += D.c.n_passes();
+        }
+        M = std::max<int64_t>(M, D.c.M);
+        small |= D.c.small ? 1 : 0;
+    }
+    const int64_t v[9] = {P->n_ops, entries, nx, partners, rp, lp, M, small, (int64_t)P->part_bytes};
+    for (int k = 0; k < std::min(count, 9); ++k) info[k] = v[k];
+    return OVQE_OK;
+} OVQE_CATCH(h)
+
+int ovqe_xpool_local(ovqe_handle h, int32_t id, const void *bra_dev) try {
+    OVQE_ENTER(h);
+    PoolPlan *P = xpool_of(h, id);
+    if (!P || !bra_dev) return OVQE_ERR_INVALID;
+    if (int rc = xpool_bra_ok(h, "ovqe_xpool_local", bra_dev)) return rc;
+    const bool real = h->opt_real_state != 0;
+    if (int rc = xpool_build(h, *P, real ? 1 : 0)) return rc;
+    const PoolCoverDev *D = xpool_cover(h, *P, 0, real ? 1 : 0);
+    h->last_passes = 0;
+    h->last_pass_bytes = 0;
+    if (!D) return OVQE_OK;   // (no operator acts inside the shard)
+    return run_pool_chunk(h, *P, *D, 0, h->state, bra_dev, real);
+} OVQE_CATCH(h)
+
+int ovqe_xpool_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chunk, const void *ket_chunk, const void *bra_dev) try {
+    OVQE_ENTER(h);
+    PoolPlan *P = xpool_of(h, id);
+    if (!P || !ket_chunk || !bra_dev) return OVQE_ERR_INVALID;
+    if (int rc = xpool_bra_ok(h, "ovqe_xpool_remote", bra_dev)) return rc;
+    if (chunk >> (h->n_local - P->chunk_bits)) return fail(h, OVQE_ERR_INVALID, "chunk index beyond the shard");
+    const bool real = h->opt_real_state != 0;
+    const PoolCoverDev *D = d ? xpool_cover(h, *P, d, real ? 1 : 0) : nullptr;
+    if (!D) return fail(h, OVQE_ERR_INVALID, "the planned pool has no entries for this rank difference (ovqe_xpool_partners)");
+    return run_pool_chunk(h, *P, *D, chunk, ket_chunk, bra_dev, real);
+} OVQE_CATCH(h)
+
+int ovqe_xpool_finish(ovqe_handle h, int32_t id, double *out_re_im) try {
+    OVQE_ENTER(h);
+    PoolPlan *P = xpool_of(h, id);
+    if (!P || (P->n_ops && !out_re_im)) return OVQE_ERR_INVALID;
+    if (P->n_ops) {
+        hipLaunchKernelGGL(k_pool_finish, dim3((unsigned)((P->n_ops + 255) / 256)), dim3(256), 0, h->stream, (double2 *)P->d_part.p,
+                           (int)pool::POOL_ROWS, (int)P->n_ops, (double2 *)P->d_out.p);
+        HIPC(h, hipGetLastError());
+        HIPC(h, hipMemcpyAsync(out_re_im, P->d_out.p, (size_t)P->n_ops * sizeof(double2), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPC(h, hipStreamSynchronize(h->stream));
+    return OVQE_OK;
+} OVQE_CATCH(h)
+
+}  // extern "C"

@@ -128,7 +128,7 @@ class HipShardEngine:
         # what the local kernels really did: passes over the shard (launches that stream it) and the bytes they move by
         # construction — fused same-x runs and LDS-tiled multi-run sweeps make this smaller than one sweep per rotation
         self.counters = {"rotations": 0, "rotation_passes": 0, "rotation_bytes": 0, "contraction_calls": 0, "contraction_passes": 0,
-                         "contraction_bytes": 0, "adjoint_passes": 0, "adjoint_bytes": 0}
+                         "contraction_bytes": 0, "adjoint_passes": 0, "adjoint_bytes": 0, "pool_plans": 0}
 
     def check_stream(self):
         if torch.cuda.current_stream(self.device).cuda_stream != self.stream.cuda_stream:
@@ -251,6 +251,33 @@ class HipShardEngine:
     def sum_apply_remote(self, sid, d, chunk, ket, out):
         self.sv.xsum_apply_remote(sid, d, chunk, ket.data_ptr(), out.data_ptr())
 
+    # -- the ADAPT pool planned once per (pool, permutation, chunk bits): ovqe_xpool_* (csrc/pool_host.inc, csrc/sv_pool.hpp).  Terms in
+    # CSR form over the operators, masks in the physical bit space of the whole register; ``bra`` = this rank's sigma shard in the shard's
+    # storage; local / remote only enqueue kernels on the engine's stream, finish synchronises
+    def plan_pool(self, offsets, xs, zs, coeffs, chunk_bits):
+        self.counters["pool_plans"] += 1
+        return self.sv.xpool_create(offsets, xs, zs, coeffs, chunk_bits)
+
+    def free_pool(self, pid):
+        self.sv.xpool_destroy(pid)
+
+    def pool_info(self, pid):
+        return self.sv.xpool_info(pid)
+
+    def pool_partners(self, pid):
+        return self.sv.xpool_partners(pid)
+
+    def pool_local(self, pid, bra):
+        self.sv.xpool_local(pid, bra.data_ptr())
+        self._count("contraction", self.sv)
+
+    def pool_remote(self, pid, d, chunk, ket, bra):
+        self.sv.xpool_remote(pid, d, chunk, ket.data_ptr(), bra.data_ptr())
+        self._count("contraction", self.sv)
+
+    def pool_finish(self, pid):
+        return self.sv.xpool_finish(pid)
+
     # -- Lanczos vector operations on shard-sized buffers of the shard's storage (ovqe_vec_*): this shard's partial sums; dot and
     # update synchronise, scale and axpy only enqueue on the engine's stream
     def vec_dot(self, a, b):
@@ -316,7 +343,9 @@ class ShardedStatevector:
                       "link_bytes": 0, "exchange_bits": 0,
                       # seconds this rank's kernels ran, by phase (each section ends with a device synchronisation)
                       "local_sweeps_s": 0.0, "expectation_local_s": 0.0, "expectation_remote_s": 0.0, "apply_s": 0.0,
-                      "adjoint_sweeps_s": 0.0}
+                      "adjoint_sweeps_s": 0.0,
+                      # the planned ADAPT screen: seconds of its pool contractions (local, per chunk, finish) and the plans made
+                      "screen_s": 0.0, "pool_plans": 0}
         # Several ranks on ONE device (the gloo runs of the tests and of bench.py's single-device mode) would time each other's
         # kernels: with a lock file every compute section takes the device alone (flock), so its seconds are this rank's own
         self.compute_lock = None
@@ -337,7 +366,7 @@ class ShardedStatevector:
         self.real_transfers = True
         # Real STORAGE (engines that offer it: the HIP engine): a compiled program whose strings all have an odd number of Y runs on
         # float64 shards — local sweeps, <H> and transfers on 8-byte amplitudes; anything that needs complex amplitudes (a rotation
-        # with an even number of Y, sigma = H psi, the gradient screens) widens the shard back first
+        # with an even number of Y, sigma = H psi of a sum that is not real-symmetric, the Taylor series) widens the shard back first
         self.real_storage = True
 
     # -- helpers ----------------------------------------------------------------------------
@@ -1000,13 +1029,17 @@ class ShardedStatevector:
         return out
 
     # -- ADAPT gradient screen on the sharded register ("ADAPT screen identical with sigma also sharded")
-    def apply_hamiltonian(self, xs, zs, coeffs, constant=0.0, plan=None):
+    def apply_hamiltonian(self, xs, zs, coeffs, constant=0.0, plan=None, keep_real=False):
         """sigma = (H + constant) psi, sharded like psi: the x_g = 0 terms act inside the shard; the other rank differences
         are accumulated chunk by chunk from the partners' psi shards (all partners of a chunk in flight at once).
+        ``keep_real``: a float64 shard stays float64 and sigma is a float64 buffer (the caller has checked that H maps real
+        vectors to real vectors: the planned ADAPT screen); otherwise the shard is widened to complex amplitudes first.
         -> this rank's sigma shard (device buffer owned by the caller until the next call)"""
         size = 1 << self.n_local
-        self._complex_storage()       # (sigma = H psi and the screens built on it work on complex amplitudes)
-        if getattr(self, "_sigma", None) is None or self._sigma.numel() < size:
+        if not (keep_real and self._storage_real()):
+            self._complex_storage()   # (sigma = H psi and what is built on it work on complex amplitudes)
+        if getattr(self, "_sigma", None) is None or self._sigma.numel() < size or self._sigma.dtype != self.engine.tensor.dtype:
+            self._sigma = None
             self._sigma = self.engine.new_buffer(size)
         sigma = self._sigma[:size]
         plan = plan if plan is not None else self._plan_for(xs, zs, coeffs, constant)
@@ -1161,8 +1194,84 @@ class ShardedStatevector:
         _progress("local sweeps")
         return lam + float(np.real(constant)), max(r2, 0.0) ** 0.5, state["m"]
 
+    #: planned pools kept (most recently used last); the evicted ones are freed
+    POOL_PLANS_KEPT = 4
+
+    def _pool_plan_for(self, pool):
+        """the engine plan of ``pool`` under the CURRENT permutation and chunk size, made once: key = (permutation, chunk bits, the
+        pool's terms)"""
+        counts = np.array([len(op[0]) for op in pool], np.int64)
+        offsets = np.zeros(len(pool) + 1, np.int64)
+        np.cumsum(counts, out=offsets[1:])
+        xs = np.array([int(x) for op in pool for x in op[0]], np.uint64)
+        zs = np.array([int(z) for op in pool for z in op[1]], np.uint64)
+        cs = np.array([complex(c) for op in pool for c in op[2]], np.complex128)
+        m = self._chunk_bits()
+        key = (tuple(self.perm), m, offsets.tobytes(), xs.tobytes(), zs.tobytes(), cs.tobytes())
+        cache = self.__dict__.setdefault("_pool_plans", {})
+        plan = cache.pop(key, None)
+        if plan is None:
+            px = np.array([self._phys(int(x)) for x in xs], np.uint64)
+            pz = np.array([self._phys(int(z)) for z in zs], np.uint64)
+            pid = self.engine.plan_pool(offsets, px, pz, cs, m)
+            self.stats["pool_plans"] += 1
+            plan = {"pid": pid, "partners": [d for d, _ in self.engine.pool_partners(pid)], "n_ops": len(pool)}
+            while len(cache) >= self.POOL_PLANS_KEPT:
+                self.engine.free_pool(cache.pop(next(iter(cache)))["pid"])
+        cache[key] = plan
+        return plan
+
+    def free_pool_plans(self):
+        cache = self.__dict__.get("_pool_plans") or {}
+        while cache:
+            self.engine.free_pool(cache.pop(next(iter(cache)))["pid"])
+
     def pool_gradients(self, ham, pool, mode="fermionic"):
         """ADAPT screen over ``pool`` = [(xs, zs, coeffs) per operator] with H = (ham_xs, ham_zs, ham_coeffs, constant):
+        sigma = H psi once (sharded), then v_k = sum_j c_j <sigma|P_j|psi>; g_k = 2 Re v_k (fermionic,
+        ref:openvqe/adapt/fermionic_adapt_vqe.py:67-73) or 2 |v_k| (qubit, ref:openvqe/adapt/qubit_adapt_vqe.py:147-150).  Same
+        values on every rank.
+
+        Engines that offer ``plan_pool`` (the HIP engine): the pool is planned once per (permutation, chunk bits, pool) and a screen
+        is one ``pool_local`` — while the first chunks travel —, one ``pool_remote`` per (partner, chunk), one ``pool_finish`` and one
+        all-reduce of the n_ops complex values; its seconds go to stats["screen_s"].  A float64 shard whose state is real stays
+        float64 when H maps real vectors to real vectors (every string an even number of Y, real coefficients): sigma, the chunks on
+        the links and the screen are then doubles.  Other engines: one batched contraction per (rank difference, chunk pair),
+        re-planned at every call."""
+        if not hasattr(self.engine, "plan_pool"):
+            return self._pool_gradients_unplanned(ham, pool, mode)
+        hx, hz, hc, const = ham
+        hcs = np.asarray(hc, np.complex128).reshape(-1)
+        keep_real = bool(self._storage_real() and self.real and np.all(hcs.imag == 0.0) and complex(const).imag == 0.0 and
+                         all(not (bin(int(x) & int(z)).count("1") & 1) for x, z in zip(hx, hz)))
+        sigma = self.apply_hamiltonian(hx, hz, hc, const, keep_real=keep_real)
+        plan = self._pool_plan_for(pool)
+        pid, partners = plan["pid"], plan["partners"]
+        done = []
+
+        def local_part():     # (posted first: the first chunk of every partner travels while the shard's own entries are contracted)
+            with self._compute("screen"):
+                self.engine.pool_local(pid, sigma)
+            done.append(True)
+
+        for c, chunks in self._partner_chunks(partners, after_first_post=local_part):
+            with self._compute("screen"):
+                for d, ket in zip(partners, chunks):
+                    self.engine.pool_remote(pid, d, c, ket, sigma)
+        if not done:
+            local_part()      # (no partner at all: nothing was posted)
+        with self._compute("screen"):
+            vals = np.asarray(self.engine.pool_finish(pid), np.complex128)
+        buf = torch.from_numpy(np.stack([vals.real, vals.imag])).to(self.engine.tensor.device)
+        _progress("all-reduce of the pool gradients")
+        if self._dist:
+            dist.all_reduce(buf, group=self.group)
+        v = buf[0].cpu().numpy() + 1j * buf[1].cpu().numpy()
+        _progress("local sweeps")
+        return 2.0 * v.real if mode == "fermionic" else 2.0 * np.abs(v)
+
+    def _pool_gradients_unplanned(self, ham, pool, mode="fermionic"):
+        """(engines without ``plan_pool``) ADAPT screen over ``pool`` = [(xs, zs, coeffs) per operator] with H = (ham_xs, ham_zs, ham_coeffs, constant):
         sigma = H psi once (sharded), then v_k = sum_j c_j <sigma|P_j|psi> with the pool terms grouped by partner shard
         — one batched launch per (rank difference, chunk pair) —, one all-reduce of the n_ops complex values;
         g_k = 2 Re v_k (fermionic, ref:openvqe/adapt/fermionic_adapt_vqe.py:67-73) or 2 |v_k| (qubit,

@@ -11,7 +11,8 @@ What maps to what:
                                                                              and one backward pass over the plan for all K derivatives
   ``init_basis`` / ``apply_exp_pauli_sum``  (the ADAPT screen state)     ->  rotations when the operator's strings commute (every JW single /
                                                                              double excitation, every pool string), else a Taylor series of sigma = A psi
-  ``pool_gradients``                                                     ->  ``ShardedStatevector.pool_gradients``
+  ``pool_gradients``                                                     ->  ``ShardedStatevector.pool_gradients``: the pool planned once per
+                                                                             permutation, screened on float64 shards while the state is real
   ``ground_state(tol, max_iter, seed)``                                  ->  ``ShardedStatevector.ground_state``: two-pass Lanczos over the shards
                                                                              (float64 shards for a real-symmetric Hamiltonian), four shard-sized
                                                                              vectors per rank
@@ -48,6 +49,8 @@ class PartitionedStatevector:
     # -- lifecycle ------------------------------------------------------------------------------------------------------
     def close(self):
         self._drop_program()
+        if self.sharded is not None:
+            self.sharded.free_pool_plans()
         self.sharded = None
 
     def __enter__(self):
@@ -62,6 +65,8 @@ class PartitionedStatevector:
     def _drop_program(self):
         if self._prog is not None and self._prog.get("ham") is not None and self.sharded is not None:
             self.sharded.free_plan(self._prog["ham"])
+        if self._prog is not None and self.sharded is not None:
+            self.sharded.free_pool_plans()     # (planned under the program's final permutation)
         self._prog = None
 
     # -- compiled evaluation --------------------------------------------------------------------------------------------
@@ -143,6 +148,9 @@ class PartitionedStatevector:
     # -- the state of the ADAPT screens ------------------------------------------------------------------------------------------
     def init_basis(self, index):
         self.sharded.perm = list(range(self.nbqbits))
+        # a basis state is real: float64 shards where the engine offers them (the first rotation with an even number of Y widens
+        # them; the ADAPT generators and pool strings never do, so the screens of the mirrors run on doubles)
+        self.sharded._choose_storage(True)
         self.sharded.init_basis(int(index))
 
     def norm2(self):
