@@ -43,16 +43,9 @@ int ovqe_pool_gradients(ovqe_handle h, int64_t n_ops, const int64_t *offsets, co
         std::vector<uint64_t> xs(T);
         for (int64_t t = 0; t < T; ++t) {
             if (x[t] & ~lmask) return fail(h, OVQE_ERR_INVALID, "x mask touches global (rank) bits");
-            const int ny = __builtin_popcountll(x[t] & z[t]) & 3;
-            const double a = coeff_re[t], b = coeff_im ? coeff_im[t] : 0.0;
             HTerm ht;
             ht.z = z[t];
-            switch (ny) {
-            case 0: ht.cr = a; ht.ci = b; break;
-            case 1: ht.cr = -b; ht.ci = a; break;
-            case 2: ht.cr = -a; ht.ci = -b; break;
-            default: ht.cr = b; ht.ci = -a; break;
-            }
+            fold_iny(coeff_re[t], coeff_im ? coeff_im[t] : 0.0, __builtin_popcountll(x[t] & z[t]), ht.cr, ht.ci);
             terms[t] = ht;
             xs[t] = x[t];
         }

@@ -202,16 +202,9 @@ int ovqe_bilinear_batch(ovqe_handle h, const void *bra_dev, const void *ket_dev,
     for (int64_t t = 0; t < T; ++t) {
         if (t == 0) xg = x[t] & ~lmask;
         if ((x[t] & ~lmask) != xg) return fail(h, OVQE_ERR_INVALID, "ovqe_bilinear_batch: one global x part per call");
-        const int ny = __builtin_popcountll(x[t] & z[t]) & 3;
-        const double a = coeff_re[t], b = coeff_im ? coeff_im[t] : 0.0;
         HTerm ht;
         ht.z = z[t];
-        switch (ny) {
-        case 0: ht.cr = a; ht.ci = b; break;
-        case 1: ht.cr = -b; ht.ci = a; break;
-        case 2: ht.cr = -a; ht.ci = -b; break;
-        default: ht.cr = b; ht.ci = -a; break;
-        }
+        fold_iny(coeff_re[t], coeff_im ? coeff_im[t] : 0.0, __builtin_popcountll(x[t] & z[t]), ht.cr, ht.ci);
         terms[t] = ht;
         xs[t] = x[t] & lmask;
     }

@@ -1,5 +1,6 @@
-// cross_host.inc — planned Pauli sums on one shard of the partitioned register: host planner and the ovqe_xsum_* entry points
-// (kernels: sv_cross.hpp; the multi-rank protocol above them: openvqe_amd/distributed.py).  Included at the end of ovqe_sv.hip.
+// cross_host.inc — planned Pauli sums on one shard of the partitioned register: the ovqe_xsum_* entry points (planner:
+// sv_cross_host.hpp; kernels: sv_cross.hpp; the multi-rank protocol above them: openvqe_amd/distributed.py).  Included at the end of
+// ovqe_sv.hip.
 //
 // Masks arrive in the PHYSICAL index-bit space of the whole register (n_local + n_global bits).  A term's x part on the rank bits,
 // d = x >> n_local, names the partner shard (rank ^ d) its ket amplitudes live in; d = 0 terms act inside the shard.  The plan is
@@ -9,181 +10,35 @@
 
 namespace {
 
-// greedy cover of one partner's groups by (tile bit set inside the chunk, displacement outside it)
-int build_cross_cover(ovqe_handle h, CrossCover &C, std::vector<CrossRawGroup> groups, int m, bool real) {
-    if (real) {   // between real vectors a term with an imaginary folded coefficient (odd number of Y) contributes nothing
-        for (CrossRawGroup &g : groups)
-            g.terms.erase(std::remove_if(g.terms.begin(), g.terms.end(), [](const HTerm &t) { return t.ci != 0.0; }), g.terms.end());
-        groups.erase(std::remove_if(groups.begin(), groups.end(), [](const CrossRawGroup &g) { return g.terms.empty(); }), groups.end());
-    }
-    C.ngroups = (int)groups.size();
-    C.nterms = 0;
-    for (const CrossRawGroup &g : groups) C.nterms += (int)g.terms.size();
-    const uint64_t lowmask = (1ull << m) - 1ull;
-    if (m < (real ? 11 : 10)) {   // too small to tile: classes of equal high x bits, one streaming launch each
-        C.small = true;
-        std::stable_sort(groups.begin(), groups.end(), [&](const CrossRawGroup &a, const CrossRawGroup &b) { return (a.x >> m) < (b.x >> m); });
-        std::vector<HGroup> hg;
-        std::vector<HTerm> ht;
-        for (size_t g = 0; g < groups.size(); ++g) {
-            const uint64_t hb = groups[g].x >> m;
-            if (C.class_h.empty() || C.class_h.back() != hb) {
-                C.class_h.push_back(hb);
-                C.class_groups.push_back({(int)g, (int)g});
-            }
-            C.class_groups.back().second = (int)g + 1;
-            HGroup gr = {};
-            gr.x = groups[g].x & lowmask;
-            gr.t0 = (int32_t)ht.size();
-            ht.insert(ht.end(), groups[g].terms.begin(), groups[g].terms.end());
-            gr.t1 = (int32_t)ht.size();
-            hg.push_back(gr);
-        }
-        int rc = upload(h, C.d_groups, hg.data(), hg.size() * sizeof(HGroup));
-        if (!rc) rc = upload(h, C.d_terms, ht.data(), ht.size() * sizeof(HTerm));
-        return rc;
-    }
-    const int M = std::min(real ? 13 : 12, m);   // (a real tile holds 2^13 doubles in the same 64 KB; index bit 0 = the pair bit is always inside)
-    C.M = M;
-    const int L = std::min(HAM_TILE_LOW, M);
-    const uint64_t lowbits = (1ull << L) - 1ull;
-    const int G = (int)groups.size();
-    std::vector<char> done(G, 0);
-    int remaining = G;
-    std::vector<ExChunkT> achunks;
-    std::vector<ExAGroupT> agroups;
-    std::vector<ExTermT> aterms;
-    const double wgt[8] = {1.0, 0.25, 0.0625, 0.015625, 0.00390625, 0.0009765625, 0.000244140625, 0.00006103515625};
-    while (remaining > 0) {
-        // the class of high x bits with the most groups left fixes the part of d_out above the chunk
-        std::map<uint64_t, int> per_class;
-        for (int g = 0; g < G; ++g)
-            if (!done[g]) ++per_class[groups[g].x >> m];
-        uint64_t hb = 0;
-        int best_n = -1;
-        for (const auto &kv : per_class)
-            if (kv.second > best_n) hb = kv.first, best_n = kv.second;
-        // grow S over the chunk bits by the bit that brings the most groups of the class inside (build_ham_tiles' rule)
-        uint64_t S = lowbits;
-        while (__builtin_popcountll(S) < M) {
-            const int room = M - __builtin_popcountll(S);
-            double score[64] = {0.0};
-            bool any = false;
-            for (int g = 0; g < G; ++g) {
-                if (done[g] || (groups[g].x >> m) != hb) continue;
-                const uint64_t miss = groups[g].x & lowmask & ~S;
-                const int nm = __builtin_popcountll(miss);
-                if (nm == 0 || nm > room) continue;
-                any = true;
-                for (uint64_t mk = miss; mk; mk &= mk - 1ull) score[__builtin_ctzll(mk)] += wgt[std::min(nm - 1, 7)];
-            }
-            if (!any) break;
-            int best = -1;
-            for (int b = 0; b < m; ++b)
-                if (!((S >> b) & 1ull) && (best < 0 || score[b] > score[best])) best = b;
-            S |= 1ull << best;
-        }
-        for (int b = 0; __builtin_popcountll(S) < M; ++b) S |= 1ull << b;
-        // the displacement below the chunk bits: the most frequent leftover (nothing left over whenever a group fits S)
-        std::map<uint64_t, int> leftovers;
-        for (int g = 0; g < G; ++g)
-            if (!done[g] && (groups[g].x >> m) == hb) ++leftovers[groups[g].x & lowmask & ~S];
-        uint64_t dl = 0;
-        int dl_n = -1;
-        for (const auto &kv : leftovers)
-            if (kv.second > dl_n) dl = kv.first, dl_n = kv.second;   // (ascending keys: 0 wins a tie)
-        CrossPass ps = {};
-        ps.smask = real ? S >> 1 : S;   // real amplitudes: the kernel's masks live in the index space of amplitude PAIRS
-        uint64_t lo = 0, mk = ps.smask;
-        for (int k = 0; k < TILE_EXPECT_LOG_NT && mk; ++k) {
-            lo |= mk & (0ull - mk);
-            mk &= mk - 1ull;
-        }
-        ps.mask_lo = lo;
-        ps.mask_hi = ps.smask & ~lo;
-        ps.d_out = (hb << m) | dl;
-        ps.a0 = (int32_t)achunks.size();
-        ExChunkT ak = {(int32_t)agroups.size(), (int32_t)agroups.size(), (int32_t)aterms.size(), (int32_t)aterms.size()};
-        int took = 0;
-        for (int g = 0; g < G; ++g) {
-            if (done[g] || (groups[g].x >> m) != hb || (groups[g].x & lowmask & ~S) != dl) continue;
-            done[g] = 1;
-            --remaining;
-            ++took;
-            const uint32_t xl = extract_bits(groups[g].x, S);
-            const std::vector<HTerm> &ts = groups[g].terms;
-            for (size_t k0 = 0; k0 < ts.size(); k0 += TILE_TERM_CAP) {   // (oversized groups in pieces: D_g is a sum over the terms)
-                const size_t k1 = std::min(ts.size(), k0 + (size_t)TILE_TERM_CAP);
-                if ((int)aterms.size() - ak.t0 + (int)(k1 - k0) > TILE_TERM_CAP || (int)agroups.size() - ak.g0 + 1 > TILE_APPLY_GROUPS) {
-                    ak.g1 = (int32_t)agroups.size();
-                    ak.t1 = (int32_t)aterms.size();
-                    achunks.push_back(ak);
-                    ak = {ak.g1, ak.g1, ak.t1, ak.t1};
-                }
-                ExAGroupT ag = {xl, (int32_t)aterms.size(), 0, 1};
-                for (size_t k = k0; k < k1; ++k) {
-                    ExTermT et = {};
-                    et.zin = extract_bits(ts[k].z, S);
-                    et.zout = ts[k].z & ~S;
-                    et.cr = ts[k].cr;
-                    et.ci = ts[k].ci;
-                    if (et.ci != 0.0) ag.pad = 0;   // bit 0 of pad: every folded coefficient of the piece is real
-                    aterms.push_back(et);
-                }
-                ag.t1 = (int32_t)aterms.size();
-                agroups.push_back(ag);
-            }
-        }
-        ak.g1 = (int32_t)agroups.size();
-        ak.t1 = (int32_t)aterms.size();
-        if (ak.g1 > ak.g0) achunks.push_back(ak);
-        ps.a1 = (int32_t)achunks.size();
-        if (took == 0) return fail(h, OVQE_ERR_INVALID, "internal: cross-shard cover made no progress");
-        C.passes.push_back(ps);
-    }
-    int rc = upload(h, C.d_achunks, achunks.data(), achunks.size() * sizeof(ExChunkT));
-    if (!rc) rc = upload(h, C.d_agroups, agroups.data(), agroups.size() * sizeof(ExAGroupT));
-    if (!rc) rc = upload(h, C.d_aterms, aterms.data(), aterms.size() * sizeof(ExTermT));
-    return rc;
-}
-
-template <int M, bool DOT>
-int launch_tile_cross(ovqe_handle h, const CrossCover &C, const CrossPass &ps, const amp_t *ket, amp_t *other, uint64_t ket_gbase,
-                      uint64_t chunk_off, unsigned grid, double2 *partials) {
-    constexpr int NT = 1 << TILE_EXPECT_LOG_NT;
-    constexpr size_t smem = tile_apply_lds<M>(sizeof(double2), NT / 64).bytes;
-    if (int rc = lds_opt_in<&k_tile_cross<M, NT, true, DOT>, &k_tile_cross<M, NT, false, DOT>>(h, smem)) return rc;
-    if (h->n_local >= 25)
-        hipLaunchKernelGGL((k_tile_cross<M, NT, true, DOT>), dim3(grid), dim3(NT), smem, h->stream, ket, other, ket_gbase, chunk_off, ps,
-                           (const ExChunkT *)C.d_achunks.p, (const ExAGroupT *)C.d_agroups.p, (const ExTermT *)C.d_aterms.p, partials);
-    else
-        hipLaunchKernelGGL((k_tile_cross<M, NT, false, DOT>), dim3(grid), dim3(NT), smem, h->stream, ket, other, ket_gbase, chunk_off, ps,
-                           (const ExChunkT *)C.d_achunks.p, (const ExAGroupT *)C.d_agroups.p, (const ExTermT *)C.d_aterms.p, partials);
+// a tile pass of cover D over one chunk: KT / KF = the kernel with and without non-temporal loads (shards of ntl_from qubits and more)
+template <auto KT, auto KF, class T>
+int launch_tile_cross(ovqe_handle h, const CrossCoverDev &D, const TilePass &ps, size_t smem, int ntl_from, const T *ket, T *other,
+                      uint64_t ket_gbase, uint64_t chunk_off, unsigned grid, double2 *partials) {
+    if (int rc = lds_opt_in<KT, KF>(h, smem)) return rc;
+    hipLaunchKernelGGL(h->n_local >= ntl_from ? KT : KF, dim3(grid), dim3(1 << TILE_EXPECT_LOG_NT), smem, h->stream, ket, other, ket_gbase,
+                       chunk_off, ps, (const ExChunkT *)D.d_achunks.p, (const ExAGroupT *)D.d_agroups.p, (const ExTermT *)D.d_aterms.p, partials);
     HIPC(h, hipGetLastError());
     return OVQE_OK;
 }
-
-template <int M, bool DOT>
-int launch_tile_cross_real(ovqe_handle h, const CrossCover &C, const CrossPass &ps, const double *ket, double *other, uint64_t ket_gbase,
-                           uint64_t chunk_off, unsigned grid, double2 *partials) {
+template <int M, bool DOT, class... A>
+int launch_tile_cross_complex(ovqe_handle h, const CrossCoverDev &D, const TilePass &ps, A... args) {
     constexpr int NT = 1 << TILE_EXPECT_LOG_NT;
-    constexpr size_t smem = tile_apply_lds<M>(sizeof(double), NT / 64).bytes;
-    if (int rc = lds_opt_in<&k_tile_cross_real<M, NT, true, DOT>, &k_tile_cross_real<M, NT, false, DOT>>(h, smem)) return rc;
-    if (h->n_local >= 26)
-        hipLaunchKernelGGL((k_tile_cross_real<M, NT, true, DOT>), dim3(grid), dim3(NT), smem, h->stream, ket, other, ket_gbase, chunk_off, ps,
-                           (const ExChunkT *)C.d_achunks.p, (const ExAGroupT *)C.d_agroups.p, (const ExTermT *)C.d_aterms.p, partials);
-    else
-        hipLaunchKernelGGL((k_tile_cross_real<M, NT, false, DOT>), dim3(grid), dim3(NT), smem, h->stream, ket, other, ket_gbase, chunk_off, ps,
-                           (const ExChunkT *)C.d_achunks.p, (const ExAGroupT *)C.d_agroups.p, (const ExTermT *)C.d_aterms.p, partials);
-    HIPC(h, hipGetLastError());
-    return OVQE_OK;
+    return launch_tile_cross<&k_tile_cross<M, NT, true, DOT>, &k_tile_cross<M, NT, false, DOT>>(
+        h, D, ps, tile_apply_lds<M>(sizeof(double2), NT / 64).bytes, 25, args...);
+}
+template <int M, bool DOT, class... A>
+int launch_tile_cross_real(ovqe_handle h, const CrossCoverDev &D, const TilePass &ps, A... args) {
+    constexpr int NT = 1 << TILE_EXPECT_LOG_NT;
+    return launch_tile_cross<&k_tile_cross_real<M, NT, true, DOT>, &k_tile_cross_real<M, NT, false, DOT>>(
+        h, D, ps, tile_apply_lds<M>(sizeof(double), NT / 64).bytes, 26, args...);
 }
 
 // the passes of cover C (real flavour) over one chunk of 2^m doubles; DOT: partials += other . (H_d ket), else other += H_d ket.
 // A partner's cover takes the received chunks (m = the plan's chunk_bits); the d = 0 cover of sigma = H psi takes the shard itself
 // as its one chunk (m = n_local, xsum_build_local).
 template <bool DOT>
-int run_cross_chunk_real(ovqe_handle h, CrossSum &X, const CrossCover &C, int m, uint64_t chunk, const double *ket, double *other) {
+int run_cross_chunk_real(ovqe_handle h, CrossSum &X, const CrossCoverDev &D, int m, uint64_t chunk, const double *ket, double *other) {
+    const cross::Cover &C = D.c;
     const uint64_t csize = 1ull << m;
     const uint64_t ket_gbase = ((h->shard ^ C.d) << h->n_local) | (chunk << m);
     double2 *partials = (double2 *)X.d_part.p;
@@ -191,18 +46,18 @@ int run_cross_chunk_real(ovqe_handle h, CrossSum &X, const CrossCover &C, int m,
         const int nb = (int)std::min<uint64_t>(DOT ? X.part_slots : 2048, std::max<uint64_t>(1, (csize + 255) / 256));
         for (size_t k = 0; k < C.class_h.size(); ++k)
             hipLaunchKernelGGL((k_cross_small_real<DOT>), dim3(nb), dim3(256), 0, h->stream, ket, other + ((chunk ^ C.class_h[k]) << m), csize,
-                               ket_gbase, (const HGroup *)C.d_groups.p, C.class_groups[k].first, C.class_groups[k].second,
-                               (const HTerm *)C.d_terms.p, partials);
+                               ket_gbase, (const HGroup *)D.d_groups.p, C.class_groups[k].first, C.class_groups[k].second,
+                               (const HTerm *)D.d_terms.p, partials);
         HIPC(h, hipGetLastError());
         return OVQE_OK;
     }
     const unsigned grid = (unsigned)(csize >> C.M);
-    for (const CrossPass &ps : C.passes) {
+    for (const TilePass &ps : C.passes) {
         int rc;
         switch (C.M) {
-        case 11: rc = launch_tile_cross_real<11, DOT>(h, C, ps, ket, other, ket_gbase, chunk << m, grid, partials); break;
-        case 12: rc = launch_tile_cross_real<12, DOT>(h, C, ps, ket, other, ket_gbase, chunk << m, grid, partials); break;
-        default: rc = launch_tile_cross_real<13, DOT>(h, C, ps, ket, other, ket_gbase, chunk << m, grid, partials); break;
+        case 11: rc = launch_tile_cross_real<11, DOT>(h, D, ps, ket, other, ket_gbase, chunk << m, grid, partials); break;
+        case 12: rc = launch_tile_cross_real<12, DOT>(h, D, ps, ket, other, ket_gbase, chunk << m, grid, partials); break;
+        default: rc = launch_tile_cross_real<13, DOT>(h, D, ps, ket, other, ket_gbase, chunk << m, grid, partials); break;
         }
         if (rc) return rc;
     }
@@ -211,7 +66,8 @@ int run_cross_chunk_real(ovqe_handle h, CrossSum &X, const CrossCover &C, int m,
 
 // every pass of partner cover C over one received chunk; DOT: partials += conj(other) . (H_d ket), else other += H_d ket
 template <bool DOT>
-int run_cross_chunk(ovqe_handle h, CrossSum &X, const CrossCover &C, uint64_t chunk, const amp_t *ket, amp_t *other) {
+int run_cross_chunk(ovqe_handle h, CrossSum &X, const CrossCoverDev &D, uint64_t chunk, const amp_t *ket, amp_t *other) {
+    const cross::Cover &C = D.c;
     const int m = X.chunk_bits;
     const uint64_t csize = 1ull << m;
     const uint64_t ket_gbase = ((h->shard ^ C.d) << h->n_local) | (chunk << m);
@@ -220,19 +76,19 @@ int run_cross_chunk(ovqe_handle h, CrossSum &X, const CrossCover &C, uint64_t ch
         const int nb = (int)std::min<uint64_t>(X.part_slots, std::max<uint64_t>(1, (csize + 255) / 256));
         for (size_t k = 0; k < C.class_h.size(); ++k) {
             amp_t *oc = other + ((chunk ^ C.class_h[k]) << m);
-            hipLaunchKernelGGL((k_cross_small<DOT>), dim3(nb), dim3(256), 0, h->stream, ket, oc, csize, ket_gbase, (const HGroup *)C.d_groups.p,
-                               C.class_groups[k].first, C.class_groups[k].second, (const HTerm *)C.d_terms.p, partials);
+            hipLaunchKernelGGL((k_cross_small<DOT>), dim3(nb), dim3(256), 0, h->stream, ket, oc, csize, ket_gbase, (const HGroup *)D.d_groups.p,
+                               C.class_groups[k].first, C.class_groups[k].second, (const HTerm *)D.d_terms.p, partials);
         }
         HIPC(h, hipGetLastError());
         return OVQE_OK;
     }
     const unsigned grid = (unsigned)(csize >> C.M);
-    for (const CrossPass &ps : C.passes) {
+    for (const TilePass &ps : C.passes) {
         int rc;
         switch (C.M) {
-        case 10: rc = launch_tile_cross<10, DOT>(h, C, ps, ket, other, ket_gbase, chunk << m, grid, partials); break;
-        case 11: rc = launch_tile_cross<11, DOT>(h, C, ps, ket, other, ket_gbase, chunk << m, grid, partials); break;
-        default: rc = launch_tile_cross<12, DOT>(h, C, ps, ket, other, ket_gbase, chunk << m, grid, partials); break;
+        case 10: rc = launch_tile_cross_complex<10, DOT>(h, D, ps, ket, other, ket_gbase, chunk << m, grid, partials); break;
+        case 11: rc = launch_tile_cross_complex<11, DOT>(h, D, ps, ket, other, ket_gbase, chunk << m, grid, partials); break;
+        default: rc = launch_tile_cross_complex<12, DOT>(h, D, ps, ket, other, ket_gbase, chunk << m, grid, partials); break;
         }
         if (rc) return rc;
     }
@@ -247,6 +103,22 @@ CrossSum *xsum_of(ovqe_handle h, int32_t id) {
     return h->xsums[id];
 }
 
+// the cover of one partner's groups (sv_cross_host.hpp), on the device.  Between real vectors the terms with an imaginary folded
+// coefficient contribute nothing and are dropped (the pool cover, which needs Im v_k, keeps them)
+int build_cross_cover(ovqe_handle h, CrossCoverDev &D, const std::vector<cross::RawGroup> &groups, int m, bool real) {
+    cross::Cover &C = D.c;
+    if (!cross::build_cover(C, groups, m, real, real)) return fail(h, OVQE_ERR_INVALID, "internal: cross-shard cover made no progress");
+    if (C.small) {
+        int rc = upload(h, D.d_groups, C.groups.data(), C.groups.size() * sizeof(HGroup));
+        if (!rc) rc = upload(h, D.d_terms, C.terms.data(), C.terms.size() * sizeof(HTerm));
+        return rc;
+    }
+    int rc = upload(h, D.d_achunks, C.achunks.data(), C.achunks.size() * sizeof(ExChunkT));
+    if (!rc) rc = upload(h, D.d_agroups, C.agroups.data(), C.agroups.size() * sizeof(ExAGroupT));
+    if (!rc) rc = upload(h, D.d_aterms, C.aterms.data(), C.aterms.size() * sizeof(ExTermT));
+    return rc;
+}
+
 // the pass lists of every partner for complex (0) or real (1) amplitudes, built at the first use of that flavour
 int xsum_build(ovqe_handle h, CrossSum &X, int real) {
     if (X.built[real]) return OVQE_OK;
@@ -255,9 +127,10 @@ int xsum_build(ovqe_handle h, CrossSum &X, int real) {
     X.partners[real].reserve(X.raw.size());
     for (const auto &kv : X.raw) {
         X.partners[real].emplace_back();
-        CrossCover &C = X.partners[real].back();
-        C.d = kv.first;
-        int rc = build_cross_cover(h, C, kv.second, X.chunk_bits, real != 0);
+        CrossCoverDev &D = X.partners[real].back();
+        const cross::Cover &C = D.c;
+        D.c.d = kv.first;
+        int rc = build_cross_cover(h, D, kv.second, X.chunk_bits, real != 0);
         if (rc) return rc;
         slots = std::max<size_t>(slots, C.small ? (size_t)std::min<uint64_t>(2048, ((1ull << X.chunk_bits) + 255) / 256)
                                                 : (size_t)1 << (X.chunk_bits - C.M));
@@ -274,14 +147,14 @@ int xsum_build(ovqe_handle h, CrossSum &X, int real) {
     return OVQE_OK;
 }
 
-const CrossCover *xsum_partner(ovqe_handle h, CrossSum &X, uint64_t d, uint64_t chunk, int real) {
+const CrossCoverDev *xsum_partner(ovqe_handle h, CrossSum &X, uint64_t d, uint64_t chunk, int real) {
     if (chunk >> (h->n_local - X.chunk_bits)) {
         fail(h, OVQE_ERR_INVALID, "chunk index beyond the shard");
         return nullptr;
     }
     if (xsum_build(h, X, real)) return nullptr;
-    for (const CrossCover &C : X.partners[real])
-        if (C.d == d) return &C;
+    for (const CrossCoverDev &D : X.partners[real])
+        if (D.c.d == d) return &D;
     fail(h, OVQE_ERR_INVALID, "the planned sum has no terms for this rank difference (ovqe_xsum_partners)");
     return nullptr;
 }
@@ -290,7 +163,7 @@ const CrossCover *xsum_partner(ovqe_handle h, CrossSum &X, uint64_t d, uint64_t 
 // (m = n_local: no x bits above the chunk, so one class / no displacement above it), built at the first real apply
 int xsum_build_local(ovqe_handle h, CrossSum &X) {
     if (X.local_built) return OVQE_OK;
-    X.local_cover.d = 0;
+    X.local_cover.c.d = 0;
     int rc = build_cross_cover(h, X.local_cover, X.raw_local, h->n_local, true);
     if (rc) return rc;
     X.local_built = true;
@@ -326,8 +199,8 @@ int ovqe_xsum_create(ovqe_handle h, int64_t T, const uint64_t *x, const uint64_t
     X->hermitian = true;
     std::vector<uint64_t> lx, lz;
     std::vector<double> lr, li;
-    std::map<uint64_t, std::map<uint64_t, CrossRawGroup>> remote;   // d -> local x -> group (ascending: the same plan on every rank)
-    std::map<uint64_t, CrossRawGroup> local_raw;                    // the d = 0 groups once more, for sigma = H psi on real amplitudes
+    std::map<uint64_t, std::map<uint64_t, cross::RawGroup>> remote;   // d -> local x -> group (ascending: the same plan on every rank)
+    std::map<uint64_t, cross::RawGroup> local_raw;                    // the d = 0 groups once more, for sigma = H psi on real amplitudes
     X->real_map = true;
     for (int64_t t = 0; t < T; ++t) {
         if ((x[t] | z[t]) & ~allmask) return fail(h, OVQE_ERR_INVALID, "Pauli mask has bits beyond the register");
@@ -337,23 +210,18 @@ int ovqe_xsum_create(ovqe_handle h, int64_t T, const uint64_t *x, const uint64_t
         const uint64_t d = x[t] >> h->n_local;
         HTerm ht;
         ht.z = z[t];
-        switch (__builtin_popcountll(x[t] & z[t]) & 3) {  // (a + ib) * i^ny
-        case 0: ht.cr = a; ht.ci = b; break;
-        case 1: ht.cr = -b; ht.ci = a; break;
-        case 2: ht.cr = -a; ht.ci = -b; break;
-        default: ht.cr = b; ht.ci = -a; break;
-        }
+        fold_iny(a, b, __builtin_popcountll(x[t] & z[t]), ht.cr, ht.ci);
         if (d == 0) {
             lx.push_back(x[t]);
             lz.push_back(z[t]);
             lr.push_back(a);
             li.push_back(b);
-            CrossRawGroup &g = local_raw[x[t]];
+            cross::RawGroup &g = local_raw[x[t]];
             g.x = x[t];
             g.terms.push_back(ht);
             continue;
         }
-        CrossRawGroup &g = remote[d][x[t] & lmask];
+        cross::RawGroup &g = remote[d][x[t] & lmask];
         g.x = x[t] & lmask;
         g.terms.push_back(ht);
     }
@@ -370,7 +238,7 @@ int ovqe_xsum_create(ovqe_handle h, int64_t T, const uint64_t *x, const uint64_t
     }
     for (auto &g : local_raw) X->raw_local.push_back(std::move(g.second));
     for (auto &kv : remote) {
-        std::vector<CrossRawGroup> groups;
+        std::vector<cross::RawGroup> groups;
         for (auto &g : kv.second) groups.push_back(std::move(g.second));
         X->raw.emplace_back(kv.first, std::move(groups));
     }
@@ -412,8 +280,8 @@ int ovqe_xsum_partners(ovqe_handle h, int32_t id, int64_t capacity, uint64_t *d,
     if (rc) return rc;
     *count = (int64_t)X->partners[f].size();
     for (int64_t k = 0; k < std::min<int64_t>(capacity, *count); ++k) {
-        if (d) d[k] = X->partners[f][k].d;
-        if (passes) passes[k] = X->partners[f][k].small ? (int64_t)X->partners[f][k].class_h.size() : (int64_t)X->partners[f][k].passes.size();
+        if (d) d[k] = X->partners[f][k].c.d;
+        if (passes) passes[k] = X->partners[f][k].c.n_passes();
     }
     return OVQE_OK;
 } OVQE_CATCH(h)
@@ -426,10 +294,11 @@ int ovqe_xsum_info(ovqe_handle h, int32_t id, int64_t *info, int count) try {
     const int f = h->opt_real_state ? 1 : 0;
     int rc = xsum_build(h, *X, f);
     if (rc) return rc;
-    for (const CrossCover &C : X->partners[f]) {
+    for (const CrossCoverDev &D : X->partners[f]) {
+        const cross::Cover &C = D.c;
         rg += C.ngroups;
         rt += C.nterms;
-        rp += C.small ? (int64_t)C.class_h.size() : (int64_t)C.passes.size();
+        rp += C.n_passes();
         small |= C.small ? 1 : 0;
         M = std::max<int64_t>(M, C.M);
     }
@@ -475,9 +344,9 @@ int ovqe_xsum_expect_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chun
     CrossSum *X = xsum_of(h, id);
     if (!X || !ket_chunk) return OVQE_ERR_INVALID;
     const bool real = h->opt_real_state != 0;
-    const CrossCover *C = xsum_partner(h, *X, d, chunk, real ? 1 : 0);
+    const CrossCoverDev *C = xsum_partner(h, *X, d, chunk, real ? 1 : 0);
     if (!C) return OVQE_ERR_INVALID;
-    h->last_passes = C->small ? (int64_t)C->class_h.size() : (int64_t)C->passes.size();
+    h->last_passes = C->c.n_passes();
     h->last_pass_bytes = (int64_t)((real ? 16.0 : 32.0) * (double)(1ull << X->chunk_bits) * (double)h->last_passes);
     if (real) return run_cross_chunk_real<true>(h, *X, *C, X->chunk_bits, chunk, (const double *)ket_chunk, (double *)h->state);
     return run_cross_chunk<true>(h, *X, *C, chunk, (const amp_t *)ket_chunk, h->state);
@@ -511,8 +380,8 @@ int ovqe_xsum_apply_local(ovqe_handle h, int32_t id, void *out_dev, double ident
         hipLaunchKernelGGL(k_axpy_real, dim3(reduce_blocks(nel)), dim3(256), 0, h->stream, (amp_t *)out_dev, (const amp_t *)h->state, ident, nel, 1);
         HIPC(h, hipGetLastError());
         if (!X->has_local) return OVQE_OK;
-        const CrossCover &C = X->local_cover;
-        h->last_passes = C.small ? (int64_t)C.class_h.size() : (int64_t)C.passes.size();
+        const CrossCoverDev &C = X->local_cover;
+        h->last_passes = C.c.n_passes();
         h->last_pass_bytes = (int64_t)(24.0 * (double)h->namps * (double)h->last_passes);   // ket read, out read and written
         return run_cross_chunk_real<false>(h, *X, C, h->n_local, 0, (const double *)h->state, (double *)out_dev);
     }
@@ -532,13 +401,13 @@ int ovqe_xsum_apply_remote(ovqe_handle h, int32_t id, uint64_t d, uint64_t chunk
     if (!X || !ket_chunk || !out_dev) return OVQE_ERR_INVALID;
     if (h->opt_real_state) {
         if (int rc = xsum_real_apply_ok(h, *X, "ovqe_xsum_apply_remote", out_dev)) return rc;
-        const CrossCover *C = xsum_partner(h, *X, d, chunk, 1);
+        const CrossCoverDev *C = xsum_partner(h, *X, d, chunk, 1);
         if (!C) return OVQE_ERR_INVALID;
-        h->last_passes = C->small ? (int64_t)C->class_h.size() : (int64_t)C->passes.size();
+        h->last_passes = C->c.n_passes();
         h->last_pass_bytes = (int64_t)(24.0 * (double)(1ull << X->chunk_bits) * (double)h->last_passes);
         return run_cross_chunk_real<false>(h, *X, *C, X->chunk_bits, chunk, (const double *)ket_chunk, (double *)out_dev);
     }
-    const CrossCover *C = xsum_partner(h, *X, d, chunk, 0);
+    const CrossCoverDev *C = xsum_partner(h, *X, d, chunk, 0);
     if (!C) return OVQE_ERR_INVALID;
     return run_cross_chunk<false>(h, *X, *C, chunk, (const amp_t *)ket_chunk, (amp_t *)out_dev);
 } OVQE_CATCH(h)

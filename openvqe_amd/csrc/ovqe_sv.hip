@@ -9,7 +9,10 @@
 //   gates_host.inc   literal gate programs -> small ops / Clifford-frame rotations                   (sv_small.hpp, sv_frame_host.hpp)
 //   sparse_host.inc  support-compacted path                                                          (kernels: sv_sparse.hpp)
 //   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc   extern "C" entry points by family (include/ovqe_sv.h)
-//   cross_host.inc   planned Pauli sums on a shard of the partitioned register, ovqe_xsum_*          (kernels: sv_cross.hpp)
+//   cross_host.inc   planned Pauli sums on a shard of the partitioned register, ovqe_xsum_*          (sv_cross_host.hpp; kernels: sv_cross.hpp)
+//   pool_host.inc    planned ADAPT pool screen on a shard, ovqe_xpool_*                              (sv_pool_host.hpp; kernels: sv_pool.hpp)
+// sv_cover_host.hpp (host-only) holds the table records planners and kernels share and the one cover rule, grow_tile_set(), that
+// tile_host.inc, sector_host.inc, sv_cross_host.hpp and sv_pool_host.hpp plan with.
 #include "../../include/ovqe_sv.h"
 
 #include <hip/hip_runtime.h>
@@ -36,6 +39,7 @@
 #include "sv_tile.hpp"
 #include "sv_sector.hpp"
 #include "sv_cross.hpp"
+#include "sv_cross_host.hpp"
 #include "sv_pool.hpp"
 #include "sv_frame_host.hpp"
 #include <hipcub/hipcub.hpp>
@@ -139,32 +143,22 @@ struct HamDev {  // grouped Pauli sum resident on the device
 
 // Pauli sum planned ONCE for a shard of the partitioned register (sv_cross.hpp, cross_host.inc): the terms without an x part on the
 // rank bits as a HamDev of their own (tile cover, pair trick), the others grouped by partner shard with a pass list each
-struct CrossCover {          // the groups of one partner (rank difference d)
-    uint64_t d = 0;
-    int ngroups = 0, nterms = 0;
-    bool small = false;      // chunks below the tile sizes: k_cross_small, one launch per class of high x bits
-    int M = 0;               // tile bits of the passes
-    std::vector<CrossPass> passes;
-    DevBuf d_achunks, d_agroups, d_aterms;          // tile form
-    std::vector<uint64_t> class_h;                   // small form: x bits above the chunk per class ...
-    std::vector<std::pair<int, int>> class_groups;   // ... and its group range
-    DevBuf d_groups, d_terms;
-};
-struct CrossRawGroup {
-    uint64_t x;                 // local x mask
-    std::vector<HTerm> terms;   // full z masks, i^ny folded
+struct CrossCoverDev {       // the groups of one partner (rank difference d): the cover (sv_cross_host.hpp) and its tables on the device
+    cross::Cover c;
+    DevBuf d_achunks, d_agroups, d_aterms;   // tile form
+    DevBuf d_groups, d_terms;                // small form
 };
 struct CrossSum {
     int chunk_bits = 0;
     bool hermitian = false;  // every coefficient real: expectation values allowed
     HamDev local;            // d = 0
     bool has_local = false;
-    std::vector<std::pair<uint64_t, std::vector<CrossRawGroup>>> raw;   // the terms of every rank difference d != 0, ascending
-    std::vector<CrossCover> partners[2];   // their pass lists: [0] complex amplitudes, [1] real amplitudes (option "real_state"); built at first use
+    std::vector<std::pair<uint64_t, std::vector<cross::RawGroup>>> raw;   // the terms of every rank difference d != 0, ascending
+    std::vector<CrossCoverDev> partners[2];   // their pass lists: [0] complex amplitudes, [1] real amplitudes (option "real_state"); built at first use
     bool built[2] = {false, false};
     bool real_map = false;   // every string an even number of Y and every coefficient real: the sum maps real vectors to real vectors
-    std::vector<CrossRawGroup> raw_local;   // the d = 0 terms in the form of `raw`, and their cover for sigma = H psi on real amplitudes
-    CrossCover local_cover;                 // (k_tile_cross_real APPLY with the shard as its own partner), built at the first real apply
+    std::vector<cross::RawGroup> raw_local;   // the d = 0 terms in the form of `raw`, and their cover for sigma = H psi on real amplitudes
+    CrossCoverDev local_cover;                // (k_tile_cross_real APPLY with the shard as its own partner), built at the first real apply
     bool local_built = false;
     DevBuf d_part;           // per-workgroup partial sums of the remote contractions of one expectation value
     size_t part_slots = 0;
@@ -574,7 +568,7 @@ void free_cross_sum(CrossSum *X) {
     for (DevBuf *b : {&X->local_cover.d_achunks, &X->local_cover.d_agroups, &X->local_cover.d_aterms, &X->local_cover.d_groups, &X->local_cover.d_terms})
         if (b->p) (void)hipFree(b->p);
     for (int f = 0; f < 2; ++f)
-        for (CrossCover &C : X->partners[f])
+        for (CrossCoverDev &C : X->partners[f])
             for (DevBuf *b : {&C.d_achunks, &C.d_agroups, &C.d_aterms, &C.d_groups, &C.d_terms})
                 if (b->p) (void)hipFree(b->p);
     if (X->d_part.p) (void)hipFree(X->d_part.p);
@@ -691,16 +685,9 @@ int build_groups(ovqe_handle h, int64_t T, const uint64_t *x, const uint64_t *z,
         if (!allow_global_x && (x[t] & ~lmask))
             return fail(h, OVQE_ERR_INVALID,
                         "x mask touches global (rank) bits: exchange shards first (openvqe_amd/distributed.py)");
-        const int ny = __builtin_popcountll(x[t] & z[t]) & 3;
-        const double a = cr[t], b = ci ? ci[t] : 0.0;
         HTerm ht;
         ht.z = z[t];
-        switch (ny) {  // (a + ib) * i^ny
-        case 0: ht.cr = a; ht.ci = b; break;
-        case 1: ht.cr = -b; ht.ci = a; break;
-        case 2: ht.cr = -a; ht.ci = -b; break;
-        default: ht.cr = b; ht.ci = -a; break;
-        }
+        fold_iny(cr[t], ci ? ci[t] : 0.0, __builtin_popcountll(x[t] & z[t]), ht.cr, ht.ci);
         if (groups.empty() || x[order[oi - 1]] != x[t]) {
             HGroup g;
             g.x = x[t] & lmask;
@@ -872,20 +859,8 @@ inline int tile_bits(ovqe_handle h, bool real = false) {
 }
 inline bool tile_ok(ovqe_handle h, bool real) {
     const int m = tile_bits(h, real);
-    return m >= (real ? 11 : 10) && m <= (real ? 13 : 12) && h->n_local >= m + 2 && h->opt_tile_low >= (real ? 1 : 0) &&
+    return m >= (real ? TILE_MIN_REAL : TILE_MIN_COMPLEX) && m <= (real ? TILE_MAX_REAL : TILE_MAX_COMPLEX) && h->n_local >= m + 2 && h->opt_tile_low >= (real ? 1 : 0) &&
            h->opt_tile_low <= 8;
-}
-
-// lowest index bits forced into every tile of the Hamiltonian's cover (a real amplitude is 8 bytes: at least one, for 16-byte chunks):
-// fewer forced bits = fewer sweeps per H psi / <H> (N2/cc-pVDZ at 24 qubits: 102 sweeps at 4; 25.4 ms per H psi at 2, 30.1 at 4)
-constexpr int HAM_TILE_LOW = 2;
-
-inline uint32_t extract_bits(uint64_t v, uint64_t mask) {  // pext
-    uint32_t r = 0;
-    int k = 0;
-    for (uint64_t mk = mask; mk; mk &= mk - 1ull, ++k)
-        if ((v >> __builtin_ctzll(mk)) & 1ull) r |= 1u << k;
-    return r;
 }
 
 #include "tile_host.inc"

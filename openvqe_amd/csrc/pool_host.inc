@@ -24,9 +24,9 @@ int xpool_build(ovqe_handle h, PoolPlan &P, int real) {
         PoolCoverDev &D = P.covers[real].back();
         D.c.d = kv.first;
         pool::build_cover(D.c, kv.second, kv.first ? P.chunk_bits : h->n_local, real != 0);
-        int rc = upload(h, D.d_chunks, D.c.chunks.data(), D.c.chunks.size() * sizeof(PoolChunk));
+        int rc = upload(h, D.d_chunks, D.c.chunks.data(), D.c.chunks.size() * sizeof(ExChunkT));
         if (!rc) rc = upload(h, D.d_entries, D.c.entries.data(), D.c.entries.size() * sizeof(PoolEntry));
-        if (!rc) rc = upload(h, D.d_terms, D.c.terms.data(), D.c.terms.size() * sizeof(PoolTerm));
+        if (!rc) rc = upload(h, D.d_terms, D.c.terms.data(), D.c.terms.size() * sizeof(ExTermT));
         if (rc) return rc;
     }
     P.built[real] = true;
@@ -40,44 +40,30 @@ const PoolCoverDev *xpool_cover(ovqe_handle h, PoolPlan &P, uint64_t d, int real
     return nullptr;
 }
 
-template <int M>
-int launch_tile_pool(ovqe_handle h, const PoolPlan &P, const PoolCoverDev &D, const PoolPass &ps, const amp_t *ket, const amp_t *bra,
-                     uint64_t ket_gbase, uint64_t chunk_off, uint32_t ntiles) {
-    constexpr int NT = 1 << pool::POOL_LOG_NT;
-    constexpr size_t smem = tile_pool_lds<M>(sizeof(double2), NT / 64).bytes;
-    static_assert(smem <= LDS_TWO_PER_CU, "two workgroups of the pool pass per CU");
-    if (int rc = lds_opt_in<&k_tile_pool<M, NT, true>, &k_tile_pool<M, NT, false>>(h, smem)) return rc;
-    const unsigned grid = std::min<uint32_t>(ntiles, pool::POOL_ROWS);
-    if (h->n_local >= 25)
-        hipLaunchKernelGGL((k_tile_pool<M, NT, true>), dim3(grid), dim3(NT), smem, h->stream, ket, bra, ket_gbase, chunk_off, ps, ntiles,
-                           (const PoolChunk *)D.d_chunks.p, (const PoolEntry *)D.d_entries.p, (const PoolTerm *)D.d_terms.p,
-                           (double2 *)P.d_part.p, (int)P.n_ops);
-    else
-        hipLaunchKernelGGL((k_tile_pool<M, NT, false>), dim3(grid), dim3(NT), smem, h->stream, ket, bra, ket_gbase, chunk_off, ps, ntiles,
-                           (const PoolChunk *)D.d_chunks.p, (const PoolEntry *)D.d_entries.p, (const PoolTerm *)D.d_terms.p,
-                           (double2 *)P.d_part.p, (int)P.n_ops);
+// a tile pass of cover D over one chunk: KT / KF = the kernel with and without non-temporal loads (shards of ntl_from qubits and more)
+template <auto KT, auto KF, class T>
+int launch_tile_pool(ovqe_handle h, const PoolPlan &P, const PoolCoverDev &D, const TilePass &ps, size_t smem, int ntl_from, const T *ket,
+                     const T *bra, uint64_t ket_gbase, uint64_t chunk_off, uint32_t ntiles) {
+    if (int rc = lds_opt_in<KT, KF>(h, smem)) return rc;
+    hipLaunchKernelGGL(h->n_local >= ntl_from ? KT : KF, dim3(std::min<uint32_t>(ntiles, pool::POOL_ROWS)), dim3(1 << TILE_EXPECT_LOG_NT), smem,
+                       h->stream, ket, bra, ket_gbase, chunk_off, ps, ntiles, (const ExChunkT *)D.d_chunks.p, (const PoolEntry *)D.d_entries.p,
+                       (const ExTermT *)D.d_terms.p, (double2 *)P.d_part.p, (int)P.n_ops);
     HIPC(h, hipGetLastError());
     return OVQE_OK;
 }
-
-template <int M>
-int launch_tile_pool_real(ovqe_handle h, const PoolPlan &P, const PoolCoverDev &D, const PoolPass &ps, const double *ket, const double *bra,
-                          uint64_t ket_gbase, uint64_t chunk_off, uint32_t ntiles) {
-    constexpr int NT = 1 << pool::POOL_LOG_NT;
+template <int M, class... A>
+int launch_tile_pool_complex(ovqe_handle h, const PoolPlan &P, const PoolCoverDev &D, const TilePass &ps, A... args) {
+    constexpr int NT = 1 << TILE_EXPECT_LOG_NT;
+    constexpr size_t smem = tile_pool_lds<M>(sizeof(double2), NT / 64).bytes;
+    static_assert(smem <= LDS_TWO_PER_CU, "two workgroups of the pool pass per CU");
+    return launch_tile_pool<&k_tile_pool<M, NT, true>, &k_tile_pool<M, NT, false>>(h, P, D, ps, smem, 25, args...);
+}
+template <int M, class... A>
+int launch_tile_pool_real(ovqe_handle h, const PoolPlan &P, const PoolCoverDev &D, const TilePass &ps, A... args) {
+    constexpr int NT = 1 << TILE_EXPECT_LOG_NT;
     constexpr size_t smem = tile_pool_lds<M>(sizeof(double), NT / 64).bytes;
     static_assert(smem <= LDS_TWO_PER_CU, "two workgroups of the pool pass per CU");
-    if (int rc = lds_opt_in<&k_tile_pool_real<M, NT, true>, &k_tile_pool_real<M, NT, false>>(h, smem)) return rc;
-    const unsigned grid = std::min<uint32_t>(ntiles, pool::POOL_ROWS);
-    if (h->n_local >= 26)
-        hipLaunchKernelGGL((k_tile_pool_real<M, NT, true>), dim3(grid), dim3(NT), smem, h->stream, ket, bra, ket_gbase, chunk_off, ps, ntiles,
-                           (const PoolChunk *)D.d_chunks.p, (const PoolEntry *)D.d_entries.p, (const PoolTerm *)D.d_terms.p,
-                           (double2 *)P.d_part.p, (int)P.n_ops);
-    else
-        hipLaunchKernelGGL((k_tile_pool_real<M, NT, false>), dim3(grid), dim3(NT), smem, h->stream, ket, bra, ket_gbase, chunk_off, ps, ntiles,
-                           (const PoolChunk *)D.d_chunks.p, (const PoolEntry *)D.d_entries.p, (const PoolTerm *)D.d_terms.p,
-                           (double2 *)P.d_part.p, (int)P.n_ops);
-    HIPC(h, hipGetLastError());
-    return OVQE_OK;
+    return launch_tile_pool<&k_tile_pool_real<M, NT, true>, &k_tile_pool_real<M, NT, false>>(h, P, D, ps, smem, 26, args...);
 }
 
 // every pass of cover D over one ket chunk of 2^m amplitudes (m = the cover's chunk bits): partials += conj(bra) . (A_k ket) per entry
@@ -95,16 +81,16 @@ int run_pool_chunk(ovqe_handle h, PoolPlan &P, const PoolCoverDev &D, uint64_t c
             const void *bc = (const char *)bra + ((chunk ^ C.class_h[k]) << m) * ab;
             if (real)
                 hipLaunchKernelGGL((k_pool_small<true>), dim3(nb), dim3(256), 0, h->stream, ket, bc, csize, ket_gbase, (const PoolEntry *)D.d_entries.p,
-                                   C.class_entries[k].first, C.class_entries[k].second, (const PoolTerm *)D.d_terms.p, (double2 *)P.d_part.p, (int)P.n_ops);
+                                   C.class_entries[k].first, C.class_entries[k].second, (const ExTermT *)D.d_terms.p, (double2 *)P.d_part.p, (int)P.n_ops);
             else
                 hipLaunchKernelGGL((k_pool_small<false>), dim3(nb), dim3(256), 0, h->stream, ket, bc, csize, ket_gbase, (const PoolEntry *)D.d_entries.p,
-                                   C.class_entries[k].first, C.class_entries[k].second, (const PoolTerm *)D.d_terms.p, (double2 *)P.d_part.p, (int)P.n_ops);
+                                   C.class_entries[k].first, C.class_entries[k].second, (const ExTermT *)D.d_terms.p, (double2 *)P.d_part.p, (int)P.n_ops);
         }
         HIPC(h, hipGetLastError());
         return OVQE_OK;
     }
     const uint32_t ntiles = (uint32_t)(csize >> C.M);
-    for (const PoolPass &ps : C.passes) {
+    for (const TilePass &ps : C.passes) {
         int rc;
         if (real) {
             switch (C.M) {
@@ -114,9 +100,9 @@ int run_pool_chunk(ovqe_handle h, PoolPlan &P, const PoolCoverDev &D, uint64_t c
             }
         } else {
             switch (C.M) {
-            case 10: rc = launch_tile_pool<10>(h, P, D, ps, (const amp_t *)ket, (const amp_t *)bra, ket_gbase, chunk << m, ntiles); break;
-            case 11: rc = launch_tile_pool<11>(h, P, D, ps, (const amp_t *)ket, (const amp_t *)bra, ket_gbase, chunk << m, ntiles); break;
-            default: rc = launch_tile_pool<12>(h, P, D, ps, (const amp_t *)ket, (const amp_t *)bra, ket_gbase, chunk << m, ntiles); break;
+            case 10: rc = launch_tile_pool_complex<10>(h, P, D, ps, (const amp_t *)ket, (const amp_t *)bra, ket_gbase, chunk << m, ntiles); break;
+            case 11: rc = launch_tile_pool_complex<11>(h, P, D, ps, (const amp_t *)ket, (const amp_t *)bra, ket_gbase, chunk << m, ntiles); break;
+            default: rc = launch_tile_pool_complex<12>(h, P, D, ps, (const amp_t *)ket, (const amp_t *)bra, ket_gbase, chunk << m, ntiles); break;
             }
         }
         if (rc) return rc;

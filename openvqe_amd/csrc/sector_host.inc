@@ -314,7 +314,7 @@ int sector_tile_bits(ovqe_handle h) {
         return OVQE_OK;                                                                           \
     } while (0)
 // ---- <H> restricted to the support E.d_sup (E.K entries, ascending), vectors in the order whose inverse map (canonical id ->
-// position) is W.inv_circ: greedy cover of the x-groups by tile bit sets (the heuristic of build_ham_tiles), then the restricted
+// position) is W.inv_circ: greedy cover of the x-groups by tile bit sets (grow_tile_set(), sv_cover_host.hpp), then the restricted
 // Hamiltonian of every (sweep, tile).  E.M = the tile bits to start from; E.bytes = what the engine holds so far.
 int build_sector_h(ovqe_handle h, SectorEngine &E, SectorScratch &W, size_t budget) {
     const uint32_t K = E.K;
@@ -348,28 +348,11 @@ int build_sector_h(ovqe_handle h, SectorEngine &E, SectorScratch &W, size_t budg
         plan.clear();
         std::vector<char> covered(G, 0);
         int remaining = G;
-        const double wgt[8] = {1.0, 0.25, 0.0625, 0.015625, 0.00390625, 0.0009765625, 0.000244140625, 0.00006103515625};
         while (remaining > 0) {
-            uint64_t S = 0;
-            while (__builtin_popcountll(S) < M) {
-                const int room = M - __builtin_popcountll(S);
-                double score[64] = {0.0};
-                bool any = false;
-                for (int g = 0; g < G; ++g) {
-                    if (covered[g]) continue;
-                    const uint64_t miss = H.groups[g].x & ~S;
-                    const int nm = __builtin_popcountll(miss);
-                    if (nm == 0 || nm > room) continue;
-                    any = true;
-                    for (uint64_t mk = miss; mk; mk &= mk - 1ull) score[__builtin_ctzll(mk)] += wgt[std::min(nm - 1, 7)];
-                }
-                if (!any) break;
-                int best = -1;
-                for (int b = 0; b < h->n_local; ++b)
-                    if (!((S >> b) & 1ull) && (best < 0 || score[b] > score[best])) best = b;
-                S |= 1ull << best;
-            }
-            for (int b = 0; __builtin_popcountll(S) < M; ++b) S |= 1ull << b;
+            std::vector<uint64_t> uncovered;
+            for (int g = 0; g < G; ++g)
+                if (!covered[g]) uncovered.push_back(H.groups[g].x);
+            const uint64_t S = grow_tile_set(uncovered, 0, M, h->n_local);
             // element offsets of a sweep are 32-bit: a bit set with many x-groups on a large support becomes several
             // sweeps (same tiles, the groups shared out)
             const size_t gmax = std::max<size_t>(1, (size_t)(3.9e9 / (double)K));

@@ -21,15 +21,12 @@
 
 namespace ovqe {
 
-struct CrossPass {
-    uint64_t smask, mask_lo, mask_hi;   // tile bits (inside the chunk), thread bits, trip bits (sv_tile.hpp ExSweep)
-    uint64_t d_out;                     // x bits of the pass's groups outside the tile: other tile = ket tile ^ d_out (local index space)
-    int32_t a0, a1;                     // chunk range of the pass's apply-form tables (ExChunkT / ExAGroupT / ExTermT)
-};
+// (a pass: TilePass of sv_cover_host.hpp, a0 / a1 = the chunk range of its apply-form tables ExChunkT / ExAGroupT / ExTermT; the
+// plan: sv_cross_host.hpp)
 
 template <int M, int NT, bool NTL, bool DOT>
 __global__ __launch_bounds__(NT) void k_tile_cross(const amp_t *__restrict__ ket, amp_t *__restrict__ other, uint64_t ket_gbase,
-                                                   uint64_t chunk_off, CrossPass ps, const ExChunkT *__restrict__ chunks,
+                                                   uint64_t chunk_off, TilePass ps, const ExChunkT *__restrict__ chunks,
                                                    const ExAGroupT *__restrict__ groups, const ExTermT *__restrict__ terms,
                                                    double2 *__restrict__ partials) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -168,7 +165,7 @@ __global__ __launch_bounds__(NT) void k_tile_cross(const amp_t *__restrict__ ket
 // one stream.  (The same invariant carries the APPLY form of k_tile_cross.)  A ket tile of zeros adds nothing: the early exit stays.
 template <int M, int NT, bool NTL, bool DOT>
 __global__ __launch_bounds__(NT) void k_tile_cross_real(const double *__restrict__ ket, double *__restrict__ other, uint64_t ket_gbase,
-                                                        uint64_t chunk_off, CrossPass ps, const ExChunkT *__restrict__ chunks,
+                                                        uint64_t chunk_off, TilePass ps, const ExChunkT *__restrict__ chunks,
                                                         const ExAGroupT *__restrict__ groups, const ExTermT *__restrict__ terms,
                                                         double2 *__restrict__ partials) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

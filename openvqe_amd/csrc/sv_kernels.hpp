@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sv_cover_host.hpp"   // HTerm, HGroup and the other table records planners and kernels share
+
 namespace ovqe {
 
 typedef double2 amp_t;  // .x = re, .y = im
@@ -23,18 +25,6 @@ struct RotParam {
     int32_t pad;
 };
 
-// Hamiltonian / pool term with i^{ny} folded into the coefficient
-struct HTerm {
-    uint64_t z;
-    double cr, ci;
-};
-
-struct HGroup {
-    uint64_t x;      // local part of the x mask
-    uint64_t jbase;  // high (global) bits of the partner's global index
-    int32_t t0, t1;  // term range
-    double tiny;     // 64 eps sum_t |c_t|: a D_g(j) at or below it is a rounding residue of a sum that cancels (see group_coeff_snap)
-};
 // D_g(j) = sum_t +-c_t of an operator application.  The strings of a number-conserving operator cancel EXACTLY on the basis states
 // they must not connect, but their coefficients come out of the caller's algebra equal to an ulp, not bit for bit: the residue
 // (1e-17 c) would plant amplitudes outside the particle-number sector, which stay harmless in value (1e-17, 1e-34, ...) and

@@ -22,12 +22,7 @@
 
 namespace ovqe {
 
-using pool::PoolChunk;
 using pool::PoolEntry;
-using pool::PoolPass;
-using pool::PoolTerm;
-static_assert(pool::POOL_TERM_CAP <= TILE_TERM_CAP && pool::POOL_ENTRY_CAP <= TILE_APPLY_GROUPS, "the pool tables respect the tile caps");
-static_assert(pool::POOL_LOG_NT == TILE_EXPECT_LOG_NT, "thread / trip masks as in the cross-shard passes");
 
 // dynamic LDS of k_tile_pool / k_tile_pool_real, one definition for kernel and host: [tile][terms][entries][one row per wave]
 struct TilePoolLds { size_t terms, entries, wacc, bytes; };   // the tile is at 0
@@ -58,8 +53,8 @@ __device__ __forceinline__ void pool_flush(const PoolEntry *le, const double2 *w
 
 template <int M, int NT, bool NTL>
 __global__ __launch_bounds__(NT) void k_tile_pool(const amp_t *__restrict__ ket, const amp_t *__restrict__ bra, uint64_t ket_gbase,
-                                                  uint64_t chunk_off, PoolPass ps, uint32_t ntiles, const PoolChunk *__restrict__ chunks,
-                                                  const PoolEntry *__restrict__ entries, const PoolTerm *__restrict__ terms,
+                                                  uint64_t chunk_off, TilePass ps, uint32_t ntiles, const ExChunkT *__restrict__ chunks,
+                                                  const PoolEntry *__restrict__ entries, const ExTermT *__restrict__ terms,
                                                   double2 *__restrict__ partials, int n_slots) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr uint32_t NEL = 1u << M;
@@ -104,10 +99,10 @@ __global__ __launch_bounds__(NT) void k_tile_pool(const amp_t *__restrict__ ket,
             b[j] = NTL ? __builtin_nontemporal_load(&q[g]) : q[g];
         }
         for (int ch = ps.a0; ch < ps.a1; ++ch) {
-            const PoolChunk ck = chunks[ch];
+            const ExChunkT ck = chunks[ch];
             __syncthreads();   // (the previous chunk's flush has read the tables and the wave rows)
             for (int t = ck.t0 + (int)threadIdx.x; t < ck.t1; t += NT) {
-                const PoolTerm et = terms[t];
+                const ExTermT et = terms[t];
                 const bool neg = parity64(gbase & et.zout);
                 ExTermLds l;
                 l.cr = neg ? -et.cr : et.cr;
@@ -165,9 +160,9 @@ __global__ __launch_bounds__(NT) void k_tile_pool(const amp_t *__restrict__ ket,
 // with an odd number of Y is purely imaginary between real vectors; its gradient is 2 |v_k|) — nothing is dropped as the <H> cover does.
 template <int M, int NT, bool NTL>
 __global__ __launch_bounds__(NT) void k_tile_pool_real(const double *__restrict__ ket, const double *__restrict__ bra, uint64_t ket_gbase,
-                                                       uint64_t chunk_off, PoolPass ps, uint32_t ntiles,
-                                                       const PoolChunk *__restrict__ chunks, const PoolEntry *__restrict__ entries,
-                                                       const PoolTerm *__restrict__ terms, double2 *__restrict__ partials, int n_slots) {
+                                                       uint64_t chunk_off, TilePass ps, uint32_t ntiles,
+                                                       const ExChunkT *__restrict__ chunks, const PoolEntry *__restrict__ entries,
+                                                       const ExTermT *__restrict__ terms, double2 *__restrict__ partials, int n_slots) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr uint32_t NEL = 1u << M;
     constexpr uint32_t NELV = NEL / 2;
@@ -212,10 +207,10 @@ __global__ __launch_bounds__(NT) void k_tile_pool_real(const double *__restrict_
             b[j] = NTL ? __builtin_nontemporal_load(&q[g]) : q[g];
         }
         for (int ch = ps.a0; ch < ps.a1; ++ch) {
-            const PoolChunk ck = chunks[ch];
+            const ExChunkT ck = chunks[ch];
             __syncthreads();
             for (int t = ck.t0 + (int)threadIdx.x; t < ck.t1; t += NT) {
-                const PoolTerm et = terms[t];
+                const ExTermT et = terms[t];
                 const bool neg = parity64(gbase & et.zout);
                 ExTermLds l;
                 l.cr = neg ? -et.cr : et.cr;
@@ -270,13 +265,13 @@ __global__ __launch_bounds__(NT) void k_tile_pool_real(const double *__restrict_
 }
 
 // Chunks below the tile sizes (the CPU-sized tests): the streaming form.  Entries [e0, e1) share the part of their x mask above the
-// chunk bits (one launch per class); `bra` is the class's bra chunk, PoolEntry::x the x mask on the chunk bits, PoolTerm::zout the
+// chunk bits (one launch per class); `bra` is the class's bra chunk, PoolEntry::x the x mask on the chunk bits, ExTermT::zout the
 // full z mask (the sign is read off the ket's GLOBAL index ket_gbase | j).  A workgroup strides over the chunk once per entry and
 // adds the entry's block sum to its row: POOL_SMALL_ROWS rows.
 template <bool REAL>
 __global__ __launch_bounds__(256) void k_pool_small(const void *__restrict__ ket_, const void *__restrict__ bra_, uint64_t csize,
                                                     uint64_t ket_gbase, const PoolEntry *__restrict__ entries, int e0, int e1,
-                                                    const PoolTerm *__restrict__ terms, double2 *__restrict__ partials, int n_slots) {
+                                                    const ExTermT *__restrict__ terms, double2 *__restrict__ partials, int n_slots) {
     __shared__ double2 red[4];
     typedef typename Amp<REAL>::T amp;
     const amp *ket = reinterpret_cast<const amp *>(ket_), *bra = reinterpret_cast<const amp *>(bra_);
@@ -289,7 +284,7 @@ __global__ __launch_bounds__(256) void k_pool_small(const void *__restrict__ ket
             const uint64_t gj = ket_gbase | j;
             double dr = 0.0, di = 0.0;
             for (int t = en.t0; t < en.t1; ++t) {
-                const PoolTerm pt = terms[t];
+                const ExTermT pt = terms[t];
                 const double sg = parity_sign64(gj & pt.zout);
                 dr = fma(pt.cr, sg, dr);
                 di = fma(pt.ci, sg, di);

@@ -7,57 +7,35 @@
 // part on the rank bits, d = x >> n_local, names the partner shard its ket amplitudes live in; that shard arrives in chunks of 2^m
 // amplitudes (d = 0: the shard itself is its one chunk, m = n_local).  Per rank difference the work items are ENTRIES — one
 // (operator, local x mask) pair with its terms, cut into pieces of at most POOL_TERM_CAP terms that feed the same accumulator — and
-// the distinct local x masks are covered greedily by passes (tile bit set S inside the chunk, displacement d_out outside it) by the
-// rule of build_cross_cover: grow S by the bit that brings the most masks inside; the x bits above the chunk, which pair ket chunk c
-// with bra chunk c ^ h, are part of d_out.  Two entries with the same x that belong to different operators never merge.
+// the distinct local x masks are covered by passes (tile bit set S inside the chunk, displacement d_out outside it) chosen by
+// pick_pass() of sv_cover_host.hpp, as in the cross-shard sums: S grows by grow_tile_set(); the x bits above the chunk, which pair
+// ket chunk c with bra chunk c ^ h, are part of d_out.  Two entries with the same x that belong to different operators never merge.
 #pragma once
-#include <algorithm>
-#include <cstdint>
-#include <map>
+#include "sv_cover_host.hpp"
+
 #include <string>
-#include <utility>
-#include <vector>
 
 namespace ovqe {
 namespace pool {
 
-constexpr int POOL_TERM_CAP = 256;    // terms of one staged chunk of a pass (<= TILE_TERM_CAP)
-constexpr int POOL_ENTRY_CAP = 64;    // entries (pieces) of one staged chunk (<= TILE_APPLY_GROUPS: the group cap)
-constexpr int POOL_LOG_NT = 9;        // threads per workgroup of the tile kernels (= TILE_EXPECT_LOG_NT: thread / trip masks)
-constexpr int POOL_TILE_LOW = 2;      // index bits every tile holds (= HAM_TILE_LOW)
+constexpr int POOL_TERM_CAP = 256;    // terms of one staged chunk of a pass
+constexpr int POOL_ENTRY_CAP = 64;    // entries (pieces) of one staged chunk
+static_assert(POOL_TERM_CAP <= TILE_TERM_CAP && POOL_ENTRY_CAP <= TILE_APPLY_GROUPS, "the pool tables respect the tile caps");
 constexpr int POOL_ROWS = 512;        // partial rows: workgroups of a tile pass (grid-stride over the tiles), whatever the shard
 constexpr int POOL_SMALL_ROWS = 16;   // ... of the streaming form
-constexpr int POOL_TILE_MIN_COMPLEX = 10, POOL_TILE_MIN_REAL = 11;   // chunks below 2^this stream (build_cross_cover's thresholds)
 
-struct PoolPass {
-    uint64_t smask, mask_lo, mask_hi;   // tile bits, thread bits, trip bits (real flavour: in the index space of amplitude PAIRS)
-    uint64_t d_out;                     // x bits outside the tile: bra tile = ket tile ^ d_out (local index space of the shard)
-    int32_t a0, a1;                     // staged chunks of the pass
-};
-struct PoolChunk {
-    int32_t g0, g1, t0, t1;             // entries, terms
-};
 struct PoolEntry {
     uint32_t x;        // tile form: tile-local x mask; streaming form: x on the chunk bits
-    int32_t t0, t1;    // terms (absolute)
+    int32_t t0, t1;    // terms (absolute; ExTermT — streaming form: zout = the full z mask, zin = 0)
     int32_t slot;      // operator k: the accumulator the entry feeds
     int32_t run;       // entries of this chunk from here on that feed the same slot (0: not the first of its run)
     int32_t pad;
 };
-struct PoolTerm {
-    uint64_t zout;     // tile form: z outside the tile; streaming form: the full z mask
-    uint32_t zin;      // z on the tile bits
-    uint32_t pad;
-    double cr, ci;     // coefficient with i^ny folded
-};
-struct RawTerm {
-    uint64_t z;
-    double cr, ci;
-};
+static_assert(sizeof(PoolEntry) == 24, "record the kernels read");
 struct RawEntry {      // one (operator, local x mask) pair of one rank difference
     int32_t slot;
     uint64_t x;
-    std::vector<RawTerm> terms;
+    std::vector<HTerm> terms;   // full z masks, i^ny folded
 };
 
 struct Cover {         // the entries of one rank difference in one flavour
@@ -66,22 +44,14 @@ struct Cover {         // the entries of one rank difference in one flavour
     bool small = false;        // streaming form
     int M = 0;                 // tile bits
     int n_entries = 0, n_x = 0, n_terms = 0;   // (operator, x) pairs, distinct x masks, terms
-    std::vector<PoolPass> passes;
-    std::vector<PoolChunk> chunks;
+    std::vector<TilePass> passes;
+    std::vector<ExChunkT> chunks;
     std::vector<PoolEntry> entries;
-    std::vector<PoolTerm> terms;
+    std::vector<ExTermT> terms;
     std::vector<uint64_t> class_h;                    // streaming form: x bits above the chunk per class ...
     std::vector<std::pair<int, int>> class_entries;   // ... and its entry range
     int64_t n_passes() const { return small ? (int64_t)class_h.size() : (int64_t)passes.size(); }
 };
-
-inline uint32_t extract(uint64_t v, uint64_t mask) {   // pext
-    uint32_t r = 0;
-    int k = 0;
-    for (; mask; mask &= mask - 1ull, ++k)
-        if (v & mask & (0ull - mask)) r |= 1u << k;
-    return r;
-}
 
 // bytes of the partial sums of a plan: POOL_ROWS rows of one double2 per operator — independent of the shard and of the entries
 inline size_t partial_bytes(int64_t n_ops) { return (size_t)POOL_ROWS * (size_t)std::max<int64_t>(n_ops, 1) * 16u; }
@@ -101,14 +71,9 @@ inline std::string collect(int n_local, int n_total, int64_t n_ops, const int64_
         for (int64_t t = offsets[k]; t < offsets[k + 1]; ++t) {
             if ((x[t] | z[t]) & ~allmask) return "Pauli mask has bits beyond the register";
             const double a = cre[t], b = cim ? cim[t] : 0.0;
-            RawTerm rt;
+            HTerm rt;
             rt.z = z[t];
-            switch (__builtin_popcountll(x[t] & z[t]) & 3) {   // (a + ib) * i^ny
-            case 0: rt.cr = a; rt.ci = b; break;
-            case 1: rt.cr = -b; rt.ci = a; break;
-            case 2: rt.cr = -a; rt.ci = -b; break;
-            default: rt.cr = b; rt.ci = -a; break;
-            }
+            fold_iny(a, b, __builtin_popcountll(x[t] & z[t]), rt.cr, rt.ci);
             RawEntry &e = mine[{x[t] >> n_local, x[t] & lmask}];
             e.slot = (int32_t)k;
             e.x = x[t] & lmask;
@@ -124,35 +89,20 @@ inline std::string collect(int n_local, int n_total, int64_t n_ops, const int64_
 inline void build_cover(Cover &C, const std::vector<RawEntry> &raw, int m, bool real) {
     C.m = m;
     C.n_entries = (int)raw.size();
-    std::map<uint64_t, int> xs;
+    std::set<uint64_t> xs;
     for (const RawEntry &e : raw) {
-        ++xs[e.x];
+        xs.insert(e.x);
         C.n_terms += (int)e.terms.size();
     }
     C.n_x = (int)xs.size();
-    const uint64_t lowmask = (1ull << m) - 1ull;
-    const int E = (int)raw.size();
-    // pieces of entry e appended to the tables; `open` is the chunk being filled
-    auto append = [&](const RawEntry &e, uint32_t xl, uint64_t S, bool tile, PoolChunk &open, bool chunked) {
+    // pieces of entry e appended to the tables; tile form (S != 0): `open` is the staged chunk being filled
+    auto append = [&](const RawEntry &e, uint32_t xl, uint64_t S, ExChunkT &open) {
         size_t k0 = 0;
         do {
             const size_t k1 = std::min(e.terms.size(), k0 + (size_t)POOL_TERM_CAP);
-            if (chunked && ((int)C.terms.size() - open.t0 + (int)(k1 - k0) > POOL_TERM_CAP ||
-                            (int)C.entries.size() - open.g0 + 1 > POOL_ENTRY_CAP)) {
-                open.g1 = (int32_t)C.entries.size();
-                open.t1 = (int32_t)C.terms.size();
-                C.chunks.push_back(open);
-                open = {open.g1, open.g1, open.t1, open.t1};
-            }
+            if (S) stage_piece(C.chunks, open, C.entries.size(), C.terms.size(), k1 - k0, POOL_TERM_CAP, POOL_ENTRY_CAP);
             PoolEntry pe = {xl, (int32_t)C.terms.size(), 0, e.slot, 0, 0};
-            for (size_t k = k0; k < k1; ++k) {
-                PoolTerm pt = {};
-                pt.zin = tile ? extract(e.terms[k].z, S) : 0u;
-                pt.zout = tile ? e.terms[k].z & ~S : e.terms[k].z;
-                pt.cr = e.terms[k].cr;
-                pt.ci = e.terms[k].ci;
-                C.terms.push_back(pt);
-            }
+            for (size_t k = k0; k < k1; ++k) C.terms.push_back(tile_term(e.terms[k], S));
             pe.t1 = (int32_t)C.terms.size();
             C.entries.push_back(pe);
             k0 = k1;
@@ -167,88 +117,37 @@ inline void build_cover(Cover &C, const std::vector<RawEntry> &raw, int m, bool 
             g = r;
         }
     };
-    if (m < (real ? POOL_TILE_MIN_REAL : POOL_TILE_MIN_COMPLEX)) {   // classes of equal high x bits, one streaming launch each
+    C.M = chunk_tile_bits(m, real);
+    if (!C.M) {   // classes of equal high x bits, one streaming launch each
         C.small = true;
-        std::vector<int> order(E);
-        for (int e = 0; e < E; ++e) order[e] = e;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return (raw[a].x >> m) < (raw[b].x >> m); });
-        PoolChunk none = {};
-        for (int e : order) {
-            const uint64_t hb = raw[e].x >> m;
-            if (C.class_h.empty() || C.class_h.back() != hb) {
-                C.class_h.push_back(hb);
-                C.class_entries.push_back({(int)C.entries.size(), (int)C.entries.size()});
-            }
-            append(raw[e], (uint32_t)(raw[e].x & lowmask), 0, false, none, false);
-            C.class_entries.back().second = (int)C.entries.size();
+        ExChunkT none = {};
+        for (int e : class_order(raw, m)) {
+            const size_t begin = C.entries.size();
+            append(raw[e], (uint32_t)(raw[e].x & ((1ull << m) - 1ull)), 0, none);
+            class_extend(C.class_h, C.class_entries, raw[e].x >> m, begin, C.entries.size());
         }
         return;
     }
-    const int M = std::min(real ? 13 : 12, m);   // (a real tile holds 2^13 doubles in the same 64 KB; index bit 0 = the pair bit is inside)
-    C.M = M;
-    const uint64_t lowbits = (1ull << std::min(POOL_TILE_LOW, M)) - 1ull;
+    const int E = (int)raw.size();
     std::vector<char> done(E, 0);
     int remaining = E;
-    const double wgt[8] = {1.0, 0.25, 0.0625, 0.015625, 0.00390625, 0.0009765625, 0.000244140625, 0.00006103515625};
     while (remaining > 0) {
-        // the class of high x bits with the most distinct masks left fixes the part of d_out above the chunk
-        std::map<uint64_t, std::map<uint64_t, int>> left;   // class -> distinct x -> entries
+        std::vector<uint64_t> x_left;
         for (int e = 0; e < E; ++e)
-            if (!done[e]) ++left[raw[e].x >> m][raw[e].x];
-        uint64_t hb = 0;
-        size_t best_n = 0;
-        for (const auto &kv : left)
-            if (kv.second.size() > best_n) hb = kv.first, best_n = kv.second.size();
-        const std::map<uint64_t, int> &masks = left[hb];
-        uint64_t S = lowbits;
-        while (__builtin_popcountll(S) < M) {
-            const int room = M - __builtin_popcountll(S);
-            double score[64] = {0.0};
-            bool any = false;
-            for (const auto &kv : masks) {
-                const uint64_t miss = kv.first & lowmask & ~S;
-                const int nm = __builtin_popcountll(miss);
-                if (nm == 0 || nm > room) continue;
-                any = true;
-                for (uint64_t mk = miss; mk; mk &= mk - 1ull) score[__builtin_ctzll(mk)] += wgt[std::min(nm - 1, 7)];
-            }
-            if (!any) break;
-            int best = -1;
-            for (int b = 0; b < m; ++b)
-                if (!((S >> b) & 1ull) && (best < 0 || score[b] > score[best])) best = b;
-            S |= 1ull << best;
-        }
-        for (int b = 0; __builtin_popcountll(S) < M; ++b) S |= 1ull << b;
-        std::map<uint64_t, int> leftovers;   // the displacement below the chunk bits: the most frequent leftover
-        for (const auto &kv : masks) ++leftovers[kv.first & lowmask & ~S];
-        uint64_t dl = 0;
-        int dl_n = -1;
-        for (const auto &kv : leftovers)
-            if (kv.second > dl_n) dl = kv.first, dl_n = kv.second;   // (ascending keys: 0 wins a tie)
-        PoolPass ps = {};
-        ps.smask = real ? S >> 1 : S;
-        uint64_t lo = 0, mk = ps.smask;
-        for (int k = 0; k < POOL_LOG_NT && mk; ++k) {
-            lo |= mk & (0ull - mk);
-            mk &= mk - 1ull;
-        }
-        ps.mask_lo = lo;
-        ps.mask_hi = ps.smask & ~lo;
-        ps.d_out = (hb << m) | dl;
-        ps.a0 = (int32_t)C.chunks.size();
-        PoolChunk open = {(int32_t)C.entries.size(), (int32_t)C.entries.size(), (int32_t)C.terms.size(), (int32_t)C.terms.size()};
+            if (!done[e]) x_left.push_back(raw[e].x);
+        PassPick pk = pick_pass(x_left, m, C.M, real);
+        pk.ps.a0 = (int32_t)C.chunks.size();
+        ExChunkT open = open_chunk(C.entries.size(), C.terms.size());
         for (int e = 0; e < E; ++e) {   // (operator order: the pieces of a slot are consecutive, so runs are as long as they can be)
-            if (done[e] || (raw[e].x >> m) != hb || (raw[e].x & lowmask & ~S) != dl) continue;
+            if (done[e] || (raw[e].x & ~pk.S) != pk.ps.d_out) continue;
             done[e] = 1;
             --remaining;
-            append(raw[e], extract(raw[e].x, S), S, true, open, true);
+            append(raw[e], extract_bits(raw[e].x, pk.S), pk.S, open);
         }
-        open.g1 = (int32_t)C.entries.size();
-        open.t1 = (int32_t)C.terms.size();
-        if (open.g1 > open.g0) C.chunks.push_back(open);
-        ps.a1 = (int32_t)C.chunks.size();
-        for (int ch = ps.a0; ch < ps.a1; ++ch) mark_runs(C.chunks[ch].g0, C.chunks[ch].g1);
-        C.passes.push_back(ps);   // (the most frequent leftover of a non-empty class always takes at least one entry)
+        close_chunk(C.chunks, open, C.entries.size(), C.terms.size());
+        pk.ps.a1 = (int32_t)C.chunks.size();
+        for (int ch = pk.ps.a0; ch < pk.ps.a1; ++ch) mark_runs(C.chunks[ch].g0, C.chunks[ch].g1);
+        C.passes.push_back(pk.ps);   // (the most frequent leftover of a non-empty class always takes at least one entry)
     }
 }
 

@@ -11,6 +11,7 @@
 // The QUCCSD templates of the reference (ref:openvqe/common_files/circuit.py:13-106: ~25 literal gates on 2 or 4
 // qubits) and the 2-/4-qubit x masks of JW excitations are exactly this shape.
 #pragma once
+#include "sv_cover_host.hpp"
 #include "sv_small.hpp"
 #include <type_traits>
 
@@ -372,22 +373,15 @@ __global__ __launch_bounds__(NT) void k_tile_adjoint(amp_t *__restrict__ psi, am
 // excitation become ONE coefficient on 2 of the 8 patterns, XX/YY number-operator families halve — and patterns whose
 // coefficients cancel exactly are never visited.  One wave owns an entry (<= 256 pairs); z bits outside the tile
 // are per-tile signs, folded into the coefficients while a chunk of the term table is staged in LDS.
-constexpr int TILE_TERM_CAP = 512;
-constexpr int TILE_APPLY_GROUPS = 128;  // x-groups of a chunk staged in LDS (operator-application form)
-constexpr int TILE_APPLY_TERMS = 16;    // terms per piece of an x-group in that form
+// (TILE_TERM_CAP, TILE_APPLY_GROUPS, TILE_EXPECT_LOG_NT and the records ExChunkT / ExAGroupT / ExTermT: sv_cover_host.hpp)
+constexpr int TILE_APPLY_TERMS = 16;    // terms per piece of an x-group in the operator-application form
 constexpr int TILE_ENTRY_PAIRS = 256;
-constexpr int TILE_EXPECT_LOG_NT = 9;   // threads per workgroup of k_tile_expect (256 measured faster than 1024)
 
 struct ExSweep {
     uint64_t smask, mask_lo, mask_hi;
     int32_t c0, c1;   // chunk range (entries with more than two merged terms: one wave per entry)
     int32_t i0, i1;   // flat items (entries with one or two merged terms: one LANE per 64 pairs)
     int32_t a0, a1;   // chunk range of the operator-application form (k_tile_apply)
-};
-struct ExAGroupT {    // x-group of the sweep with its raw terms (k_tile_apply)
-    uint32_t x;       // tile-local x mask
-    int32_t t0, t1;   // terms (absolute, in the apply term table)
-    int32_t pad;
 };
 // A (group, pattern) entry with at most two merged terms — nearly all of them: a JW double excitation leaves ONE
 // coefficient per active pattern — costs more in per-entry set-up than in arithmetic when a whole wave serves it.
@@ -405,9 +399,6 @@ struct ExItemT {
     uint32_t istart;  // tile-local index of the item's first pair (pattern bits included)
     uint32_t count;   // pairs (<= TILE_ITEM_PAIRS, even)
     uint32_t pad;
-};
-struct ExChunkT {
-    int32_t g0, g1, t0, t1;  // entries, terms
 };
 struct ExEntryT {
     uint32_t x;       // tile-local x mask (0: diagonal group)
@@ -427,12 +418,6 @@ struct ExEntryT {
 };
 static_assert(sizeof(ExEntryT) == 128, "one entry = two cache lines of scalar loads");
 constexpr int TILE_UNSPLIT_PAIRS = 1024;   // pairs per piece of an unsplit entry (16 rows of a wave: the per-entry set-up amortised)
-struct ExTermT {
-    uint64_t zout;    // z outside the tile
-    uint32_t zin;     // z on the tile bits, x positions cleared
-    uint32_t pad;
-    double cr, ci;    // i^ny and the pattern's sign folded
-};
 struct ExTermLds {
     double cr, ci;
     uint32_t zin, pad;

@@ -2,8 +2,8 @@
 // diagonal group), the compact cover, and the multi-op tile sweeps (kernels: sv_tile.hpp).  Included by ovqe_sv.hip inside its anonymous namespace.
 
 // ---- tiled expectation (sv_tile.hpp) -----------------------------------------------------------------------
-// Greedy cover of the x-groups by tile bit sets: a set starts from the mandatory low bits and grows by the bit that
-// brings the most still-uncovered groups within reach (groups that are nearly inside count more).
+// Greedy cover of the x-groups by tile bit sets: a set starts from the mandatory low bits and grows by grow_tile_set()
+// (sv_cover_host.hpp) over the still-uncovered groups.
 static int achunks_g0(const std::vector<ExChunkT> &a, int a0, const ExChunkT &cur) { return a0 < (int)a.size() ? a[a0].g0 : cur.g0; }
 static int achunks_t0(const std::vector<ExChunkT> &a, int a0, const ExChunkT &cur) { return a0 < (int)a.size() ? a[a0].t0 : cur.t0; }
 
@@ -74,43 +74,20 @@ int build_ham_tiles(ovqe_handle h, HamDev &H, bool real) {
             ++remaining;
         }
     }
-    const double wgt[8] = {1.0, 0.25, 0.0625, 0.015625, 0.00390625, 0.0009765625, 0.000244140625, 0.00006103515625};
     while (remaining > 0) {
-        uint64_t S = lowbits;
-        while (__builtin_popcountll(S) < M) {
-            const int room = M - __builtin_popcountll(S);
-            double score[64] = {0.0};
-            bool any = false;
-            for (int g = 0; g < G; ++g) {
-                if (covered[g]) continue;
-                const uint64_t miss = H.groups[g].x & ~S;
-                const int nm = __builtin_popcountll(miss);
-                if (nm == 0 || nm > room) continue;
-                any = true;
-                for (uint64_t mk = miss; mk; mk &= mk - 1ull) score[__builtin_ctzll(mk)] += wgt[std::min(nm - 1, 7)];
-            }
-            if (!any) break;
-            int best = -1;
-            for (int b = 0; b < h->n_local; ++b)
-                if (!((S >> b) & 1ull) && (best < 0 || score[b] > score[best])) best = b;
-            S |= 1ull << best;
-        }
-        for (int b = 0; __builtin_popcountll(S) < M; ++b) S |= 1ull << b;
+        std::vector<uint64_t> uncovered;
+        for (int g = 0; g < G; ++g)
+            if (!covered[g]) uncovered.push_back(H.groups[g].x);
+        const uint64_t S = grow_tile_set(uncovered, lowbits, M, h->n_local);
         ExSweep sw = {};
         sw.smask = real ? S >> 1 : S;  // real state: masks in the index space of amplitude pairs (sv_tile.hpp)
-        uint64_t lo = 0, mk = sw.smask;
-        for (int k = 0; k < TILE_EXPECT_LOG_NT; ++k) {  // thread bits
-            lo |= mk & (0ull - mk);
-            mk &= mk - 1ull;
-        }
-        sw.mask_lo = lo;
-        sw.mask_hi = sw.smask & ~lo;
+        std::tie(sw.mask_lo, sw.mask_hi) = thread_trip_masks(sw.smask, TILE_EXPECT_LOG_NT);
         sw.c0 = (int32_t)chunks.size();
         sw.i0 = (int32_t)titems.size();
-        ExChunkT ck = {(int32_t)tgroups.size(), (int32_t)tgroups.size(), (int32_t)tterms.size(), (int32_t)tterms.size()};
+        ExChunkT ck = open_chunk(tgroups.size(), tterms.size());
         int took = 0;
         sw.a0 = (int32_t)achunks.size();
-        ExChunkT ak = {(int32_t)agroups.size(), (int32_t)agroups.size(), (int32_t)aterms.size(), (int32_t)aterms.size()};
+        ExChunkT ak = open_chunk(agroups.size(), aterms.size());
         for (int g = 0; g < G; ++g) {
             if (covered[g] || (H.groups[g].x & ~S)) continue;
             covered[g] = 1;
@@ -130,23 +107,9 @@ int build_ham_tiles(ovqe_handle h, HamDev &H, bool real) {
                 // Z strings no longer keeps a single wave busy while the others idle
                 for (size_t k0 = 0; k0 < keep.size(); k0 += TILE_APPLY_TERMS) {
                     const size_t k1 = std::min(keep.size(), k0 + TILE_APPLY_TERMS);
-                    if ((int)aterms.size() - ak.t0 + (int)(k1 - k0) > TILE_TERM_CAP ||
-                        (int)agroups.size() - ak.g0 + 1 > TILE_APPLY_GROUPS) {
-                        ak.g1 = (int32_t)agroups.size();
-                        ak.t1 = (int32_t)aterms.size();
-                        achunks.push_back(ak);
-                        ak = {ak.g1, ak.g1, ak.t1, ak.t1};
-                    }
+                    stage_piece(achunks, ak, agroups.size(), aterms.size(), k1 - k0, TILE_TERM_CAP, TILE_APPLY_GROUPS);
                     ExAGroupT ag = {xl, (int32_t)aterms.size(), 0, 0};
-                    for (size_t k = k0; k < k1; ++k) {
-                        const HTerm &ht = H.terms[keep[k]];
-                        ExTermT et = {};
-                        et.zin = extract_bits(ht.z, S);
-                        et.zout = ht.z & ~S;
-                        et.cr = ht.cr;
-                        et.ci = ht.ci;
-                        aterms.push_back(et);
-                    }
+                    for (size_t k = k0; k < k1; ++k) aterms.push_back(tile_term(H.terms[keep[k]], S));
                     ag.t1 = (int32_t)aterms.size();
                     ag.pad = 1;   // bit 0: every folded coefficient of the piece is real (a real-symmetric H: all of them)
                     for (int32_t t = ag.t0; t < ag.t1; ++t)
@@ -162,23 +125,12 @@ int build_ham_tiles(ovqe_handle h, HamDev &H, bool real) {
             // w = 4: 25 per pair).  Its 2^(M-1) pairs (pivot bit of i clear) are walked in pieces of 512 with the x part of z left in
             // the terms' masks; en.x = the pivot bit alone (what the index walk skips), en.pad = the mask that leads to the partner.
             if (!real && w >= 2 && gr.t1 - gr.t0 <= 2 && M - 1 >= 9) {
-                if ((int)tterms.size() - ck.t0 + (gr.t1 - gr.t0) > TILE_TERM_CAP) {
-                    ck.g1 = (int32_t)tgroups.size();
-                    ck.t1 = (int32_t)tterms.size();
-                    chunks.push_back(ck);
-                    ck = {ck.g1, ck.g1, ck.t1, ck.t1};
-                }
+                stage_piece(chunks, ck, tgroups.size(), tterms.size(), (size_t)(gr.t1 - gr.t0), TILE_TERM_CAP);
                 const int32_t t0 = (int32_t)tterms.size();
                 bool real_only = true;
                 for (int t = gr.t0; t < gr.t1; ++t) {
-                    const HTerm &ht = H.terms[t];
-                    ExTermT et = {};
-                    et.zin = extract_bits(ht.z, S);
-                    et.zout = ht.z & ~S;
-                    et.cr = ht.cr;
-                    et.ci = ht.ci;
-                    if (et.ci != 0.0) real_only = false;
-                    tterms.push_back(et);
+                    if (H.terms[t].ci != 0.0) real_only = false;
+                    tterms.push_back(tile_term(H.terms[t], S));
                 }
                 const int npairs = 1 << (M - 1), piece = std::min(npairs, TILE_UNSPLIT_PAIRS);
                 for (int k0 = 0; k0 < npairs; k0 += piece) {
@@ -258,12 +210,7 @@ int build_ham_tiles(ovqe_handle h, HamDev &H, bool real) {
                 }
                 for (size_t m0 = 0; m0 < mt.size(); m0 += TILE_TERM_CAP) {  // oversized lists are split (linear)
                     const size_t m1 = std::min(mt.size(), m0 + TILE_TERM_CAP);
-                    if ((int)tterms.size() - ck.t0 + (int)(m1 - m0) > TILE_TERM_CAP) {
-                        ck.g1 = (int32_t)tgroups.size();
-                        ck.t1 = (int32_t)tterms.size();
-                        chunks.push_back(ck);
-                        ck = {ck.g1, ck.g1, ck.t1, ck.t1};
-                    }
+                    stage_piece(chunks, ck, tgroups.size(), tterms.size(), m1 - m0, TILE_TERM_CAP);
                     const int32_t t0 = (int32_t)tterms.size();
                     tterms.insert(tterms.end(), mt.begin() + m0, mt.begin() + m1);
                     for (int k0 = 0; k0 < nk_total; k0 += TILE_ENTRY_PAIRS) {
@@ -281,14 +228,10 @@ int build_ham_tiles(ovqe_handle h, HamDev &H, bool real) {
                 }
             }
         }
-        ck.g1 = (int32_t)tgroups.size();
-        ck.t1 = (int32_t)tterms.size();
-        if (ck.g1 > ck.g0) chunks.push_back(ck);
+        close_chunk(chunks, ck, tgroups.size(), tterms.size());
         sw.c1 = (int32_t)chunks.size();
         sw.i1 = (int32_t)titems.size();
-        ak.g1 = (int32_t)agroups.size();
-        ak.t1 = (int32_t)aterms.size();
-        if (ak.g1 > ak.g0) achunks.push_back(ak);
+        close_chunk(achunks, ak, agroups.size(), aterms.size());
         sw.a1 = (int32_t)achunks.size();
         if (took == 0) return fail(h, OVQE_ERR_INVALID, "internal: tile cover made no progress");
         if (std::getenv("OVQE_DEBUG_COVER"))

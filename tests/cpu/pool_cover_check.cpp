@@ -6,7 +6,7 @@
 // term-by-term definition to 1e-12 max(1, |c_k|_1), for the complex and the real flavour.  Conditions on the tables: every
 // (operator, x) entry lies in exactly one pass, passes per rank difference <= its distinct x masks, the staged chunks respect the
 // caps, the partial storage depends on the operator count alone.
-//   usage: pool_cover_check <cases> <seed>
+//   usage: pool_cover_check <cases> <seed> [hash]      (hash: also print one 64-bit hash over every table built)
 #include "../../openvqe_amd/csrc/sv_pool_host.hpp"
 
 #include <cmath>
@@ -16,6 +16,7 @@
 #include <random>
 #include <set>
 
+using namespace ovqe;
 using namespace ovqe::pool;
 typedef std::complex<double> cplx;
 
@@ -28,6 +29,22 @@ static int failures = 0;
             if (++failures > 20) std::exit(1); \
         }                                     \
     } while (0)
+
+static uint64_t table_hash = 1469598103934665603ull;   // FNV-1a over the bytes of every table
+static void hash_bytes(const void *p, size_t n) {
+    for (size_t k = 0; k < n; ++k) table_hash = (table_hash ^ ((const unsigned char *)p)[k]) * 1099511628211ull;
+}
+template <class T>
+static void hash_vec(const std::vector<T> &v) {   // (every record is free of implicit padding and value-initialised)
+    const uint64_t n = v.size();
+    hash_bytes(&n, sizeof n);
+    if (n) hash_bytes(v.data(), n * sizeof(T));
+}
+static void hash_cover(const Cover &C) {
+    const int64_t head[8] = {(int64_t)C.d, C.m, C.small ? 1 : 0, C.M, C.n_entries, C.n_x, C.n_terms, 0};
+    hash_bytes(head, sizeof head);
+    hash_vec(C.passes), hash_vec(C.chunks), hash_vec(C.entries), hash_vec(C.terms), hash_vec(C.class_h), hash_vec(C.class_entries);
+}
 
 static uint64_t spread(uint64_t v, uint64_t mask) {   // pdep
     uint64_t r = 0;
@@ -72,6 +89,7 @@ static void replay_rank(int nl, int g, uint64_t rank, const std::map<uint64_t, s
         C.d = d;
         const int m = d ? chunk_bits : nl;
         build_cover(C, kv.second, m, REAL);
+        hash_cover(C);
         const uint64_t csize = 1ull << m;
         // --- conditions on the tables
         std::set<uint64_t> xs;
@@ -88,14 +106,14 @@ static void replay_rank(int nl, int g, uint64_t rank, const std::map<uint64_t, s
         } else {
             CHECK(C.M == std::min(REAL ? 13 : 12, m), "tile bits");
             for (size_t pi = 0; pi < C.passes.size(); ++pi) {
-                const PoolPass &ps = C.passes[pi];
+                const auto &ps = C.passes[pi];
                 const uint64_t S = REAL ? (ps.smask << 1) | 1ull : ps.smask;
                 CHECK(__builtin_popcountll(S) == C.M && !(S >> m) && !(ps.d_out & S) && (ps.mask_lo | ps.mask_hi) == ps.smask &&
-                          !(ps.mask_lo & ps.mask_hi) && __builtin_popcountll(ps.mask_lo) == std::min(POOL_LOG_NT, __builtin_popcountll(ps.smask)),
+                          !(ps.mask_lo & ps.mask_hi) && __builtin_popcountll(ps.mask_lo) == std::min(TILE_EXPECT_LOG_NT, __builtin_popcountll(ps.smask)),
                       "pass masks");
                 CHECK(ps.a1 > ps.a0, "empty pass");
                 for (int ch = ps.a0; ch < ps.a1; ++ch) {
-                    const PoolChunk &ck = C.chunks[ch];
+                    const auto &ck = C.chunks[ch];
                     CHECK(ck.g1 - ck.g0 >= 1 && ck.g1 - ck.g0 <= POOL_ENTRY_CAP && ck.t1 - ck.t0 <= POOL_TERM_CAP, "chunk caps");
                     int covered = 0;
                     for (int e = ck.g0; e < ck.g1; ++e) {
@@ -140,7 +158,7 @@ static void replay_rank(int nl, int g, uint64_t rank, const std::map<uint64_t, s
             }
             const uint64_t ntiles = csize >> C.M;
             const uint64_t grid = std::min<uint64_t>(ntiles, POOL_ROWS);
-            for (const PoolPass &ps : C.passes) {
+            for (const auto &ps : C.passes) {
                 const uint64_t S = REAL ? (ps.smask << 1) | 1ull : ps.smask;
                 for (uint64_t tl = 0; tl < ntiles; ++tl) {
                     uint64_t tb = tile_base(tl, ps.smask);   // (REAL: pair-index space)
@@ -151,7 +169,7 @@ static void replay_rank(int nl, int g, uint64_t rank, const std::map<uint64_t, s
                     CHECK(ob < shard && !(ob & S), "bra tile beyond the shard");
                     cplx *row = &rows[(tl % grid) * std::max<int64_t>(n_ops, 1)];
                     for (int ch = ps.a0; ch < ps.a1; ++ch) {
-                        const PoolChunk &ck = C.chunks[ch];
+                        const auto &ck = C.chunks[ch];
                         for (int e = ck.g0; e < ck.g1; ++e) {
                             const PoolEntry &en = C.entries[e];
                             CHECK(en.x < (1u << C.M), "tile-local x");
@@ -269,5 +287,6 @@ int main(int argc, char **argv) {
     }
     if (failures) return 1;
     std::printf("pool cover ok: %d cases, %d tiled covers, %d streamed, %d with several passes\n", cases, tiled, streamed, multi_pass);
+    if (argc > 3) std::printf("hash %016llx\n", (unsigned long long)table_hash);
     return (tiled && streamed && multi_pass) ? 0 : 1;
 }
