@@ -1,87 +1,116 @@
 // abi_solvers.inc — C-ABI entry points: device Lanczos (whole register and sector tables) and the adjoint gradient.
 // Included by ovqe_sv.hip inside extern "C".
 
-// ---- ground state of the stored Hamiltonian: Lanczos on the device -------------------------------------------
+// ---- vector operations of the Lanczos recurrence ----------------------------------------------------------------------------------
+// One launcher each, for RegisterSpace below, the ovqe_vec_* entry points and the <H> of ovqe_energy_gradient.  Operands are device
+// buffers read as `nel` double2 elements; the reductions need d_partials for reduce_blocks(nel) sums and d_result (vec_reduce_prepare).
 namespace {
 
-// lowest eigenpair of the symmetric tridiagonal matrix (a[0..m), b[0..m-1)): bisection on the Sturm count, then
-// inverse iteration with a shift just below the eigenvalue (T - mu is positive definite: LDL^T without pivoting)
-void tridiag_lowest(const std::vector<double> &a, const std::vector<double> &b, int m, double *lam,
-                    std::vector<double> &s) {
-    double lo = 1e300, hi = -1e300;
-    for (int i = 0; i < m; ++i) {
-        const double r = (i > 0 ? std::fabs(b[i - 1]) : 0.0) + (i < m - 1 ? std::fabs(b[i]) : 0.0);
-        lo = std::min(lo, a[i] - r);
-        hi = std::max(hi, a[i] + r);
-    }
-    const double scale = std::max({std::fabs(lo), std::fabs(hi), 1e-300});
-    auto below = [&](double x) {  // number of eigenvalues < x
-        int c = 0;
-        double d = 1.0;
-        for (int i = 0; i < m; ++i) {
-            d = a[i] - x - (i > 0 ? b[i - 1] * b[i - 1] / d : 0.0);
-            if (std::fabs(d) < 1e-300) d = -1e-300;
-            if (d < 0.0) ++c;
-        }
-        return c;
-    };
-    for (int it = 0; it < 300 && hi - lo > 4e-16 * scale; ++it) {
-        const double mid = 0.5 * (lo + hi);
-        if (below(mid) >= 1) hi = mid; else lo = mid;
-    }
-    *lam = 0.5 * (lo + hi);
-    const double mu = *lam - 1e-9 * scale;
-    std::vector<double> d(m), l(std::max(m - 1, 0));
-    d[0] = a[0] - mu;
-    for (int i = 0; i + 1 < m; ++i) {
-        l[i] = b[i] / d[i];
-        d[i + 1] = a[i + 1] - mu - l[i] * b[i];
-    }
-    s.assign(m, 1.0 / std::sqrt((double)m));
-    for (int it = 0; it < 6; ++it) {
-        for (int i = 1; i < m; ++i) s[i] -= l[i - 1] * s[i - 1];
-        for (int i = 0; i < m; ++i) s[i] /= d[i];
-        for (int i = m - 2; i >= 0; --i) s[i] -= l[i] * s[i + 1];
-        double nrm = 0.0;
-        for (int i = 0; i < m; ++i) nrm += s[i] * s[i];
-        nrm = 1.0 / std::sqrt(nrm);
-        for (int i = 0; i < m; ++i) s[i] *= nrm;
-    }
+inline uint64_t vec_elements(ovqe_handle h) { return h->opt_real_state ? std::max<uint64_t>(h->namps >> 1, 1) : h->namps; }
+int vec_reduce_prepare(ovqe_handle h, int nb) {
+    int rc = ensure(h, h->d_partials, (size_t)nb * sizeof(double2));
+    if (!rc) rc = ensure(h, h->d_result, 64 * sizeof(double2));
+    return rc;
+}
+int vec_dot(ovqe_handle h, const amp_t *a, const amp_t *b, uint64_t nel, double2 *out) {
+    const int nb = reduce_blocks(nel);
+    hipLaunchKernelGGL(k_dot, dim3(nb), dim3(256), 0, h->stream, a, b, nel, (double2 *)h->d_partials.p);
+    return reduce_to_host(h, h->d_partials.p, nb, out);
+}
+// w -= alpha v + beta vprev (vprev may be null);  *norm2 = |w|^2
+int vec_update(ovqe_handle h, amp_t *w, const amp_t *v, const amp_t *vprev, double alpha, double beta, uint64_t nel, double *norm2) {
+    const int nb = reduce_blocks(nel);
+    hipLaunchKernelGGL(k_lanczos_update, dim3(nb), dim3(256), 0, h->stream, w, v, vprev, alpha, beta, nel, (double2 *)h->d_partials.p);
+    return reduce_to_host(h, h->d_partials.p, nb, norm2);
+}
+int vec_scale(ovqe_handle h, amp_t *v, uint64_t nel, double s) {
+    hipLaunchKernelGGL(k_scale, dim3(reduce_blocks(nel)), dim3(256), 0, h->stream, v, nel, s);
+    HIPC(h, hipGetLastError());
+    return OVQE_OK;
+}
+int vec_axpy(ovqe_handle h, amp_t *y, const amp_t *x, double s, uint64_t nel, bool overwrite) {
+    hipLaunchKernelGGL(k_axpy_real, dim3(reduce_blocks(nel)), dim3(256), 0, h->stream, y, x, s, nel, overwrite ? 1 : 0);
+    HIPC(h, hipGetLastError());
+    return OVQE_OK;
+}
+// the seeded fill of a whole register (complex amplitudes), normalised
+int vec_start(ovqe_handle h, amp_t *v, uint64_t seed) {
+    const int nb = reduce_blocks(h->namps);
+    hipLaunchKernelGGL(k_randomize, dim3(nb), dim3(256), 0, h->stream, v, h->namps, h->base, seed, 1.0, (double2 *)h->d_partials.p);
+    double n2 = 0.0;
+    if (int rc = reduce_to_host(h, h->d_partials.p, nb, &n2)) return rc;
+    return vec_scale(h, v, h->namps, 1.0 / std::sqrt(n2));
 }
 
-struct Lanczos {
+// ---- ground state of the stored Hamiltonian: Lanczos on the device -------------------------------------------
+// The whole register as a Lanczos space (sv_lanczos_host.hpp): work vectors scratch[0], scratch[1] and `tmp`, the Ritz vector in h->state.
+// One pass while the Lanczos vectors fit in HBM (24 qubits: 256 MiB each, 150 of them = 40 GB of the 288): v_0..v_j stay
+// where they were written and the Ritz vector is their combination.  Beyond the budget ("lanczos_keep_gb", and never more
+// than 60 % of the free memory) the kept vectors are dropped and the recurrence is run a second time for the Ritz vector.
+struct RegisterSpace {
+    typedef amp_t *Vec;
     ovqe_handle h;
-    int nb;
-    int reduce_to_host(double2 *out) {
-        hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, h->stream, (const double2 *)h->d_partials.p, (int64_t)nb,
-                           (double2 *)h->d_result.p, 0);
-        HIPC(h, hipGetLastError());
-        HIPC(h, hipMemcpyAsync(h->h_result, h->d_result.p, sizeof(double2), hipMemcpyDeviceToHost, h->stream));
-        HIPC(h, hipStreamSynchronize(h->stream));
-        *out = h->h_result[0];
-        return OVQE_OK;
+    amp_t *tmp;
+    uint64_t seed;
+    const size_t vec_bytes = h->namps * sizeof(amp_t);
+    size_t keep_budget = 0;
+    bool keeping = false;
+    std::vector<amp_t *> kept;
+    RegisterSpace(ovqe_handle h, amp_t *tmp, uint64_t seed) : h(h), tmp(tmp), seed(seed) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+            keep_budget = std::min<size_t>((size_t)std::max(h->opt_lanczos_keep_gb, 0) << 30, free_b / 5 * 3);
+        keeping = keep_budget >= 8 * vec_bytes;
     }
-    int apply_h(amp_t *out, const amp_t *in) { return apply_hamiltonian(h, out, in, 0.0); }
-    int dot(const amp_t *a, const amp_t *b, double2 *out) {
-        hipLaunchKernelGGL(k_dot, dim3(nb), dim3(256), 0, h->stream, a, b, h->namps, (double2 *)h->d_partials.p);
-        return reduce_to_host(out);
-    }
-    int update(amp_t *w, const amp_t *v, const amp_t *vprev, double alpha, double beta, double *norm) {
-        hipLaunchKernelGGL(k_lanczos_update, dim3(nb), dim3(256), 0, h->stream, w, v, vprev, alpha, beta, h->namps,
-                           (double2 *)h->d_partials.p);
-        double2 r;
-        int rc = reduce_to_host(&r);
-        *norm = std::sqrt(r.x);
+    Vec work(int i) const { return i == 2 ? tmp : h->scratch[i]; }
+    Vec ritz() const { return h->state; }
+    int start(Vec v) { return vec_start(h, v, seed); }
+    int apply(Vec out, Vec in) { return apply_hamiltonian(h, out, in, 0.0); }
+    int dot(Vec a, Vec b, double *re) {
+        double2 d = make_double2(0.0, 0.0);
+        const int rc = vec_dot(h, a, b, h->namps, &d);
+        *re = d.x;
         return rc;
     }
-    int start(amp_t *v, uint64_t seed) {
-        hipLaunchKernelGGL(k_randomize, dim3(nb), dim3(256), 0, h->stream, v, h->namps, h->base, seed, 1.0,
-                           (double2 *)h->d_partials.p);
-        double2 r;
-        int rc = reduce_to_host(&r);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_scale, dim3(nb), dim3(256), 0, h->stream, v, h->namps, 1.0 / std::sqrt(r.x));
+    int update(Vec w, Vec v, Vec vprev, double alpha, double beta, double *norm2) {
+        return vec_update(h, w, v, vprev, alpha, beta, h->namps, norm2);
+    }
+    int scale(Vec v, double a) { return vec_scale(h, v, h->namps, a); }
+    int axpy(Vec y, Vec x, double a, bool first) { return vec_axpy(h, y, x, a, h->namps, first); }
+    void drop_kept() {
+        for (amp_t *v : kept) (void)hipFree(v);
+        kept.clear();
+        keeping = false;
+    }
+    int keep(Vec vj) {
+        if (!keeping) return OVQE_OK;
+        // v_j has served as v_{j-1}'s successor: a copy stays in `kept` from here on, as long as the budget lasts — a device-to-device
+        // copy at HBM rate (0.1 ms at 24 qubits) next to a 40 ms H psi.  The first vector that cannot be kept drops them all.
+        amp_t *fresh = nullptr;
+        if ((kept.size() + 1) * vec_bytes <= keep_budget && hipMalloc((void **)&fresh, vec_bytes) == hipSuccess &&
+            hipMemcpyAsync(fresh, vj, vec_bytes, hipMemcpyDeviceToDevice, h->stream) == hipSuccess) {
+            kept.push_back(fresh);
+            return OVQE_OK;
+        }
+        (void)hipGetLastError();
+        if (fresh) (void)hipFree(fresh);
+        drop_kept();
         return OVQE_OK;
+    }
+    int ritz_from_kept(const std::vector<double> &s, int m, bool *done) {
+        *done = keeping && (int)kept.size() == m - 1;
+        if (!*done) return OVQE_OK;   // (then nothing is held: keep() drops all or none)
+        // kept = v_0..v_{m-2}; v_{m-1} is the vector the last step multiplied, still in its work buffer: scratch[(m-1) % 3 ...]
+        // (the rotation A <- B <- C <- A moves one buffer per step, starting from B = scratch[1])
+        amp_t *ring[3] = {h->scratch[1], tmp, h->scratch[0]};
+        for (int j = 0; j < m; ++j)
+            if (int rc = axpy(h->state, j < m - 1 ? kept[j] : ring[(m - 1) % 3], s[j], j == 0)) return rc;
+        return OVQE_OK;
+    }
+    int release_kept() {
+        const bool synced = hipStreamSynchronize(h->stream) == hipSuccess;
+        drop_kept();
+        return synced ? OVQE_OK : fail(h, OVQE_ERR_HIP, "ground_state: sync failed");
     }
 };
 
@@ -95,164 +124,35 @@ extern "C" int ovqe_ground_state(ovqe_handle h, double tol, int max_iter, uint64
     if (h->n_global) return fail(h, OVQE_ERR_INVALID, "ovqe_ground_state is single-device");
     int rc = ensure_scratch(h, 0);
     if (!rc) rc = ensure_scratch(h, 1);
-    Lanczos L{h, reduce_blocks(h->namps)};
-    if (!rc) rc = ensure(h, h->d_partials, (size_t)L.nb * sizeof(double2));
-    if (!rc) rc = ensure(h, h->d_result, 64 * sizeof(double2));
+    if (!rc) rc = vec_reduce_prepare(h, reduce_blocks(h->namps));
     if (rc) return rc;
     max_iter = (int)std::min<uint64_t>((uint64_t)max_iter, h->namps);
     amp_t *tmp = nullptr;
     if (hipMalloc((void **)&tmp, h->namps * sizeof(amp_t)) != hipSuccess) return fail(h, OVQE_ERR_ALLOC, "hipMalloc Lanczos vector");
-    std::vector<double> alpha, beta, s;
-    double lam = 0.0, est = 0.0;
-    int m = 0;
-    // One pass while the Lanczos vectors fit in HBM (24 qubits: 256 MiB each, 150 of them = 40 GB of the 288): v_0..v_j stay
-    // where they were written and the Ritz vector is their combination.  Beyond the budget ("lanczos_keep_gb", and never more
-    // than 60 % of the free memory) the kept vectors are dropped and the recurrence is run a second time for the Ritz vector.
-    std::vector<amp_t *> kept;
-    size_t keep_budget = 0;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-            keep_budget = std::min<size_t>((size_t)std::max(h->opt_lanczos_keep_gb, 0) << 30, free_b / 5 * 3);
-    }
-    const size_t vec_bytes = h->namps * sizeof(amp_t);
-    bool keeping = keep_budget >= 8 * vec_bytes;
-    auto drop_kept = [&]() {
-        for (amp_t *v : kept) (void)hipFree(v);
-        kept.clear();
-        keeping = false;
-    };
-    auto recurrence = [&](bool accumulate) -> int {
-        amp_t *A = h->scratch[0], *B = h->scratch[1], *C = tmp;  // v_{j-1}, v_j, w
-        int r = L.start(B, seed);
-        if (r) return r;
-        if (accumulate)
-            hipLaunchKernelGGL(k_axpy_real, dim3(L.nb), dim3(256), 0, h->stream, h->state, (const amp_t *)B, s[0], h->namps, 1);
-        const int steps = accumulate ? m - 1 : max_iter;
-        for (int j = 0; j < steps; ++j) {
-            r = L.apply_h(C, B);
-            if (r) return r;
-            double bj;
-            if (accumulate) {
-                r = L.update(C, B, j ? A : nullptr, alpha[j], j ? beta[j - 1] : 0.0, &bj);
-                if (r) return r;
-                bj = beta[j];
-            } else {
-                double2 d;
-                r = L.dot(B, C, &d);
-                if (r) return r;
-                alpha.push_back(d.x);
-                r = L.update(C, B, j ? A : nullptr, d.x, j ? beta[j - 1] : 0.0, &bj);
-                if (r) return r;
-                m = j + 1;
-                const bool last = j + 1 == steps || bj < 1e-13 * std::max(1.0, std::fabs(d.x));
-                if (last || (j >= 4 && j % 5 == 4)) {
-                    tridiag_lowest(alpha, beta, m, &lam, s);
-                    est = std::fabs(bj * s[m - 1]);
-                    if (last || est < tol * std::max(1.0, std::fabs(lam))) return OVQE_OK;
-                }
-                beta.push_back(bj);
-            }
-            hipLaunchKernelGGL(k_scale, dim3(L.nb), dim3(256), 0, h->stream, C, h->namps, 1.0 / bj);
-            if (!accumulate && keeping) {
-                // v_j (B) has served as v_{j-1}'s successor: it stays in `kept` from here on; the three working buffers are
-                // re-filled from fresh allocations as long as the budget lasts.  A (v_{j-1}) is already kept or is a work buffer.
-                amp_t *fresh = nullptr;
-                if ((kept.size() + 1) * vec_bytes <= keep_budget && hipMalloc((void **)&fresh, vec_bytes) == hipSuccess) {
-                    // keep a copy of v_j: device-to-device copy at HBM rate (0.1 ms at 24 qubits) next to a 40 ms H psi
-                    if (hipMemcpyAsync(fresh, B, vec_bytes, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) {
-                        (void)hipFree(fresh);
-                        drop_kept();
-                    } else {
-                        kept.push_back(fresh);
-                    }
-                } else {
-                    (void)hipGetLastError();
-                    drop_kept();
-                }
-            }
-            amp_t *t = A;
-            A = B;
-            B = C;
-            C = t;
-            if (accumulate)
-                hipLaunchKernelGGL(k_axpy_real, dim3(L.nb), dim3(256), 0, h->stream, h->state, (const amp_t *)B, s[j + 1],
-                                   h->namps, 0);
-        }
-        return OVQE_OK;
-    };
-    rc = recurrence(false);       // pass 1: the tridiagonal matrix
-    if (!rc && keeping && (int)kept.size() == m - 1) {
-        // kept = v_0..v_{m-2}; v_{m-1} is the vector the last step multiplied, still in its work buffer: scratch[(m-1) % 3 ...]
-        // (the rotation A <- B <- C <- A moves one buffer per step, starting from B = scratch[1])
-        amp_t *ring[3] = {h->scratch[1], tmp, h->scratch[0]};
-        const amp_t *vlast = ring[(m - 1) % 3];
-        for (int j = 0; j < m; ++j)
-            hipLaunchKernelGGL(k_axpy_real, dim3(L.nb), dim3(256), 0, h->stream, h->state, j < m - 1 ? (const amp_t *)kept[j] : vlast,
-                               s[j], h->namps, j == 0 ? 1 : 0);
-        if (hipGetLastError() != hipSuccess) rc = fail(h, OVQE_ERR_HIP, "ground_state: launch failed");
-    } else if (!rc) {
-        drop_kept();
-        rc = recurrence(true);  // pass 2: the Ritz vector, same recurrence
-    }
-    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(h, OVQE_ERR_HIP, "ground_state: sync failed");
-    drop_kept();
-    double true_res = 0.0;
-    if (!rc) {
-        // normalise, Rayleigh quotient and true residual |H y - lambda y|
-        double2 d;
-        rc = L.dot(h->state, h->state, &d);
-        if (!rc) {
-            hipLaunchKernelGGL(k_scale, dim3(L.nb), dim3(256), 0, h->stream, h->state, h->namps, 1.0 / std::sqrt(d.x));
-            rc = L.apply_h(tmp, h->state);
-            if (!rc) rc = L.dot(h->state, tmp, &d);
-        }
-        if (!rc) {
-            lam = d.x;
-            rc = L.update(tmp, h->state, nullptr, lam, 0.0, &true_res);
-        }
-    }
+    RegisterSpace V(h, tmp, seed);
+    LanczosResult res;
+    rc = lanczos_lowest(V, tol, max_iter, res);
     if (!rc && hipGetLastError() != hipSuccess) rc = fail(h, OVQE_ERR_HIP, "ground_state: launch failed");
     (void)hipFree(tmp);
     if (rc) return rc;
-    *energy = lam + h->ham.constant;
-    if (residual) *residual = true_res;
-    if (iterations) *iterations = m;
-    (void)est;
+    *energy = res.lam + h->ham.constant;
+    if (residual) *residual = res.residual;
+    if (iterations) *iterations = res.m;
     return OVQE_OK;
 } OVQE_CATCH(h)
 
 // ---- Lanczos vector operations on caller-held shard buffers ----------------------------------------------------------------------
-// What struct Lanczos does inside ovqe_ground_state, for a host layer that runs the recurrence over a partitioned register
+// What RegisterSpace does inside ovqe_ground_state, for a host layer that runs the recurrence over a partitioned register
 // (openvqe_amd/distributed.py: ShardedStatevector.ground_state).  Operands are device buffers of the handle's storage: 2^n_local
 // amp_t, or 2^n_local doubles under "real_state" — the kernels read a buffer as double2 elements, and a real buffer is half as many
 // elements with the same sums.  Every value returned is the partial of THIS shard: the caller reduces over the ranks.
-namespace {
-inline uint64_t vec_elements(ovqe_handle h) { return h->opt_real_state ? std::max<uint64_t>(h->namps >> 1, 1) : h->namps; }
-int vec_reduce_prepare(ovqe_handle h, int nb) {
-    int rc = ensure(h, h->d_partials, (size_t)nb * sizeof(double2));
-    if (!rc) rc = ensure(h, h->d_result, 64 * sizeof(double2));
-    return rc;
-}
-int vec_reduce_to_host(ovqe_handle h, int nb, double2 *out) {
-    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, h->stream, (const double2 *)h->d_partials.p, (int64_t)nb, (double2 *)h->d_result.p, 0);
-    HIPC(h, hipGetLastError());
-    HIPC(h, hipMemcpyAsync(h->h_result, h->d_result.p, sizeof(double2), hipMemcpyDeviceToHost, h->stream));
-    HIPC(h, hipStreamSynchronize(h->stream));
-    *out = h->h_result[0];
-    return OVQE_OK;
-}
-}  // namespace
-
 extern "C" int ovqe_vec_dot(ovqe_handle h, const void *a_dev, const void *b_dev, double *out_re_im) try {
     OVQE_ENTER(h);
     if (!h || !a_dev || !b_dev || !out_re_im) return OVQE_ERR_INVALID;
     const uint64_t nel = vec_elements(h);
-    const int nb = reduce_blocks(nel);
-    if (int rc = vec_reduce_prepare(h, nb)) return rc;
-    hipLaunchKernelGGL(k_dot, dim3(nb), dim3(256), 0, h->stream, (const amp_t *)a_dev, (const amp_t *)b_dev, nel, (double2 *)h->d_partials.p);
+    if (int rc = vec_reduce_prepare(h, reduce_blocks(nel))) return rc;
     double2 r;
-    if (int rc = vec_reduce_to_host(h, nb, &r)) return rc;
+    if (int rc = vec_dot(h, (const amp_t *)a_dev, (const amp_t *)b_dev, nel, &r)) return rc;
     out_re_im[0] = r.x;
     out_re_im[1] = h->opt_real_state ? 0.0 : r.y;   // (the y sum of doubles read as pairs means nothing)
     return OVQE_OK;
@@ -264,32 +164,20 @@ extern "C" int ovqe_vec_lanczos_update(ovqe_handle h, void *w_dev, const void *v
     if (!h || !w_dev || !v_dev || !norm2_out) return OVQE_ERR_INVALID;
     if (w_dev == v_dev || w_dev == vprev_dev) return fail(h, OVQE_ERR_INVALID, "ovqe_vec_lanczos_update: w must differ from v and v_prev");
     const uint64_t nel = vec_elements(h);
-    const int nb = reduce_blocks(nel);
-    if (int rc = vec_reduce_prepare(h, nb)) return rc;
-    hipLaunchKernelGGL(k_lanczos_update, dim3(nb), dim3(256), 0, h->stream, (amp_t *)w_dev, (const amp_t *)v_dev, (const amp_t *)vprev_dev, alpha, beta,
-                       nel, (double2 *)h->d_partials.p);
-    double2 r;
-    if (int rc = vec_reduce_to_host(h, nb, &r)) return rc;
-    *norm2_out = r.x;
-    return OVQE_OK;
+    if (int rc = vec_reduce_prepare(h, reduce_blocks(nel))) return rc;
+    return vec_update(h, (amp_t *)w_dev, (const amp_t *)v_dev, (const amp_t *)vprev_dev, alpha, beta, nel, norm2_out);
 } OVQE_CATCH(h)
 
 extern "C" int ovqe_vec_scale(ovqe_handle h, void *v_dev, double s) try {
     OVQE_ENTER(h);
     if (!h || !v_dev) return OVQE_ERR_INVALID;
-    const uint64_t nel = vec_elements(h);
-    hipLaunchKernelGGL(k_scale, dim3(reduce_blocks(nel)), dim3(256), 0, h->stream, (amp_t *)v_dev, nel, s);
-    HIPC(h, hipGetLastError());
-    return OVQE_OK;
+    return vec_scale(h, (amp_t *)v_dev, vec_elements(h), s);
 } OVQE_CATCH(h)
 
 extern "C" int ovqe_vec_axpy(ovqe_handle h, void *y_dev, const void *x_dev, double s, int overwrite) try {
     OVQE_ENTER(h);
     if (!h || !y_dev || !x_dev) return OVQE_ERR_INVALID;
-    const uint64_t nel = vec_elements(h);
-    hipLaunchKernelGGL(k_axpy_real, dim3(reduce_blocks(nel)), dim3(256), 0, h->stream, (amp_t *)y_dev, (const amp_t *)x_dev, s, nel, overwrite ? 1 : 0);
-    HIPC(h, hipGetLastError());
-    return OVQE_OK;
+    return vec_axpy(h, (amp_t *)y_dev, (const amp_t *)x_dev, s, vec_elements(h), overwrite != 0);
 } OVQE_CATCH(h)
 
 // ---- lowest eigenpair inside the support of the stored program (sector tables) ------------------------------------
@@ -399,11 +287,10 @@ extern "C" int ovqe_energy_gradient(ovqe_handle h, const double *theta, int32_t 
     }
     rc = run_program_streaming(h, theta);  // psi = U(theta)|hf>; angle table: original rotations at offset S
     if (!rc) rc = ensure_scratch(h, 0);
-    Lanczos L{h, reduce_blocks(h->namps)};
     // backward sweeps: one pair per thread while that stays below 65536 workgroups (a grid-stride loop of dependent
     // load -> rotate -> store trips exposes the memory latency of both states), partial sums per workgroup and rotation
     const int nb = (int)std::min<uint64_t>(65536, std::max<uint64_t>(1, (h->namps / 2 + 255) / 256));
-    if (!rc) rc = ensure(h, h->d_partials, (size_t)std::max(L.nb, ADJ_MAX_ROT * nb) * sizeof(double2));
+    if (!rc) rc = ensure(h, h->d_partials, (size_t)std::max(reduce_blocks(h->namps), ADJ_MAX_ROT * nb) * sizeof(double2));
     if (!rc) rc = ensure(h, h->d_result, 64 * sizeof(double2));
     const size_t R = h->rots.size(), S = h->srots.size();
     DevBuf d_w;
@@ -411,8 +298,8 @@ extern "C" int ovqe_energy_gradient(ovqe_handle h, const double *theta, int32_t 
     if (rc) return rc;
     amp_t *lam = h->scratch[0];
     double2 e = make_double2(0.0, 0.0);
-    rc = L.apply_h(lam, h->state);
-    if (!rc) rc = L.dot(h->state, lam, &e);
+    rc = apply_hamiltonian(h, lam, h->state, 0.0);
+    if (!rc) rc = vec_dot(h, h->state, lam, h->namps, &e);
     const RotParam *d_rp = (const RotParam *)h->d_rp.p + S;
     double *partials = (double *)h->d_partials.p;
     for (int oi = (int)h->ops.size() - 1; oi >= 0 && !rc; --oi) {

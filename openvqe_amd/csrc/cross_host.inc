@@ -327,11 +327,7 @@ int ovqe_xsum_expect_local(ovqe_handle h, int32_t id, double *out) try {
         if (rc) return rc;
         hipLaunchKernelGGL(k_expect_pairs_real, dim3(nb), dim3(256), 0, h->stream, (const double *)h->state, h->namps, (const HGroup *)H.d_groups.p, 0,
                            (int)H.groups.size(), (const HTerm *)H.d_terms.p, (double2 *)h->d_partials.p);
-        hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, h->stream, (const double2 *)h->d_partials.p, (int64_t)nb, (double2 *)h->d_result.p, 0);
-        HIPC(h, hipGetLastError());
-        HIPC(h, hipMemcpyAsync(h->h_result, h->d_result.p, sizeof(double2), hipMemcpyDeviceToHost, h->stream));
-        HIPC(h, hipStreamSynchronize(h->stream));
-        res = h->h_result[0];
+        rc = reduce_to_host(h, h->d_partials.p, nb, &res);
     } else if (!rc && !tiled) {
         rc = run_bilinear(h, h->state, h->state, H.groups, (const HGroup *)H.d_groups.p, (const HTerm *)H.d_terms.p, &res, true);
     }

@@ -42,6 +42,7 @@
 #include "sv_cross_host.hpp"
 #include "sv_pool.hpp"
 #include "sv_frame_host.hpp"
+#include "sv_lanczos_host.hpp"
 #include <hipcub/hipcub.hpp>
 #include <unordered_map>
 #include <unordered_set>
@@ -662,6 +663,30 @@ inline int reduce_blocks(uint64_t namps) {
     return (int)std::min<uint64_t>(2048, std::max<uint64_t>(1, (namps + 255) / 256));
 }
 
+// The sum of `count` per-workgroup partials on the host, in two halves: enqueue_reduce() leaves it in slot `slot` of d_result (64 slots,
+// sized by the caller), fetch_result() copies the first `nslots` slots to h_result and waits for the stream.  reduce_to_host(): both.
+inline int enqueue_reduce(ovqe_handle h, const void *partials, int64_t count, int slot = 0) {
+    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, h->stream, (const double2 *)partials, count, (double2 *)h->d_result.p, slot);
+    HIPC(h, hipGetLastError());
+    return OVQE_OK;
+}
+inline int fetch_result(ovqe_handle h, double2 *out, int nslots = 1) {
+    HIPC(h, hipMemcpyAsync(h->h_result, h->d_result.p, (size_t)nslots * sizeof(double2), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    std::copy(h->h_result, h->h_result + nslots, out);
+    return OVQE_OK;
+}
+inline int reduce_to_host(ovqe_handle h, const void *partials, int64_t count, double2 *out) {
+    if (int rc = enqueue_reduce(h, partials, count)) return rc;
+    return fetch_result(h, out);
+}
+inline int reduce_to_host(ovqe_handle h, const void *partials, int64_t count, double *re) {   // the real part alone
+    double2 sum = make_double2(0.0, 0.0);
+    const int rc = reduce_to_host(h, partials, count, &sum);
+    *re = sum.x;
+    return rc;
+}
+
 // sort terms by x (stable), fold i^ny into the coefficient, build per-x groups
 int build_groups(ovqe_handle h, int64_t T, const uint64_t *x, const uint64_t *z, const double *cr, const double *ci,
                  bool allow_global_x, std::vector<HGroup> &groups, std::vector<HTerm> &terms,
@@ -844,13 +869,7 @@ int run_bilinear(ovqe_handle h, const amp_t *bra, const amp_t *ket, const std::v
                                d_terms, (double2 *)h->d_partials.p + (size_t)c * nb);
         }
     }
-    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, h->stream, (const double2 *)h->d_partials.p,
-                       (int64_t)nchunks * nb, (double2 *)h->d_result.p, 0);
-    HIPC(h, hipGetLastError());
-    HIPC(h, hipMemcpyAsync(h->h_result, h->d_result.p, sizeof(double2), hipMemcpyDeviceToHost, h->stream));
-    HIPC(h, hipStreamSynchronize(h->stream));
-    *out = h->h_result[0];
-    return OVQE_OK;
+    return reduce_to_host(h, h->d_partials.p, (int64_t)nchunks * nb, out);
 }
 
 inline int tile_bits(ovqe_handle h, bool real = false) {
@@ -864,9 +883,6 @@ inline bool tile_ok(ovqe_handle h, bool real) {
 }
 
 #include "tile_host.inc"
-
-
-void tridiag_lowest(const std::vector<double> &a, const std::vector<double> &b, int m, double *lam, std::vector<double> &s);
 
 #include "sector_host.inc"
 
@@ -1471,12 +1487,9 @@ int ovqe_randomize(ovqe_handle h, uint64_t seed, double norm2_total, double *sca
     else
         hipLaunchKernelGGL(k_randomize, dim3(nb), dim3(256), 0, h->stream, h->state, h->namps, h->base, seed, 1.0,
                            (double2 *)h->d_partials.p);
-    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, h->stream, (const double2 *)h->d_partials.p, (int64_t)nb,
-                       (double2 *)h->d_result.p, 0);
-    HIPC(h, hipGetLastError());
-    HIPC(h, hipMemcpyAsync(h->h_result, h->d_result.p, sizeof(double2), hipMemcpyDeviceToHost, h->stream));
-    HIPC(h, hipStreamSynchronize(h->stream));
-    const double n2 = norm2_total > 0.0 ? norm2_total : h->h_result[0].x;
+    double sum = 0.0;
+    if ((rc = reduce_to_host(h, h->d_partials.p, nb, &sum))) return rc;
+    const double n2 = norm2_total > 0.0 ? norm2_total : sum;
     const double scale = 1.0 / std::sqrt(n2);
     hipLaunchKernelGGL(k_scale, dim3(nb), dim3(256), 0, h->stream, h->state, h->opt_real_state ? std::max<uint64_t>(h->namps >> 1, 1) : h->namps, scale);
     HIPC(h, hipGetLastError());
@@ -1495,13 +1508,7 @@ int ovqe_norm2(ovqe_handle h, double *out) try {
     // (real state: the 2^n_local doubles read as 2^(n_local - 1) complex numbers have the same sum of squares)
     hipLaunchKernelGGL(k_norm2, dim3(nb), dim3(256), 0, h->stream, h->state, h->opt_real_state ? std::max<uint64_t>(h->namps >> 1, 1) : h->namps,
                        (double2 *)h->d_partials.p);
-    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, h->stream, (const double2 *)h->d_partials.p, (int64_t)nb,
-                       (double2 *)h->d_result.p, 0);
-    HIPC(h, hipGetLastError());
-    HIPC(h, hipMemcpyAsync(h->h_result, h->d_result.p, sizeof(double2), hipMemcpyDeviceToHost, h->stream));
-    HIPC(h, hipStreamSynchronize(h->stream));
-    *out = h->h_result[0].x;
-    return OVQE_OK;
+    return reduce_to_host(h, h->d_partials.p, nb, out);
 } OVQE_CATCH(h)
 
 #include "abi_unit.inc"

@@ -1429,9 +1429,7 @@ int run_sector_energy(ovqe_handle h, const double *theta, double2 *out, bool *ok
         hipLaunchKernelGGL(k_sector_finish, dim3(1), dim3(256), 0, h->stream, (const double2 *)h->d_partials.p, (int64_t)nparts,
                            (const int *)E.d_flag.p, h->d_fin);
     } else {
-        hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, h->stream, (const double2 *)h->d_partials.p, (int64_t)nparts,
-                           (double2 *)h->d_result.p, 0);
-        HIPC(h, hipGetLastError());
+        if ((rc = enqueue_reduce(h, h->d_partials.p, (int64_t)nparts))) return rc;
         HIPC(h, hipMemcpyAsync(h->h_result, h->d_result.p, sizeof(double2), hipMemcpyDeviceToHost, h->stream));
         HIPC(h, hipMemcpyAsync(h->h_result + 1, E.d_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     }
@@ -1707,9 +1705,7 @@ int run_sector_gradient(ovqe_handle h, const double *theta, double *energy, doub
     if (rc) return rc;
     hipLaunchKernelGGL(k_sec_dot, dim3(nbd), dim3(256), 0, h->stream, (const double *)E.d_buf[last].p, (const double *)E.d_lam[0].p,
                        E.K, (double2 *)h->d_partials.p);
-    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, h->stream, (const double2 *)h->d_partials.p, (int64_t)nbd,
-                       (double2 *)h->d_result.p, 0);
-    HIPC(h, hipGetLastError());
+    if ((rc = enqueue_reduce(h, h->d_partials.p, nbd))) return rc;
     if (regular) {
         rc = launch_sector_adjoint_reg(h, E, last);
     } else if (second) {
@@ -1780,6 +1776,47 @@ int sector_matvec(ovqe_handle h, SectorEngine &E, const double *in, double *out)
     return OVQE_OK;
 }
 
+// The compact support as a Lanczos space (sv_lanczos_host.hpp): vectors are K doubles, the operator is sector_matvec, and the start vector
+// and every update are projected on `reach`, the 0/1 mask of the block of H connected to the reference determinant.  Two-pass only.
+struct SectorSpace : LanczosTwoPass {
+    typedef double *Vec;
+    ovqe_handle h;
+    SectorEngine &E;
+    DevBuf *vec;   // v_{j-1}, v_j, w, Ritz vector, reach
+    uint64_t seed;
+    const uint32_t K = E.K;
+    const int nb = (int)std::min<uint32_t>(1024u, (K + 255u) / 256u);
+    const double *reach = (const double *)vec[4].p;
+    SectorSpace(ovqe_handle h, SectorEngine &E, DevBuf *vec, uint64_t seed) : h(h), E(E), vec(vec), seed(seed) {}
+    Vec work(int i) const { return (double *)vec[i].p; }
+    Vec ritz() const { return (double *)vec[3].p; }
+    int reduce(double *out) { return reduce_to_host(h, h->d_partials.p, nb, out); }
+    int start(Vec v) {
+        hipLaunchKernelGGL(k_sec_randomize, dim3(nb), dim3(256), 0, h->stream, v, reach, K, seed, (double2 *)h->d_partials.p);
+        double n2 = 0.0;
+        if (int rc = reduce(&n2)) return rc;
+        return scale(v, 1.0 / std::sqrt(n2));
+    }
+    int apply(Vec out, Vec in) { return sector_matvec(h, E, in, out); }
+    int dot(Vec a, Vec b, double *re) {
+        hipLaunchKernelGGL(k_sec_dot, dim3(nb), dim3(256), 0, h->stream, (const double *)a, (const double *)b, K, (double2 *)h->d_partials.p);
+        return reduce(re);
+    }
+    int update(Vec w, Vec v, Vec vprev, double alpha, double beta, double *norm2) {
+        hipLaunchKernelGGL(k_sec_lanczos_update, dim3(nb), dim3(256), 0, h->stream, w, (const double *)v, (const double *)vprev, alpha, beta, K,
+                           (double2 *)h->d_partials.p, reach);
+        return reduce(norm2);
+    }
+    int scale(Vec v, double a) {
+        hipLaunchKernelGGL(k_sec_scale, dim3(nb), dim3(256), 0, h->stream, v, K, a);
+        return OVQE_OK;
+    }
+    int axpy(Vec y, Vec x, double a, bool first) {
+        hipLaunchKernelGGL(k_sec_axpy, dim3(nb), dim3(256), 0, h->stream, y, (const double *)x, a, K, first ? 1 : 0);
+        return OVQE_OK;
+    }
+};
+
 int run_sector_ground_state(ovqe_handle h, SectorEngine &E, double tol, int max_iter, uint64_t seed, double *energy, double *residual,
                             int *iterations) {
     const uint32_t K = E.K;
@@ -1794,19 +1831,7 @@ int run_sector_ground_state(ovqe_handle h, SectorEngine &E, double tol, int max_
         return code;
     };
     if (rc) return cleanup(rc);
-    auto reduce = [&](double *out) -> int {
-        hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, h->stream, (const double2 *)h->d_partials.p, (int64_t)nb,
-                           (double2 *)h->d_result.p, 0);
-        HIPC(h, hipGetLastError());
-        HIPC(h, hipMemcpyAsync(h->h_result, h->d_result.p, sizeof(double2), hipMemcpyDeviceToHost, h->stream));
-        HIPC(h, hipStreamSynchronize(h->stream));
-        *out = h->h_result[0].x;
-        return OVQE_OK;
-    };
-    auto dot = [&](const double *a, const double *b, double *out) -> int {
-        hipLaunchKernelGGL(k_sec_dot, dim3(nb), dim3(256), 0, h->stream, a, b, K, (double2 *)h->d_partials.p);
-        return reduce(out);
-    };
+    SectorSpace V(h, E, vec, seed);
     // The support may be a superset of the reference determinant's symmetry sector (tables from the one-angle-per-rotation
     // probe hold every determinant the program can touch): Lanczos runs inside the block of H connected to |hf>, found here
     double *reach = (double *)vec[4].p;
@@ -1827,7 +1852,7 @@ int run_sector_ground_state(ovqe_handle h, SectorEngine &E, double tol, int max_
             if (rc) return cleanup(rc);
             hipLaunchKernelGGL(k_sec_reach_step, dim3(nb), dim3(256), 0, h->stream, reach, (const double *)vec[2].p, K,
                                0x5ec70full + (uint64_t)it, reach_thresh, (double2 *)h->d_partials.p);
-            rc = reduce(&cnt);
+            rc = V.reduce(&cnt);
             if (rc) return cleanup(rc);
         }
         if (cnt != prev)   // never diagonalise a truncated block: the number would lie above the sector's minimum
@@ -1839,86 +1864,22 @@ int run_sector_ground_state(ovqe_handle h, SectorEngine &E, double tol, int max_
         h->last_fci_rounds = it;
     }
     max_iter = (int)std::min<uint64_t>((uint64_t)max_iter, std::max(members, 1u));
-    std::vector<double> alpha, beta, s;
-    double lam = 0.0;
-    int m = 0;
-    double *ritz = (double *)vec[3].p;
-    auto recurrence = [&](bool accumulate) -> int {
-        double *A = (double *)vec[0].p, *B = (double *)vec[1].p, *C = (double *)vec[2].p;
-        hipLaunchKernelGGL(k_sec_randomize, dim3(nb), dim3(256), 0, h->stream, B, (const double *)reach, K, seed, (double2 *)h->d_partials.p);
-        double n2 = 0.0;
-        int r = reduce(&n2);
-        if (r) return r;
-        hipLaunchKernelGGL(k_sec_scale, dim3(nb), dim3(256), 0, h->stream, B, K, 1.0 / std::sqrt(n2));
-        if (accumulate) hipLaunchKernelGGL(k_sec_axpy, dim3(nb), dim3(256), 0, h->stream, ritz, (const double *)B, s[0], K, 1);
-        const int steps = accumulate ? m - 1 : max_iter;
-        for (int j = 0; j < steps; ++j) {
-            r = sector_matvec(h, E, B, C);
-            if (r) return r;
-            double a = accumulate ? alpha[j] : 0.0, bj = 0.0;
-            if (!accumulate) {
-                r = dot(B, C, &a);
-                if (r) return r;
-                alpha.push_back(a);
-            }
-            hipLaunchKernelGGL(k_sec_lanczos_update, dim3(nb), dim3(256), 0, h->stream, C, (const double *)B,
-                               j ? (const double *)A : (const double *)nullptr, a, j ? beta[j - 1] : 0.0, K, (double2 *)h->d_partials.p,
-                               (const double *)reach);
-            r = reduce(&bj);
-            if (r) return r;
-            bj = std::sqrt(bj);
-            if (accumulate) {
-                bj = beta[j];
-            } else {
-                m = j + 1;
-                const bool last = j + 1 == steps || bj < 1e-13 * std::max(1.0, std::fabs(a));
-                if (last || (j >= 4 && j % 5 == 4)) {
-                    tridiag_lowest(alpha, beta, m, &lam, s);
-                    if (last || std::fabs(bj * s[m - 1]) < tol * std::max(1.0, std::fabs(lam))) return OVQE_OK;
-                }
-                beta.push_back(bj);
-            }
-            hipLaunchKernelGGL(k_sec_scale, dim3(nb), dim3(256), 0, h->stream, C, K, 1.0 / bj);
-            double *t = A;
-            A = B;
-            B = C;
-            C = t;
-            if (accumulate) hipLaunchKernelGGL(k_sec_axpy, dim3(nb), dim3(256), 0, h->stream, ritz, (const double *)B, s[j + 1], K, 0);
-        }
-        return OVQE_OK;
-    };
-    rc = recurrence(false);
-    if (!rc) rc = recurrence(true);
-    double true_res = 0.0;
-    if (!rc) {   // normalise, Rayleigh quotient, true residual |H y - lambda y|
-        double n2 = 0.0;
-        rc = dot(ritz, ritz, &n2);
-        if (!rc) {
-            hipLaunchKernelGGL(k_sec_scale, dim3(nb), dim3(256), 0, h->stream, ritz, K, 1.0 / std::sqrt(n2));
-            rc = sector_matvec(h, E, ritz, (double *)vec[2].p);
-        }
-        if (!rc) rc = dot(ritz, (const double *)vec[2].p, &lam);
-        if (!rc) {
-            hipLaunchKernelGGL(k_sec_lanczos_update, dim3(nb), dim3(256), 0, h->stream, (double *)vec[2].p, (const double *)ritz,
-                               (const double *)nullptr, lam, 0.0, K, (double2 *)h->d_partials.p, (const double *)reach);
-            rc = reduce(&true_res);
-            true_res = std::sqrt(true_res);
-        }
-    }
+    LanczosResult res;
+    rc = lanczos_lowest(V, tol, max_iter, res);
     const bool canonical = E.segs.empty();   // an engine without a circuit (build_screen_sector) keeps its vectors in ascending-index order
     if (!rc && h->state && (canonical || E.segs.back().L.d_cid.p)) {
         // the normalised eigenvector as the handle's state (zeros outside the support), like ovqe_ground_state leaves it
         if (hipMemsetAsync(h->state, 0, (size_t)h->namps * sizeof(amp_t), h->stream) != hipSuccess) rc = fail(h, OVQE_ERR_HIP, "sector_ground_state: memset");
         if (!rc)
-            hipLaunchKernelGGL(k_sec_scatter_dense, dim3((K + 255u) / 256u), dim3(256), 0, h->stream, (const double *)ritz,
+            hipLaunchKernelGGL(k_sec_scatter_dense, dim3((K + 255u) / 256u), dim3(256), 0, h->stream, (const double *)V.ritz(),
                                canonical ? (const uint32_t *)nullptr : (const uint32_t *)E.segs.back().L.d_cid.p, (const uint32_t *)E.d_sup.p, K,
                                (double2 *)h->state);
         if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, OVQE_ERR_HIP, "sector_ground_state: scatter");
     }
     if (!rc && hipGetLastError() != hipSuccess) rc = fail(h, OVQE_ERR_HIP, "sector_ground_state: launch failed");
     if (rc) return cleanup(rc);
-    *energy = lam + h->ham.constant;
-    if (residual) *residual = true_res;
-    if (iterations) *iterations = m;
+    *energy = res.lam + h->ham.constant;
+    if (residual) *residual = res.residual;
+    if (iterations) *iterations = res.m;
     return cleanup(OVQE_OK);
 }

@@ -456,12 +456,7 @@ int run_expectation_tiled(ovqe_handle h, HamDev &H, double2 *out, bool *used, bo
                                (const HGroup *)H.d_rest.p, 0, H.n_rest, (const HTerm *)H.d_terms.p, partials + count);
         count += nb;
     }
-    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, h->stream, (const double2 *)partials, count,
-                       (double2 *)h->d_result.p, 0);
-    HIPC(h, hipGetLastError());
-    HIPC(h, hipMemcpyAsync(h->h_result, h->d_result.p, sizeof(double2), hipMemcpyDeviceToHost, h->stream));
-    HIPC(h, hipStreamSynchronize(h->stream));
-    *out = h->h_result[0];
+    if (int rc = reduce_to_host(h, partials, count, out)) return rc;
     *used = true;
     h->last_passes = ns + (H.n_rest ? 1 : 0);
     h->last_pass_bytes = (int64_t)((real ? 8.0 : 16.0) * (double)h->namps * (double)(ns + H.n_rest));
@@ -609,16 +604,14 @@ int run_expectation_compact(ovqe_handle h, HamDev &H, double2 *out, bool *ok, bo
     if (rc) return rc;
     // fixed-order reduction: per sweep over its tiles, then over the sweeps
     hipLaunchKernelGGL(k_reduce_rows2, dim3((unsigned)ns), dim3(256), 0, h->stream, (const double2 *)partials, (int)C.ntiles, rows);
-    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, h->stream, (const double2 *)rows, (int64_t)ns, (double2 *)h->d_result.p, 0);
-    if (!psic_ready)
-        hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, h->stream, (const double2 *)pnorm, (int64_t)nbg,
-                           (double2 *)h->d_result.p, 1);
-    HIPC(h, hipGetLastError());
-    HIPC(h, hipMemcpyAsync(h->h_result, h->d_result.p, 2 * sizeof(double2), hipMemcpyDeviceToHost, h->stream));
-    HIPC(h, hipStreamSynchronize(h->stream));
+    rc = enqueue_reduce(h, rows, ns);
+    if (!rc && !psic_ready) rc = enqueue_reduce(h, pnorm, nbg, 1);
+    double2 sums[2];   // <H>, norm on the support
+    if (!rc) rc = fetch_result(h, sums, 2);
+    if (rc) return rc;
     // guard: the circuit is unitary, so the amplitudes on the support must carry the whole norm
-    if (!psic_ready && std::fabs(h->h_result[1].x - 1.0) > 1e-9) return OVQE_OK;
-    *out = h->h_result[0];
+    if (!psic_ready && std::fabs(sums[1].x - 1.0) > 1e-9) return OVQE_OK;
+    *out = sums[0];
     *ok = true;
     return OVQE_OK;
 }

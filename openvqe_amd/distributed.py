@@ -1101,9 +1101,9 @@ class ShardedStatevector:
         mean to ``backend.Statevector.ground_state``.  Afterwards the register holds the normalised eigenvector y under the
         identity permutation.
 
-        Two passes of the three-term recurrence, as ``ovqe_ground_state`` runs it when its vectors do not fit: pass 1 builds the
-        tridiagonal matrix (stop test |beta_m s_m| < tol max(1, |lambda|) every fifth step), pass 2 repeats it from the same
-        seeded start and accumulates the Ritz vector; then the Rayleigh quotient and the true residual of y.  NO Lanczos vector is
+        Two passes of the three-term recurrence: the algorithm of ``lanczos_lowest`` (csrc/sv_lanczos_host.hpp), which the
+        one-device solvers run, restated here over the shards.  Pass 1 builds the tridiagonal matrix (stop test
+        |beta_m s_m| < tol max(1, |lambda|) every fifth step), pass 2 repeats it from the same seeded start and accumulates the Ritz vector; then the Rayleigh quotient and the true residual of y.  NO Lanczos vector is
         kept at shard size — at the register sizes this path is for nothing is left to keep them in: a rank holds four
         shard-sized vectors (v_{j-1}, v_j, w and y) and the double buffers of the partner chunks, whatever the step count.
         alpha_j and beta_j are all-reduced before any use (two all-reduces per step), so every rank solves the identical
