@@ -4,10 +4,12 @@
 // Instances of the workgroup geometry of the rows form (k_sparse_vqe_rows_shared<NW, RPT, EPR, SSTRIDE>), smaller first.  An instance
 // holds a program when its entries are at most 64 NW x EPT (the capacity criterion its name carries), its state fits the stride, its
 // LDS fits half a CU (launch_rows_shared) AND the entries pack into 64 NW x RPT owner pieces of EPR slots (sparse_pack.hpp).  The
-// shapes RPT x EPR are the measured ones of profiles/owner_rows/README.md.
-struct SharedInstance { int nw, ept, sstride, rpt, epr; };
-constexpr SharedInstance SHARED_13 = {4, 13, 2568, 1, 17};   // LiH: 225 states, 3243 entries: 18 LDS reads per thread and state
-constexpr SharedInstance SHARED_37 = {4, 37, 4104, 4, 10};   // H2O: 441 states, 9443 entries: 44
+// shapes RPT x EPR are the measured ones of profiles/owner_rows/README.md.  te: the pipelined item loop (sv_sparse.hpp) keeps the table
+// records of 32 te distinct angles in registers (profiles/pipelined_rows/README.md).  Both instances: no scratch.  H2O 230 VGPRs, two
+// waves per SIMD; LiH 148, THREE waves per SIMD (three workgroups per CU; four with the plain loop, which was slower at every batch size).
+struct SharedInstance { int nw, ept, sstride, rpt, epr, te; };
+constexpr SharedInstance SHARED_13 = {4, 13, 2568, 1, 17, 3};   // LiH: 225 states, 3243 entries: 18 LDS reads per thread and state
+constexpr SharedInstance SHARED_37 = {4, 37, 4104, 4, 10, 5};   // H2O: 441 states, 9443 entries: 44
 constexpr SharedInstance SHARED_INSTANCES[2] = {SHARED_13, SHARED_37};
 
 // ---- support-compacted path (sv_sparse.hpp) -------------------------------------------------------------------
@@ -470,21 +472,21 @@ enum : uint32_t {
     // ... the instances of k_sparse_vqe_rows_shared (entries in registers as owner pieces).  The names ("shared_e37_s4104",
     // "shared_e13_s2568" in backend.py) identify the INSTANCE — its capacity criterion, 37 / 13 entries per thread, and its stride —
     // not the slot layout of the pieces (SHARED_37 / SHARED_13 above)
-    SPG_SHARED_37 = 1u << 11,    // k_sparse_vqe_rows_shared<4, 4, 10, 4104>  (H2O: 441 states, 9443 entries)
-    SPG_SHARED_13 = 1u << 12,    // k_sparse_vqe_rows_shared<4, 1, 17, 2568>  (LiH: 225 states)
+    SPG_SHARED_37 = 1u << 11,    // k_sparse_vqe_rows_shared<4, 4, 10, 4104, ...>  (H2O: 441 states, 9443 entries)
+    SPG_SHARED_13 = 1u << 12,    // k_sparse_vqe_rows_shared<4, 1, 17, 2568, ...>  (LiH: 225 states)
 };
 
 // the workgroup geometry of the rows form: batches from SHARED_MIN_B on — measured (tools/exp_shared_sweep.py, profiles/shared_rows): it
 // wins beyond the spread at every batch size the rows form takes, 2048 included (H2O: 35.6 against 40.3 us)
 constexpr int64_t SHARED_MIN_B = 2048;
 
-template <int NW, int RPT, int EPR, int SSTRIDE, int DBG>
+template <int NW, int RPT, int EPR, int SSTRIDE, int TE, int DBG>
 int launch_rows_shared_dbg(ovqe_handle h, const SparseArgs &R, size_t smem) {
     constexpr int NS = 2 * NW;
     // workgroups one CU holds at once at this much LDS, cached per device: both in ONE word (smem << 8 | per_cu; smem <= 80 KiB,
     // per_cu <= 32), so that two threads with a handle each never see one without the other
     static std::atomic<uint32_t> per_dev[64];
-    constexpr auto kern = &k_sparse_vqe_rows_shared<NW, RPT, EPR, SSTRIDE, DBG>;
+    constexpr auto kern = &k_sparse_vqe_rows_shared<NW, RPT, EPR, SSTRIDE, TE, DBG>;
     constexpr size_t slots = (size_t)RPT * EPR * NW * 64;   // the packed tables: coefficients, then 16-bit offsets (sparse_pack.hpp)
     const double *hc = (const double *)h->d_sp_hpack.p;
     const uint16_t *ho = (const uint16_t *)(hc + slots);
@@ -516,20 +518,21 @@ int launch_rows_shared_dbg(ovqe_handle h, const SparseArgs &R, size_t smem) {
 template <int K>
 int launch_rows_shared(ovqe_handle h, const SparseArgs &R, bool *taken) {
     constexpr SharedInstance I = SHARED_INSTANCES[K];
-    constexpr int NW = I.nw, RPT = I.rpt, EPR = I.epr, SSTRIDE = I.sstride;
+    constexpr int NW = I.nw, RPT = I.rpt, EPR = I.epr, SSTRIDE = I.sstride, TE = I.te;
     const size_t smem = sp_rows_shared_lds<NW, SSTRIDE>(R.ntab).bytes;
     *taken = h->sp_pack_inst == K && R.nent >= 1 && R.nent <= NW * 64 * I.ept && (size_t)R.mpad * sizeof(double) <= (size_t)SSTRIDE &&
              smem <= LDS_TWO_PER_CU;
     if (!*taken) return OVQE_OK;
 #ifdef OVQE_TESTING
     switch (h->opt_sparse_dbg) {
-    case 1: return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, 1>(h, R, smem);
-    case 2: return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, 2>(h, R, smem);
-    case 3: return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, 3>(h, R, smem);
+    case 1: return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, TE, 1>(h, R, smem);
+    case 2: return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, TE, 2>(h, R, smem);
+    case 3: return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, TE, 3>(h, R, smem);
+    case 4: return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, TE, 4>(h, R, smem);
     default: break;
     }
 #endif
-    return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, 0>(h, R, smem);
+    return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, TE, 0>(h, R, smem);
 }
 
 // on_device: theta / energies are device pointers (inputs already resident in HBM, results left there).  *done = false: no compact

@@ -44,7 +44,7 @@ struct SparseArgs {
     int hf;       // compact slot of |hf>
     int64_t B;
     double constant;
-    int dbg = 0;  // measurements ("sparse_dbg"; the rows kernels take it as a template argument): 1 no sincos, 2 no circuit rows, 3 no Hamiltonian entries
+    int dbg = 0;  // measurements ("sparse_dbg"; the rows kernels take it as a template argument): 1 no sincos, 2 no circuit rows, 3 no Hamiltonian entries, 4 (k_sparse_vqe_rows_shared) no theta loads
 };
 
 struct SpVqeLds { size_t cs, ops, pairs, bytes; };   // the spw states ([spw][mpad]) are at 0
@@ -307,14 +307,37 @@ __host__ __device__ constexpr SpRowsSharedLds sp_rows_shared_lds(int ntab) {
 // same shift for all lanes of an instruction, the arrangement keeps its meaning.  DBG as k_sparse_vqe_rows.
 // hc / ho: the packed tables of sparse_pack.hpp for NT = 64 NW threads — coefficients [RPT * EPR][NT]; 16-bit byte offsets
 // [RPT * EPR][NT] of the slots, then [RPT][NT] of the owners.
-template <int NW, int RPT, int EPR, int SSTRIDE, int DBG = 0>
+//
+// THE ITEM LOOP IS PIPELINED (profiles/pipelined_rows/README.md).  The four waves walk the work items in lock step, so
+// whatever one of them waits for nothing else on the CU covers.  What an item needs from global memory is known one item ahead:
+//   * table records (parameter index, coefficient) are the same for every evaluation of a launch: lane l of each half-wave holds
+//     those of entries l + 32 k, k < TE, in registers from before the loop (entries beyond 32 TE — programs with more distinct
+//     angles than that — keep the loads at sincos time);
+//   * the theta values of item w + gridDim.x are loaded behind the last circuit row of item w, BEFORE the first barrier, and first
+//     used behind the contraction, which issues no vector-memory instruction: a whole contraction hides them.  (Not earlier: vmcnt
+//     retires in order and the row loop waits on it for its row words — a theta load in front of a row stalls that row.)
+//   * the next item's cos/sin table is written behind the contraction and this wave's partial sums, before the second barrier,
+//     into the SAME LDS region: a wave's own table is dead once its circuit is done, no other wave reads it, and a wave's DS
+//     instructions execute in order.  Same sincos of the same product coeff * theta: every energy keeps its bits.  The code has
+//     ONE table site: the loop is rotated so that it serves the first item of a workgroup too (then nothing precedes it);
+//   * the last trip of the row loop fetches rows 0..3 again instead of the spare rows behind the table: the next item starts on
+//     row words it already holds.
+// The zero-fill of the states stays behind the second barrier: other waves read this wave's states in the contraction.
+// What it costs is registers that live across the contraction, the kernel's pressure peak: TE records and TE theta values per lane
+// (H2O 198 -> 230 VGPRs, two waves per SIMD as before; LiH 128 -> 148, three instead of four).  Measured, 65 536 evaluations: H2O
+// 0.519 -> 0.484 ms, LiH 0.272 -> 0.259; the plain loop and the carried row words alone were built from a build-time switch for
+// that comparison (no gain from the row words alone) and are gone.
+// DBG as k_sparse_vqe_rows; 4: no theta load at all, a constant in its place (what the loads themselves cost).
+template <int NW, int RPT, int EPR, int SSTRIDE, int TE, int DBG = 0>
 __global__ __launch_bounds__(NW * 64) void k_sparse_vqe_rows_shared(SparseArgs A, const double *__restrict__ theta,
                                                                     const SmallRot *__restrict__ tabrots, const uint64_t *__restrict__ rows,
                                                                     int nrows4, const double *__restrict__ hc, const uint16_t *__restrict__ ho,
                                                                     double *__restrict__ energies) {
     constexpr int NT = NW * 64, NS = 2 * NW, SD = SSTRIDE / 8;
+    constexpr int TR = TE, TRN = TR ? TR : 1;   // table records in registers per lane
     static_assert(SSTRIDE % 8 == 0 && SSTRIDE % 512 != 0 && NS * SSTRIDE <= 65536 && (NS * SSTRIDE) % 16 == 0,
                   "state offsets are DS instruction immediates; a stride the ds_read2 forms cannot encode (see above)");
+    static_assert(TE >= 0, "table records per lane");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int ntab1 = A.ntab + 1;
     const SpRowsSharedLds L = sp_rows_shared_lds<NW, SSTRIDE>(A.ntab);
@@ -342,27 +365,75 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_vqe_rows_shared(SparseArgs A
             ojj[r][k] = lo | (hi << 16);
         }
     }
+    // ... and this lane's table records (a lane past the table holds the last record: its theta load is a valid one, nothing is
+    // written for it)
+    int32_t tp[TRN];
+    double tc[TRN];
+#pragma unroll
+    for (int k = 0; k < TR; ++k) {
+        const int e = l + 32 * k;
+        const SmallRot sr = tabrots[e < A.ntab ? e : A.ntab - 1];
+        tp[k] = sr.pidx;
+        tc[k] = sr.coeff;
+    }
     const int64_t nwork = (A.B + NS - 1) / NS;
     const uint64_t *rp = rows + l;
-    for (int64_t w = blockIdx.x; w < nwork; w += gridDim.x) {
-        const int64_t b0 = w * NS;
-        uint64_t w0 = rp[0], w1 = rp[32], w2 = rp[64], w3 = rp[96];   // (the table ends with four spare rows)
-        for (int i = l; i < SD; i += 32) sst[i] = i == A.hf ? 1.0 : 0.0;
-        {
-            const int64_t b = b0 + my < A.B ? b0 + my : A.B - 1;
-            const double *th = theta + b * A.K;
-            for (int e = l; e < A.ntab; e += 32) {
+    // the parameter row of this half-wave's evaluation of work item w (the spare states of the last item run the clamped last row)
+    auto theta_row = [&](int64_t w) {
+        const int64_t b = w * NS + my;
+        return theta + (b < A.B ? b : A.B - 1) * A.K;
+    };
+    auto fetch = [&](int64_t w, double (&tv)[TRN]) {
+        const double *th = theta_row(w);
+#pragma unroll
+        for (int k = 0; k < TR; ++k) tv[k] = DBG == 4 ? 0.05 : th[tp[k]];
+    };
+    auto entry = [&](int e, double x) {
+        double sn, c;
+        if (DBG == 1) {
+            sn = x;
+            c = 1.0;
+        } else {
+            sincos(x, &sn, &c);
+        }
+        csm[e] = make_double2(c, sn);
+    };
+    auto table = [&](int64_t w, const double (&tv)[TRN]) {
+#pragma unroll
+        for (int k = 0; k < TR; ++k)
+            if (l + 32 * k < A.ntab) entry(l + 32 * k, tc[k] * tv[k]);
+        if (32 * TR < A.ntab) {
+            const double *th = theta_row(w);
+            for (int e = l + 32 * TR; e < A.ntab; e += 32) {
                 const SmallRot sr = tabrots[e];
-                double sn, c;
-                if (DBG == 1) {
-                    sn = sr.coeff * th[sr.pidx];
-                    c = 1.0;
-                } else {
-                    sincos(sr.coeff * th[sr.pidx], &sn, &c);
-                }
-                csm[e] = make_double2(c, sn);
+                entry(e, sr.coeff * (DBG == 4 ? 0.05 : th[sr.pidx]));
             }
-            if (l == 0) csm[A.ntab] = make_double2(1.0, 0.0);
+        }
+    };
+    auto zero_fill = [&]() {
+        for (int i = l; i < SD; i += 32) sst[i] = i == A.hf ? 1.0 : 0.0;
+    };
+    auto reduce = [&](int64_t b0) {   // partial sums in wave order
+        if (tid < NS && b0 + tid < A.B) {
+            double e = 0.0;
+#pragma unroll
+            for (int v = 0; v < NW; ++v) e += red[v * NS + tid];
+            energies[b0 + tid] = e + A.constant;
+        }
+    };
+    int64_t w = blockIdx.x, bprev = 0;
+    if (w >= nwork) return;
+    uint64_t w0 = rp[0], w1 = rp[32], w2 = rp[64], w3 = rp[96];
+    double tv[TRN];
+    fetch(w, tv);
+    if (l == 0) csm[A.ntab] = make_double2(1.0, 0.0);   // the identity entry: nothing overwrites it
+    zero_fill();
+    for (bool first = true;; first = false) {
+        table(w, tv);   // (behind the contraction of the item before)
+        if (!first) {
+            __syncthreads();   // partial sums complete; the states may be overwritten
+            reduce(bprev);
+            zero_fill();
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         auto apply = [&](uint64_t word) {
@@ -376,8 +447,7 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_vqe_rows_shared(SparseArgs A
             *pj = t.x * v - sn * u;
             asm volatile("" ::: "memory");   // a wave's DS instructions execute in issue order (see k_sparse_vqe_rows)
         };
-        for (int r = 0; r < (DBG == 2 ? 0 : nrows4); r += 4) {
-            const uint64_t *nx = rp + (size_t)(r + 4) * 32;
+        auto trip = [&](const uint64_t *nx) {
             apply(w0);
             w0 = nx[0];
             apply(w1);
@@ -386,7 +456,14 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_vqe_rows_shared(SparseArgs A
             w2 = nx[64];
             apply(w3);
             w3 = nx[96];
+        };
+        if (DBG != 2) {
+            for (int r = 0; r < nrows4 - 4; r += 4) trip(rp + (size_t)(r + 4) * 32);   // (fetch the four rows behind their own)
+            trip(rp);   // the last trip: rows 0..3, for the next item
         }
+        const int64_t wnext = w + gridDim.x;
+        const bool more = wnext < nwork;
+        if (more) fetch(wnext, tv);   // in flight across the barrier and the contraction
         __syncthreads();   // all 2 NW states of the workgroup are final
         double acc[NS];
 #pragma unroll
@@ -421,14 +498,12 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_vqe_rows_shared(SparseArgs A
             const double tot = wave_sum(acc[q]);
             if (lane == 0) red[wave * NS + q] = tot;
         }
-        __syncthreads();   // partial sums complete; the states may be overwritten
-        if (tid < NS && b0 + tid < A.B) {
-            double e = 0.0;
-#pragma unroll
-            for (int v = 0; v < NW; ++v) e += red[v * NS + tid];
-            energies[b0 + tid] = e + A.constant;
-        }
+        bprev = w * NS;
+        if (!more) break;
+        w = wnext;
     }
+    __syncthreads();
+    reduce(bprev);
 }
 
 // ---- latency form (round 3): ONE evaluation per workgroup of NT threads ---------------------------------------------------------
