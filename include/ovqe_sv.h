@@ -124,6 +124,8 @@ int ovqe_set_stream(ovqe_handle h, void *hip_stream);
  *                     closure of the support under the operator's x-groups within the same bound (bit-identical amplitudes)
  *   "lanczos_keep_gb" (160) ovqe_ground_state keeps its Lanczos vectors in HBM up to this many GB (and 60 % of the free memory): one pass of
  *                     the recurrence gives the Ritz vector; 0 or vectors that do not fit: the recurrence runs twice
+ *   "rdm_workspace_mb" (1024)  ovqe_rdm materialises its rows in chunks of at most this many MB of device memory (at least one staging
+ *                     tile of 16 or 32 rows); the buffer is allocated at the first call that needs it and kept on the handle
  *
  *   "real_state" (0)  the state buffer holds 2^n_local DOUBLES (8 bytes per amplitude: a shard of the partitioned register while its
  *                     amplitudes are real).  BUFFER-SIZE CONTRACT: while it is set, the state and every shard-sized operand of
@@ -417,6 +419,28 @@ int ovqe_ground_state(ovqe_handle h, double tol, int max_iter, uint64_t seed, do
  * (the tables are those of the ADAPT screens, option "screen_sector", and are kept for them). */
 int ovqe_sector_ground_state(ovqe_handle h, double tol, int max_iter, uint64_t seed, double *energy, double *residual,
                              int *iterations);
+
+/* ---- one- and two-particle reduced density matrices of the resident state psi (what a chemist takes from a converged wave function;
+ * the reference takes a one-particle density from its PySCF run and diagonalises it to select active spaces by natural-orbital
+ * occupations, ref:openvqe/common_files/molecule_factory_with_sparse.py:293-324).  CONVENTION: the register is read as n = n_qubits spin orbitals under the
+ * JORDAN-WIGNER transform — the only encoding this call knows — with orbital p = reference qubit p = index bit n-1-p, and, for the
+ * spin-resolved helpers of openvqe_amd/rdm.py, even orbitals alpha, odd orbitals beta (openvqe_amd/fermion.py spin_orbital_integrals).
+ *   order 1: out = n*n complex (re,im), row-major  gamma[p][q] = <psi| a+_p a_q |psi>
+ *   order 2: out = P*P complex, P = n(n-1)/2 pairs (p<q) in lexicographic order,
+ *            D2[(p<q)][(r<s)] = <psi| a+_p a+_q a_s a_r |psi>,  so that  Gamma[p][q][r][s] = <a+_p a+_q a_r a_s> = -D2[(p,q)][(r,s)]
+ * Both are Gram matrices (Hermitian — to the bit — and positive semidefinite) of rows v_K, one per register index K that lies one /
+ * two annihilations below a non-zero amplitude:  v_K[a] = (-1)^{occ_K(t<a)} psi[K | bit(a)],  v_K[(a<b)] = (-1)^{occ_K(a<t<b)}
+ * psi[K | bit(a) | bit(b)].  The rows are found from a bitmap of the support and materialised in chunks (option "rdm_workspace_mb");
+ * a state without imaginary parts (every UCC / ADAPT / Lanczos state) runs in 8-byte arithmetic.  COST: the number of rows — for a
+ * sparse state (a symmetry sector) a small multiple of its support, for a DENSE register 2^n rows of n or P entries each: the call
+ * is meant for sparse states or small registers.  The state is only read; partial sums are reduced in a fixed order (bit-identical
+ * results from call to call).  Synchronous.  Plain handles of any n >= 1; OVQE_ERR_INVALID for an order other than 1 or 2, order 2
+ * with n < 2 and a NULL output; OVQE_ERR_STATE on a shard of a partitioned register and under option "real_state". */
+int ovqe_rdm(ovqe_handle h, int order, double *out_re_im);
+/* of the last ovqe_rdm call, up to `count` entries of: [0] non-zero amplitudes [1] rows [2] row chunks [3] 1 = real form [4] workspace bytes
+ * [5] Gram launches [6] block pairs (64 x 64 outputs, upper triangle) [7] row slices per chunk  [8..11] HIP-event times in microseconds:
+ * census + shadows + row list, rows kernels, Gram kernels, final reduction ([9..11] stay 0 beyond 64 chunks); zeros before the first call */
+int ovqe_rdm_info(ovqe_handle h, int64_t *info, int count);
 
 /* ---- measurement support (bench.py): average device time in ms of `reps` back-to-back launches of
  * one Pauli-rotation sweep, bracketed by HIP events on the handle's stream */

@@ -99,6 +99,8 @@ SIGNATURES = {
                                  ctypes.POINTER(_int)]),
     "ovqe_sector_ground_state": (_int, [_H, _dbl, _int, _u64, ctypes.POINTER(_dbl), ctypes.POINTER(_dbl),
                                         ctypes.POINTER(_int)]),
+    "ovqe_rdm": (_int, [_H, _int, _f64p]),
+    "ovqe_rdm_info": (_int, [_H, ctypes.POINTER(ctypes.c_int64), _int]),
     "ovqe_program_info": (_int, [_H, ctypes.POINTER(ctypes.c_int64), _int]),
     "ovqe_get_rotation_program": (_int, [_H, _i64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.POINTER(ctypes.c_int64)]),

@@ -525,6 +525,35 @@ class Statevector:
                                                   ctypes.byref(r), ctypes.byref(it)))
         return e.value, r.value, it.value
 
+    # -- reduced density matrices of the resident state (ovqe_rdm, csrc/rdm_host.inc) -------------------------------------------
+    def rdm1(self):
+        """gamma[p, q] = <a+_p a_q> of the resident state, (n, n) complex128: Jordan-Wigner, orbital p = qubit p, spin orbitals
+        interleaved (even alpha, odd beta) — the conventions of ``fermion.spin_orbital_integrals``; helpers in ``openvqe_amd.rdm``"""
+        n = self.n_local
+        out = np.empty((n, n), np.complex128)
+        self._ck(self._L.ovqe_rdm(self._h, 1, out.view(np.float64).reshape(-1)))
+        return out
+
+    def rdm2(self, packed=False):
+        """Gamma[p, q, r, s] = <a+_p a+_q a_r a_s> of the resident state, (n, n, n, n) complex128 — so that E = constant +
+        sum h_pq gamma_pq + 1/2 sum h_pqrs Gamma_pqrs with the integrals of ``fermion.spin_orbital_integrals`` — or, ``packed``,
+        what the device computes: D2[(p<q), (r<s)] = <a+_p a+_q a_s a_r>, (P, P) with the P = n(n-1)/2 pairs in lexicographic order"""
+        from . import rdm
+        n = self.n_local
+        P = n * (n - 1) // 2
+        out = np.empty((P, P), np.complex128)
+        self._ck(self._L.ovqe_rdm(self._h, 2, out.view(np.float64).reshape(-1)))
+        return out if packed else rdm.unpack_rdm2(out, n)
+
+    def rdm_info(self):
+        """figures of the last rdm1 / rdm2 call: support size, rows, row chunks, real or complex form, workspace bytes, launch geometry
+        of the Gram kernel, HIP-event times of the phases in microseconds"""
+        out = (ctypes.c_int64 * 12)()
+        self._ck(self._L.ovqe_rdm_info(self._h, out, 12))
+        keys = ("nonzeros", "rows", "chunks", "real", "workspace_bytes", "gram_launches", "block_pairs", "row_slices",
+                "list_us", "rows_us", "gram_us", "finish_us")
+        return dict(zip(keys, [int(v) for v in out]))
+
     def program_info(self):
         """shape of the compiled program: ops, rotations, literal gates, sweeps per evaluation, tiled sweeps,
         fused-kernel ops, support size (-1 = not analysed yet)"""

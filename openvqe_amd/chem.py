@@ -460,6 +460,11 @@ class Problem:
         ops, theta, hf = fermion.cluster_ops_and_mp2_guess(self.n_elec, self.orb_energies_full, self.hpqrs)
         return len(ops), ops, [spin_operator(o, transform) for o in ops], theta, hf
 
+    def rdm_energy(self, g1, g2):
+        """the energy re-assembled from this problem's integrals and the density matrices of a state (``Statevector.rdm1`` /
+        ``rdm2``): an independent check of <H>"""
+        from . import rdm
+        return rdm.energy(self.hpq, self.hpqrs, self.constant, g1, g2)
 
     def fci_energy(self, tol=1e-10, device=0):
         """full-CI energy of this (active-space) problem in the Hartree-Fock determinant's (N_alpha, N_beta) sector — the

@@ -8,7 +8,8 @@
 //   sector_host.inc  symmetry-sector tables, sweeps, <H>, adjoint, Lanczos inside the support        (kernels: sv_sector.hpp)
 //   gates_host.inc   literal gate programs -> small ops / Clifford-frame rotations                   (sv_small.hpp, sv_frame_host.hpp)
 //   sparse_host.inc  support-compacted path                                                          (kernels: sv_sparse.hpp)
-//   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc   extern "C" entry points by family (include/ovqe_sv.h)
+//   rdm_host.inc     density matrices of the resident state: census, shadows, row list, rows, Gram    (sv_rdm_host.hpp; kernels: sv_rdm.hpp)
+//   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc / abi_rdm.inc   extern "C" entry points by family (include/ovqe_sv.h)
 //   cross_host.inc   planned Pauli sums on a shard of the partitioned register, ovqe_xsum_*          (sv_cross_host.hpp; kernels: sv_cross.hpp)
 //   pool_host.inc    planned ADAPT pool screen on a shard, ovqe_xpool_*                              (sv_pool_host.hpp; kernels: sv_pool.hpp)
 // sv_cover_host.hpp (host-only) holds the table records planners and kernels share and the one cover rule, grow_tile_set(), that
@@ -43,6 +44,7 @@
 #include "sv_pool.hpp"
 #include "sv_frame_host.hpp"
 #include "sv_lanczos_host.hpp"
+#include "sv_rdm.hpp"
 #include <hipcub/hipcub.hpp>
 #include <unordered_map>
 #include <unordered_set>
@@ -266,6 +268,8 @@ struct SectorEngine {
     size_t h_stream_bytes = 0;    // bytes k_sector_expect reads per evaluation (elements + index arrays)
 };
 
+struct RdmDev;   // rdm_host.inc
+
 }  // namespace
 
 struct ovqe_sv {
@@ -477,6 +481,8 @@ struct ovqe_sv {
     int num_cus = 0;              // compute units of the device (first use)
     std::vector<CrossSum *> xsums;   // ovqe_xsum_create (slots of destroyed sums are nullptr)
     std::vector<PoolPlan *> xpools;  // ovqe_xpool_create (likewise)
+    RdmDev *rdm = nullptr;           // buffers and figures of ovqe_rdm (first call)
+    int opt_rdm_workspace_mb = 1024; // rows of a density-matrix call are materialised in chunks of at most this many MB
 };
 
 namespace {
@@ -1115,6 +1121,8 @@ void push_rotation(ovqe_handle h, uint64_t x, uint64_t z, double coeff, double p
 
 #include "sparse_host.inc"
 
+#include "rdm_host.inc"
+
 int check_theta(ovqe_handle h, const double *theta, int32_t K) {
     if (!h->prog_set) return fail(h, OVQE_ERR_STATE, "no program set (ovqe_set_program / ovqe_set_gate_program)");
     if (K != h->K) return fail(h, OVQE_ERR_INVALID, "K does not match the program's parameter count");
@@ -1222,6 +1230,7 @@ int ovqe_destroy(ovqe_handle h) try {
     free_sector(h->scr);
     for (CrossSum *X : h->xsums) free_cross_sum(X);
     for (PoolPlan *P : h->xpools) free_pool_plan(P);
+    free_rdm(h->rdm);
     h->kept_blocks.flush();
     if (h->h_rp) (void)hipHostFree(h->h_rp);
     if (h->h_result) (void)hipHostFree(h->h_result);
@@ -1340,6 +1349,7 @@ int ovqe_set_option(ovqe_handle h, const char *name, int64_t value) try {
         reset_sector(h);
     }
     else if (k == "lanczos_keep_gb") h->opt_lanczos_keep_gb = (int)value;
+    else if (k == "rdm_workspace_mb") h->opt_rdm_workspace_mb = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
     else if (k == "screen_sparse") h->opt_screen_sparse = (int)std::max<int64_t>(0, value);
 #ifdef OVQE_TESTING
     else if (k == "tile_flat") h->opt_tile_flat = (int)value;
@@ -1518,6 +1528,8 @@ int ovqe_norm2(ovqe_handle h, double *out) try {
 #include "abi_adapt.inc"
 
 #include "abi_solvers.inc"
+
+#include "abi_rdm.inc"
 
 // ---- measurement support ------------------------------------------------------------------------
 int ovqe_time_pauli_rotation(ovqe_handle h, uint64_t x, uint64_t z, double phi, int warmup, int reps, double *avg_ms) try {

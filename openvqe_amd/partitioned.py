@@ -239,6 +239,12 @@ class PartitionedStatevector:
         raise NotImplementedError("sector tables are a one-device structure (ovqe_sector_ground_state); on the partitioned register "
                                   "ground_state() is the path: Lanczos over the whole register")
 
+    def rdm1(self, *args, **kwargs):
+        raise NotImplementedError("density matrices are computed on one device (ovqe_rdm reads a whole register): not available on the "
+                                  "partitioned register")
+
+    rdm2 = rdm1
+
     def last_screen_support(self):
         return -1
 

@@ -1,0 +1,119 @@
+"""Helpers of the density-matrix tests (tests/test_rdm_host.py, tests/test_gpu_rdm.py) — not product code.  Two independent oracles
+for gamma[p,q] = <a+_p a_q> and D2[(p<q),(r<s)] = <a+_p a+_q a_s a_r> (pairs in lexicographic order):
+
+(a) ``pauli_rdm``: every element as the expectation value of its ``fermion.jw_product`` Pauli sum, applied with ``oracle.masks`` —
+    no fermionic sign rule of its own, any complex state, O(P^2 2^n).
+(b) ``det_rdm``: a determinant loop over the non-zero amplitudes that applies the ladder operators one at a time with the
+    Jordan-Wigner sign of each step — for sparse states at larger n.
+"""
+import itertools
+
+import numpy as np
+
+from openvqe_amd import fermion
+from oracle import masks
+
+
+def pairs(n):
+    return list(itertools.combinations(range(n), 2))
+
+
+def _index_masks(n, psum):
+    """jw_product's (x, z) masks live in qubit space (bit q = qubit q): to index-bit space (qubit q = bit n-1-q)"""
+    def flip(m):
+        return sum(1 << (n - 1 - q) for q in range(n) if (m >> q) & 1)
+    xs, zs, cs = [], [], []
+    for (x, z), c in psum.items():
+        if c != 0:
+            xs.append(flip(x))
+            zs.append(flip(z))
+            cs.append(c)
+    return xs, zs, cs
+
+
+def pauli_expectation(psi, n, ladder_ops):
+    """<psi| prod ladder_ops |psi> (complex) through the Pauli sum of the product"""
+    xs, zs, cs = _index_masks(n, fermion.jw_product(ladder_ops))
+    return np.vdot(psi, masks.apply_pauli_sum(psi, xs, zs, cs))
+
+
+def pauli_rdm(psi, n, order, upper_only=False):
+    """oracle (a).  order 1 -> (n, n); order 2 -> (P, P).  upper_only: the lower triangle stays NaN (not computed)"""
+    psi = np.asarray(psi, np.complex128)
+    if order == 1:
+        cols = [(p,) for p in range(n)]
+    else:
+        cols = pairs(n)
+    W = len(cols)
+    out = np.full((W, W), np.nan + 0j, np.complex128)
+    for i, ci in enumerate(cols):
+        for j, cj in enumerate(cols):
+            if upper_only and j < i:
+                continue
+            # a+_p a_q   /   a+_p a+_q a_s a_r
+            ops = [(p, True) for p in ci] + [(r, False) for r in reversed(cj)]
+            out[i, j] = pauli_expectation(psi, n, ops)
+    return out
+
+
+def _annihilate(det, n, orb):
+    """a_orb |det> -> (sign, det') or None; the sign counts the occupied orbitals before orb"""
+    bit = 1 << (n - 1 - orb)
+    if not det & bit:
+        return None
+    below = sum((det >> (n - 1 - t)) & 1 for t in range(orb))
+    return (-1) ** below, det & ~bit
+
+
+def det_rdm(indices, amps, n, order):
+    """oracle (b): the vectors a_q |psi> (order 1) / a_s a_r |psi> (order 2, r < s) from a loop over the determinants, one ladder operator
+    at a time; the density matrix is their matrix of inner products"""
+    cols = [(p,) for p in range(n)] if order == 1 else pairs(n)
+    col_of = {c: i for i, c in enumerate(cols)}
+    rows = {}
+    entries = []
+    for det, amp in zip(indices, amps):
+        det = int(det)
+        occ = [q for q in range(n) if (det >> (n - 1 - q)) & 1]
+        for c in (itertools.combinations(occ, order)):
+            sign, cur = 1, det
+            for orb in c:            # a_r first, then a_s
+                s, cur = _annihilate(cur, n, orb)
+                sign *= s
+            entries.append((rows.setdefault(cur, len(rows)), col_of[c], sign * amp))
+    M = np.zeros((max(len(rows), 1), len(cols)), np.complex128)
+    for r, c, v in entries:
+        M[r, c] += v
+    return M.conj().T @ M
+
+
+def expected_rows(indices, n, order):
+    """register indices that lie `order` annihilations below one of `indices`"""
+    out = set()
+    for det in indices:
+        det = int(det)
+        occ = [1 << (n - 1 - q) for q in range(n) if (det >> (n - 1 - q)) & 1]
+        for c in itertools.combinations(occ, order):
+            out.add(det & ~sum(c))
+    return len(out)
+
+
+def number_operator(n, orbs_weights):
+    """dense diagonal of sum_p w_p n_p over the register (index bit n-1-p)"""
+    idx = np.arange(1 << n)
+    d = np.zeros(1 << n)
+    for p, w in orbs_weights:
+        d += w * ((idx >> (n - 1 - p)) & 1)
+    return d
+
+
+def s2_expectation(psi, n):
+    """<S^2> = <S_z> + <S_z^2> + <S_- S_+>... built from jw_product: S_+ = sum_i a+_{2i} a_{2i+1}, S^2 = S_- S_+ + S_z + S_z^2"""
+    psi = np.asarray(psi, np.complex128)
+    m = n // 2
+    sp = np.zeros_like(psi)
+    for i in range(m):
+        xs, zs, cs = _index_masks(n, fermion.jw_product([(2 * i, True), (2 * i + 1, False)]))
+        sp += masks.apply_pauli_sum(psi, xs, zs, cs)
+    sz = 0.5 * number_operator(n, [(2 * i, 1.0) for i in range(m)] + [(2 * i + 1, -1.0) for i in range(m)])
+    return float(np.vdot(sp, sp).real + np.vdot(psi, sz * psi).real + np.vdot(psi, sz * sz * psi).real)
