@@ -6,6 +6,8 @@
 //   - the schedule: every (row, block pair) belongs to exactly one (chunk, slice, tile) and the owned columns tile a block
 //   - a replay of k_rdm_rows + k_rdm_gram + k_rdm_finish with the kernels' indexing (workspace chunks, staged 16-byte units, 256 threads
 //     with 4 x 4 accumulators, slabs per (block pair, slice) summed in slice order) against the definition, to 1e-13
+//   - the schedules of the cases A - F of tests/test_gpu_rdm_edges.py at 256 compute units: the cover of every chunk by (pair, slice,
+//     tile), the empty slices of the last launch, the trips of the grid-stride loops; block_pair / block_pair_index for 1 - 7 blocks
 //   usage: rdm_plan_check [seed]
 #include "../../openvqe_amd/csrc/sv_rdm_host.hpp"
 
@@ -143,6 +145,65 @@ static void check_schedule(const rdm::Schedule &S) {
             for (int j = 0; j < 4; ++j) ++owner[rdm::owned_column(real != 0, t, j)];
         for (int v : owner) CHECK(v == 1, "owned columns");
     }
+}
+
+// the slices of chunk c that hold no row (their workgroups return before they touch their slab)
+static std::vector<int> empty_slices(const rdm::Schedule &S, int64_t c) {
+    const int64_t cr = std::min(S.chunk_rows, S.rows - c * S.chunk_rows);
+    std::vector<int> out;
+    for (int s = 0; s < S.slices; ++s)
+        if ((int64_t)s * S.slice_rows >= cr) out.push_back(s);
+    return out;
+}
+
+// trips of k_rdm_rows' grid-stride loop over the largest chunk (grid: run_rdm), and of k_rdm_census' loop over the bitmap words
+static int64_t rows_trips(const rdm::Schedule &S, int num_cus) {
+    const uint64_t total = (uint64_t)std::min(S.chunk_rows, S.rows) * (uint64_t)S.wpad;
+    const uint64_t grid = std::min<uint64_t>((total + 255) / 256, (uint64_t)num_cus * 16u);
+    return grid ? (int64_t)((total + grid * 256 - 1) / (grid * 256)) : 0;
+}
+static int64_t census_trips(int n) {
+    const uint64_t words = rdm::bitmap_words(n), grid = std::min<uint64_t>(1024, (words + 3) / 4);
+    return (int64_t)((words + grid * 4 - 1) / (grid * 4));
+}
+
+// one case of tests/test_gpu_rdm_edges.py: what goes into plan() and what the test expects of the schedule
+struct EdgeCase {
+    const char *name;
+    int n, order;
+    bool real;
+    int64_t rows, workspace_mb;
+    int64_t chunks, last_chunk_rows;   // expected
+    int nblk, slices;
+    int64_t tiles_per_slice;
+    int empty_in_last;                 // empty slices of the last launch
+    bool rows_wrap, census_wraps;
+};
+
+static void check_edge_case(const EdgeCase &e) {
+    const int cus = 256;
+    const rdm::Schedule S = rdm::plan(e.n, e.order, e.real, e.rows, e.workspace_mb, cus);
+    check_schedule(S);
+    CHECK(S.elem_bytes == (e.real ? 8u : 16u), "%s: element size", e.name);
+    CHECK(S.nchunks == e.chunks, "%s: %lld chunks", e.name, (long long)S.nchunks);
+    CHECK(S.rows - (S.nchunks - 1) * S.chunk_rows == e.last_chunk_rows, "%s: last chunk of %lld rows", e.name,
+          (long long)(S.rows - (S.nchunks - 1) * S.chunk_rows));
+    CHECK(S.nblk == e.nblk && S.npairs == e.nblk * (e.nblk + 1) / 2, "%s: %d blocks", e.name, S.nblk);
+    CHECK(S.slices == e.slices, "%s: %d slices", e.name, S.slices);
+    CHECK(S.slice_rows == e.tiles_per_slice * S.tile_rows, "%s: %lld tiles per slice", e.name, (long long)(S.slice_rows / S.tile_rows));
+    CHECK((S.nchunks > rdm::TIMED_CHUNKS_MAX) == (e.chunks > 64), "%s: timed", e.name);
+    for (int64_t c = 0; c < S.nchunks; ++c) {
+        const std::vector<int> empty = empty_slices(S, c);
+        if (c + 1 < S.nchunks) {
+            CHECK(empty.empty(), "%s: an empty slice in the full chunk %lld", e.name, (long long)c);
+            continue;
+        }
+        CHECK((int)empty.size() == e.empty_in_last, "%s: %d empty slices in the last launch", e.name, (int)empty.size());
+        for (size_t k = 0; k < empty.size(); ++k)   // exactly the slices behind the last row
+            CHECK(empty[k] == S.slices - (int)empty.size() + (int)k, "%s: empty slice %d", e.name, empty[k]);
+    }
+    CHECK((rows_trips(S, cus) > 1) == e.rows_wrap, "%s: %lld trips of the rows kernel", e.name, (long long)rows_trips(S, cus));
+    CHECK((census_trips(e.n) > 1) == e.census_wraps, "%s: %lld trips of the census", e.name, (long long)census_trips(e.n));
 }
 
 // what k_rdm_rows, k_rdm_gram and k_rdm_finish do, index for index (REAL: 8-byte elements, the imaginary parts are not carried)
@@ -337,6 +398,30 @@ int main(int argc, char **argv) {
                 const rdm::Schedule S = rdm::plan(n, order, real != 0, 5000 + 13 * n, 1, 256);
                 check_schedule(S);
             }
+    // the cases of tests/test_gpu_rdm_edges.py (row counts: those of its seeded states), order 2 unless named otherwise
+    const EdgeCase edge_cases[] = {
+        // name            n  order real   rows    MB  chunks last blocks slices tiles/slice empty  rows wrap  census wraps
+        {"A",             14, 2, false,  16369, 1024,   1, 16369, 2, 256,  4,  0, true,  false},
+        {"A order 1",     14, 1, false,  16383, 1024,   1, 16383, 1, 256,  4,  0, false, false},
+        {"B",             14, 2, true,   16369, 1024,   1, 16369, 2, 256,  2,  0, true,  false},
+        {"C",             20, 2, true,  131981, 1024,   1, 131981, 3, 165, 25, 0, true,  true},
+        {"C'",            20, 2, false, 131981, 1024,   1, 131981, 3, 169, 49, 0, true,  true},
+        {"D",             12, 2, false,   4083,    0, 256,     3, 2,   1,  1,  0, false, false},
+        {"D one chunk",   12, 2, false,   4083, 1024,   1,  4083, 2, 256,  1,  0, false, false},
+        {"E",             13, 2, false,   1653,    1,   4,   117, 2,  32,  1, 24, false, false},
+        {"F",             24, 2, true,  138006, 1024,   1, 138006, 5,  69, 63, 0, true,  true},
+    };
+    for (const EdgeCase &e : edge_cases) check_edge_case(e);
+    for (int nblk = 1; nblk <= 7; ++nblk) {   // block_pair and block_pair_index are inverse, both ways
+        int pair = 0;
+        for (int I = 0; I < nblk; ++I)
+            for (int J = I; J < nblk; ++J, ++pair) {
+                int i, j;
+                rdm::block_pair(pair, nblk, &i, &j);
+                CHECK(i == I && j == J && rdm::block_pair_index(I, J, nblk) == pair, "block pair %d of %d blocks", pair, nblk);
+            }
+        CHECK(pair == nblk * (nblk + 1) / 2, "pairs of %d blocks", nblk);
+    }
     if (g_fail) return 1;
     std::printf("rdm plan ok\n");
     return 0;

@@ -1,10 +1,14 @@
-"""Helpers of the density-matrix tests (tests/test_rdm_host.py, tests/test_gpu_rdm.py) — not product code.  Two independent oracles
+"""Helpers of the density-matrix tests (tests/test_rdm_host.py, tests/test_gpu_rdm.py, tests/test_gpu_rdm_edges.py) — not product
+code.  Two independent oracles
 for gamma[p,q] = <a+_p a_q> and D2[(p<q),(r<s)] = <a+_p a+_q a_s a_r> (pairs in lexicographic order):
 
 (a) ``pauli_rdm``: every element as the expectation value of its ``fermion.jw_product`` Pauli sum, applied with ``oracle.masks`` —
     no fermionic sign rule of its own, any complex state, O(P^2 2^n).
 (b) ``det_rdm``: a determinant loop over the non-zero amplitudes that applies the ladder operators one at a time with the
     Jordan-Wigner sign of each step — for sparse states at larger n.
+(c) ``vec_rdm``: oracle (b) with numpy over the whole array of determinants instead of a Python loop per determinant — for dense
+    states of 14 qubits and for thousands of determinants at 20 – 24 qubits (tests/test_gpu_rdm_edges.py); pinned to (a) and (b) in
+    tests/test_rdm_host.py.
 """
 import itertools
 
@@ -85,6 +89,65 @@ def det_rdm(indices, amps, n, order):
     for r, c, v in entries:
         M[r, c] += v
     return M.conj().T @ M
+
+
+def _parity(x):
+    """popcount of every element of a uint64 array, modulo 2"""
+    x = x.copy()
+    for s in (32, 16, 8, 4, 2, 1):
+        x ^= x >> np.uint64(s)
+    return x & np.uint64(1)
+
+
+def vec_rdm(indices, amps, n, order, block_rows=1 << 14):
+    """oracle (c): what ``det_rdm`` computes, one ladder operator at a time, over all determinants at once.  For every column (an
+    orbital, or a pair r < s) and each of its orbitals in turn — a_r first, then a_s — keep the determinants that hold the orbital,
+    take the sign from the number of occupied orbitals before it and clear its bit: what is left is (row key, column, value).
+    The rows are the distinct keys (``np.unique``), M[row, column] the summed values (``np.add.at``), the result M^H M — summed over
+    blocks of ``block_rows`` rows, so that M is never held whole (135 000 rows x 276 columns at 24 qubits).
+    -> (matrix, number of distinct rows)"""
+    idx = np.asarray(indices).astype(np.uint64)
+    amps = np.asarray(amps, np.complex128)
+    cols = [(p,) for p in range(n)] if order == 1 else pairs(n)
+    keys, col_ids, vals = [], [], []
+    for j, c in enumerate(cols):
+        cur, val = idx, amps
+        for orb in c:
+            bit = np.uint64(1 << (n - 1 - orb))
+            held = (cur & bit) != 0
+            cur, val = cur[held], val[held]
+            before = cur >> np.uint64(n - orb)              # the orbitals t < orb are the index bits above bit n-1-orb
+            val = np.where(_parity(before) == 1, -val, val)
+            cur = cur & ~bit
+        keys.append(cur)
+        col_ids.append(np.full(cur.shape[0], j, np.int64))
+        vals.append(val)
+    keys, col_ids, vals = np.concatenate(keys), np.concatenate(col_ids), np.concatenate(vals)
+    rows, row_of = np.unique(keys, return_inverse=True)
+    row_of = row_of.reshape(-1)
+    by_row = np.argsort(row_of, kind="stable")
+    row_of, col_ids, vals = row_of[by_row], col_ids[by_row], vals[by_row]
+    out = np.zeros((len(cols), len(cols)), np.complex128)
+    if not vals.imag.any():
+        vals = vals.real                                    # a real state: M in doubles, half the work
+    for r0 in range(0, len(rows), block_rows):
+        r1 = min(r0 + block_rows, len(rows))
+        lo, hi = np.searchsorted(row_of, [r0, r1])
+        M = np.zeros((r1 - r0, len(cols)), vals.dtype)
+        np.add.at(M, (row_of[lo:hi] - r0, col_ids[lo:hi]), vals[lo:hi])
+        out += M.conj().T @ M
+    return out, len(rows)
+
+
+def sparse_state(n, count, seed, complex_amps=False):
+    """`count` distinct register indices drawn uniformly (no particular particle number), ascending, with normalised Gaussian
+    amplitudes (float64, or complex128 with ``complex_amps``) -> (indices, amplitudes)"""
+    rng = np.random.default_rng(seed)
+    idx = np.sort(rng.choice(1 << n, size=count, replace=False)).astype(np.int64)
+    amps = rng.normal(size=count)
+    if complex_amps:
+        amps = amps + 1j * rng.normal(size=count)
+    return idx, amps / np.linalg.norm(amps)
 
 
 def expected_rows(indices, n, order):

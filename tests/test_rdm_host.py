@@ -1,4 +1,4 @@
-"""CPU tests of the density matrices (ovqe_rdm): the two oracles of tests/rdm_cases.py against each other, the numpy helpers of
+"""CPU tests of the density matrices (ovqe_rdm): the oracles of tests/rdm_cases.py against each other, the numpy helpers of
 openvqe_amd/rdm.py against dense operators, the new symbols in header / cdef / ctypes table, and the host-side plan
 (openvqe_amd/csrc/sv_rdm_host.hpp) replayed by tests/cpu/rdm_plan_check.cpp under ASan + UBSan with g++ alone."""
 import os
@@ -40,6 +40,37 @@ def test_determinant_oracle_equals_pauli_oracle(n):
         assert np.abs(a - b).max() < 1e-14
         assert np.abs(a - a.conj().T).max() < 1e-14
         assert rdm_cases.expected_rows(idx, n, order) == (1 << n) - sum(1 for k in idx if n - bin(k).count("1") < order)
+
+
+@pytest.mark.parametrize("n", [4, 6])
+def test_vectorised_oracle_equals_both_oracles(n):
+    """vec_rdm (the oracle of the large GPU cases) on a random complex state: every element against the Pauli sums and against the
+    determinant loop, and its row count against the set of shadows"""
+    psi = _random_state(n, 300 + n)
+    idx = np.arange(1 << n)
+    for order in (1, 2):
+        got, rows = rdm_cases.vec_rdm(idx, psi, n, order)
+        a = rdm_cases.pauli_rdm(psi, n, order)
+        b = rdm_cases.det_rdm(idx, psi, n, order)
+        assert got.shape == a.shape
+        assert np.abs(got - a).max() < 1e-14 and np.abs(got - b).max() < 1e-14
+        assert rows == rdm_cases.expected_rows(idx, n, order)
+        small, rows_small = rdm_cases.vec_rdm(idx, psi, n, order, block_rows=5)      # several row blocks, a short last one
+        assert rows_small == rows and np.abs(small - a).max() < 1e-14
+
+
+@pytest.mark.parametrize("complex_amps", [False, True])
+def test_vectorised_oracle_on_a_sparse_state(complex_amps):
+    """n = 10, 60 determinants of no particular particle number: the signs of orbitals far apart, rows shared by few determinants"""
+    n = 10
+    idx, amps = rdm_cases.sparse_state(n, 60, 77, complex_amps)
+    assert len(set(bin(int(i)).count("1") for i in idx)) > 3
+    for order in (1, 2):
+        got, rows = rdm_cases.vec_rdm(idx, amps, n, order)
+        want = rdm_cases.det_rdm(idx, amps, n, order)
+        assert np.abs(got - want).max() < 1e-14
+        assert rows == rdm_cases.expected_rows(idx, n, order)
+        assert (np.abs(got.imag).max() > 0) == complex_amps
 
 
 def test_unpack_antisymmetry(six):
