@@ -469,7 +469,13 @@ int ovqe_last_batch_ms(ovqe_handle h, double *ms);
  * (batches <= 256), 1 / 2 one evaluation per wave with / without its op table staged in LDS, 3 two per wave on rows of 64-bit
  * words (batches >= 2048), 4 / 5 two / four per wave without rows; 6 / 7 / 8 ovqe_energy_gradient per workgroup / per wave
  * staged / per wave; 9 a call that wanted the path was served by the other paths (no compact support, or no form fits the
- * program's LDS budget) */
+ * program's LDS budget).  which = 8..13: the most recent launch of the fused whole-circuit kernel (registers up to 16 qubits) since
+ * the program was set, zeros when there was none.  8: its form as bits — 0 real amplitudes, 1 state in LDS (else one global slice per
+ * workgroup), 2-3 threads per workgroup (0 = 64, 1 = 256, 2 = 1024), 4 parameters and energies through the mapped buffer, 5 result
+ * polled in that buffer, 6 device-resident entry point (ovqe_energy_batch_device).  9: workgroups launched (below B: a workgroup
+ * takes several evaluations in turn).  10: segments of the program (runs of ops whose entries fit the LDS cos/sin table).
+ * 11: chunks the terms of the general expectation entries are staged in.  12: general (x-group, pattern) entries.  13: flat
+ * single-term items */
 int ovqe_last_support(ovqe_handle h, int32_t which, int64_t *support);
 /* shape of the compiled program (diagnostics / tests), up to `count` entries of:
  *   [0] ops of the sequential program  [1] Pauli rotations  [2] literal X/H/CNOT ops  [3] streaming sweeps per

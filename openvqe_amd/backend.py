@@ -491,6 +491,19 @@ class Statevector:
         self._ck(self._L.ovqe_last_support(self._h, 7, ctypes.byref(out)))
         return {name for bit, name in enumerate(self.SPARSE_GEOMETRIES) if (out.value >> (10 + bit)) & 1}
 
+    def fused_launch(self):
+        """the most recent launch of the fused whole-circuit kernel on this handle since its program was set (ovqe_last_support,
+        which = 8..13) -> dict; ``launched`` is False, and every count 0, when there was none"""
+        v = []
+        for which in range(8, 14):
+            out = ctypes.c_int64()
+            self._ck(self._L.ovqe_last_support(self._h, which, ctypes.byref(out)))
+            v.append(out.value)
+        bits = v[0]
+        return {"launched": v[1] > 0, "real": bool(bits & 1), "lds_state": bool(bits & 2), "threads": (64, 256, 1024, 0)[(bits >> 2) & 3],
+                "mapped_io": bool(bits & 16), "polled": bool(bits & 32), "device_entry": bool(bits & 64), "form_bits": bits,
+                "workgroups": v[1], "segments": v[2], "exp_chunks": v[3], "exp_entries": v[4], "flat_items": v[5]}
+
     def last_exp_support(self):
         """amplitudes the Taylor steps of the last ``apply_exp_pauli_sum`` call ran over (-1: the register)"""
         out = ctypes.c_int64()

@@ -36,6 +36,7 @@ int ovqe_set_program(ovqe_handle h, int64_t R, const uint64_t *x, const uint64_t
     OVQE_ENTER(h);
     if (h) h->prog_from_gates = false;
     if (h) h->forms_used = h->sp_forms = 0;
+    if (h) std::fill(h->fused_launch, h->fused_launch + 6, 0);
     if (!h || R < 0 || K < 0 || (R && (!x || !z || !coeff || !pidx))) return OVQE_ERR_INVALID;
     const int ntot = h->n_local + h->n_global;
     const uint64_t allmask = ntot >= 64 ? ~0ull : ((1ull << ntot) - 1ull);
@@ -91,6 +92,7 @@ int ovqe_set_gate_program(ovqe_handle h, int64_t G, const int32_t *opcode, const
     h->prog_from_gates = false;
     h->prog_extends_prev = false;
     h->forms_used = h->sp_forms = 0;
+    std::fill(h->fused_launch, h->fused_launch + 6, 0);
     h->prev_x.clear();
     if (h->opt_clifford_frame) {
         bool done = false;

@@ -221,6 +221,8 @@ int build_exp_tables(ovqe_handle h, int lbits, bool real) {
     std::vector<ExpTerm> et;
     std::vector<FlatItem> flat;
     const int n = h->n_local;
+    // terms the LDS staging area (the idle rotation table) holds
+    const int stage_cap = (int)((size_t)h->cs_capacity * sizeof(RotLds) / sizeof(ExpTerm));
     auto squeeze = [](uint64_t z, const int *pos, int np) {  // remove the bit positions pos[] (ascending)
         for (int f = np - 1; f >= 0; --f) {
             const uint64_t low = (1ull << pos[f]) - 1ull;
@@ -248,22 +250,26 @@ int build_exp_tables(ovqe_handle h, int lbits, bool real) {
             }
             return;
         }
-        ExpGroup out = {};
-        out.x = x;
-        out.ibits = ibits;
-        out.fixmask = 0;
-        for (int f = 0; f < np; ++f) out.fixmask |= 1u << pos[f];
-        out.t0 = (int32_t)et.size();
-        std::vector<ExpTerm> bucket[8];
-        for (const ExpTerm &e : list) bucket[(e.zk >> lbits) & 7].push_back(e);
-        int off = 0;
-        for (int b = 0; b < 8; ++b) {
-            out.off[b] = off;
-            for (const ExpTerm &e : bucket[b]) et.push_back(e);
-            off += (int)bucket[b].size();
+        // a list longer than the staging area becomes consecutive entries with the same pairs: the expectation is linear in the terms
+        for (size_t l0 = 0; l0 < list.size(); l0 += (size_t)stage_cap) {
+            const size_t l1 = std::min(list.size(), l0 + (size_t)stage_cap);
+            ExpGroup out = {};
+            out.x = x;
+            out.ibits = ibits;
+            out.fixmask = 0;
+            for (int f = 0; f < np; ++f) out.fixmask |= 1u << pos[f];
+            out.t0 = (int32_t)et.size();
+            std::vector<ExpTerm> bucket[8];
+            for (size_t l = l0; l < l1; ++l) bucket[(list[l].zk >> lbits) & 7].push_back(list[l]);
+            int off = 0;
+            for (int b = 0; b < 8; ++b) {
+                out.off[b] = off;
+                for (const ExpTerm &e : bucket[b]) et.push_back(e);
+                off += (int)bucket[b].size();
+            }
+            out.off[8] = off;
+            eg.push_back(out);
         }
-        out.off[8] = off;
-        eg.push_back(out);
     };
     for (const HGroup &g : h->ham.groups) {
         const uint64_t x = g.x;
@@ -337,14 +343,12 @@ int build_exp_tables(ovqe_handle h, int lbits, bool real) {
             emit((uint32_t)x, (uint32_t)ibits, pos, np, nz, &nzc);
         }
     }
-    // chunks of general groups whose terms fit the LDS staging area (the idle rotation table)
-    const int stage_cap = (int)((size_t)h->cs_capacity * sizeof(RotLds) / sizeof(ExpTerm));
+    // chunks of general groups whose terms fit the LDS staging area (no entry is longer than it: emit)
     std::vector<ExpChunk> chunks;
     {
         ExpChunk cur = {0, 0, 0, 0};
         for (int g = 0; g < (int)eg.size(); ++g) {
             const int gt1 = eg[g].t0 + eg[g].off[8];
-            if (eg[g].off[8] > stage_cap) return fail(h, OVQE_ERR_INVALID, "x-group with too many terms for the fused kernel");
             if (gt1 - cur.t0 > stage_cap) {
                 if (cur.g1 > cur.g0) chunks.push_back(cur);
                 cur = {g, g, eg[g].t0, eg[g].t0};
@@ -451,6 +455,13 @@ int run_small(ovqe_handle h, int64_t B, const double *theta, double *energies, b
         else rc = launch_small<false, true, 64, 6>(h, A, grid, smem);
     }
     if (rc) return rc;
+    h->fused_launch[0] = (real ? 1 : 0) | (lds_state ? 2 : 0) | ((nt == 1024 ? 2 : (nt == 256 ? 1 : 0)) << 2) | (zero_copy ? 16 : 0) |
+                         (poll ? 32 : 0) | (on_device ? 64 : 0);
+    h->fused_launch[1] = grid;
+    h->fused_launch[2] = A.nsegs;
+    h->fused_launch[3] = A.nchunks;
+    h->fused_launch[4] = A.ngroups;
+    h->fused_launch[5] = A.nflat;
     if (zero_copy) {
         if (!poll || !poll_mapped_slots(h->h_io + (size_t)B * h->K, B)) HIPC(h, hipStreamSynchronize(h->stream));
         std::memcpy(energies, h->h_io + (size_t)B * h->K, (size_t)B * sizeof(double));

@@ -373,6 +373,9 @@ struct ovqe_sv {
     uint32_t forms_used = 0;
     // ... and of the support-compacted path (ovqe_last_support which = 7, SPF_* in sparse_host.inc)
     uint32_t sp_forms = 0;
+    // ... and what the most recent k_small_vqe launch since then was (ovqe_last_support which = 8..13, run_small): form bits, workgroups,
+    // segments, expectation chunks, general (group, pattern) entries, flat items; zeros when there was none
+    int64_t fused_launch[6] = {0, 0, 0, 0, 0, 0};
     bool nz_super = false, nz_super_prev = false, state_exposed = false;
     uint64_t nz_super_count = 0;
     DevBuf d_tile_smasks, d_tile_lists, d_tile_counts;   // non-empty tiles per sweep of H psi on a listed state (k_tile_lists)  // support list of the screened state (k_pool_grad_nz)
@@ -1613,10 +1616,10 @@ int ovqe_get_rotation_program(ovqe_handle h, int64_t capacity, uint64_t *x, uint
 
 int ovqe_last_support(ovqe_handle h, int32_t which, int64_t *support) try {
     OVQE_ENTER(h);
-    if (!h || !support || which < 0 || which > 7) return OVQE_ERR_INVALID;
+    if (!h || !support || which < 0 || which > 13) return OVQE_ERR_INVALID;
     const int64_t v[8] = {h->last_screen_support, h->last_exp_support, h->last_screen_sector, h->last_fci_rounds, h->last_passes, h->last_pass_bytes,
                           (int64_t)h->forms_used, (int64_t)h->sp_forms};
-    *support = v[which];
+    *support = which < 8 ? v[which] : h->fused_launch[which - 8];
     return OVQE_OK;
 } OVQE_CATCH(h)
 

@@ -444,7 +444,20 @@ def test_index_streams_match_in_kernel_indices(SV):
         for level in (1, 0):
             sv.set_option("index_streams", level)
             out[level] = sv.energy_batch(thetas)
+        # 441 determinants: both settings above ran the support-compacted kernel.  The fused dense kernel (force_path = 1) is what
+        # reads the streams: small_pass_tab_stream against small_pass_tab
+        assert not sv.fused_launch()["launched"]
+        sv.set_option("force_path", 1)
+        for level in (1, 0):
+            sv.set_option("index_streams", level)
+            out["fused", level] = sv.energy_batch(thetas)
+            f = sv.fused_launch()
+            assert f["launched"] and f["real"] and f["lds_state"] and f["threads"] == 1024 and f["form_bits"] & 0xf == 0xb
+            info = sv.program_info()
+            assert info["fused_ops"] < info["rotations"]       # the runs are table ops
     assert np.abs(out[1] - out[0]).max() < 1e-10
+    assert np.abs(out["fused", 1] - out["fused", 0]).max() < 1e-10
+    assert np.abs(out["fused", 1] - out[1]).max() < 1e-10
 
 
 def test_sharded_statevector_single_rank_hip_engine(gpu_lib):
@@ -527,7 +540,15 @@ def test_batched_path_above_lds_capacity(SV, n):
         sv.set_ucc_program(gens, hf)
         batch = sv.energy_batch(thetas)        # B = 40 >= 32: fused kernel
         single = np.array([sv.energy(t) for t in thetas[:3]])   # streaming kernels
+        # a program with a compact support is served by the support-compacted kernel before the fused one is asked: force_path = 1
+        # is what launches the instance with the state in a global slice per workgroup
+        sv.set_option("force_path", 1)
+        fused = sv.energy_batch(thetas)
+        f = sv.fused_launch()
+        assert f["launched"] and not f["lds_state"] and f["threads"] == 1024 and f["workgroups"] == 40
+        assert f["form_bits"] & 0xe == 0x8     # no LDS state, 1024 threads
     assert np.abs(batch[:3] - single).max() < 1e-10 * max(1.0, np.abs(cs).sum())
+    assert np.abs(fused - batch).max() < 1e-10 * max(1.0, np.abs(cs).sum())
     psi = np.zeros(1 << n, complex)
     psi[hf] = 1
     for g, th in zip(gens, thetas[0]):
@@ -535,6 +556,7 @@ def test_batched_path_above_lds_capacity(SV, n):
             x, z = masks.pack_pauli(n, t.op, t.qbits)
             psi = masks.rotate(psi, x, z, th * t.coeff)
     assert abs(batch[0] - masks.expectation(psi, xs, zs, cs.real, ham.constant_coeff)) < 1e-10 * max(1.0, np.abs(cs).sum())
+    assert abs(fused[0] - masks.expectation(psi, xs, zs, cs.real, ham.constant_coeff)) < 1e-10 * max(1.0, np.abs(cs).sum())
 
 
 def test_device_resident_batches_and_sparse_fallbacks(SV):
