@@ -910,8 +910,28 @@ def test_planned_cross_shard_sums_against_oracle(SV, n, g, chunk_bits):
         assert abs(total - want_e) < 1e-11 * l1
         got_sigma = np.concatenate([o.cpu().numpy() for o in outs])
         assert np.abs(got_sigma - want_sigma).max() < 1e-11 * l1
-        # complex coefficients: sigma only; an expectation value of a non-Hermitian sum is refused
+        # complex coefficients: sigma only — the whole sum over every partner and chunk, and the four diagonal strings alone ...
+        ccs = cs * (1.0 + 0.5j)
+        couts = [torch.full((1 << nl,), 7.0, dtype=torch.complex128, device="cuda") for _ in range(W)]     # (apply_local overwrites)
+        for s, sv in enumerate(shards):
+            csid = sv.xsum_create(xs, zs, ccs, chunk_bits)
+            sv.xsum_apply_local(csid, couts[s].data_ptr(), 0.3)
+            for d, _ in sv.xsum_partners(csid):
+                for c in range(1 << (nl - chunk_bits)):
+                    sv.xsum_apply_remote(csid, d, c, bufs[s ^ d][c * csize:(c + 1) * csize].data_ptr(), couts[s].data_ptr())
+            sv.xsum_destroy(csid)
+        torch.cuda.synchronize()
+        want_csigma = 0.3 * psi + masks.apply_pauli_sum(psi, xs, zs, ccs)
+        assert np.abs(np.concatenate([o.cpu().numpy() for o in couts]) - want_csigma).max() < 1e-11 * float(np.abs(ccs).sum())
         sid = shards[0].xsum_create(xs[:4], zs[:4], cs[:4] * (1.0 + 0.5j), chunk_bits)
+        assert shards[0].xsum_partners(sid) == []
+        shards[0].xsum_apply_local(sid, couts[0].data_ptr(), 0.0)
+        torch.cuda.synchronize()
+        want_diag = masks.apply_pauli_sum(psi, xs[:4], zs[:4], cs[:4] * (1.0 + 0.5j))[:1 << nl]
+        assert np.abs(couts[0].cpu().numpy() - want_diag).max() < 1e-11 * float(np.abs(cs[:4] * (1.0 + 0.5j)).sum())
+        for b, psi_s in zip(bufs, np.split(psi, W)):
+            assert np.array_equal(b.cpu().numpy(), psi_s)            # the states were only read
+        # ... while an expectation value of a non-Hermitian sum is refused
         with pytest.raises(BackendError, match="complex coefficients"):
             shards[0].xsum_expect_local(sid)
         with pytest.raises(BackendError, match="bits beyond the register"):
