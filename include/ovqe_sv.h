@@ -496,7 +496,14 @@ int ovqe_last_support(ovqe_handle h, int32_t which, int64_t *support);
  *   the register that the reference's QUCCSD templates populate; option "sector_regular", default 1): slot bits of a circuit
  *   tile — the sweeps then run from bit arithmetic, without pair words — and the number of free (dependent) index bits; 0 else
  *   [30..32] support-compacted program, batched workgroup kernel (0 when no instance of it holds the program): owner pieces of the
- *   restricted Hamiltonian that hold entries, entry slots per thread, LDS reads per thread and state of the <H> contraction */
+ *   restricted Hamiltonian that hold entries, entry slots per thread, LDS reads per thread and state of the <H> contraction
+ *   [33..37] support-compacted program: LDS array cycles per evaluation by the host planner's bank model (an access of 32 lanes
+ *   costs, per group of lanes it is served in, the largest number of distinct 8-byte words on one bank: reads one group of 32
+ *   against 32 banks, writes two groups of 16 against 16; conflict-free: 1 and 2) — [33] the reads and [34] the writes of both
+ *   amplitudes over the rows of 32 lanes of the circuit with the tables in use, [35] the slot and owner reads of the <H>
+ *   contraction of the batched workgroup kernel (0 when no instance holds the program), [36] / [37] the reads / writes of the
+ *   rows with the support numbered in discovery order, pairs in list order.  The rows the kernel adds to fill its pipeline
+ *   (conflict-free by construction) are not counted */
 int ovqe_program_info(ovqe_handle h, int64_t *info, int count);
 /* The stored program as its sequence of Pauli rotations exp(-i (coeff[r] theta[pidx[r]] + phi0[r]) P_r), P_r = (x[r], z[r]) in
  * index-bit space, in execution order (pidx < 0: a constant angle) — for a gate program in Clifford-frame form

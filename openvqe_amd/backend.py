@@ -570,15 +570,17 @@ class Statevector:
     def program_info(self):
         """shape of the compiled program: ops, rotations, literal gates, sweeps per evaluation, tiled sweeps,
         fused-kernel ops, support size (-1 = not analysed yet)"""
-        out = (ctypes.c_int64 * 33)()
-        self._ck(self._L.ovqe_program_info(self._h, out, 33))
+        out = (ctypes.c_int64 * 38)()
+        self._ck(self._L.ovqe_program_info(self._h, out, 38))
         keys = ("ops", "rotations", "literal_gates", "sweeps", "tiled_sweeps", "fused_ops", "support",
                 "h_tile_sweeps", "h_untiled_groups", "h_entries", "h_merged_terms", "h_pair_terms_per_tile",
                 "real_stream", "sp_ops", "sp_pairs", "sp_h_entries",
                 "sector_support", "sector_sweeps", "sector_pairs", "sector_h_sweeps", "sector_h_elements", "sector_bytes",
                 "sector_circuit_us", "sector_expect_us", "sector_h_stream_bytes", "sector_fci_block",
                 "sp_conflicts_discovery_order", "sp_conflicts", "sector_regular_slot_bits", "sector_free_bits",
-                "sp_h_pieces", "sp_h_slots", "sp_h_reads_per_state")
+                "sp_h_pieces", "sp_h_slots", "sp_h_reads_per_state",
+                "sp_lds_row_reads", "sp_lds_row_writes", "sp_lds_h_reads",
+                "sp_lds_row_reads_discovery_order", "sp_lds_row_writes_discovery_order")
         return dict(zip(keys, [int(v) for v in out]))
 
     def rotation_program(self):

@@ -343,6 +343,9 @@ struct ovqe_sv {
     int sp_nrows8 = 0;            // rows of 64 of the latency kernel (multiple of eight; 0: not built)
     int sp_mp = 0, sp_hf = 0;     // slots of the compact state (support padded to a multiple of 32 when renumbered), slot of |hf>
     int64_t sp_conflicts_before = 0, sp_conflicts_after = 0;   // colliding lane pairs per evaluation, discovery order / renumbered
+    // modelled LDS array cycles per evaluation (sparse_plan.hpp): row reads, row writes, <H> contraction reads of the tables in use;
+    // row reads, row writes of plain rows in discovery order
+    int64_t sp_cycles[5] = {0, 0, 0, 0, 0};
     int64_t sp_npairs = 0;
     DevBuf d_sp_ops, d_sp_pairs, d_sp_entries;
     // the entries as owner pieces for k_sparse_vqe_rows_shared (sparse_pack.hpp): the instance they were packed for (index into
@@ -1588,6 +1591,7 @@ int ovqe_program_info(ovqe_handle h, int64_t *info, int count) try {
     const int64_t pv[3] = {packed ? (int64_t)h->sp_h_pieces : 0, packed ? (int64_t)h->sp_h_rpt * h->sp_h_epr : 0,
                            packed ? (int64_t)h->sp_h_rpt * (h->sp_h_epr + 1) : 0};
     for (int i = 30; i < count && i < 33; ++i) info[i] = pv[i - 30];
+    for (int i = 33; i < count && i < 38; ++i) info[i] = h->sp_valid ? h->sp_cycles[i - 33] : 0;
     return OVQE_OK;
 } OVQE_CATCH(h)
 

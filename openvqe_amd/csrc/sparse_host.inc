@@ -93,224 +93,21 @@ int build_sparse_program(ovqe_handle h) {
             if (entries.size() > (size_t)16 << 20) return OVQE_OK;
         }
     }
-    // ---- compact numbering against LDS bank conflicts in the circuit (round 3) ---------------------------------------------------
-    // The lanes of an evaluation rotate the (up to 32) pairs of an op with ONE ds_read_b64 per member: 32 lanes against 32
-    // bank pairs, bank = compact index mod 32.  In discovery order the members of an op collide (rocprofv3: 55 % of the LDS
-    // cycles of k_sparse_vqe were conflict replays).  The numbering is the host's to choose: residues mod 32 are assigned by
-    // a deterministic local search (swap two elements' residues, keep the swap when the sum over ops and sides of the
-    // colliding lane pairs does not grow, with a little annealing) and the support is padded to a multiple of 32 slots.
-    int mp = m, hf_slot = 0;
-    h->sp_conflicts_before = h->sp_conflicts_after = 0;
-    if (h->opt_sparse_renumber && m > 32 && m <= 4064 && !ops.empty()) {
-        const int nh = 2 * (int)ops.size();
-        const int rows = (m + 31) / 32;
-        std::vector<std::array<uint16_t, 32>> hist((size_t)nh);
-        for (auto &a : hist) a.fill(0);
-        std::vector<int> cap((size_t)nh);
-        std::vector<std::vector<int>> inc((size_t)m);
-        for (size_t o = 0; o < ops.size(); ++o) {
-            cap[2 * o] = cap[2 * o + 1] = (ops[o].npairs + 31) / 32;
-            for (int k = 0; k < ops[o].npairs; ++k) {
-                const uint32_t pw = pairs[(size_t)ops[o].first + k];
-                inc[pw & 0xfffu].push_back((int)(2 * o));
-                inc[(pw >> 12) & 0xfffu].push_back((int)(2 * o + 1));
-            }
-        }
-        std::vector<int> res((size_t)m), count(32, 0);
-        for (int k = 0; k < m; ++k) {
-            res[k] = k & 31;
-            ++count[k & 31];
-            for (int hid : inc[k]) ++hist[hid][k & 31];
-        }
-        auto excess = [](int n, int c) { return n > c ? (int64_t)(n - c) * (n - c + 1) / 2 : (int64_t)0; };
-        int64_t cost = 0;
-        for (int hid = 0; hid < nh; ++hid)
-            for (int r = 0; r < 32; ++r) cost += excess(hist[hid][r], cap[hid]);
-        h->sp_conflicts_before = cost;
-        auto move = [&](int e, int to) {   // -> change of the cost
-            const int from = res[e];
-            int64_t d = 0;
-            for (int hid : inc[e]) {
-                auto &hh = hist[hid];
-                d += excess(hh[from] - 1, cap[hid]) - excess(hh[from], cap[hid]) + excess(hh[to] + 1, cap[hid]) - excess(hh[to], cap[hid]);
-                --hh[from];
-                ++hh[to];
-            }
-            res[e] = to;
-            return d;
-        };
-        size_t total_inc = 0;
-        for (const auto &v : inc) total_inc += v.size();
-        const double avg_inc = std::max(1.0, (double)total_inc / m);
-        const int64_t proposals = cost ? (int64_t)std::min(400.0 * m, 6e7 / avg_inc) : 0;
-        uint64_t rng = 0x9e3779b97f4a7c15ull;
-        auto next = [&]() {
-            rng ^= rng << 13;
-            rng ^= rng >> 7;
-            rng ^= rng << 17;
-            return rng;
-        };
-        for (int64_t it = 0; it < proposals && cost > 0; ++it) {
-            const double temp = 0.6 * (1.0 - (double)it / (double)proposals) + 0.02;
-            const int a = (int)(next() % (uint64_t)m);
-            int64_t d;
-            int b = -1, ra = res[a], rb;
-            if ((next() & 3u) == 0) {                       // move into a residue class with a free slot
-                rb = (int)(next() & 31u);
-                if (rb == ra || count[rb] >= rows) continue;
-                d = move(a, rb);
-            } else {                                        // swap residues with another element
-                b = (int)(next() % (uint64_t)m);
-                rb = res[b];
-                if (rb == ra) continue;
-                d = move(a, rb);
-                d += move(b, ra);
-            }
-            const bool accept = d <= 0 || (double)(next() >> 11) * (1.0 / 9007199254740992.0) < std::exp(-(double)d / temp);
-            if (accept) {
-                cost += d;
-                if (b < 0) {
-                    --count[ra];
-                    ++count[rb];
-                }
-            } else {
-                move(a, ra);
-                if (b >= 0) move(b, rb);
-            }
-        }
-        h->sp_conflicts_after = cost;
-        // slots: residue + 32 * (rank inside the residue class, by discovery order)
-        std::vector<int> slot((size_t)m), fill(32, 0);
-        for (int k = 0; k < m; ++k) slot[k] = res[k] + 32 * fill[res[k]]++;
-        mp = 32 * rows;
-        hf_slot = slot[0];
-        for (uint32_t &pw : pairs)
-            pw = (pw & ~0xffffffu) | (uint32_t)slot[pw & 0xfffu] | ((uint32_t)slot[(pw >> 12) & 0xfffu] << 12);
-        for (SpEntry &e : entries) e.ij = (uint32_t)slot[e.ij & 0xfffu] | ((uint32_t)slot[(e.ij >> 12) & 0xfffu] << 12);
-        // (chunks of 32 are split into two halves of 16 below, for the stores)
-        // ops with more than 32 pairs: chunks of 32 with distinct residues on both sides where the pairs allow it
-        for (const SpOp &so : ops) {
-            if (so.npairs <= 32) continue;
-            std::vector<uint32_t> left(pairs.begin() + so.first, pairs.begin() + so.first + so.npairs), out;
-            out.reserve(left.size());
-            while (!left.empty()) {
-                uint32_t ui = 0, uj = 0;
-                std::vector<uint32_t> rest;
-                size_t taken = 0;
-                for (uint32_t pw : left) {
-                    const uint32_t bi = pw & 31u, bj = (pw >> 12) & 31u;
-                    if (taken < 32 && !((ui >> bi) & 1u) && !((uj >> bj) & 1u)) {
-                        ui |= 1u << bi;
-                        uj |= 1u << bj;
-                        out.push_back(pw);
-                        ++taken;
-                    } else {
-                        rest.push_back(pw);
-                    }
-                }
-                while (taken < 32 && !rest.empty()) {   // pad the chunk so that later chunks stay aligned
-                    out.push_back(rest.back());
-                    rest.pop_back();
-                    ++taken;
-                }
-                left.swap(rest);
-            }
-            std::copy(out.begin(), out.end(), pairs.begin() + so.first);
-        }
-        // The two ds_write_b64 of a rotation are served in groups of 16 lanes against 16 bank pairs (bank = slot mod 16): inside
-        // every chunk of 32 pairs the two halves of 16 are chosen so that slots equal mod 16 — at most two per side once the
-        // residues mod 32 are distinct — fall into different halves (twins on the first and on the second index form paths and
-        // even cycles: two-colourable; greedy here, balanced halves).
-        for (const SpOp &so : ops) {
-            for (int c0 = 0; c0 < so.npairs; c0 += 32) {
-                const int cn = std::min(32, so.npairs - c0);
-                if (cn <= 1) continue;
-                uint32_t *pw = pairs.data() + so.first + c0;
-                std::vector<uint32_t> half[2];
-                int cnt_i[2][16] = {}, cnt_j[2][16] = {};
-                const int cap0 = std::min(16, cn), cap1 = cn - std::min(16, cn) < 0 ? 0 : 16;
-                (void)cap1;
-                for (int k = 0; k < cn; ++k) {
-                    const uint32_t bi = pw[k] & 15u, bj = (pw[k] >> 12) & 15u;
-                    const int c0s = cnt_i[0][bi] + cnt_j[0][bj], c1s = cnt_i[1][bi] + cnt_j[1][bj];
-                    int side = c0s < c1s ? 0 : (c1s < c0s ? 1 : (half[0].size() <= half[1].size() ? 0 : 1));
-                    if ((int)half[side].size() >= 16) side ^= 1;
-                    if (side == 0 && (int)half[0].size() >= cap0) side = 1;
-                    half[side].push_back(pw[k]);
-                    ++cnt_i[side][bi];
-                    ++cnt_j[side][bj];
-                }
-                // lanes 0..15 take half 0; when half 0 is short of 16 and half 1 not empty the chunk stays contiguous: pad from half 1
-                while (half[0].size() < 16 && !half[1].empty()) {
-                    half[0].push_back(half[1].back());
-                    half[1].pop_back();
-                }
-                int k = 0;
-                for (uint32_t w : half[0]) pw[k++] = w;
-                for (uint32_t w : half[1]) pw[k++] = w;
-            }
-        }
+    // ---- compact numbering, lanes and orientation against LDS bank conflicts in the circuit: the planner (sparse_plan.hpp) -----------
+    // The lanes of an evaluation rotate the (up to 32) pairs of an op with ONE ds_read_b64 per member and one ds_write_b64 each; which
+    // banks they meet on is the host's to choose.  The entries of the restricted Hamiltonian follow the numbering.
+    SparsePlan plan;
+    {
+        std::vector<PlanOp> pops;
+        for (const SpOp &so : ops) pops.push_back({so.first, so.npairs});
+        plan_sparse_program(m, pops, pairs, h->opt_sparse_renumber != 0, &plan);
     }
-    // LDS bank conflicts: a wave reads the two amplitudes of 64 consecutive entries at once (ds_read_b64 is served in two
-    // 32-lane groups, bank = double slot mod 32).  The entries are a plain sum, so their order is free: they are
-    // re-arranged greedily so that inside every aligned group of 32 the first indices are distinct mod 32 and so are the
-    // second ones — conflict-free reads wherever the entry set allows it (a fixed order: results stay reproducible).
-    if (entries.size() > 64) {
-        std::vector<std::vector<uint32_t>> by_bank(32);
-        for (uint32_t e = 0; e < (uint32_t)entries.size(); ++e) by_bank[entries[e].ij & 31u].push_back(e);
-        std::vector<SpEntry> arranged;
-        arranged.reserve(entries.size());
-        size_t left = entries.size();
-        std::vector<uint32_t> order(32);
-        while (left) {
-            std::iota(order.begin(), order.end(), 0u);
-            std::stable_sort(order.begin(), order.end(),
-                             [&](uint32_t a, uint32_t b) { return by_bank[a].size() > by_bank[b].size(); });
-            uint32_t used_j = 0;
-            size_t taken = 0;
-            for (uint32_t bi : order) {
-                std::vector<uint32_t> &lst = by_bank[bi];
-                if (lst.empty()) continue;
-                size_t pick = lst.size();
-                for (size_t k = lst.size(); k-- > 0;) {           // newest first: cheap erase
-                    const uint32_t bj = (entries[lst[k]].ij >> 12) & 31u;
-                    if (!((used_j >> bj) & 1u)) {
-                        pick = k;
-                        break;
-                    }
-                }
-                if (pick == lst.size()) continue;                 // every candidate collides on the second index
-                used_j |= 1u << ((entries[lst[pick]].ij >> 12) & 31u);
-                arranged.push_back(entries[lst[pick]]);
-                lst.erase(lst.begin() + (long)pick);
-                ++taken;
-                --left;
-            }
-            if (taken == 0) {                                     // only colliding entries remain: take one anyway
-                for (auto &lst : by_bank)
-                    if (!lst.empty()) {
-                        arranged.push_back(entries[lst.back()]);
-                        lst.pop_back();
-                        --left;
-                        break;
-                    }
-            }
-            // pad the group to 32 with whatever is left so that later groups stay aligned
-            while (taken && taken < 32 && left) {
-                bool any = false;
-                for (auto &lst : by_bank)
-                    if (!lst.empty() && taken < 32) {
-                        arranged.push_back(entries[lst.back()]);
-                        lst.pop_back();
-                        --left;
-                        ++taken;
-                        any = true;
-                    }
-                if (!any) break;
-            }
-        }
-        entries.swap(arranged);
-    }
+    pairs.swap(plan.pairs);
+    const int mp = plan.mp, hf_slot = plan.slot[0];
+    h->sp_conflicts_before = plan.conflicts_discovery;
+    h->sp_conflicts_after = plan.conflicts;
+    for (SpEntry &e : entries) e.ij = (uint32_t)plan.slot[e.ij & 0xfffu] | ((uint32_t)plan.slot[(e.ij >> 12) & 0xfffu] << 12);
+    arrange_entries(entries);   // (the entry stream of the per-wave kernels)
     // rows of 32 padded 64-bit words for the throughput kernel (k_sparse_vqe_rows): only when every byte offset fits 16 bits
     std::vector<uint64_t> rows;
     h->sp_nrows4 = 0;
@@ -346,18 +143,19 @@ int build_sparse_program(ovqe_handle h) {
             return (uint64_t)((uint32_t)(mp + lane) * 8u) | ((uint64_t)((uint32_t)(mp + 32 + lane) * 8u) << 16) |
                    ((uint64_t)((uint32_t)nprim * 16u) << 32);
         };
+        size_t at = 0;   // the planner's rows: those of an op in a block, ops in order
         for (const SpOp &so : ops)
             for (int c0 = 0; c0 < so.npairs; c0 += 32)
                 for (int lane = 0; lane < 32; ++lane) {
-                    if (c0 + lane >= so.npairs) {
-                        rows.push_back(pad_word(lane));
+                    const RowLane &rl = plan.rows[at++];
+                    const uint64_t slots = (uint64_t)(rl.si * 8u) | ((uint64_t)(rl.sj * 8u) << 16);
+                    if (rl.pair < 0) {
+                        rows.push_back(slots | ((uint64_t)((uint32_t)nprim * 16u) << 32));
                         continue;
                     }
-                    const uint32_t pw = pairs[(size_t)so.first + c0 + lane];
-                    const uint32_t ci = pw & 0xfffu, cj = (pw >> 12) & 0xfffu, ent = (uint32_t)so.tab0 + (pw >> 25);
-                    const bool neg = ((pw >> 24) & 1u) != (uint32_t)prim_neg[ent];
-                    rows.push_back((uint64_t)(ci * 8u) | ((uint64_t)(cj * 8u) << 16) | ((uint64_t)((uint32_t)prim_of[ent] * 16u) << 32) |
-                                   (neg ? (1ull << 63) : 0ull));
+                    const uint32_t pw = pairs[(size_t)rl.pair], ent = (uint32_t)so.tab0 + (pw >> 25);
+                    const bool neg = ((pw >> 24) & 1u) != (uint32_t)prim_neg[ent];   // (the word's sign is the orientation's)
+                    rows.push_back(slots | ((uint64_t)((uint32_t)prim_of[ent] * 16u) << 32) | (neg ? (1ull << 63) : 0ull));
                 }
         const int nrows = (int)(rows.size() / 32);
         const int nrows4 = (nrows + 3) & ~3;
@@ -375,23 +173,41 @@ int build_sparse_program(ovqe_handle h) {
             return (uint64_t)((uint32_t)(mp + lane) * 8u) | ((uint64_t)((uint32_t)(mp + 64 + lane) * 8u) << 16) |
                    ((uint64_t)((uint32_t)nprim * 16u) << 32);
         };
-        for (const SpOp &so : ops)
-            for (int c0 = 0; c0 < so.npairs; c0 += 64)
-                for (int lane = 0; lane < 64; ++lane) {
-                    if (c0 + lane >= so.npairs) {
-                        // padded lanes rotate their (zero) spare slots by the row's FIRST cos/sin entry: rows of one entry stay
-                        // uniform for the gradient kernel's wave sums
-                        const uint32_t pw0 = pairs[(size_t)so.first + c0];
-                        const uint32_t ent0 = (uint32_t)prim_of[(uint32_t)so.tab0 + (pw0 >> 25)];
-                        rows64.push_back((pad_word(lane) & 0xffffffffull) | ((uint64_t)(ent0 * 16u) << 32));
-                        continue;
+        // a row of 64 is two of the planner's rows of 32 side by side (a read is served per 32 lanes, a write per 16: the banks they
+        // were chosen on hold); the pads of the upper half move to the upper 32 spare slots of each range
+        size_t at = 0;
+        for (const SpOp &so : ops) {
+            const int nch = (so.npairs + 31) / 32;
+            for (int c = 0; c < nch; c += 2) {
+                const int halves = std::min(2, nch - c);
+                // padded lanes rotate their (zero) spare slots by the cos/sin entry of the row's FIRST pair: rows of one entry stay
+                // uniform for the gradient kernel's wave sums
+                uint32_t ent0 = (uint32_t)nprim;
+                for (int l = 0; l < 32 * halves; ++l)
+                    if (plan.rows[at + l].pair >= 0) {
+                        ent0 = (uint32_t)prim_of[(uint32_t)so.tab0 + (pairs[(size_t)plan.rows[at + l].pair] >> 25)];
+                        break;
                     }
-                    const uint32_t pw = pairs[(size_t)so.first + c0 + lane];
-                    const uint32_t ci = pw & 0xfffu, cj = (pw >> 12) & 0xfffu, ent = (uint32_t)so.tab0 + (pw >> 25);
-                    const bool neg = ((pw >> 24) & 1u) != (uint32_t)prim_neg[ent];
-                    rows64.push_back((uint64_t)(ci * 8u) | ((uint64_t)(cj * 8u) << 16) | ((uint64_t)((uint32_t)prim_of[ent] * 16u) << 32) |
-                                     (neg ? (1ull << 63) : 0ull));
-                }
+                for (int hh = 0; hh < 2; ++hh)
+                    for (int l = 0; l < 32; ++l) {
+                        if (hh >= halves) {
+                            rows64.push_back((pad_word(32 + l) & 0xffffffffull) | ((uint64_t)(ent0 * 16u) << 32));
+                            continue;
+                        }
+                        const RowLane &rl = plan.rows[at + 32 * hh + l];
+                        if (rl.pair < 0) {
+                            const uint32_t si = rl.si + 32u * hh, sj = rl.sj + 32u + 32u * hh;
+                            rows64.push_back((uint64_t)(si * 8u) | ((uint64_t)(sj * 8u) << 16) | ((uint64_t)(ent0 * 16u) << 32));
+                            continue;
+                        }
+                        const uint32_t pw = pairs[(size_t)rl.pair], ent = (uint32_t)so.tab0 + (pw >> 25);
+                        const bool neg = ((pw >> 24) & 1u) != (uint32_t)prim_neg[ent];
+                        rows64.push_back((uint64_t)(rl.si * 8u) | ((uint64_t)(rl.sj * 8u) << 16) |
+                                         ((uint64_t)((uint32_t)prim_of[ent] * 16u) << 32) | (neg ? (1ull << 63) : 0ull));
+                    }
+                at += (size_t)32 * halves;
+            }
+        }
         const int nrows = (int)(rows64.size() / 64);
         const int nrows8 = (nrows + 7) & ~7;
         for (int r = nrows; r < nrows8 + 8; ++r)
@@ -401,6 +217,12 @@ int build_sparse_program(ovqe_handle h) {
     // owner pieces of the restricted Hamiltonian for the first instance of the workgroup geometry that holds the program
     h->sp_pack_inst = -1;
     h->sp_h_pieces = h->sp_h_rpt = h->sp_h_epr = 0;
+    // modelled LDS array cycles per evaluation (ovqe_program_info [33..37])
+    h->sp_cycles[0] = plan.cycles.reads;
+    h->sp_cycles[1] = plan.cycles.writes;
+    h->sp_cycles[2] = 0;
+    h->sp_cycles[3] = plan.cycles_discovery.reads;
+    h->sp_cycles[4] = plan.cycles_discovery.writes;
     std::vector<unsigned char> hpack;
     if (h->sp_nrows4 && !entries.empty() && h->opt_sparse_pack) {
         std::vector<uint32_t> ei(entries.size()), ej(entries.size());
@@ -425,6 +247,8 @@ int build_sparse_program(ovqe_handle h) {
             h->sp_h_pieces = P.pieces;
             h->sp_h_rpt = I.rpt;
             h->sp_h_epr = I.epr;
+            const PackCycles pc = pack_cycles(P);
+            h->sp_cycles[2] = pc.slot_reads + pc.owner_reads;
         }
     }
     int rc = upload(h, h->d_sp_ops, ops.data(), ops.size() * sizeof(SpOp));

@@ -12,6 +12,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "sparse_plan.hpp"
+
 namespace ovqe {
 
 struct OwnerPack {
@@ -21,6 +23,248 @@ struct OwnerPack {
     std::vector<uint16_t> oj;    // [rpt * epr][nt]  byte offset of the slot's other amplitude (padding: the owner's)
     std::vector<double> c;       // [rpt * epr][nt]  coefficient (padding and empty pieces: 0)
 };
+
+// One slot of a piece as instruction k of a group of 32 lanes reads it.
+struct PackSlot {
+    uint32_t o;   // the slot read
+    double c;
+    int real;     // 0: padding (c = 0; the owner's slot, or the one slot of an empty piece)
+};
+
+// The order of the slots inside the pieces of ONE group of 32 lanes.  in: tab[l] the entries of lane l's piece (at most epr; own[l]
+// its owner, 0xffffffff: an empty piece).  out: tab[l] of exactly epr slots, own[l] a valid slot for every lane.
+// Instruction k reads tab[.][k]: one LDS cycle when the slots differ mod 32 (equal slots are one word).  The lanes and the 32
+// banks are the two sides of a bipartite multigraph with one edge per slot, an order of the slots is a colouring of its edges with
+// epr colours, and an instruction without conflict is a colour that no bank sees twice.  When no bank carries more than epr edges
+// such a colouring exists (Koenig) and alternating paths find it: first with the padding counted (a tail reads its owner's slot,
+// an empty piece ONE slot on the least loaded bank), else for the entries alone with the padding in the colours they leave.  What
+// conflicts remain goes to a local search on the model: two slots of one lane change places when that shortens the two instructions
+// together.  A bank with more than epr edges need not cost anything — lanes that read the SAME slot in one instruction read one word,
+// and a restricted Hamiltonian has slots that most pieces of a group read — but then a slot's instruction ties lanes together and
+// the problem is no edge colouring any more: the start is greedy (the most shared slots first), the rest the same search.
+inline void pack_group_slots(std::vector<PackSlot> (&tab)[32], uint32_t (&own)[32], int nslots, int epr) {
+    int deg[32] = {}, deg_real[32] = {};
+    for (int l = 0; l < 32; ++l) {
+        if (own[l] == 0xffffffffu) continue;
+        for (const PackSlot &s : tab[l]) {
+            ++deg[s.o & 31u];
+            ++deg_real[s.o & 31u];
+        }
+        deg[own[l] & 31u] += epr - (int)tab[l].size();
+    }
+    for (int l = 0; l < 32; ++l) {
+        if (own[l] != 0xffffffffu) continue;
+        uint32_t best = 0;
+        for (uint32_t s = 1; s < (uint32_t)std::min(nslots, 32); ++s)
+            if (deg[s & 31u] < deg[best & 31u]) best = s;
+        own[l] = best;
+        deg[best & 31u] += epr;
+    }
+    for (int l = 0; l < 32; ++l)
+        while ((int)tab[l].size() < epr) tab[l].push_back({own[l], 0.0, 0});
+    int worst = 0, worst_real = 0;
+    for (int b = 0; b < 32; ++b) {
+        worst = std::max(worst, deg[b]);
+        worst_real = std::max(worst_real, deg_real[b]);
+    }
+    const bool all = worst <= epr, reals = !all && worst_real <= epr;
+    if (all || reals) {
+        // edge (l, q) = tab[l][q] as it stands; colour[l][q] = the instruction that reads it
+        std::vector<int> colour((size_t)32 * epr, -1), at_lane((size_t)32 * epr, -1), at_bank((size_t)32 * epr, -1);   // [.][colour] -> edge l * epr + q
+        auto bank_of = [&](int e) { return (int)(tab[e / epr][(size_t)(e % epr)].o & 31u); };
+        auto put = [&](int e, int col) {
+            colour[(size_t)e] = col;
+            at_lane[(size_t)(e / epr) * epr + col] = e;
+            at_bank[(size_t)bank_of(e) * epr + col] = e;
+        };
+        std::vector<int> path;
+        for (int l = 0; l < 32; ++l)
+            for (int q = 0; q < epr; ++q) {
+                if (!all && !tab[l][(size_t)q].real) continue;
+                const int e = l * epr + q, b = bank_of(e);
+                int ca = 0, cb = 0;
+                while (at_lane[(size_t)l * epr + ca] >= 0) ++ca;   // free at the lane (its degree is at most epr)
+                while (at_bank[(size_t)b * epr + cb] >= 0) ++cb;   // free at the bank
+                if (at_bank[(size_t)b * epr + ca] >= 0) {
+                    // the path from the bank along colours ca, cb, ca, ...: it cannot reach lane l (every lane on it is entered on ca)
+                    path.clear();
+                    for (int bb = b;;) {
+                        const int e1 = at_bank[(size_t)bb * epr + ca];
+                        if (e1 < 0) break;
+                        path.push_back(e1);
+                        const int e2 = at_lane[(size_t)(e1 / epr) * epr + cb];
+                        if (e2 < 0) break;
+                        path.push_back(e2);
+                        bb = bank_of(e2);
+                    }
+                    for (int f : path) {
+                        at_lane[(size_t)(f / epr) * epr + colour[(size_t)f]] = -1;
+                        at_bank[(size_t)bank_of(f) * epr + colour[(size_t)f]] = -1;
+                    }
+                    for (int f : path) put(f, colour[(size_t)f] == ca ? cb : ca);
+                }
+                put(e, ca);
+            }
+        for (int l = 0; l < 32; ++l) {
+            std::vector<PackSlot> ordered((size_t)epr, PackSlot{own[l], 0.0, 0});
+            std::vector<char> filled((size_t)epr, 0);
+            for (int q = 0; q < epr; ++q)
+                if (colour[(size_t)l * epr + q] >= 0) {
+                    ordered[(size_t)colour[(size_t)l * epr + q]] = tab[l][(size_t)q];
+                    filled[(size_t)colour[(size_t)l * epr + q]] = 1;
+                }
+            int k = 0;
+            for (int q = 0; q < epr; ++q)
+                if (colour[(size_t)l * epr + q] < 0) {   // padding into the colours left
+                    while (filled[(size_t)k]) ++k;
+                    ordered[(size_t)k] = tab[l][(size_t)q];
+                    filled[(size_t)k] = 1;
+                }
+            tab[l].swap(ordered);
+        }
+        if (all) return;
+    }
+    if (!all && !reals) {
+        // no exact colouring: the slots that most lanes share first, each into the instruction where its bank is free and most of its
+        // lanes still are (they read ONE word there), what finds no such instruction into the colours left
+        struct Want { uint32_t o; std::vector<int> lanes; };
+        std::vector<Want> wants;
+        {
+            std::vector<std::pair<uint32_t, int>> sl;
+            for (int l = 0; l < 32; ++l)
+                for (const PackSlot &s : tab[l])
+                    if (s.real) sl.push_back({s.o, l});
+            std::sort(sl.begin(), sl.end());
+            for (size_t k = 0; k < sl.size(); ++k) {
+                if (!k || sl[k].first != sl[k - 1].first) wants.push_back({sl[k].first, {}});
+                wants.back().lanes.push_back(sl[k].second);
+            }
+            std::stable_sort(wants.begin(), wants.end(), [](const Want &a, const Want &b) { return a.lanes.size() > b.lanes.size(); });
+        }
+        std::vector<int> lane_free((size_t)32 * epr, 1), bank_slot((size_t)epr * 32, -1);
+        std::vector<PackSlot> placed[32];
+        for (int l = 0; l < 32; ++l) placed[l].assign((size_t)epr, PackSlot{own[l], 0.0, -1});   // real = -1: colour not taken
+        auto coeff = [&](int l, uint32_t o) {
+            for (const PackSlot &s : tab[l])
+                if (s.real && s.o == o) return s.c;
+            return 0.0;
+        };
+        std::vector<std::pair<int, uint32_t>> rest;   // (lane, slot) without an instruction
+        for (Want &w : wants) {
+            std::vector<int> left = w.lanes;
+            while (!left.empty()) {
+                int best = -1, best_n = 0;
+                for (int k = 0; k < epr; ++k) {
+                    const int held = bank_slot[(size_t)k * 32 + (w.o & 31u)];
+                    if (held >= 0 && (uint32_t)held != w.o) continue;
+                    int n = 0;
+                    for (int l : left) n += lane_free[(size_t)l * epr + k];
+                    if (n > best_n) {
+                        best_n = n;
+                        best = k;
+                    }
+                }
+                if (best < 0) break;
+                bank_slot[(size_t)best * 32 + (w.o & 31u)] = (int)w.o;
+                std::vector<int> still;
+                for (int l : left)
+                    if (lane_free[(size_t)l * epr + best]) {
+                        lane_free[(size_t)l * epr + best] = 0;
+                        placed[l][(size_t)best] = {w.o, coeff(l, w.o), 1};
+                    } else {
+                        still.push_back(l);
+                    }
+                left.swap(still);
+            }
+            for (int l : left) rest.push_back({l, w.o});
+        }
+        for (auto &lo : rest)
+            for (int k = 0; k < epr; ++k)
+                if (lane_free[(size_t)lo.first * epr + k]) {
+                    lane_free[(size_t)lo.first * epr + k] = 0;
+                    placed[lo.first][(size_t)k] = {lo.second, coeff(lo.first, lo.second), 1};
+                    break;
+                }
+        for (int l = 0; l < 32; ++l) {
+            for (PackSlot &s : placed[l])
+                if (s.real < 0) s.real = 0;
+            tab[l].swap(placed[l]);
+        }
+    }
+    // local search.  First on the colliding pairs, sum over instructions and banks of d (d - 1) / 2 for d distinct slots — it
+    // falls with every slot that leaves a crowded bank, where the cycle count (the largest d of an instruction) stays flat —
+    // then on the model's cycles themselves, for what the first leaves on a plateau of the second.
+    std::vector<uint32_t> ids;
+    for (int l = 0; l < 32; ++l)
+        for (const PackSlot &s : tab[l]) ids.push_back(s.o);
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    const size_t nid = ids.size();
+    std::vector<int> id((size_t)32 * epr), refs((size_t)epr * nid, 0), dist((size_t)epr * 32, 0);
+    int64_t q = 0;
+    auto add = [&](int k, int i) {
+        if (refs[(size_t)k * nid + (size_t)i]++ == 0) q += dist[(size_t)k * 32 + (ids[(size_t)i] & 31u)]++;
+    };
+    auto drop = [&](int k, int i) {
+        if (--refs[(size_t)k * nid + (size_t)i] == 0) q -= --dist[(size_t)k * 32 + (ids[(size_t)i] & 31u)];
+    };
+    for (int l = 0; l < 32; ++l)
+        for (int k = 0; k < epr; ++k) {
+            id[(size_t)l * epr + k] = (int)(std::lower_bound(ids.begin(), ids.end(), tab[l][(size_t)k].o) - ids.begin());
+            add(k, id[(size_t)l * epr + k]);
+        }
+    auto exchange = [&](int l, int k1, int k2) {
+        int &a = id[(size_t)l * epr + k1], &b = id[(size_t)l * epr + k2];
+        drop(k1, a);
+        drop(k2, b);
+        add(k1, b);
+        add(k2, a);
+        std::swap(a, b);
+        std::swap(tab[l][(size_t)k1], tab[l][(size_t)k2]);
+    };
+    for (int sweep = 0; sweep < 64 && q > 0; ++sweep) {
+        bool any = false;
+        for (int l = 0; l < 32; ++l)
+            for (int k1 = 0; k1 < epr; ++k1)
+                for (int k2 = k1 + 1; k2 < epr; ++k2) {
+                    if (id[(size_t)l * epr + k1] == id[(size_t)l * epr + k2]) continue;
+                    const int64_t before = q;
+                    exchange(l, k1, k2);
+                    if (q < before)
+                        any = true;
+                    else
+                        exchange(l, k1, k2);
+                }
+        if (!any) break;
+    }
+    auto cycles = [&](int k) {
+        int worst = 0;
+        for (int b = 0; b < 32; ++b) worst = std::max(worst, dist[(size_t)k * 32 + b]);
+        return worst;
+    };
+    for (int sweep = 0; sweep < 8; ++sweep) {
+        bool any = false;
+        for (int k1 = 0; k1 < epr; ++k1)
+            for (int l = 0; l < 32; ++l) {
+                const int c1 = cycles(k1);
+                if (c1 <= 1) break;
+                if (dist[(size_t)k1 * 32 + (tab[l][(size_t)k1].o & 31u)] < c1) continue;   // (not on a bank that sets the cycles)
+                for (int k2 = 0; k2 < epr; ++k2) {
+                    if (k2 == k1 || id[(size_t)l * epr + k1] == id[(size_t)l * epr + k2]) continue;
+                    const int c2 = cycles(k2);
+                    const int64_t before = q;
+                    exchange(l, k1, k2);
+                    const int d = cycles(k1) + cycles(k2) - c1 - c2;
+                    if (d < 0 || (d == 0 && q < before)) {
+                        any = true;
+                        break;
+                    }
+                    exchange(l, k1, k2);
+                }
+            }
+        if (!any) break;
+    }
+}
 
 // si, sj: slots (amplitude index in the LDS state, < nslots <= 8192), c: coefficient of c a_i a_j, every unordered pair at most
 // once.  -> false when sum_i ceil(load_i / epr) > nt * rpt for the owners found (nothing usable in *out).
@@ -135,47 +379,47 @@ inline bool pack_owner_pieces(const std::vector<uint32_t> &si, const std::vector
                     --left;
                 }
             for (int l = taken; l < 32; ++l) lane_piece[l] = -1;
-            // slots: per instruction (slot k of the group) other amplitudes that differ mod 32 where the pieces allow, one greedy pass
-            std::vector<uint32_t> rest[32];
+            // slots: which of a lane's entries instruction k reads (pack_group_slots above)
+            std::vector<PackSlot> tab[32];
+            uint32_t own[32];
+            for (int l = 0; l < 32; ++l) {
+                own[l] = 0xffffffffu;
+                if (lane_piece[l] < 0) continue;
+                const Piece &p = pcs[(size_t)lane_piece[l]];
+                own[l] = p.owner;
+                for (uint32_t e : p.ent) tab[l].push_back({si[e] == p.owner ? sj[e] : si[e], c[e], 1});
+            }
+            pack_group_slots(tab, own, nslots, epr);
             for (int l = 0; l < 32; ++l) {
                 const size_t t = (size_t)t0 + l;
-                if (lane_piece[l] < 0) {   // empty piece: any valid slot, coefficients 0
-                    const uint16_t off = (uint16_t)(((uint32_t)l % (uint32_t)nslots) * 8u);
-                    out->oi[(size_t)r * nt + t] = off;
-                    for (int k = 0; k < epr; ++k) out->oj[((size_t)r * epr + k) * nt + t] = off;
-                    continue;
-                }
-                const Piece &p = pcs[(size_t)lane_piece[l]];
-                out->oi[(size_t)r * nt + t] = (uint16_t)(p.owner * 8u);
-                rest[l] = p.ent;
-            }
-            for (int k = 0; k < epr; ++k) {
-                uint32_t used = 0;
-                for (int l = 0; l < 32; ++l) {
-                    if (lane_piece[l] < 0) continue;
-                    const size_t at = ((size_t)r * epr + k) * nt + (size_t)t0 + l;
-                    const uint32_t own = pcs[(size_t)lane_piece[l]].owner;
-                    if (rest[l].empty()) {   // tail: the owner's amplitude with coefficient 0
-                        out->oj[at] = (uint16_t)(own * 8u);
-                        continue;
-                    }
-                    size_t pick = 0;
-                    for (size_t q = 0; q < rest[l].size(); ++q) {
-                        const uint32_t e = rest[l][q], o = si[e] == own ? sj[e] : si[e];
-                        if (!((used >> (o & 31u)) & 1u)) {
-                            pick = q;
-                            break;
-                        }
-                    }
-                    const uint32_t e = rest[l][pick], o = si[e] == own ? sj[e] : si[e];
-                    used |= 1u << (o & 31u);
-                    out->oj[at] = (uint16_t)(o * 8u);
-                    out->c[at] = c[e];
-                    rest[l].erase(rest[l].begin() + (long)pick);
+                out->oi[(size_t)r * nt + t] = (uint16_t)(own[l] * 8u);
+                for (int k = 0; k < epr; ++k) {
+                    const size_t at = ((size_t)r * epr + k) * nt + t;
+                    out->oj[at] = (uint16_t)(tab[l][(size_t)k].o * 8u);
+                    out->c[at] = tab[l][(size_t)k].c;
                 }
             }
         }
     return left == 0;
+}
+
+// Modelled LDS array cycles of the contraction per state (sparse_plan.hpp: lds_access_cycles): every aligned group of 32 threads
+// reads rpt * epr slots and rpt owners.
+struct PackCycles { int64_t slot_reads = 0, owner_reads = 0; };
+inline PackCycles pack_cycles(const OwnerPack &P) {
+    PackCycles c;
+    uint32_t s[32];
+    for (int t0 = 0; t0 + 32 <= P.nt; t0 += 32) {
+        for (int k = 0; k < P.rpt * P.epr; ++k) {
+            for (int l = 0; l < 32; ++l) s[l] = P.oj[(size_t)k * P.nt + (size_t)t0 + l] / 8u;
+            c.slot_reads += lds_read_cycles(s);
+        }
+        for (int r = 0; r < P.rpt; ++r) {
+            for (int l = 0; l < 32; ++l) s[l] = P.oi[(size_t)r * P.nt + (size_t)t0 + l] / 8u;
+            c.owner_reads += lds_read_cycles(s);
+        }
+    }
+    return c;
 }
 
 }  // namespace ovqe
