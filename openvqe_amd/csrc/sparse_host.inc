@@ -5,8 +5,9 @@
 // holds a program when its entries are at most 64 NW x EPT (the capacity criterion its name carries), its state fits the stride, its
 // LDS fits half a CU (launch_rows_shared) AND the entries pack into 64 NW x RPT owner pieces of EPR slots (sparse_pack.hpp).  The
 // shapes RPT x EPR are the measured ones of profiles/owner_rows/README.md.  te: the pipelined item loop (sv_sparse.hpp) keeps the table
-// records of 32 te distinct angles in registers (profiles/pipelined_rows/README.md).  Both instances: no scratch.  H2O 230 VGPRs, two
-// waves per SIMD; LiH 148, THREE waves per SIMD (three workgroups per CU; four with the plain loop, which was slower at every batch size).
+// records of 32 te distinct angles in registers (profiles/pipelined_rows/README.md).  Both instances: no scratch.  H2O 252 VGPRs, two
+// waves per SIMD; LiH 164, THREE waves per SIMD (three workgroups per CU; four with the plain loop, which was slower at every batch size).
+// Both are four registers under the next step (256, 168): the contraction holds one slot group in flight (profiles/contraction_ahead).
 struct SharedInstance { int nw, ept, sstride, rpt, epr, te; };
 constexpr SharedInstance SHARED_13 = {4, 13, 2568, 1, 17, 3};   // LiH: 225 states, 3243 entries: 18 LDS reads per thread and state
 constexpr SharedInstance SHARED_37 = {4, 37, 4104, 4, 10, 5};   // H2O: 441 states, 9443 entries: 44

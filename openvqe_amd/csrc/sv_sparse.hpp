@@ -327,6 +327,24 @@ __host__ __device__ constexpr SpRowsSharedLds sp_rows_shared_lds(int ntab) {
 // (H2O 198 -> 230 VGPRs, two waves per SIMD as before; LiH 128 -> 148, three instead of four).  Measured, 65 536 evaluations: H2O
 // 0.519 -> 0.484 ms, LiH 0.272 -> 0.259; the plain loop and the carried row words alone were built from a build-time switch for
 // that comparison (no gain from the row words alone) and are gone.
+//
+// THE CONTRACTION READS ONE GROUP AHEAD (profiles/contraction_ahead/README.md).  The pins that keep the sums in state order are
+// asm statements, and to the scheduler each is a barrier for memory operations too: no read of slot k + 1 moves above the fma of
+// slot k.  Written slot by slot the phase is RPT (EPR + 1) times "NS reads, s_waitcnt lgkmcnt(0), NS fma": one whole LDS round
+// trip per group, in series, with two (H2O) or three (LiH) waves per SIMD to cover it.  So the rotation is in the SOURCE: the
+// pieces are one sequence of groups g = r (EPR + 1) + k (k = EPR: the owner read), the NS reads of group g + 1 are issued in
+// front of the fma of group g, a sched_barrier(0) on either side of the arithmetic holds them there, and the compiler's own
+// counted waits (lgkmcnt(14) ... (8)) let each fma go when its operand is back.  Same reads, same fma in the same order per
+// state: every energy keeps its bits.  It costs the NS doubles of the group in flight: H2O 230 -> 252 VGPRs, LiH 148 -> 164,
+// four registers under the steps to one wave less per SIMD (256, 168); no scratch.  (Without the pins the rotation takes 256 VGPRs
+// + 256 AGPRs + 1220 bytes of scratch; with the reads and fma of a group interleaved one by one through sched_group_barrier the
+// compiler reuses the registers of consumed operands, 240 / 154 VGPRs, and the kernel is no faster than the parent — measured.)
+// In the rows loop the cos/sin entry of row r + 1 is read behind the amplitude reads of row r, in front of its two writes: the
+// entry depends on the row word alone, and the 16-byte read leaves the chain read -> fma -> write of the next row.  The order
+// of all state reads and writes is the same; no register at the peak.  Measured, 65 536 evaluations of H2O, each step against
+// the one before: the contraction ahead 0.431 -> 0.422 ms (about 2 %: the LDS pipeline is busy for over half of the launch and
+// shared with the rows of the CU's other workgroup, the round trips were not all that the phase waited for), the entry ahead
+// 0.422 -> 0.391 (a row's chain is longest while the other workgroup contracts).  LiH 0.229 -> 0.225.
 // DBG as k_sparse_vqe_rows; 4: no theta load at all, a constant in its place (what the loads themselves cost).
 template <int NW, int RPT, int EPR, int SSTRIDE, int TE, int DBG = 0>
 __global__ __launch_bounds__(NW * 64) void k_sparse_vqe_rows_shared(SparseArgs A, const double *__restrict__ theta,
@@ -436,25 +454,30 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_vqe_rows_shared(SparseArgs A
             zero_fill();
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        auto apply = [&](uint64_t word) {
+        // the cos/sin entry of a row is read ONE ROW AHEAD, behind the amplitude reads of the row before and in front of its writes:
+        // it does not depend on the state (see above)
+        auto cs_of = [&](uint64_t word) { return *reinterpret_cast<const double2 *>(cbase + ((uint32_t)(word >> 32) & 0xffffu)); };
+        double2 tn = cs_of(w0);   // (this item's table is complete: the wait above)
+        auto apply = [&](uint64_t word, uint64_t next) {
             const uint32_t lo = (uint32_t)word, hi = (uint32_t)(word >> 32);
             double *pi = reinterpret_cast<double *>(sbase + (lo & 0xffffu));
             double *pj = reinterpret_cast<double *>(sbase + (lo >> 16));
-            const double2 t = *reinterpret_cast<const double2 *>(cbase + (hi & 0xffffu));
+            const double2 t = tn;
             const double sn = __hiloint2double(__double2hiint(t.y) ^ (int)(hi & 0x80000000u), __double2loint(t.y));
             const double u = *pi, v = *pj;
+            tn = cs_of(next);   // (the last row of an item reads the entry of row 0 from this item's table: never used)
             *pi = t.x * u + sn * v;
             *pj = t.x * v - sn * u;
             asm volatile("" ::: "memory");   // a wave's DS instructions execute in issue order (see k_sparse_vqe_rows)
         };
         auto trip = [&](const uint64_t *nx) {
-            apply(w0);
+            apply(w0, w1);
             w0 = nx[0];
-            apply(w1);
+            apply(w1, w2);
             w1 = nx[32];
-            apply(w2);
+            apply(w2, w3);
             w2 = nx[64];
-            apply(w3);
+            apply(w3, w0);
             w3 = nx[96];
         };
         if (DBG != 2) {
@@ -469,28 +492,50 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_vqe_rows_shared(SparseArgs A
 #pragma unroll
         for (int q = 0; q < NS; ++q) acc[q] = 0.0;
         if (DBG != 3) {
+            // the pieces as ONE sequence of read groups, g = r (EPR + 1) + k: k < EPR slot k of piece r, k = EPR its owner
+            constexpr int GPP = EPR + 1, G = RPT * GPP;
+            auto goff = [&](int g) -> uint32_t {
+                const int r = g / GPP, k = g % GPP;
+                if (k == EPR) {
+                    uint32_t po = oi[r];
+                    asm volatile("" : "+v"(po));   // (keeps the address arithmetic inside the loop)
+                    return po;
+                }
+                uint32_t pk = ojj[r][k / 2];
+                asm volatile("" : "+v"(pk));   // (keeps the unpacking inside the loop: EPR registers less per piece)
+                return (k & 1) ? pk >> 16 : pk & 0xffffu;
+            };
+            double cur[NS], nxt[NS], t[NS];
+            {
+                const uint32_t o = goff(0);
 #pragma unroll
-            for (int r = 0; r < RPT; ++r) {
-                uint32_t po = oi[r];
-                asm volatile("" : "+v"(po));   // (keeps the address arithmetic inside the loop)
-                double t[NS];
+                for (int q = 0; q < NS; ++q) cur[q] = *reinterpret_cast<const double *>(smem + o + q * SSTRIDE);
+            }
 #pragma unroll
-                for (int k = 0; k < EPR; ++k) {
-                    uint32_t pk = ojj[r][k / 2];
-                    asm volatile("" : "+v"(pk));   // (keeps the unpacking inside the loop: EPR registers less per piece)
-                    const uint32_t oj = (k & 1) ? pk >> 16 : pk & 0xffffu;
+            for (int g = 0; g < G; ++g) {
+                const int r = g / GPP, k = g % GPP;
+                if (g + 1 < G) {   // group g + 1 in flight while group g is consumed
+                    const uint32_t o = goff(g + 1);
 #pragma unroll
-                    for (int q = 0; q < NS; ++q) {
-                        const double aj = *reinterpret_cast<const double *>(smem + oj + q * SSTRIDE);
-                        t[q] = k ? fma(ec[r][k], aj, t[q]) : ec[r][k] * aj;
-                    }
+                    for (int q = 0; q < NS; ++q) nxt[q] = *reinterpret_cast<const double *>(smem + o + q * SSTRIDE);
+                }
+                __builtin_amdgcn_sched_barrier(0);   // (the reads stay in front of this group's arithmetic)
+                if (k < EPR) {
+#pragma unroll
+                    for (int q = 0; q < NS; ++q) t[q] = k ? fma(ec[r][k], cur[q], t[q]) : ec[r][k] * cur[q];
 #pragma unroll
                     for (int q = 0; q < NS; ++q) asm volatile("" : "+v"(t[q]));
+                } else {
+#pragma unroll
+                    for (int q = 0; q < NS; ++q) acc[q] = fma(cur[q], t[q], acc[q]);
+#pragma unroll
+                    for (int q = 0; q < NS; ++q) asm volatile("" : "+v"(acc[q]));
                 }
+                __builtin_amdgcn_sched_barrier(0);   // (... and the next group's reads behind it: ONE group ahead, not more)
+                if (g + 1 < G) {
 #pragma unroll
-                for (int q = 0; q < NS; ++q) acc[q] = fma(*reinterpret_cast<const double *>(smem + po + q * SSTRIDE), t[q], acc[q]);
-#pragma unroll
-                for (int q = 0; q < NS; ++q) asm volatile("" : "+v"(acc[q]));
+                    for (int q = 0; q < NS; ++q) cur[q] = nxt[q];
+                }
             }
         }
 #pragma unroll
