@@ -97,6 +97,8 @@ int ovqe_sector_ground_state(ovqe_handle h, double tol, int max_iter, uint64_t s
                              int *iterations);
 int ovqe_rdm(ovqe_handle h, int order, double *out_re_im);
 int ovqe_rdm_info(ovqe_handle h, int64_t *info, int count);
+int ovqe_metric_tensor(ovqe_handle h, const double *theta, int32_t K, double *metric);
+int ovqe_metric_info(ovqe_handle h, int64_t *info, int count);
 int ovqe_time_pauli_rotation(ovqe_handle h, uint64_t x, uint64_t z, double phi, int warmup, int reps,
                              double *avg_ms);
 int ovqe_last_batch_ms(ovqe_handle h, double *ms);

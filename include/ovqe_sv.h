@@ -126,6 +126,8 @@ int ovqe_set_stream(ovqe_handle h, void *hip_stream);
  *                     the recurrence gives the Ritz vector; 0 or vectors that do not fit: the recurrence runs twice
  *   "rdm_workspace_mb" (1024)  ovqe_rdm materialises its rows in chunks of at most this many MB of device memory (at least one staging
  *                     tile of 16 or 32 rows); the buffer is allocated at the first call that needs it and kept on the handle
+ *   "metric_workspace_mb" (0)  cap of the tangent store of ovqe_metric_tensor in MB; 0: 60 % of the free device memory.  A store beyond
+ *                     the cap is refused with OVQE_ERR_ALLOC; the buffer is allocated at the first call and kept on the handle
  *
  *   "real_state" (0)  the state buffer holds 2^n_local DOUBLES (8 bytes per amplitude: a shard of the partitioned register while its
  *                     amplitudes are real).  BUFFER-SIZE CONTRACT: while it is set, the state and every shard-sized operand of
@@ -441,6 +443,35 @@ int ovqe_rdm(ovqe_handle h, int order, double *out_re_im);
  * [5] Gram launches [6] block pairs (64 x 64 outputs, upper triangle) [7] row slices per chunk  [8..11] HIP-event times in microseconds:
  * census + shadows + row list, rows kernels, Gram kernels, final reduction ([9..11] stay 0 beyond 64 chunks); zeros before the first call */
 int ovqe_rdm_info(ovqe_handle h, int64_t *info, int count);
+
+/* ---- Fubini-Study metric of the ansatz state (the real part of the quantum geometric tensor): with psi = U(theta)|hf> of the stored
+ * program and the tangent vectors T_k = d psi / d theta_k,
+ *   metric[K*K], row-major:  g_ij = Re( <T_i|T_j> - <T_i|psi><psi|T_j> )      K x K, real, symmetric, positive semidefinite
+ * — the ingredient of natural-gradient descent / imaginary-time evolution (the gradient-descent optimiser with natural_gradient=True
+ * of the qat-variational package the reference's requirements pin; openvqe_amd/common_files/natural_gradient.py is its counterpart here).
+ * CONTRACT.  The angle of rotation r is coeff_r theta[pidx_r] + phi0_r (of a gate: ascale theta[pidx] + aconst), so
+ *   T_k = sum_{r: pidx_r = k} coeff_r U_{>r} (-i P_r) U_{<=r} |hf>      (RX / RY / RZ: the factor -i/2 with the gate's axis, and ascale);
+ * a parameter shared by several rotations sums their contributions; a parameter no rotation uses, or a rotation with pidx < 0, gives a
+ * zero row and column.  Gate programs in Clifford-frame form are evaluated on the frame state: the net Clifford operator is a fixed
+ * unitary and drops out of g.  The result is symmetric to the bit and bit-identical from call to call (fixed-order reductions, no
+ * atomics).  The state buffer is unspecified after the call (as after ovqe_energy); cached tables of the handle stay valid: an
+ * ovqe_energy before the call and one after it return the same bits.  No Hamiltonian is needed.
+ * TWO PATHS (ovqe_metric_info [0]).  1, compact support: a real-amplitude program (every string an odd number of Y, no literal gate left)
+ * whose reachable support holds at most 4096 basis states (the H2O / LiH class) — one workgroup per parameter carries psi and its tangent
+ * through the program's pair lists in LDS, one launch for all K tangents, then the Gram matrix of the tangents (<psi|T_k> = 0 on a
+ * real state).  2, streaming (any other program, option "force_path" = 2): psi and the K tangents as columns of a store of 2^n rows behind
+ * option "metric_workspace_mb"; the op list is walked once, every op applied to psi and all live tangents in one launch, behind each
+ * parameterised rotation its tangent takes coeff (-i P) psi; then the Gram matrix and the <T_i|psi> correction.  COST of path 2:
+ * O(K R) sweeps of the register for R rotations — meant for small registers and short programs.  Out of scope: tangents on the sector
+ * tables and the partitioned register (24-qubit N2 with 1715 parameters is answered OVQE_ERR_ALLOC).
+ * OVQE_ERR_STATE with no program set, on a shard of a partitioned register and under option "real_state"; OVQE_ERR_INVALID for a K other
+ * than the program's, a NULL theta or metric (K = 0: only metric is checked); OVQE_ERR_ALLOC, with the bytes needed in the text, when
+ * the tangent store does not fit its cap. */
+int ovqe_metric_tensor(ovqe_handle h, const double *theta, int32_t K, double *metric);
+/* of the last ovqe_metric_tensor call, up to `count` entries of: [0] path (1 compact support, 2 streaming) [1] K [2] amplitudes per tangent
+ * [3] bytes of the tangent store [4] launches of the tangent stage [5] Gram launches [6..8] HIP-event times in microseconds: tangents,
+ * Gram, finish; zeros before the first call */
+int ovqe_metric_info(ovqe_handle h, int64_t *info, int count);
 
 /* ---- measurement support (bench.py): average device time in ms of `reps` back-to-back launches of
  * one Pauli-rotation sweep, bracketed by HIP events on the handle's stream */

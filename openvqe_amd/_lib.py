@@ -101,6 +101,8 @@ SIGNATURES = {
                                         ctypes.POINTER(_int)]),
     "ovqe_rdm": (_int, [_H, _int, _f64p]),
     "ovqe_rdm_info": (_int, [_H, ctypes.POINTER(ctypes.c_int64), _int]),
+    "ovqe_metric_tensor": (_int, [_H, _OptF64, ctypes.c_int32, _OptF64]),
+    "ovqe_metric_info": (_int, [_H, ctypes.POINTER(ctypes.c_int64), _int]),
     "ovqe_program_info": (_int, [_H, ctypes.POINTER(ctypes.c_int64), _int]),
     "ovqe_get_rotation_program": (_int, [_H, _i64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.POINTER(ctypes.c_int64)]),

@@ -567,6 +567,26 @@ class Statevector:
                 "list_us", "rows_us", "gram_us", "finish_us")
         return dict(zip(keys, [int(v) for v in out]))
 
+    # -- Fubini-Study metric of the ansatz state (ovqe_metric_tensor, csrc/metric_host.inc) ----------------------------------------
+    def metric_tensor(self, theta):
+        """g[i, j] = Re(<T_i|T_j> - <T_i|psi><psi|T_j>), T_k = d psi / d theta_k, of the stored program at ``theta``: (K, K) float64,
+        symmetric to the bit — the matrix of natural-gradient descent (``common_files.natural_gradient``)"""
+        K = self._K
+        theta = np.ascontiguousarray(theta, np.float64).reshape(-1)[:K]
+        if theta.shape[0] != K:
+            raise ValueError(f"expected {K} parameters")
+        out = np.zeros((K, K), np.float64)
+        self._ck(self._L.ovqe_metric_tensor(self._h, theta if K else np.zeros(1), K, out.reshape(-1) if K else np.zeros(1)))
+        return out
+
+    def metric_info(self):
+        """figures of the last ``metric_tensor`` call: path (1 compact support, 2 streaming), parameters, amplitudes per tangent, bytes
+        of the tangent store, launches of the tangent stage and of the Gram kernel, HIP-event times of the phases in microseconds"""
+        out = (ctypes.c_int64 * 9)()
+        self._ck(self._L.ovqe_metric_info(self._h, out, 9))
+        keys = ("path", "K", "tangent_amplitudes", "store_bytes", "tangent_launches", "gram_launches", "tangents_us", "gram_us", "finish_us")
+        return dict(zip(keys, [int(v) for v in out]))
+
     def program_info(self):
         """shape of the compiled program: ops, rotations, literal gates, sweeps per evaluation, tiled sweeps,
         fused-kernel ops, support size (-1 = not analysed yet)"""

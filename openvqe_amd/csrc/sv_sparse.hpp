@@ -15,6 +15,7 @@
 // One WAVE owns SPW evaluations: no workgroup barrier exists anywhere; LDS traffic of a wave is in order.
 #pragma once
 #include "sv_small.hpp"
+#include "sv_metric_host.hpp"
 
 namespace ovqe {
 
@@ -900,6 +901,107 @@ __global__ __launch_bounds__(NT) void k_sparse_grad_wg(SparseArgs A, const doubl
         __syncthreads();
         for (int k = tid; k < A.K; k += NT) grads[b * A.K + k] = gk[k];
         __syncthreads();
+    }
+}
+
+// ---- tangent vectors of the ansatz state on the compact support (ovqe_metric_tensor, path 1) -------------------------------------------
+// T_k = d psi / d theta_k for ALL K parameters of one parameter vector in one launch: workgroup (one wave) k carries psi and ONE tangent
+// t through the pair lists of the metric's own compact program (sv_metric_host.hpp: pair words as above, one table entry per distinct
+// angle, constant angles and offsets kept).  A pair with table entry e = (c, s), sign sigma does u' = c u + sigma s v, v' = c v - sigma s u
+// on both vectors; when entry e belongs to parameter k the derivative of that Givens rotation is added on top, t_i += coeff_e sigma v',
+// t_j -= coeff_e sigma u' (psi AFTER the rotation).  The pairs of one op are disjoint and a wave's DS instructions execute in issue
+// order: no atomic, no barrier, and the same bits from call to call.  Until the first op that holds an entry of parameter k (first_op, from
+// the host) t is zero and psi rotates alone.  The finished tangent goes to column k of the index-major store (row i = compact index,
+// wpad columns): the Gram kernel of the density matrices reads that layout as it stands.
+struct SpMetricArgs {
+    int m, mpad, K, nops, ntab, npairs, hf;
+    int64_t wpad;
+};
+struct SpMetricLds { size_t t, cs, dk, ops, pairs, bytes; };   // psi ([mpad]) is at 0
+__host__ __device__ inline SpMetricLds sp_metric_lds(const SpMetricArgs &A, bool stage) {
+    static_assert(sizeof(metric::Op) == 16, "16-byte records behind an even number of doubles");
+    const size_t t = (size_t)A.mpad * sizeof(double);                       // [mpad]
+    const size_t cs = 2 * t;                                                // [ntab]
+    const size_t dk = cs + (size_t)A.ntab * sizeof(double2);                // [ntab]: coeff_e where the entry is parameter k's, else 0
+    const size_t ops = dk + (size_t)((A.ntab + 1) & ~1) * sizeof(double);   // [nops]   (stage)
+    const size_t pairs = ops + (size_t)A.nops * sizeof(metric::Op);         // [npairs] (stage)
+    return {t, cs, dk, ops, pairs, stage ? pairs + (size_t)A.npairs * sizeof(uint32_t) : ops};
+}
+template <bool STAGE>
+__global__ __launch_bounds__(64) void k_sparse_metric(SpMetricArgs A, const double *__restrict__ theta, const metric::TabEntry *__restrict__ tab,
+                                                      const metric::Op *__restrict__ ops, const uint32_t *__restrict__ pairs,
+                                                      const int32_t *__restrict__ first_op, double *__restrict__ store) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const SpMetricLds L = sp_metric_lds(A, STAGE);
+    double *psi = reinterpret_cast<double *>(smem);
+    double *t = reinterpret_cast<double *>(smem + L.t);
+    double2 *cs = reinterpret_cast<double2 *>(smem + L.cs);
+    double *dk = reinterpret_cast<double *>(smem + L.dk);
+    metric::Op *lops = reinterpret_cast<metric::Op *>(smem + L.ops);
+    uint32_t *lpairs = reinterpret_cast<uint32_t *>(smem + L.pairs);
+    const int lane = threadIdx.x;
+    if constexpr (STAGE) {
+        for (int i = lane; i < A.nops; i += 64) lops[i] = ops[i];
+        for (int i = lane; i < A.npairs; i += 64) lpairs[i] = pairs[i];
+    }
+    const metric::Op *opv = STAGE ? lops : ops;
+    const uint32_t *pv = STAGE ? lpairs : pairs;
+    for (int k = blockIdx.x; k < A.K; k += gridDim.x) {
+        for (int i = lane; i < A.mpad; i += 64) {
+            psi[i] = i == A.hf ? 1.0 : 0.0;
+            t[i] = 0.0;
+        }
+        for (int e = lane; e < A.ntab; e += 64) {
+            const metric::TabEntry te = tab[e];
+            double sn, c;
+            sincos(te.phi0 + (te.pidx >= 0 ? te.coeff * theta[te.pidx] : 0.0), &sn, &c);
+            cs[e] = make_double2(c, sn);
+            dk[e] = te.pidx == k ? te.coeff : 0.0;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        int o1 = first_op[k];
+        o1 = __builtin_amdgcn_readfirstlane(o1 < A.nops ? o1 : A.nops);
+        for (int o = 0; o < o1; ++o) {   // psi alone
+            metric::Op op = opv[o];
+            op.first = __builtin_amdgcn_readfirstlane(op.first);
+            op.npairs = __builtin_amdgcn_readfirstlane(op.npairs);
+            op.tab0 = __builtin_amdgcn_readfirstlane(op.tab0);
+            for (int pe = lane; pe < op.npairs; pe += 64) {
+                const uint32_t pw = pv[op.first + pe];
+                const uint32_t ci = pw & 0xfffu, cj = (pw >> 12) & 0xfffu;
+                const double2 r = cs[op.tab0 + (int)(pw >> 25)];
+                const double sn = (pw & (1u << 24)) ? -r.y : r.y;
+                const double u = psi[ci], v = psi[cj];
+                psi[ci] = r.x * u + sn * v;
+                psi[cj] = r.x * v - sn * u;
+            }
+            asm volatile("" ::: "memory");   // a wave's DS instructions execute in issue order (see k_sparse_vqe)
+        }
+        for (int o = o1; o < A.nops; ++o) {   // psi and the tangent
+            metric::Op op = opv[o];
+            op.first = __builtin_amdgcn_readfirstlane(op.first);
+            op.npairs = __builtin_amdgcn_readfirstlane(op.npairs);
+            op.tab0 = __builtin_amdgcn_readfirstlane(op.tab0);
+            for (int pe = lane; pe < op.npairs; pe += 64) {
+                const uint32_t pw = pv[op.first + pe];
+                const uint32_t ci = pw & 0xfffu, cj = (pw >> 12) & 0xfffu;
+                const int e = op.tab0 + (int)(pw >> 25);
+                const double2 r = cs[e];
+                const bool neg = (pw & (1u << 24)) != 0u;
+                const double sn = neg ? -r.y : r.y;
+                const double d = neg ? -dk[e] : dk[e];
+                const double u = psi[ci], v = psi[cj], tu = t[ci], tv = t[cj];
+                const double u1 = r.x * u + sn * v, v1 = r.x * v - sn * u;
+                psi[ci] = u1;
+                psi[cj] = v1;
+                t[ci] = r.x * tu + sn * tv + d * v1;
+                t[cj] = r.x * tv - sn * tu - d * u1;
+            }
+            asm volatile("" ::: "memory");
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        for (int i = lane; i < A.m; i += 64) store[(size_t)i * (size_t)A.wpad + (size_t)k] = t[i];
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
 }
 

@@ -74,6 +74,11 @@ class _Evaluator:
         self._activate()
         return self.sv.energy_gradient(np.asarray(theta, dtype=np.float64)[: self.n_params])
 
+    def metric_tensor(self, theta):
+        """Fubini-Study metric of the ansatz state at ``theta`` (ovqe_metric_tensor), (K, K)"""
+        self._activate()
+        return self.sv.metric_tensor(np.asarray(theta, dtype=np.float64)[: self.n_params])
+
     def state(self, theta):
         self._activate()
         self.sv.prepare_state(np.asarray(theta, dtype=np.float64))

@@ -245,6 +245,10 @@ class PartitionedStatevector:
 
     rdm2 = rdm1
 
+    def metric_tensor(self, *args, **kwargs):
+        raise NotImplementedError("the Fubini-Study metric is computed on one device (ovqe_metric_tensor keeps K tangent vectors next to "
+                                  "the state): not available on the partitioned register")
+
     def last_screen_support(self):
         return -1
 

@@ -4,7 +4,7 @@ reference's; the simulation runs in libovqe_sv instead of myQLM)."""
 import numpy as np
 import scipy.optimize
 
-from ..common_files import bfgs
+from ..common_files import bfgs, natural_gradient
 
 from ..common_files.circuit import count
 from ..evaluator import UCCEvaluator
@@ -18,6 +18,9 @@ class EnergyUCC:
     #: opt-in: exact Jacobian by the adjoint method (ovqe_energy_gradient): about three circuit executions for all K
     #: derivatives; iterates differ from the reference's forward-difference path at the 1e-8 level
     adjoint_gradient = False
+    #: opt-in: natural-gradient descent (common_files/natural_gradient.py) instead of BFGS — exact gradient and the Fubini-Study metric
+    #: of the ansatz state (ovqe_metric_tensor) per step; ``tolerance`` bounds the largest gradient component
+    natural_gradient = False
 
     def __init__(self):
         self._cache = {}
@@ -61,6 +64,22 @@ class EnergyUCC:
     def _minimize(self, hamiltonian_sp, ops, hf_init_sp, x0, energies, method, tolerance):
         fun = lambda theta: self.ucc_action(theta, hamiltonian_sp, ops, hf_init_sp, energies)  # noqa: E731
         jac = None
+        if self.natural_gradient:
+            n_params = min(len(ops), len(x0))
+            ev = self._evaluator(hamiltonian_sp, ops, hf_init_sp, n_params)
+            x0 = np.asarray(x0, dtype=float)
+
+            def fun_and_grad(theta):   # (parameters beyond the operators are not applied: zero derivative)
+                e, g = ev.energy_gradient(theta)
+                energies.append(e)
+                return e, np.concatenate([g, np.zeros(len(theta) - n_params)])
+
+            def metric(theta):
+                g = np.zeros((len(theta), len(theta)))
+                g[:n_params, :n_params] = ev.metric_tensor(theta)
+                return g
+
+            return natural_gradient.minimize(fun_and_grad, metric, x0, tol=tolerance, maxiter=50000)
         if self.adjoint_gradient:
             n_params = min(len(ops), len(x0))
             ev = self._evaluator(hamiltonian_sp, ops, hf_init_sp, n_params)
