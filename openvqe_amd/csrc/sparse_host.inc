@@ -354,6 +354,7 @@ int launch_rows_shared(ovqe_handle h, const SparseArgs &R, bool *taken) {
     case 2: return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, TE, 2>(h, R, smem);
     case 3: return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, TE, 3>(h, R, smem);
     case 4: return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, TE, 4>(h, R, smem);
+    case 5: return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, TE, 5>(h, R, smem);
     default: break;
     }
 #endif
@@ -466,6 +467,9 @@ int run_sparse(ovqe_handle h, int64_t B, const double *theta, double *energies, 
             case 1: OVQE_ROWS(1); break;
             case 2: OVQE_ROWS(2); break;
             case 3: OVQE_ROWS(3); break;
+#ifdef OVQE_TESTING
+            case 5: OVQE_ROWS(5); break;
+#endif
             default: OVQE_ROWS(0);
             }
 #undef OVQE_ROWS

@@ -16,6 +16,7 @@
 #pragma once
 #include "sv_small.hpp"
 #include "sv_metric_host.hpp"
+#include "sv_wave_reduce.hpp"
 
 namespace ovqe {
 
@@ -45,7 +46,7 @@ struct SparseArgs {
     int hf;       // compact slot of |hf>
     int64_t B;
     double constant;
-    int dbg = 0;  // measurements ("sparse_dbg"; the rows kernels take it as a template argument): 1 no sincos, 2 no circuit rows, 3 no Hamiltonian entries, 4 (k_sparse_vqe_rows_shared) no theta loads
+    int dbg = 0;  // measurements ("sparse_dbg"; the rows kernels take it as a template argument): 1 no sincos, 2 no circuit rows, 3 no Hamiltonian entries, 4 (k_sparse_vqe_rows_shared) no theta loads, 5 nothing left out: wave sums by __shfl_down, as before sv_wave_reduce.hpp
 };
 
 struct SpVqeLds { size_t cs, ops, pairs, bytes; };   // the spw states ([spw][mpad]) are at 0
@@ -155,7 +156,7 @@ __global__ __launch_bounds__(64) void k_sparse_vqe(SparseArgs A, const double *_
         }
 #pragma unroll
         for (int s = 0; s < SPW; ++s) {
-            const double tot = wave_sum(acc[s]);
+            const double tot = wave_sum_lane0(WaveLanes{lane}, acc[s]);   // (the tree of wave_sum: sv_wave_reduce.hpp)
             if (lane == 0 && b0 + s < A.B) energies[b0 + s] = tot + A.constant;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -179,7 +180,7 @@ __host__ __device__ inline SpRowsLds sp_rows_lds(const SparseArgs &A, int spw) {
 //   bits 0-15 byte offset of amplitude i | 16-31 byte offset of amplitude j | 32-47 byte offset of the cos/sin entry | 63 sign
 // Padded lanes rotate two private spare slots behind the support by the identity entry behind the table (no branch).  Rows are
 // fetched four ahead in registers; per row: one 8-byte load, three LDS reads, four f64 operations, two LDS writes.
-template <int SPW, int DBG = 0>   // DBG: measurements ("sparse_dbg": 1 no sincos, 2 no circuit rows, 3 no Hamiltonian entries) — a
+template <int SPW, int DBG = 0>   // DBG: measurements ("sparse_dbg": 1 no sincos, 2 no circuit rows, 3 no Hamiltonian entries; 5: the wave sums by wave_sum) — a
 // run-time test of A.dbg in the loop bounds cost the product kernel 12 % (0.714 -> 0.80 ms per 65 536 evaluations), hence compile time
 __global__ __launch_bounds__(64) void k_sparse_vqe_rows(SparseArgs A, const double *__restrict__ theta,
                                                         const SmallRot *__restrict__ tabrots, const uint64_t *__restrict__ rows,
@@ -266,7 +267,7 @@ __global__ __launch_bounds__(64) void k_sparse_vqe_rows(SparseArgs A, const doub
         }
 #pragma unroll
         for (int q = 0; q < SPW; ++q) {
-            const double tot = wave_sum(acc[q]);
+            const double tot = DBG == 5 ? wave_sum(acc[q]) : wave_sum_lane0(WaveLanes{lane}, acc[q]);
             if (lane == 0 && b0 + q < A.B) energies[b0 + q] = tot + A.constant;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -346,7 +347,20 @@ __host__ __device__ constexpr SpRowsSharedLds sp_rows_shared_lds(int ntab) {
 // the one before: the contraction ahead 0.431 -> 0.422 ms (about 2 %: the LDS pipeline is busy for over half of the launch and
 // shared with the rows of the CU's other workgroup, the round trips were not all that the phase waited for), the entry ahead
 // 0.422 -> 0.391 (a row's chain is longest while the other workgroup contracts).  LiH 0.229 -> 0.225.
-// DBG as k_sparse_vqe_rows; 4: no theta load at all, a constant in its place (what the loads themselves cost).
+//
+// THE WAVE SUMS STAY IN REGISTERS (sv_wave_reduce.hpp; profiles/wave_sums/README.md).  Behind the contraction every wave sums its
+// NS = 8 accumulators over its lanes.  With wave_sum that was 8 x 6 __shfl_down steps on doubles: 96 ds_bpermute_b32, an
+// s_waitcnt lgkmcnt(0) in front of each of the 48 v_add_f64, each state's total through its own exec-masked ds_write_b64 — 48 LDS
+// round trips in strict series per wave and work item, all four waves at once, in front of the second barrier and through the LDS
+// queue that the rows of the CU's other workgroup need.  wave_sums8 reduces the eight states TRANSPOSED on the VALU: four
+// v_permlane32_swap pairs leave states 0..3 in lanes 0-31 and states 4..7 in lanes 32-63, two v_permlane16_swap pairs two states
+// per row of 16 lanes, a select and a DPP row_ror:8 one state per octet, row_shl:4 / 2 / 1 finish inside the octet: 12 swaps, 8 DPP
+// moves, 4 v_cndmask, 10 v_add_f64, and ONE ds_write_b64 from lanes 8 q into red[wave][q].  Every level adds the same two operands
+// as the __shfl_down tree of lane 0 (addition commutes bit for bit): every energy keeps its bits.  No ds_bpermute_b32 is left in
+// either instance; 250 / 162 VGPRs (the tail lies behind the register peak).  reduce(), the red layout and the wave-order addition
+// of the NW partial sums are as they were.
+// DBG as k_sparse_vqe_rows; 4: no theta load at all, a constant in its place (what the loads themselves cost); 5: the wave sums by
+// wave_sum as before (testing build: the reference of tests/test_gpu_sparse_reduce.py, and the cost of the old tail in one build).
 template <int NW, int RPT, int EPR, int SSTRIDE, int TE, int DBG = 0>
 __global__ __launch_bounds__(NW * 64) void k_sparse_vqe_rows_shared(SparseArgs A, const double *__restrict__ theta,
                                                                     const SmallRot *__restrict__ tabrots, const uint64_t *__restrict__ rows,
@@ -357,6 +371,7 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_vqe_rows_shared(SparseArgs A
     static_assert(SSTRIDE % 8 == 0 && SSTRIDE % 512 != 0 && NS * SSTRIDE <= 65536 && (NS * SSTRIDE) % 16 == 0,
                   "state offsets are DS instruction immediates; a stride the ds_read2 forms cannot encode (see above)");
     static_assert(TE >= 0, "table records per lane");
+    static_assert(NS == 8, "the transposed wave sums (wave_sums8) are built for eight states per workgroup");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int ntab1 = A.ntab + 1;
     const SpRowsSharedLds L = sp_rows_shared_lds<NW, SSTRIDE>(A.ntab);
@@ -539,10 +554,15 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_vqe_rows_shared(SparseArgs A
                 }
             }
         }
+        if constexpr (DBG == 5) {
 #pragma unroll
-        for (int q = 0; q < NS; ++q) {
-            const double tot = wave_sum(acc[q]);
-            if (lane == 0) red[wave * NS + q] = tot;
+            for (int q = 0; q < NS; ++q) {
+                const double tot = wave_sum(acc[q]);
+                if (lane == 0) red[wave * NS + q] = tot;
+            }
+        } else {
+            const double z = wave_sums8(WaveLanes{lane}, acc);   // lane 8 q: the total of state q
+            if ((lane & 7) == 0) red[wave * NS + (lane >> 3)] = z;
         }
         bprev = w * NS;
         if (!more) break;

@@ -1,7 +1,8 @@
 """the headline workload (H2O/STO-3G UCCSD, 65 536 evaluations per launch) on both geometries of the rows form in one process —
 k_sparse_vqe_rows_shared (workgroup geometry, "sparse_shared" = 1) and k_sparse_vqe_rows<2> (one wave per pair of evaluations,
 "sparse_shared" = 0) — each without one of its phases ("sparse_dbg": 1 no sincos, 2 no circuit rows, 3 no Hamiltonian entries; the workgroup geometry
-also 4: a constant in place of every theta load): where the time goes.  Needs the testing build (OVQE_LIB=testing).  python tools/exp_value_phases.py [geoms=1,0] [name=value]"""
+also 4: a constant in place of every theta load): where the time goes.  5 leaves nothing out: the wave sums behind the contraction by
+__shfl_down, as before sv_wave_reduce.hpp — its "phase left out" is NEGATIVE, minus the cost of the old sums.  Needs the testing build (OVQE_LIB=testing).  python tools/exp_value_phases.py [geoms=1,0] [name=value]"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -25,7 +26,9 @@ with Statevector(ham.nbqbits) as sv:
     for geom in geoms:
         sv.set_option("sparse_shared", geom)
         for dbg, label in ((0, "whole kernel"), (1, "no sincos"), (2, "no circuit rows"), (3, "no Hamiltonian entries"),
-                           (4, "no theta loads"))[:5 if geom else 4]:
+                           (4, "no theta loads"), (5, "wave sums by __shfl_down")):
+            if dbg == 4 and not geom:
+                continue
             sv.set_option("sparse_dbg", dbg)
             sv.energy_batch(th)
             ts = sorted((sv.energy_batch(th), sv.last_batch_ms())[1] for _ in range(7))
