@@ -99,6 +99,15 @@ int ovqe_rdm(ovqe_handle h, int order, double *out_re_im);
 int ovqe_rdm_info(ovqe_handle h, int64_t *info, int count);
 int ovqe_metric_tensor(ovqe_handle h, const double *theta, int32_t K, double *metric);
 int ovqe_metric_info(ovqe_handle h, int64_t *info, int count);
+int ovqe_sample(ovqe_handle h, int64_t n_shots, uint64_t seed, uint64_t stream, uint64_t first_shot, uint64_t *indices);
+int ovqe_measure_paulis(ovqe_handle h, uint64_t xbasis, uint64_t ybasis, int64_t n_shots, uint64_t seed, uint64_t stream,
+                        uint64_t first_shot, int64_t T, const uint64_t *mask, const double *coeff, int64_t *term_sums,
+                        double *value_sums, uint64_t *indices);
+int ovqe_measure_groups(ovqe_handle h, int64_t capacity, int32_t *group_of_term, uint64_t *xbasis, uint64_t *ybasis,
+                        int64_t *n_groups);
+int ovqe_energy_sampled(ovqe_handle h, const double *theta, int32_t K, int64_t n_shots, uint64_t seed, double *energy,
+                        double *std_error);
+int ovqe_measure_info(ovqe_handle h, int64_t *info, int count);
 int ovqe_time_pauli_rotation(ovqe_handle h, uint64_t x, uint64_t z, double phi, int warmup, int reps,
                              double *avg_ms);
 int ovqe_last_batch_ms(ovqe_handle h, double *ms);

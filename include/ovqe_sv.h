@@ -473,6 +473,59 @@ int ovqe_metric_tensor(ovqe_handle h, const double *theta, int32_t K, double *me
  * Gram, finish; zeros before the first call */
 int ovqe_metric_info(ovqe_handle h, int64_t *info, int count);
 
+/* ---- finite-shot measurement: outcomes drawn from the state in the buffer, and energies with shot noise (what a submission with
+ * nbshots > 0 asks of a QPU: openvqe_amd/qat_compat.py; every call site of the reference submits nbshots = 0, the exact paths above).
+ * Plain handles of any size; OVQE_ERR_STATE on a shard of a partitioned register and under option "real_state".  The state buffer is
+ * only read: psi is the same to the bit afterwards.
+ *
+ * UNIFORMS.  With mix64 the hash of ovqe_randomize (openvqe_amd/synth.py restates both on the host, bit for bit):
+ *     key = mix64(seed ^ mix64(stream)),    u(s) = (mix64(key ^ mix64(s)) >> 11) * 2^-53  in [0, 1),    s the ABSOLUTE shot number.
+ * Shots [0, S) drawn in one call or in pieces (first_shot) are the same bits; (seed, stream) pairs give independent sequences.
+ *
+ * OUTCOME OF A SHOT.  p_i = |a_i|^2, W = sum_i p_i (the state need not be normalised; W = 0 or not finite: OVQE_ERR_STATE), C_i the
+ * inclusive prefix sum of p in index order: the outcome is the smallest i with C_i > u W.  The device sums C in a fixed blocked order,
+ * so the same call returns the same bits every time and C agrees with the exact prefix sums to (2^n - 1) 2^-53 W; an index with
+ * p_i = 0 is never returned (zero entries are marked in the prefix array and stepped over, also for u close to 1 on a state whose tail
+ * is zero).  Outcome bit (n-1-q) is qubit q's result, bit 1 <-> eigenvalue -1.
+ *
+ * BASIS.  xbasis / ybasis: disjoint masks of index bits inside the register (else OVQE_ERR_INVALID), measured in X / in Y; the other
+ * bits in Z.  Outcomes are drawn from |phi|^2, phi = B psi, B the tensor product of H on the x bits and H S^+ on the y bits:
+ * (|0> + i|1>)/sqrt 2 measured in Y gives bit 0.  phi lives in scratch: 8 * 2^n bytes for the prefix array, 16 * 2^n more once a
+ * rotated bit lies above the 2^11-amplitude tile of the basis-change kernel; allocated at first use and kept on the handle,
+ * OVQE_ERR_ALLOC with the byte count in the text when that would take more than 60 % of the free device memory.
+ *
+ * indices[k] receives the outcome of shot first_shot + k, k < n_shots (0 <= n_shots <= 2^31). */
+int ovqe_sample(ovqe_handle h, int64_t n_shots, uint64_t seed, uint64_t stream, uint64_t first_shot, uint64_t *indices);
+/* the same shots in the given basis, scored on T diagonal terms: with b_s the outcome of shot s,
+ *     term_sums[t] = sum_s (-1)^popcount(b_s & mask[t])   (integers, exact),
+ *     value_sums   = { sum_s v_s, sum_s v_s^2 },   v_s = sum_t coeff[t] (-1)^popcount(b_s & mask[t]),
+ * both sums in a fixed order (integer atomics, a fixed tree over the waves): bit-identical from call to call.  For a Pauli string
+ * (x, z) that the basis diagonalises, mask = x | z; whether a term is diagonal in the basis is the caller's business.  indices may
+ * be NULL (the outcomes are then not stored); T = 0 with no basis change is ovqe_sample. */
+int ovqe_measure_paulis(ovqe_handle h, uint64_t xbasis, uint64_t ybasis, int64_t n_shots, uint64_t seed, uint64_t stream,
+                        uint64_t first_shot, int64_t T, const uint64_t *mask, const double *coeff, int64_t *term_sums,
+                        double *value_sums, uint64_t *indices);
+/* the measurement plan of the stored Hamiltonian (OVQE_ERR_STATE without one), built once per Hamiltonian and kept on the handle.
+ * A term acts on bit b with X if x & ~z, Y if x & z, Z if z & ~x.  Identity terms go to the constant and get group -1.  The others
+ * are taken by |coeff| descending, ties by stored position; each goes into the FIRST group whose basis agrees with the term on every
+ * bit where both act (qubit-wise commutation), and joining extends that group's basis; groups are numbered in creation order.
+ * *n_groups receives the number of groups G; group_of_term takes up to `capacity` of the T entries, xbasis / ybasis up to `capacity`
+ * of the G (G <= T; the arrays may be NULL when capacity is 0). */
+int ovqe_measure_groups(ovqe_handle h, int64_t capacity, int32_t *group_of_term, uint64_t *xbasis, uint64_t *ybasis,
+                        int64_t *n_groups);
+/* <H> of the stored program at theta from n_shots shots PER GROUP of that plan.  Leaves U(theta)|hf> in the state buffer exactly as
+ * ovqe_prepare_state does, then measures group g with stream = g, shots 0 .. n_shots - 1:
+ *     energy = constant + sum_g mean_g,    std_error = sqrt(sum_g s_g^2 / n_shots),
+ * mean_g and s_g^2 the mean and the unbiased sample variance of v over the shots of group g (a variance that rounding leaves below
+ * zero counts as zero; equal values over a power-of-two number of shots give exactly zero).  n_shots < 2: OVQE_ERR_INVALID; no
+ * Hamiltonian or no program: OVQE_ERR_STATE.  One wait for the whole call. */
+int ovqe_energy_sampled(ovqe_handle h, const double *theta, int32_t K, int64_t n_shots, uint64_t seed, double *energy,
+                        double *std_error);
+/* of the last measuring call, up to `count` entries of: [0] groups measured (1 for ovqe_sample / ovqe_measure_paulis) [1] shots per
+ * group [2] scratch bytes held [3] kernel launches [4..6] HIP-event times in microseconds summed over the groups: basis change,
+ * scan, draw + score [7] terms scored [8] streaming passes for rotated bits above the tile; zeros before the first call */
+int ovqe_measure_info(ovqe_handle h, int64_t *info, int count);
+
 /* ---- measurement support (bench.py): average device time in ms of `reps` back-to-back launches of
  * one Pauli-rotation sweep, bracketed by HIP events on the handle's stream */
 int ovqe_time_pauli_rotation(ovqe_handle h, uint64_t x, uint64_t z, double phi, int warmup, int reps,

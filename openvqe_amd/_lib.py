@@ -32,6 +32,13 @@ class _OptF64(object):
         return _f64p.from_param(obj)
 
 
+def _optional(ptr_type):
+    """ndpointer that also accepts None (NULL)."""
+    return type("_Opt", (object,), {"from_param": classmethod(lambda cls, obj: None if obj is None else ptr_type.from_param(obj))})
+
+
+_OptU64, _OptI64 = _optional(_u64p), _optional(_i64p)
+
 # every symbol declared in include/ovqe_sv.h: name -> (restype, argtypes)
 SIGNATURES = {
     "ovqe_version": (_int, []),
@@ -103,6 +110,11 @@ SIGNATURES = {
     "ovqe_rdm_info": (_int, [_H, ctypes.POINTER(ctypes.c_int64), _int]),
     "ovqe_metric_tensor": (_int, [_H, _OptF64, ctypes.c_int32, _OptF64]),
     "ovqe_metric_info": (_int, [_H, ctypes.POINTER(ctypes.c_int64), _int]),
+    "ovqe_sample": (_int, [_H, _i64, _u64, _u64, _u64, _OptU64]),
+    "ovqe_measure_paulis": (_int, [_H, _u64, _u64, _i64, _u64, _u64, _u64, _i64, _OptU64, _OptF64, _OptI64, _f64p, _OptU64]),
+    "ovqe_measure_groups": (_int, [_H, _i64, _i32p, _u64p, _u64p, ctypes.POINTER(_i64)]),
+    "ovqe_energy_sampled": (_int, [_H, _OptF64, ctypes.c_int32, _i64, _u64, ctypes.POINTER(_dbl), ctypes.POINTER(_dbl)]),
+    "ovqe_measure_info": (_int, [_H, ctypes.POINTER(ctypes.c_int64), _int]),
     "ovqe_program_info": (_int, [_H, ctypes.POINTER(ctypes.c_int64), _int]),
     "ovqe_get_rotation_program": (_int, [_H, _i64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.POINTER(ctypes.c_int64)]),

@@ -346,6 +346,7 @@ class Statevector:
         coeff = np.array([_real_coeff(c, "observable") for c in cs], np.float64)
         const = _real_coeff(getattr(hamiltonian, "constant_coeff", 0.0) or 0.0, "observable constant")
         self._ck(self._L.ovqe_set_hamiltonian(self._h, xs.shape[0], xs, zs, coeff, const))
+        self._ham_terms = int(xs.shape[0])
 
     def set_rotation_program(self, xs, zs, coeffs, pidx, n_params, hf_init, phi0=None):
         xs = np.ascontiguousarray(xs, np.uint64)
@@ -585,6 +586,60 @@ class Statevector:
         out = (ctypes.c_int64 * 9)()
         self._ck(self._L.ovqe_metric_info(self._h, out, 9))
         keys = ("path", "K", "tangent_amplitudes", "store_bytes", "tangent_launches", "gram_launches", "tangents_us", "gram_us", "finish_us")
+        return dict(zip(keys, [int(v) for v in out]))
+
+    # -- finite-shot measurement (ovqe_sample ..., csrc/measure_host.inc) --------------------------------------------------------
+    def sample(self, n_shots, seed=0, stream=0, first_shot=0):
+        """outcomes of shots ``first_shot .. first_shot + n_shots - 1`` drawn from |amplitude|^2 of the state in the buffer (which
+        need not be normalised): uint64 basis indices, bit n-1-q = qubit q.  Shot s uses ``synth.shot_uniforms(seed, stream, s, 1)``."""
+        out = np.zeros(int(n_shots), np.uint64)
+        self._ck(self._L.ovqe_sample(self._h, int(n_shots), int(seed), int(stream), int(first_shot), out if n_shots else None))
+        return out
+
+    def measure_paulis(self, masks, coeffs, n_shots, xbasis=0, ybasis=0, seed=0, stream=0, first_shot=0, return_indices=False):
+        """the same shots after the basis change (X on the index bits of ``xbasis``, Y on those of ``ybasis``), scored on diagonal
+        terms: -> (term_sums int64 [T], (sum v, sum v^2)[, indices]) with v_s = sum_t coeffs[t] (-1)^popcount(b_s & masks[t])"""
+        masks = np.ascontiguousarray(masks, np.uint64).reshape(-1)
+        coeffs = np.ascontiguousarray(coeffs, np.float64).reshape(-1)
+        if masks.shape != coeffs.shape:
+            raise ValueError("masks and coeffs differ in length")
+        T = masks.shape[0]
+        tsum = np.zeros(T, np.int64)
+        vsum = np.zeros(2, np.float64)
+        idx = np.zeros(int(n_shots), np.uint64) if return_indices else None
+        self._ck(self._L.ovqe_measure_paulis(self._h, int(xbasis), int(ybasis), int(n_shots), int(seed), int(stream), int(first_shot), T,
+                                             masks if T else None, coeffs if T else None, tsum if T else None, vsum,
+                                             idx if return_indices and n_shots else None))
+        return (tsum, vsum, idx) if return_indices else (tsum, vsum)
+
+    def measurement_groups(self):
+        """the measurement plan of the stored Hamiltonian: (group of every stored term, -1 for identity terms; xbasis per group;
+        ybasis per group) — qubit-wise commuting groups, first fit by |coeff| descending (include/ovqe_sv.h)"""
+        G = ctypes.c_int64()
+        cap = max(int(getattr(self, "_ham_terms", 0)), 1)
+        got = np.full(cap, -1, np.int32)
+        xb = np.zeros(cap, np.uint64)
+        yb = np.zeros(cap, np.uint64)
+        self._ck(self._L.ovqe_measure_groups(self._h, cap, got, xb, yb, ctypes.byref(G)))
+        return got[:int(getattr(self, "_ham_terms", 0))], xb[:G.value], yb[:G.value]
+
+    def energy_sampled(self, theta, n_shots, seed=0):
+        """<H> of the stored program at ``theta`` from ``n_shots`` shots per measurement group -> (energy, standard error); leaves
+        U(theta)|hf> in the state buffer like ``prepare_state``"""
+        K = self._K
+        theta = np.ascontiguousarray(theta, np.float64).reshape(-1)[:K]
+        if theta.shape[0] != K:
+            raise ValueError(f"expected {K} parameters")
+        e, s = ctypes.c_double(), ctypes.c_double()
+        self._ck(self._L.ovqe_energy_sampled(self._h, theta if K else None, K, int(n_shots), int(seed), ctypes.byref(e), ctypes.byref(s)))
+        return e.value, s.value
+
+    def measure_info(self):
+        """figures of the last measuring call: groups, shots per group, scratch bytes, launches, HIP-event times of the phases in
+        microseconds (summed over the groups), terms scored, streaming passes for rotated bits above the LDS tile"""
+        out = (ctypes.c_int64 * 9)()
+        self._ck(self._L.ovqe_measure_info(self._h, out, 9))
+        keys = ("groups", "shots", "scratch_bytes", "launches", "basis_us", "scan_us", "draw_us", "terms", "high_passes")
         return dict(zip(keys, [int(v) for v in out]))
 
     def program_info(self):

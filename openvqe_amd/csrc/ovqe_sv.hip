@@ -47,6 +47,7 @@
 #include "sv_lanczos_host.hpp"
 #include "sv_rdm.hpp"
 #include "sv_metric.hpp"
+#include "sv_measure.hpp"
 #include <hipcub/hipcub.hpp>
 #include <unordered_map>
 #include <unordered_set>
@@ -272,6 +273,7 @@ struct SectorEngine {
 
 struct RdmDev;   // rdm_host.inc
 struct MetricDev;   // metric_host.inc
+struct MeasureDev;   // measure_host.inc
 
 }  // namespace
 
@@ -494,6 +496,7 @@ struct ovqe_sv {
     int opt_rdm_workspace_mb = 1024; // rows of a density-matrix call are materialised in chunks of at most this many MB
     MetricDev *metric = nullptr;     // buffers and figures of ovqe_metric_tensor (first call)
     int opt_metric_workspace_mb = 0; // cap of its tangent store in MB (0: 60 % of the free device memory)
+    MeasureDev *measure = nullptr;   // scratch, plan and figures of the finite-shot measurements (first call)
 };
 
 namespace {
@@ -1136,6 +1139,8 @@ void push_rotation(ovqe_handle h, uint64_t x, uint64_t z, double coeff, double p
 
 #include "metric_host.inc"
 
+#include "measure_host.inc"
+
 int check_theta(ovqe_handle h, const double *theta, int32_t K) {
     if (!h->prog_set) return fail(h, OVQE_ERR_STATE, "no program set (ovqe_set_program / ovqe_set_gate_program)");
     if (K != h->K) return fail(h, OVQE_ERR_INVALID, "K does not match the program's parameter count");
@@ -1245,6 +1250,7 @@ int ovqe_destroy(ovqe_handle h) try {
     for (PoolPlan *P : h->xpools) free_pool_plan(P);
     free_rdm(h->rdm);
     free_metric(h->metric);
+    free_measure(h->measure);
     h->kept_blocks.flush();
     if (h->h_rp) (void)hipHostFree(h->h_rp);
     if (h->h_result) (void)hipHostFree(h->h_result);
@@ -1547,6 +1553,8 @@ int ovqe_norm2(ovqe_handle h, double *out) try {
 #include "abi_rdm.inc"
 
 #include "abi_metric.inc"
+
+#include "abi_measure.inc"
 
 // ---- measurement support ------------------------------------------------------------------------
 int ovqe_time_pauli_rotation(ovqe_handle h, uint64_t x, uint64_t z, double phi, int warmup, int reps, double *avg_ms) try {

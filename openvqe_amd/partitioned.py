@@ -249,6 +249,12 @@ class PartitionedStatevector:
         raise NotImplementedError("the Fubini-Study metric is computed on one device (ovqe_metric_tensor keeps K tangent vectors next to "
                                   "the state): not available on the partitioned register")
 
+    def sample(self, *args, **kwargs):
+        raise NotImplementedError("finite-shot measurement draws from the prefix sums of one device's register (ovqe_sample, "
+                                  "ovqe_energy_sampled): shots (nbshots > 0) are not available on the partitioned register")
+
+    measure_paulis = measurement_groups = energy_sampled = sample
+
     def last_screen_support(self):
         return -1
 

@@ -324,12 +324,17 @@ class Circuit:
             raise ValueError(job_type)
         if job_type == "OBS" and observable is None:
             raise ValueError("OBS job without observable")
-        return Job(self, job_type, observable)
+        if int(nbshots) < 0:
+            raise ValueError("nbshots must not be negative")
+        return Job(self, job_type, observable, int(nbshots))
 
 
 class Job:
-    def __init__(self, circuit, job_type, observable):
-        self.circuit, self.type, self.observable = circuit, job_type, observable
+    """``nbshots`` = 0 (every call site of the reference): the exact value / the exact amplitudes; > 0: that many shots (per measurement
+    group for an observable)"""
+
+    def __init__(self, circuit, job_type, observable, nbshots=0):
+        self.circuit, self.type, self.observable, self.nbshots = circuit, job_type, observable, int(nbshots)
 
 
 class _State:
@@ -345,18 +350,23 @@ class _State:
 class Sample:
     __slots__ = ("state", "amplitude", "probability")
 
-    def __init__(self, index, amplitude, nbqbits):
+    def __init__(self, index, amplitude, nbqbits, probability=None):
         self.state = _State(index, nbqbits)
-        self.amplitude = complex(amplitude)
-        self.probability = abs(amplitude) ** 2
+        if amplitude is None:    # a sampled state: its observed frequency, no amplitude
+            self.amplitude = None
+            self.probability = float(probability)
+        else:
+            self.amplitude = complex(amplitude)
+            self.probability = abs(amplitude) ** 2
 
 
 class Result:
     """value of an observable job, or the samples of a state-vector job.  The samples of a large register are kept as
     the arrays the device listed (``indices`` ascending, ``amplitudes``); Sample objects are made when somebody iterates."""
 
-    def __init__(self, value=None, samples=None, indices=None, amplitudes=None, nbqbits=None):
+    def __init__(self, value=None, samples=None, indices=None, amplitudes=None, nbqbits=None, error=None):
         self.value = value
+        self.error = error        # standard error of ``value`` when it was estimated from shots, else None
         self.indices = indices
         self.amplitudes = amplitudes
         self._nbqbits = nbqbits
@@ -378,6 +388,15 @@ class Result:
 
 
 # ------------------------------------------------------------------------------------ execution
+def _mix64(v):
+    """the hash of the backend's counter-based generators (csrc/sv_kernels.hpp ``mix64``, synth.py) on Python integers"""
+    m = (1 << 64) - 1
+    v = (v + 0x9E3779B97F4A7C15) & m
+    v = ((v ^ (v >> 30)) * 0xBF58476D1CE4E5B9) & m
+    v = ((v ^ (v >> 27)) * 0x94D049BB133111EB) & m
+    return v ^ (v >> 31)
+
+
 def lower_circuit(circuit, theta=None):
     """-> (hf_index, kind, payload): kind 'rotations' -> (xs, zs, coeff, phi0, pidx);
     kind 'gates' -> list of (name, qubits, scale, const, pidx).  Leading X gates / the ``init`` of a leading
@@ -424,7 +443,9 @@ def lower_circuit(circuit, theta=None):
 
 
 class HipQPU:
-    """``get_default_qpu()`` stand-in: exact (nbshots=0) simulation on the MI355X backend.
+    """``get_default_qpu()`` stand-in: exact (nbshots=0) simulation on the MI355X backend, or finite-shot sampling of it (nbshots > 0:
+    ``Statevector.energy_sampled`` / ``Statevector.sample``; one device only).  Submissions are counted and a sampled one draws with
+    ``seed`` hashed with its number: successive submissions are independent, a rerun of a script repeats its numbers.
 
     The reference rebuilds Program / Circuit / Job for every energy evaluation (ref:openvqe/ucc_family/get_energy_ucc.py:35-50).
     A circuit made of Pauli evolutions of the SAME operator objects as the previous one (what an optimiser loop submits)
@@ -434,7 +455,9 @@ class HipQPU:
     names, qubits, quarter-turn angles — with every other rotation gate as a parameter of its own, so the second submission
     of a template only passes its angles (and the Clifford-frame / sector paths keep their tables)."""
 
-    def __init__(self, device=None):
+    def __init__(self, device=None, seed=0):
+        self.seed = int(seed)
+        self.submissions = 0
         self.device = device    # None: this rank's GPU (replicas.device()); registers too large for one device are partitioned
         self._sv = {}
         self._compiled = {}   # nbqbits -> (skeleton key, operator objects kept alive, n_params)
@@ -553,14 +576,23 @@ class HipQPU:
         n = circ.nbqbits
         sv = self._backend(n)
         theta = self._load(sv, circ)
+        self.submissions += 1
+        nbshots = int(getattr(job, "nbshots", 0) or 0)
+        shot_seed = _mix64(self.seed ^ _mix64(self.submissions))
         if job.type == "OBS":
             seen = self._observable.get(n)
             fp = self._fingerprint(job.observable)
             if seen is None or seen[0] is not job.observable or seen[1] != fp:
                 sv.set_hamiltonian(job.observable)
                 self._observable[n] = (job.observable, fp)
+            if nbshots > 0:
+                value, error = sv.energy_sampled(theta, nbshots, seed=shot_seed)
+                return Result(value=value, error=error)
             return Result(value=sv.energy(theta))
         sv.prepare_state(theta)
+        if nbshots > 0:
+            states, counts = np.unique(sv.sample(nbshots, seed=shot_seed), return_counts=True)   # ascending
+            return Result(samples=[Sample(int(i), None, circ.nbqbits, probability=c / nbshots) for i, c in zip(states, counts)])
         listed = sv.get_support() if n >= 16 else None   # non-zero amplitudes listed on the device (ovqe_get_support)
         if listed is not None:
             return Result(indices=listed[0].astype(np.int64), amplitudes=listed[1], nbqbits=circ.nbqbits)

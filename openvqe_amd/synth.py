@@ -26,3 +26,15 @@ def amplitudes(seed, global_indices):
         re = _unit(_mix64(h ^ np.uint64(0x1234567)))
         im = _unit(_mix64(h ^ np.uint64(0x89ABCDEF)))
     return re + 1j * im
+
+
+def shot_uniforms(seed, stream, first, count):
+    """the uniforms of shots ``first .. first + count - 1`` of a finite-shot measurement (include/ovqe_sv.h, csrc/sv_measure.hpp
+    ``k_meas_draw``): key = mix64(seed ^ mix64(stream)), u(s) = (mix64(key ^ mix64(s)) >> 11) * 2^-53 in [0, 1), s the absolute
+    shot number — so a draw in pieces gives the bits of the whole draw"""
+    m = (1 << 64) - 1
+    with np.errstate(over="ignore"):
+        key = _mix64(np.uint64(int(seed) & m) ^ _mix64(np.uint64(int(stream) & m)))
+        s = np.uint64(int(first) & m) + np.arange(int(count), dtype=np.uint64)
+        bits = _mix64(key ^ _mix64(s))
+    return (bits >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
