@@ -470,7 +470,8 @@ int ovqe_rdm_info(ovqe_handle h, int64_t *info, int count);
 int ovqe_metric_tensor(ovqe_handle h, const double *theta, int32_t K, double *metric);
 /* of the last ovqe_metric_tensor call, up to `count` entries of: [0] path (1 compact support, 2 streaming) [1] K [2] amplitudes per tangent
  * [3] bytes of the tangent store [4] launches of the tangent stage [5] Gram launches [6..8] HIP-event times in microseconds: tangents,
- * Gram, finish; zeros before the first call */
+ * Gram, finish [9] form of the tangent kernel: 0 streaming, 1 compact with ops and pair words staged in LDS, 2 compact with both read
+ * from global memory [10] dynamic LDS bytes of the tangent launch (0 on the streaming path); zeros before the first call */
 int ovqe_metric_info(ovqe_handle h, int64_t *info, int count);
 
 /* ---- finite-shot measurement: outcomes drawn from the state in the buffer, and energies with shot noise (what a submission with

@@ -582,10 +582,13 @@ class Statevector:
 
     def metric_info(self):
         """figures of the last ``metric_tensor`` call: path (1 compact support, 2 streaming), parameters, amplitudes per tangent, bytes
-        of the tangent store, launches of the tangent stage and of the Gram kernel, HIP-event times of the phases in microseconds"""
-        out = (ctypes.c_int64 * 9)()
-        self._ck(self._L.ovqe_metric_info(self._h, out, 9))
-        keys = ("path", "K", "tangent_amplitudes", "store_bytes", "tangent_launches", "gram_launches", "tangents_us", "gram_us", "finish_us")
+        of the tangent store, launches of the tangent stage and of the Gram kernel, HIP-event times of the phases in microseconds, form of
+        the tangent kernel (0 streaming, 1 compact with its tables staged in LDS, 2 compact with the tables read from global memory) and
+        the dynamic LDS bytes of its launch"""
+        out = (ctypes.c_int64 * 11)()
+        self._ck(self._L.ovqe_metric_info(self._h, out, 11))
+        keys = ("path", "K", "tangent_amplitudes", "store_bytes", "tangent_launches", "gram_launches", "tangents_us", "gram_us", "finish_us",
+                "tangent_form", "tangent_lds_bytes")
         return dict(zip(keys, [int(v) for v in out]))
 
     # -- finite-shot measurement (ovqe_sample ..., csrc/measure_host.inc) --------------------------------------------------------

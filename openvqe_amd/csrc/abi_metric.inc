@@ -16,6 +16,6 @@ int ovqe_metric_tensor(ovqe_handle h, const double *theta, int32_t K, double *me
 int ovqe_metric_info(ovqe_handle h, int64_t *info, int count) try {
     OVQE_ENTER(h);
     if (!h || !info || count < 0) return OVQE_ERR_INVALID;
-    for (int i = 0; i < count && i < 9; ++i) info[i] = h->metric ? h->metric->info[i] : 0;
+    for (int i = 0; i < count && i < 11; ++i) info[i] = h->metric ? h->metric->info[i] : 0;
     return OVQE_OK;
 } OVQE_CATCH(h)

@@ -13,7 +13,7 @@ struct MetricDev {
     bool compact_ok = false;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     std::vector<double2> host_out;
-    int64_t info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t info[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 void free_metric(MetricDev *M) {
@@ -65,7 +65,7 @@ int run_metric(ovqe_handle h, const double *theta, double *out) {
     const int K = h->K;
     if (!h->metric) h->metric = new MetricDev();
     MetricDev &M = *h->metric;
-    std::fill(M.info, M.info + 9, 0);
+    std::fill(M.info, M.info + 11, 0);
     if (K == 0) return OVQE_OK;
     if (h->num_cus <= 0) {
         int cus = 0;
@@ -116,18 +116,20 @@ int run_metric(ovqe_handle h, const double *theta, double *out) {
     HIPC(h, hipMemsetAsync(M.d_store.p, 0, st.bytes, h->stream));   // (the padding columns of the Gram blocks read as zeros)
     HIPC(h, hipMemsetAsync(M.d_slabs.p, 0, slab_bytes, h->stream));
     int64_t launches = 0;
+    size_t tangent_lds = 0;
     HIPC(h, hipEventRecord(M.ev[0], h->stream));
     if (compact) {
         A.wpad = st.wpad;
+        tangent_lds = sp_metric_lds(A, stage).bytes;
         HIPC(h, hipMemcpyAsync(M.d_theta.p, theta, (size_t)K * sizeof(double), hipMemcpyHostToDevice, h->stream));
         rc = lds_opt_in<&k_sparse_metric<true>, &k_sparse_metric<false>>(h, LDS_WG_MAX);
         if (rc) return rc;
         if (stage)
-            hipLaunchKernelGGL((k_sparse_metric<true>), dim3(K), dim3(64), sp_metric_lds(A, true).bytes, h->stream, A, (const double *)M.d_theta.p,
+            hipLaunchKernelGGL((k_sparse_metric<true>), dim3(K), dim3(64), tangent_lds, h->stream, A, (const double *)M.d_theta.p,
                                (const metric::TabEntry *)M.d_tab.p, (const metric::Op *)M.d_ops.p, (const uint32_t *)M.d_pairs.p,
                                (const int32_t *)M.d_first.p, (double *)M.d_store.p);
         else
-            hipLaunchKernelGGL((k_sparse_metric<false>), dim3(K), dim3(64), sp_metric_lds(A, false).bytes, h->stream, A, (const double *)M.d_theta.p,
+            hipLaunchKernelGGL((k_sparse_metric<false>), dim3(K), dim3(64), tangent_lds, h->stream, A, (const double *)M.d_theta.p,
                                (const metric::TabEntry *)M.d_tab.p, (const metric::Op *)M.d_ops.p, (const uint32_t *)M.d_pairs.p,
                                (const int32_t *)M.d_first.p, (double *)M.d_store.p);
         HIPC(h, hipGetLastError());
@@ -218,5 +220,7 @@ int run_metric(ovqe_handle h, const double *theta, double *out) {
         HIPC(h, hipEventElapsedTime(&ms, M.ev[k], M.ev[k + 1]));
         M.info[6 + k] = (int64_t)(1e3 * ms);
     }
+    M.info[9] = compact ? (stage ? 1 : 2) : 0;
+    M.info[10] = (int64_t)tangent_lds;
     return OVQE_OK;
 }

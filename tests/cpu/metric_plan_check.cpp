@@ -5,10 +5,16 @@
 // tangents are compared with a dense complex forward-mode simulation of exp(-i phi P).  Then the tangent store is laid out and the Gram
 // schedule replayed the way k_rdm_gram / k_rdm_finish index it, against the plain Gram matrix.
 //   usage: metric_plan_check [seed]
+//          metric_plan_check boundary      the programs at the limits of the compact path: a support of exactly MAX_SUPPORT states
+//                                          (compact index 4095 in the 12-bit fields of the pair words) with 20, 21, 3669 and 3670
+//                                          rotations — the last program whose tables are staged in LDS, the first whose tables stay in
+//                                          global memory, the last and the first beyond a workgroup's LDS budget — and the refusal at
+//                                          the first state beyond the cap; prints the table sizes (tests/test_metric_cases.py)
 #include <cmath>
 #include <complex>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 
 #include "../../openvqe_amd/csrc/sv_metric_host.hpp"
@@ -74,6 +80,9 @@ static bool fuse(const std::vector<Rot> &run, std::vector<metric::InRot> &rots, 
     return true;
 }
 
+static bool check_program(std::mt19937_64 &rng, int n, uint64_t hf, const std::vector<Rot> &prog, const std::vector<double> &theta, int K,
+                          bool fuse_runs, metric::Compact *out);
+
 static void one_program(std::mt19937_64 &rng, int n, int R, int K, bool fuse_runs) {
     std::uniform_real_distribution<double> U(-1.0, 1.0);
     const uint64_t N = 1ull << n;
@@ -106,6 +115,15 @@ static void one_program(std::mt19937_64 &rng, int n, int R, int K, bool fuse_run
     }
     std::vector<double> theta((size_t)K);
     for (double &t : theta) t = U(rng);
+    metric::Compact C;
+    CHECK(check_program(rng, n, hf, prog, theta, K, fuse_runs, &C), "build_compact declined a real program (n = %d)", n);
+}
+
+// false: build_compact declined the program
+static bool check_program(std::mt19937_64 &rng, int n, uint64_t hf, const std::vector<Rot> &prog, const std::vector<double> &theta, int K,
+                          bool fuse_runs, metric::Compact *out) {
+    const uint64_t N = 1ull << n;
+    metric::Compact &C = *out;
     // ---- the fused-kernel program: same-x runs, fused where the structure allows
     std::vector<metric::InOp> ops;
     std::vector<metric::InRot> rots;
@@ -124,10 +142,7 @@ static void one_program(std::mt19937_64 &rng, int n, int R, int K, bool fuse_run
         }
         r = e;
     }
-    metric::Compact C;
-    const bool ok = metric::build_compact(hf, ops, rots, K, &C);
-    CHECK(ok, "build_compact declined a real program (n = %d)", n);
-    if (!ok) return;
+    if (!metric::build_compact(hf, ops, rots, K, &C)) return false;
     CHECK(C.m >= 1 && C.m <= metric::MAX_SUPPORT && (int)C.first_op.size() == K, "shape");
     // ---- dense forward mode
     std::vector<cd> psi(N, 0.0);
@@ -238,11 +253,123 @@ static void one_program(std::mt19937_64 &rng, int n, int R, int K, bool fuse_run
         }
     CHECK(worst <= 1e-12 * scale, "metric differs from the dense simulation by %.3e (n = %d, K = %d, fused = %d)", worst, n, K, (int)fuse_runs);
     if (K >= 1) {   // the unused last parameter: a zero column
-        for (int i = 0; i < C.m; ++i) CHECK(store[(size_t)i * st.wpad + (size_t)(K - 1)] == 0.0 || K == 1, "unused parameter");
+        bool used = false;
+        for (const Rot &q : prog) used = used || q.pidx == K - 1;
+        for (int i = 0; i < C.m; ++i) CHECK(used || store[(size_t)i * st.wpad + (size_t)(K - 1)] == 0.0 || K == 1, "unused parameter");
+    }
+    return true;
+}
+
+// ---- boundary mode ------------------------------------------------------------------------------------------------------------------
+// the tangent kernel's dynamic LDS, restated from sp_metric_lds (sv_sparse.hpp, a HIP header): psi [mpad] at 0, the tangent [mpad], cos / sin
+// [ntab] as 16-byte pairs, the derivative coefficient [ntab] padded to an even count; staged: 16-byte op records [nops], pair words [npairs]
+struct Lds { size_t t, cs, dk, ops, pairs, bytes; };
+static Lds lds_layout(const metric::Compact &C, bool stage) {
+    const size_t mpad = (size_t)((C.m + 1) & ~1), ntab = C.tab.size();
+    Lds L;
+    L.t = mpad * 8;
+    L.cs = 2 * L.t;
+    L.dk = L.cs + ntab * 16;
+    L.ops = L.dk + ((ntab + 1) & ~(size_t)1) * 8;
+    L.pairs = L.ops + C.ops.size() * sizeof(metric::Op);
+    L.bytes = stage ? L.pairs + C.pairs.size() * 4 : L.ops;
+    return L;
+}
+constexpr size_t LDS_BUDGET = 150 * 1024, LDS_MAX = 160 * 1024;   // LDS_WG_BUDGET / LDS_WG_MAX of ovqe_sv.hip
+
+// cube program: a single Y on bit r for r < n (the support doubles up to the whole register), then odd-Y strings of weight 2..5; every
+// rotation with an offset, so that none is fused; pidx from -1..K-1
+static std::vector<Rot> cube_program(std::mt19937_64 &rng, int n, int R, int K) {
+    std::uniform_real_distribution<double> U(0.2, 1.0);
+    std::vector<Rot> prog;
+    const double scale = std::min(0.6, 1.2 / std::sqrt((double)R / (K + 1)));
+    for (int r = 0; r < R; ++r) {
+        Rot q{0, 0, 0, 0, 0};
+        if (r < n) {
+            q.x = q.z = 1ull << (n - 1 - r);
+        } else {
+            for (;;) {
+                q.x = q.z = 0;
+                const int w = 2 + (int)(rng() % 4);
+                while (__builtin_popcountll(q.x | q.z) < w) {
+                    const uint64_t bit = 1ull << (rng() % (uint64_t)n);
+                    if ((q.x | q.z) & bit) continue;
+                    const int letter = (int)(rng() % 3);   // X, Y, Z
+                    if (letter != 2) q.x |= bit;
+                    if (letter != 0) q.z |= bit;
+                }
+                if (__builtin_popcountll(q.x & q.z) & 1) break;
+            }
+        }
+        q.pidx = r <= K ? r - 1 : (int)(rng() % (uint64_t)(K + 1)) - 1;
+        q.coeff = ((rng() & 1) ? scale : -scale) * (0.1 + U(rng));
+        q.phi0 = ((rng() & 1) ? 1.0 : -1.0) * U(rng);
+        prog.push_back(q);
+    }
+    return prog;
+}
+
+static void boundary() {
+    std::mt19937_64 rng(12);
+    std::uniform_real_distribution<double> U(-0.8, 0.8);
+    std::vector<double> theta(6);
+    for (double &t : theta) t = U(rng);
+    for (int R : {20, 21, 3669, 3670}) {
+        const int n = 12, K = R < 100 ? 6 : 2;   // (the long programs with two parameters: the replay and the dense simulation cost R K 2^n)
+        const std::vector<Rot> prog = cube_program(rng, n, R, K);
+        metric::Compact C;
+        const bool ok = check_program(rng, n, rng() & ((1ull << n) - 1), prog, theta, K, true, &C);   // (fusion on: the offsets refuse it)
+        CHECK(ok, "build_compact declined the cube program n = %d R = %d", n, R);
+        if (!ok) continue;
+        uint32_t max_ci = 0, max_cj = 0;
+        for (const uint32_t pw : C.pairs) {
+            max_ci = std::max(max_ci, pw & 0xfffu);
+            max_cj = std::max(max_cj, (pw >> 12) & 0xfffu);
+            CHECK((pw >> 25) == 0, "a plain op with a pattern");
+        }
+        CHECK(C.m == metric::MAX_SUPPORT && max_cj == 4095u, "m = %d, max cj = %u", C.m, max_cj);
+        CHECK((int)C.tab.size() == R && (int)C.ops.size() == R, "one op and one table entry per rotation: %zu, %zu", C.ops.size(), C.tab.size());
+        // the LDS regions the kernel indexes: psi / t by ci, cj < mpad, cs / dk by e < ntab, the op records and pair words when staged
+        const Lds Ls = lds_layout(C, true), Lu = lds_layout(C, false);
+        const int form = Ls.bytes <= LDS_BUDGET ? 1 : Lu.bytes <= LDS_BUDGET ? 2 : 0;
+        const Lds &L = form == 1 ? Ls : Lu;
+        const size_t mpad = (size_t)((C.m + 1) & ~1);
+        CHECK(((size_t)std::max(max_ci, max_cj) + 1) * 8 <= L.t && L.t + mpad * 8 <= L.cs, "psi / tangent region");
+        CHECK(L.cs % 16 == 0 && L.cs + C.tab.size() * 16 <= L.dk && L.dk + C.tab.size() * 8 <= L.ops && L.ops % 16 == 0, "table regions");
+        if (form == 1) CHECK(L.ops + C.ops.size() * 16 <= L.pairs && L.pairs + C.pairs.size() * 4 == L.bytes, "staged regions");
+        if (form) CHECK(L.bytes <= LDS_BUDGET && L.bytes <= LDS_MAX, "the launch exceeds the budget");
+        for (size_t o = 0; o < C.ops.size(); ++o)
+            CHECK(C.ops[o].first >= 0 && (size_t)C.ops[o].first + (size_t)C.ops[o].npairs <= C.pairs.size() && C.ops[o].tab0 == (int)o, "op %zu", o);
+        std::printf("cube n=%d R=%d ok=1 m=%d ntab=%zu nops=%zu npairs=%zu max_ci=%u max_cj=%u staged=%zu unstaged=%zu form=%d\n", n, R, C.m,
+                    C.tab.size(), C.ops.size(), C.pairs.size(), max_ci, max_cj, Ls.bytes, Lu.bytes, form);
+    }
+    // one qubit more: the 13th Y rotation reaches state 4097 and build_compact declines, with or without rotations behind it
+    const int K = 6;
+    for (int R : {13, 21}) {
+        const std::vector<Rot> prog = cube_program(rng, 13, R, K);
+        metric::Compact C;
+        const bool ok = check_program(rng, 13, 5, prog, theta, K, true, &C);
+        CHECK(!ok, "a support of 8192 states accepted (R = %d)", R);
+        std::printf("cube n=13 R=%d ok=%d\n", R, (int)ok);
+    }
+    // ... and the 12 Y rotations alone are accepted, at the cap
+    {
+        const std::vector<Rot> prog = cube_program(rng, 12, 12, K);
+        metric::Compact C;
+        CHECK(check_program(rng, 12, 77, prog, theta, K, true, &C) && C.m == metric::MAX_SUPPORT, "the cap itself declined");
     }
 }
 
 int main(int argc, char **argv) {
+    if (argc > 1 && !std::strcmp(argv[1], "boundary")) {
+        boundary();
+        if (fails) {
+            std::printf("metric plan: %d failures\n", fails);
+            return 1;
+        }
+        std::printf("metric plan boundary ok\n");
+        return 0;
+    }
     std::mt19937_64 rng(argc > 1 ? std::strtoull(argv[1], nullptr, 10) : 1);
     const int Ks[] = {1, 2, 5, 63, 64, 65, 129};
     int programs = 0;

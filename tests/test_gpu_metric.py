@@ -51,27 +51,7 @@ def lih():
     return Mol("LiH")
 
 
-def _call(sv, theta, path):
-    """the metric twice, with the checks every result gets -> (g, info)"""
-    g = sv.metric_tensor(theta)
-    info = sv.metric_info()
-    again = sv.metric_tensor(theta)
-    K = len(theta)
-    assert g.shape == (K, K) and g.dtype == np.float64
-    assert np.array_equal(g, g.T)
-    assert np.array_equal(g.view(np.int64), again.view(np.int64))
-    assert info["path"] == path and info["K"] == K, info
-    if K:
-        low = np.linalg.eigvalsh(g)[0]
-        print(f"path {path} K {K} smallest eigenvalue {low:.3e} info {info}")
-        assert low >= -metric_cases.bound(g)
-    return g, info
-
-
-def _compare(g, want, what):
-    err = np.abs(g - want).max() if g.size else 0.0
-    print(f"{what}: max|delta g| = {err:.3e}, bound {metric_cases.bound(want):.3e}, max g_kk = {np.max(np.diag(want)) if g.size else 0:.4f}")
-    assert err <= metric_cases.bound(want)
+_call, _compare = metric_cases.call_metric, metric_cases.compare
 
 
 # ---- compact support ----------------------------------------------------------------------------------------------------------------
@@ -199,6 +179,8 @@ def test_refusals(SV):
     with SV(n) as sv:
         info = (ctypes.c_int64 * 9)(*([7] * 9))
         assert sv._L.ovqe_metric_info(sv._h, info, 9) == 0 and not any(info)            # zeros before the first call
+        info = (ctypes.c_int64 * 11)(*([7] * 11))
+        assert sv._L.ovqe_metric_info(sv._h, info, 11) == 0 and not any(info)           # ... the tangent form and its LDS bytes included
         _refused(sv, STATE, "no program set", theta, K, out)
         sv.set_rotation_program(rx, rz, rc, pidx, K, hf, phi0=phi0)
         _refused(sv, INVALID, "K = 4", theta, K - 1, out)
