@@ -108,6 +108,9 @@ int ovqe_measure_groups(ovqe_handle h, int64_t capacity, int32_t *group_of_term,
 int ovqe_energy_sampled(ovqe_handle h, const double *theta, int32_t K, int64_t n_shots, uint64_t seed, double *energy,
                         double *std_error);
 int ovqe_measure_info(ovqe_handle h, int64_t *info, int count);
+int ovqe_subspace_matrices(ovqe_handle h, int64_t n_ops, const int64_t *offsets, const uint64_t *x, const uint64_t *z,
+                           const double *coeff_re, const double *coeff_im, double *h_out_re_im, double *s_out_re_im);
+int ovqe_subspace_info(ovqe_handle h, int64_t *info, int count);
 int ovqe_time_pauli_rotation(ovqe_handle h, uint64_t x, uint64_t z, double phi, int warmup, int reps,
                              double *avg_ms);
 int ovqe_last_batch_ms(ovqe_handle h, double *ms);

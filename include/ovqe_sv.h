@@ -128,6 +128,8 @@ int ovqe_set_stream(ovqe_handle h, void *hip_stream);
  *                     tile of 16 or 32 rows); the buffer is allocated at the first call that needs it and kept on the handle
  *   "metric_workspace_mb" (0)  cap of the tangent store of ovqe_metric_tensor in MB; 0: 60 % of the free device memory.  A store beyond
  *                     the cap is refused with OVQE_ERR_ALLOC; the buffer is allocated at the first call and kept on the handle
+ *   "subspace_workspace_mb" (0)  cap of the store of ovqe_subspace_matrices (expansion vectors and their H images) in MB; 0: 60 % of the
+ *                     free device memory.  A store beyond the cap is refused with OVQE_ERR_ALLOC; allocated at the first call, kept on the handle
  *
  *   "real_state" (0)  the state buffer holds 2^n_local DOUBLES (8 bytes per amplitude: a shard of the partitioned register while its
  *                     amplitudes are real).  BUFFER-SIZE CONTRACT: while it is set, the state and every shard-sized operand of
@@ -526,6 +528,37 @@ int ovqe_energy_sampled(ovqe_handle h, const double *theta, int32_t K, int64_t n
  * group [2] scratch bytes held [3] kernel launches [4..6] HIP-event times in microseconds summed over the groups: basis change,
  * scan, draw + score [7] terms scored [8] streaming passes for rotated bits above the tile; zeros before the first call */
 int ovqe_measure_info(ovqe_handle h, int64_t *info, int count);
+
+/* ---- excited states by subspace expansion (quantum subspace expansion; with an excitation pool the qEOM family): around the resident
+ * state psi, with m = n_ops expansion operators O_j given as Pauli sums in the CSR form of ovqe_pool_gradients (operator k = terms
+ * [offsets[k], offsets[k+1]), complex coefficients, strings as in ovqe_apply_pauli_sum: x & z = Y with its i^ny phase, x = z = 0 the
+ * identity; an operator without terms is allowed and gives a zero row and column),
+ *   phi_j = O_j psi,    s_out[i*m + j] = <phi_i|phi_j>,    h_out[i*m + j] = <phi_i|H|phi_j>        m x m complex (re,im), row-major
+ * with H the stored Hamiltonian INCLUDING its constant (constant * S_ij), as ovqe_ground_state reports energies.  The generalised
+ * eigenproblem H y = E S y is the caller's (openvqe_amd/excited.py); the reference's only excited-state code is a weighted
+ * subspace-search demo on an Ising chain (ref:openvqe/common_files/get_energy_WSSVQE.py) and has no call site for this.
+ * s_out is Hermitian to the bit with a real diagonal (upper triangle mirrored).  h_out holds all m^2 entries of Phi^H (H Phi) AS
+ * COMPUTED — Hermitian up to rounding, the caller symmetrises.  h_out may be NULL: only S is formed, the sigma stage and its half of
+ * the store are skipped and no Hamiltonian is needed.
+ * STAGES (ovqe_subspace_info).  Rows R = { i : psi[i ^ x] != 0 for some distinct x mask of the pool }, a superset of every supp(phi_j),
+ * from the bitmap of psi's support; the expansion vectors into an index-major store of |R| rows (16-byte amplitudes; columns [0, m) phi_j,
+ * padded to mb = m rounded up to 64, then columns [mb, mb + m) sigma_j); sigma_j = H phi_j ON R — per row the coefficient of every
+ * x-group of H once, applied to the m contiguous columns of the partner row; a partner outside R holds exact zeros and rows outside R
+ * are never needed, since H_ij only sums over rows where phi_i is non-zero; then 64 x 64 Gram blocks of (Phi, Phi) and (Phi, Sigma) —
+ * never (Sigma, Sigma).  When R is the whole register the row lookup is skipped (dense form).
+ * COST.  The store is |R| * wpad * 16 bytes, wpad = 2 mb (mb when h_out is NULL), behind option "subspace_workspace_mb"; sigma costs
+ * (matrix elements of H inside R) x m complex FMAs; the Gram stage |R| * 3/2 mb^2.
+ * psi is only read: the state buffer holds the same bits afterwards.  Cached tables of the handle stay valid: an ovqe_energy before
+ * the call and one after it return the same bits.  All reductions run in a fixed order without atomics: two calls return identical
+ * bits.  Synchronous.  OVQE_ERR_STATE: h_out given but no Hamiltonian set, a shard of a partitioned register, option "real_state";
+ * OVQE_ERR_INVALID: n_ops < 1, NULL offsets / s_out, decreasing offsets, a mask with a bit at or above n_qubits; OVQE_ERR_ALLOC, with
+ * the bytes needed in the text, when the store exceeds its cap (no column chunking) — the handle stays usable. */
+int ovqe_subspace_matrices(ovqe_handle h, int64_t n_ops, const int64_t *offsets, const uint64_t *x, const uint64_t *z,
+                           const double *coeff_re, const double *coeff_im, double *h_out_re_im, double *s_out_re_im);
+/* of the last ovqe_subspace_matrices call, up to `count` entries of: [0] m [1] rows |R| [2] 1 = dense form (no lookup) [3] store bytes
+ * [4] distinct x masks of the pool [5] Hamiltonian x-groups (0 when h_out was NULL) [6] expand launches [7] sigma launches [8] Gram
+ * launches [9] block pairs computed [10..13] HIP-event times in microseconds: rows, expand, sigma, Gram + finish; zeros before the first call */
+int ovqe_subspace_info(ovqe_handle h, int64_t *info, int count);
 
 /* ---- measurement support (bench.py): average device time in ms of `reps` back-to-back launches of
  * one Pauli-rotation sweep, bracketed by HIP events on the handle's stream */

@@ -115,6 +115,8 @@ SIGNATURES = {
     "ovqe_measure_groups": (_int, [_H, _i64, _i32p, _u64p, _u64p, ctypes.POINTER(_i64)]),
     "ovqe_energy_sampled": (_int, [_H, _OptF64, ctypes.c_int32, _i64, _u64, ctypes.POINTER(_dbl), ctypes.POINTER(_dbl)]),
     "ovqe_measure_info": (_int, [_H, ctypes.POINTER(ctypes.c_int64), _int]),
+    "ovqe_subspace_matrices": (_int, [_H, _i64, _i64p, _u64p, _u64p, _f64p, _OptF64, _OptF64, _OptF64]),
+    "ovqe_subspace_info": (_int, [_H, ctypes.POINTER(ctypes.c_int64), _int]),
     "ovqe_program_info": (_int, [_H, ctypes.POINTER(ctypes.c_int64), _int]),
     "ovqe_get_rotation_program": (_int, [_H, _i64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.POINTER(ctypes.c_int64)]),

@@ -56,6 +56,7 @@ class Statevector:
         self.n_local = int(n_qubits)
         self.n_global = int(n_global)
         self.shard_index = int(shard_index)
+        self.device = int(device)
         if view_of is not None:
             if n_global:
                 raise ValueError("a view is a single-device handle")
@@ -589,6 +590,60 @@ class Statevector:
         self._ck(self._L.ovqe_metric_info(self._h, out, 11))
         keys = ("path", "K", "tangent_amplitudes", "store_bytes", "tangent_launches", "gram_launches", "tangents_us", "gram_us", "finish_us",
                 "tangent_form", "tangent_lds_bytes")
+        return dict(zip(keys, [int(v) for v in out]))
+
+    # -- excited states by subspace expansion (ovqe_subspace_matrices, csrc/subspace_host.inc) ----------------------------------
+    def _pack_pool_with_constants(self, ops):
+        """CSR form of a list of operators, an operator's ``constant_coeff`` as a term on the identity string (x = z = 0); cached
+        like the pool of ``pool_gradients`` (the pool is the same object from call to call)"""
+        cache = getattr(self, "_subspace_cache", None)
+        if cache is not None and cache[0] is ops and cache[1] == len(ops):
+            return cache[2]
+        offsets = np.zeros(len(ops) + 1, np.int64)
+        xs, zs, cs = [], [], []
+        for k, op in enumerate(ops):
+            px, pz, pc = pack_terms(self.nbqbits, op.terms)
+            const = complex(getattr(op, "constant_coeff", 0.0) or 0.0)
+            if const != 0:
+                px, pz, pc = np.append(px, np.uint64(0)), np.append(pz, np.uint64(0)), np.append(pc, const)
+            xs.append(px)
+            zs.append(pz)
+            cs.append(pc)
+            offsets[k + 1] = offsets[k] + px.shape[0]
+        xs = np.concatenate(xs) if xs else np.zeros(0, np.uint64)
+        zs = np.concatenate(zs) if zs else np.zeros(0, np.uint64)
+        cs = np.concatenate(cs) if cs else np.zeros(0, np.complex128)
+        if xs.shape[0] == 0:
+            xs, zs, cs = np.zeros(1, np.uint64), np.zeros(1, np.uint64), np.zeros(1, np.complex128)
+        packed = (offsets, np.ascontiguousarray(xs, np.uint64), np.ascontiguousarray(zs, np.uint64), np.ascontiguousarray(cs.real),
+                  np.ascontiguousarray(cs.imag))
+        self._subspace_cache = (ops, len(ops), packed)
+        return packed
+
+    def subspace_matrices(self, ops, hamiltonian=True, raw=False):
+        """(H, S) of the subspace spanned by phi_j = O_j psi around the resident state, (m, m) complex128 each: S[i, j] = <phi_i|phi_j>
+        (Hermitian to the bit), H[i, j] = <phi_i|H|phi_j> with the stored Hamiltonian and its constant, symmetrised as (G + G^H) / 2
+        unless ``raw`` (then G = Phi^H (H Phi) as the device computed it).  ``hamiltonian=False``: only S, no Hamiltonian needed.
+        ``ops``: operators with ``.terms`` (complex coefficients allowed) and optionally ``.constant_coeff``; solver: ``excited``"""
+        m = len(ops)
+        offsets, xs, zs, cre, cim = self._pack_pool_with_constants(ops)
+        S = np.zeros((m, m), np.complex128)
+        G = np.zeros((m, m), np.complex128) if hamiltonian else None
+        self._ck(self._L.ovqe_subspace_matrices(self._h, m, offsets, xs, zs, cre, cim,
+                                                G.view(np.float64).reshape(-1) if hamiltonian and m else None,
+                                                S.view(np.float64).reshape(-1) if m else None))
+        if not hamiltonian:
+            return S
+        return (G if raw else 0.5 * (G + G.conj().T)), S
+
+    def subspace_info(self):
+        """figures of the last ``subspace_matrices`` call: operators, rows of the store, dense form (no row lookup), store bytes,
+        distinct x masks of the pool, x-groups of the Hamiltonian, launches of the expand / sigma / Gram stages, 64 x 64 block pairs
+        computed, HIP-event times of the stages in microseconds"""
+        out = (ctypes.c_int64 * 14)()
+        self._ck(self._L.ovqe_subspace_info(self._h, out, 14))
+        keys = ("m", "rows", "dense", "store_bytes", "distinct_x", "h_groups", "expand_launches", "sigma_launches", "gram_launches",
+                "block_pairs", "rows_us", "expand_us", "sigma_us", "gram_us")
         return dict(zip(keys, [int(v) for v in out]))
 
     # -- finite-shot measurement (ovqe_sample ..., csrc/measure_host.inc) --------------------------------------------------------

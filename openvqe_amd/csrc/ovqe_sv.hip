@@ -10,7 +10,8 @@
 //   sparse_host.inc  support-compacted path                                                          (kernels: sv_sparse.hpp)
 //   rdm_host.inc     density matrices of the resident state: census, shadows, row list, rows, Gram    (sv_rdm_host.hpp; kernels: sv_rdm.hpp)
 //   metric_host.inc  Fubini-Study metric of the ansatz state: tangent store, compact / streaming tangents, Gram    (sv_metric_host.hpp; kernels: sv_sparse.hpp, sv_metric.hpp)
-//   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc / abi_rdm.inc / abi_metric.inc   extern "C" entry points by family (include/ovqe_sv.h)
+//   subspace_host.inc  subspace-expansion matrices around the resident state: rows, expansion vectors, sigma = H Phi, Gram    (sv_subspace_host.hpp; kernels: sv_subspace.hpp, sv_rdm.hpp)
+//   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc / abi_rdm.inc / abi_metric.inc / abi_subspace.inc   extern "C" entry points by family (include/ovqe_sv.h)
 //   cross_host.inc   planned Pauli sums on a shard of the partitioned register, ovqe_xsum_*          (sv_cross_host.hpp; kernels: sv_cross.hpp)
 //   pool_host.inc    planned ADAPT pool screen on a shard, ovqe_xpool_*                              (sv_pool_host.hpp; kernels: sv_pool.hpp)
 // sv_cover_host.hpp (host-only) holds the table records planners and kernels share and the one cover rule, grow_tile_set(), that
@@ -48,6 +49,7 @@
 #include "sv_rdm.hpp"
 #include "sv_metric.hpp"
 #include "sv_measure.hpp"
+#include "sv_subspace.hpp"
 #include <hipcub/hipcub.hpp>
 #include <unordered_map>
 #include <unordered_set>
@@ -273,6 +275,7 @@ struct SectorEngine {
 
 struct RdmDev;   // rdm_host.inc
 struct MetricDev;   // metric_host.inc
+struct SubspaceDev; // subspace_host.inc
 struct MeasureDev;   // measure_host.inc
 
 }  // namespace
@@ -497,6 +500,8 @@ struct ovqe_sv {
     MetricDev *metric = nullptr;     // buffers and figures of ovqe_metric_tensor (first call)
     int opt_metric_workspace_mb = 0; // cap of its tangent store in MB (0: 60 % of the free device memory)
     MeasureDev *measure = nullptr;   // scratch, plan and figures of the finite-shot measurements (first call)
+    SubspaceDev *subspace = nullptr; // buffers and figures of ovqe_subspace_matrices (first call)
+    int opt_subspace_workspace_mb = 0; // cap of its store in MB (0: 60 % of the free device memory)
 };
 
 namespace {
@@ -1141,6 +1146,8 @@ void push_rotation(ovqe_handle h, uint64_t x, uint64_t z, double coeff, double p
 
 #include "measure_host.inc"
 
+#include "subspace_host.inc"
+
 int check_theta(ovqe_handle h, const double *theta, int32_t K) {
     if (!h->prog_set) return fail(h, OVQE_ERR_STATE, "no program set (ovqe_set_program / ovqe_set_gate_program)");
     if (K != h->K) return fail(h, OVQE_ERR_INVALID, "K does not match the program's parameter count");
@@ -1251,6 +1258,7 @@ int ovqe_destroy(ovqe_handle h) try {
     free_rdm(h->rdm);
     free_metric(h->metric);
     free_measure(h->measure);
+    free_subspace(h->subspace);
     h->kept_blocks.flush();
     if (h->h_rp) (void)hipHostFree(h->h_rp);
     if (h->h_result) (void)hipHostFree(h->h_result);
@@ -1371,6 +1379,7 @@ int ovqe_set_option(ovqe_handle h, const char *name, int64_t value) try {
     else if (k == "lanczos_keep_gb") h->opt_lanczos_keep_gb = (int)value;
     else if (k == "rdm_workspace_mb") h->opt_rdm_workspace_mb = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
     else if (k == "metric_workspace_mb") h->opt_metric_workspace_mb = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
+    else if (k == "subspace_workspace_mb") h->opt_subspace_workspace_mb = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
     else if (k == "screen_sparse") h->opt_screen_sparse = (int)std::max<int64_t>(0, value);
 #ifdef OVQE_TESTING
     else if (k == "tile_flat") h->opt_tile_flat = (int)value;
@@ -1555,6 +1564,8 @@ int ovqe_norm2(ovqe_handle h, double *out) try {
 #include "abi_metric.inc"
 
 #include "abi_measure.inc"
+
+#include "abi_subspace.inc"
 
 // ---- measurement support ------------------------------------------------------------------------
 int ovqe_time_pauli_rotation(ovqe_handle h, uint64_t x, uint64_t z, double phi, int warmup, int reps, double *avg_ms) try {

@@ -1,0 +1,89 @@
+"""Excited states by quantum subspace expansion (QSE; with an excitation pool the qEOM family) around the state in the buffer.
+
+With expansion operators O_1 .. O_m and phi_j = O_j psi, the device forms S_ij = <phi_i|phi_j> and H_ij = <phi_i|H|phi_j>
+(``Statevector.subspace_matrices``, ovqe_subspace_matrices); the generalised eigenproblem H y = E S y is solved here, on the host, by
+canonical orthogonalisation.  The reference has no call site for this: its only excited-state code is a weighted subspace-search
+demo on an Ising chain (ref:openvqe/common_files/get_energy_WSSVQE.py).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import fermion
+from .operators import Hamiltonian
+
+
+def excitation_operators(n_spatial, n_occ_spatial, deexcitations=False, identity=True):
+    """The JW images of the BARE spin-conserving excitations a+_a a_i and a+_b a+_a a_i a_j of ``fermion.uccsd_excitations`` (not the
+    anti-Hermitian generators): [identity,] singles, doubles [, their adjoints in the same order].  Complex coefficients."""
+    nq = 2 * n_spatial
+    singles, doubles = fermion.uccsd_excitations(n_spatial, n_occ_spatial)
+    ladders = [([a], [i]) for i, a in singles] + [([b, a], [i, j]) for i, j, a, b in doubles]
+    ops = [Hamiltonian(nq, [], 1.0)] if identity else []
+    for creators, annihilators in ladders:
+        t = fermion.jw_product([(p, True) for p in creators] + [(p, False) for p in annihilators])
+        ops.append(fermion.psum_to_hamiltonian(nq, t, tol=1e-13))
+    if deexcitations:
+        for creators, annihilators in ladders:
+            t = fermion.jw_product([(p, True) for p in reversed(annihilators)] + [(p, False) for p in reversed(creators)])
+            ops.append(fermion.psum_to_hamiltonian(nq, t, tol=1e-13))
+    return ops
+
+
+def solve(H, S, rcond=1e-10):
+    """H y = E S y by canonical orthogonalisation: eigenvectors of S with eigenvalue <= rcond * lambda_max are dropped, H is projected
+    on the rest.  -> (energies ascending [rank], coefficients y [m, rank] with y^H S y = 1, rank)"""
+    H = np.asarray(H, np.complex128)
+    S = np.asarray(S, np.complex128)
+    if H.shape != S.shape or H.ndim != 2 or H.shape[0] != H.shape[1]:
+        raise ValueError("H and S must be square matrices of one size")
+    w, U = np.linalg.eigh(0.5 * (S + S.conj().T))
+    if w.size == 0 or w[-1] <= 0.0:
+        raise ValueError("the overlap matrix has no positive eigenvalue: every expansion vector is zero")
+    keep = w > rcond * w[-1]
+    X = U[:, keep] / np.sqrt(w[keep])
+    Hp = X.conj().T @ (0.5 * (H + H.conj().T)) @ X
+    e, v = np.linalg.eigh(0.5 * (Hp + Hp.conj().T))
+    return e, X @ v, int(keep.sum())
+
+
+def qse(sv, ops, rcond=1e-10):
+    """``sv.subspace_matrices(ops)`` followed by ``solve`` -> (energies, coefficients, rank)"""
+    H, S = sv.subspace_matrices(ops)
+    return solve(H, S, rcond)
+
+
+def merged_pauli_sum(nbqbits, ops, y):
+    """sum_j y_j O_j as one Pauli sum in index-space masks -> (xs, zs, coeffs); equal strings merged, constants on x = z = 0"""
+    from .operators import pack_terms
+    total = {}
+    for yj, op in zip(np.asarray(y, np.complex128).reshape(-1), ops):
+        xs, zs, cs = pack_terms(nbqbits, op.terms)
+        for x, z, c in zip(xs.tolist(), zs.tolist(), cs.tolist()):
+            total[(x, z)] = total.get((x, z), 0.0) + yj * c
+        const = complex(getattr(op, "constant_coeff", 0.0) or 0.0)
+        if const != 0:
+            total[(0, 0)] = total.get((0, 0), 0.0) + yj * const
+    keys = list(total)
+    return (np.array([k[0] for k in keys], np.uint64), np.array([k[1] for k in keys], np.uint64),
+            np.array([total[k] for k in keys], np.complex128))
+
+
+def load_ritz_state(sv, ops, y):
+    """puts the normalised sum_j y_j O_j psi into the state buffer of ``sv`` (psi: the state in the buffer): one merged Pauli sum
+    through ``apply_pauli_sum``.  ``rdm1`` / ``rdm2`` / ``rdm.spin_expectations`` then describe the excited state.  -> the norm^2
+    before normalisation (y^H S y: 1 for a column of ``solve``)"""
+    y = np.asarray(y, np.complex128).reshape(-1)
+    if y.shape[0] != len(ops):
+        raise ValueError(f"expected {len(ops)} coefficients")
+    xs, zs, cs = merged_pauli_sum(sv.nbqbits, ops, y)
+    with type(sv)(sv.n_local, device=sv.device) as scratch:     # a second register of the same size: the sum cannot be applied in place
+        buf = scratch.state_ptr()
+        sv.apply_pauli_sum(xs, zs, cs, buf)
+        state = sv.state_ptr()
+        sv.vec_axpy(state, buf, 1.0, overwrite=True)
+        norm2 = sv.norm2()          # (waits for the copy: the scratch register may go)
+    if not norm2 > 0.0:
+        raise ValueError("the Ritz vector is zero")
+    sv.vec_scale(state, 1.0 / np.sqrt(norm2))
+    return norm2

@@ -249,6 +249,10 @@ class PartitionedStatevector:
         raise NotImplementedError("the Fubini-Study metric is computed on one device (ovqe_metric_tensor keeps K tangent vectors next to "
                                   "the state): not available on the partitioned register")
 
+    def subspace_matrices(self, *args, **kwargs):
+        raise NotImplementedError("subspace-expansion matrices are computed on one device (ovqe_subspace_matrices keeps the expansion "
+                                  "vectors next to the state): not available on the partitioned register")
+
     def sample(self, *args, **kwargs):
         raise NotImplementedError("finite-shot measurement draws from the prefix sums of one device's register (ovqe_sample, "
                                   "ovqe_energy_sampled): shots (nbshots > 0) are not available on the partitioned register")
