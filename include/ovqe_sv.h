@@ -557,7 +557,12 @@ int ovqe_subspace_matrices(ovqe_handle h, int64_t n_ops, const int64_t *offsets,
                            const double *coeff_re, const double *coeff_im, double *h_out_re_im, double *s_out_re_im);
 /* of the last ovqe_subspace_matrices call, up to `count` entries of: [0] m [1] rows |R| [2] 1 = dense form (no lookup) [3] store bytes
  * [4] distinct x masks of the pool [5] Hamiltonian x-groups (0 when h_out was NULL) [6] expand launches [7] sigma launches [8] Gram
- * launches [9] block pairs computed [10..13] HIP-event times in microseconds: rows, expand, sigma, Gram + finish; zeros before the first call */
+ * launches [9] block pairs computed [10..13] HIP-event times in microseconds: rows, expand, sigma, Gram + finish; then which path the
+ * call took: [14] row slices of the Gram launch [15] rows per slice (a multiple of the 16-row staging tile: above 16 a workgroup stages
+ * several tiles) [16] column blocks of 64 a lane of the sigma kernel accumulates — the instantiation that ran: 1, 2 or 4 — and [17] its
+ * column groups (grid y), both 0 when no sigma kernel ran (h_out NULL or no rows) [18] workgroups in x of the sigma launch (4 rows
+ * each; fewer than rows / 4: the rows are strided) [19] workgroups of the expand launch (256 store elements each; fewer than
+ * rows * mb / 256: strided), 0 without rows.  Callers that ask for 14 entries see no change; zeros before the first call */
 int ovqe_subspace_info(ovqe_handle h, int64_t *info, int count);
 
 /* ---- measurement support (bench.py): average device time in ms of `reps` back-to-back launches of

@@ -639,11 +639,14 @@ class Statevector:
     def subspace_info(self):
         """figures of the last ``subspace_matrices`` call: operators, rows of the store, dense form (no row lookup), store bytes,
         distinct x masks of the pool, x-groups of the Hamiltonian, launches of the expand / sigma / Gram stages, 64 x 64 block pairs
-        computed, HIP-event times of the stages in microseconds"""
-        out = (ctypes.c_int64 * 14)()
-        self._ck(self._L.ovqe_subspace_info(self._h, out, 14))
+        computed, HIP-event times of the stages in microseconds, and the path the call took: row slices of the Gram launch and rows
+        per slice, column blocks per lane of the sigma kernel that ran (1, 2 or 4; 0: none ran) and its column groups, workgroups in x
+        of the sigma launch and workgroups of the expand launch"""
+        out = (ctypes.c_int64 * 20)()
+        self._ck(self._L.ovqe_subspace_info(self._h, out, 20))
         keys = ("m", "rows", "dense", "store_bytes", "distinct_x", "h_groups", "expand_launches", "sigma_launches", "gram_launches",
-                "block_pairs", "rows_us", "expand_us", "sigma_us", "gram_us")
+                "block_pairs", "rows_us", "expand_us", "sigma_us", "gram_us", "slices", "slice_rows", "sigma_blocks", "sigma_col_groups",
+                "sigma_grid", "expand_grid")
         return dict(zip(keys, [int(v) for v in out]))
 
     # -- finite-shot measurement (ovqe_sample ..., csrc/measure_host.inc) --------------------------------------------------------

@@ -25,6 +25,6 @@ int ovqe_subspace_matrices(ovqe_handle h, int64_t n_ops, const int64_t *offsets,
 int ovqe_subspace_info(ovqe_handle h, int64_t *info, int count) try {
     OVQE_ENTER(h);
     if (!h || !info || count < 0) return OVQE_ERR_INVALID;
-    for (int i = 0; i < count && i < 14; ++i) info[i] = h->subspace ? h->subspace->info[i] : 0;
+    for (int i = 0; i < count && i < 20; ++i) info[i] = h->subspace ? h->subspace->info[i] : 0;
     return OVQE_OK;
 } OVQE_CATCH(h)

@@ -11,7 +11,7 @@ struct SubspaceDev {
     DevBuf d_bitmap[2], d_census, d_counts, d_start, d_scan_temp, d_rows, d_dx, d_off, d_xs, d_terms, d_store, d_slabs, d_out;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     std::vector<double2> host_out;
-    int64_t info[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t info[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 void free_subspace(SubspaceDev *Q) {
@@ -25,7 +25,7 @@ void free_subspace(SubspaceDev *Q) {
 }
 
 template <bool DENSE>
-int launch_sub_sigma(ovqe_handle h, SubspaceDev &Q, const sub::Plan &P, int64_t *launches) {
+int launch_sub_sigma(ovqe_handle h, SubspaceDev &Q, const sub::Plan &P, int64_t *launches, int64_t *grid_x) {
     const unsigned gx = (unsigned)std::min<int64_t>(P.sigma_row_tiles, (int64_t)h->num_cus * 32);
     const dim3 grid(gx, (unsigned)P.sigma_col_groups), block(sub::SIGMA_THREADS);
     const HGroup *groups = (const HGroup *)h->ham.d_groups.p;
@@ -41,6 +41,7 @@ int launch_sub_sigma(ovqe_handle h, SubspaceDev &Q, const sub::Plan &P, int64_t 
         hipLaunchKernelGGL((k_sub_sigma<DENSE, sub::SIGMA_MAX_BLOCKS>), grid, block, 0, h->stream, store, rows, P.rows, bitmap, start, groups, ng, terms, h->ham.constant, P.nb, P.mb, P.wpad);
     HIPC(h, hipGetLastError());
     ++*launches;
+    *grid_x = gx;
     return OVQE_OK;
 }
 
@@ -50,7 +51,7 @@ int run_subspace(ovqe_handle h, int64_t m, const int64_t *offsets, const uint64_
     const int n = h->n_local;
     if (!h->subspace) h->subspace = new SubspaceDev();
     SubspaceDev &Q = *h->subspace;
-    std::fill(Q.info, Q.info + 14, 0);
+    std::fill(Q.info, Q.info + 20, 0);
     if (h->num_cus <= 0) {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus <= 0) cus = 256;
@@ -136,7 +137,7 @@ int run_subspace(ovqe_handle h, int64_t m, const int64_t *offsets, const uint64_
         HIPC(h, hipGetLastError());
     }
     HIPC(h, hipEventRecord(Q.ev[1], h->stream));
-    int64_t expand_launches = 0, sigma_launches = 0, gram_launches = 0;
+    int64_t expand_launches = 0, sigma_launches = 0, gram_launches = 0, expand_grid = 0, sigma_grid = 0;
     // ---- expand: Phi
     if (nrows > 0) {
         const unsigned eb = (unsigned)std::min<uint64_t>(((uint64_t)nrows * (uint64_t)P.mb + 255) / 256, (uint64_t)h->num_cus * 16u);
@@ -148,11 +149,12 @@ int run_subspace(ovqe_handle h, int64_t m, const int64_t *offsets, const uint64_
                                (const int64_t *)Q.d_off.p, (const uint64_t *)Q.d_xs.p, (const HTerm *)Q.d_terms.p, m, P.mb, P.wpad, (v2d *)Q.d_store.p);
         HIPC(h, hipGetLastError());
         ++expand_launches;
+        expand_grid = eb;
     }
     HIPC(h, hipEventRecord(Q.ev[2], h->stream));
     // ---- sigma: H Phi on R, the stored Hamiltonian's x-groups and its constant
     if (with_h && nrows > 0) {
-        rc = dense ? launch_sub_sigma<true>(h, Q, P, &sigma_launches) : launch_sub_sigma<false>(h, Q, P, &sigma_launches);
+        rc = dense ? launch_sub_sigma<true>(h, Q, P, &sigma_launches, &sigma_grid) : launch_sub_sigma<false>(h, Q, P, &sigma_launches, &sigma_grid);
         if (rc) return rc;
     }
     HIPC(h, hipEventRecord(Q.ev[3], h->stream));
@@ -192,5 +194,12 @@ int run_subspace(ovqe_handle h, int64_t m, const int64_t *offsets, const uint64_
         HIPC(h, hipEventElapsedTime(&ms, Q.ev[k], Q.ev[k + 1]));
         Q.info[10 + k] = (int64_t)(1e3 * ms);
     }
+    // which path the call took: the Gram slices, the sigma instantiation and its grid (zeros when no sigma kernel ran), the expand grid
+    Q.info[14] = P.slices;
+    Q.info[15] = P.slice_rows;
+    Q.info[16] = sigma_launches ? P.sigma_blocks : 0;
+    Q.info[17] = sigma_launches ? P.sigma_col_groups : 0;
+    Q.info[18] = sigma_grid;
+    Q.info[19] = expand_grid;
     return OVQE_OK;
 }

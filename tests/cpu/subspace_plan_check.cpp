@@ -2,8 +2,12 @@
 // tests/test_subspace_cases.py): the bitmap arithmetic of the row set, the store layout, the block-pair list of the Gram kernel and
 // the row schedules of the Gram and sigma kernels for random (rows, m), indexed the way the kernels index them.
 //   usage: subspace_plan_check [seed]
+//          subspace_plan_check boundary rows,m,with_h,cus ...     the plan of each tuple, printed, with every row placed in its
+//                                                                 (slice, tile) and every column block in its (column group, b), then
+//                                                                 the pair lists at nb = 4, 5, 6 and the bitmap words of 1 .. 5 qubits
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <set>
 #include <utility>
@@ -109,7 +113,123 @@ static int check_plan(int64_t rows, int64_t m, bool with_h, int cus) {
     return 0;
 }
 
+// ---- boundary mode ------------------------------------------------------------------------------------------------------------------------
+// every row in exactly one (slice, tile) the way k_sub_gram walks them, no slice without rows; every column block in exactly one
+// (column group, b) with blk0 + b < nb the way k_sub_sigma walks them; every row in exactly one pass of a strided sigma grid
+static int check_boundary_tuple(int64_t rows, int64_t m, bool with_h, int cus) {
+    if (check_plan(rows, m, with_h, cus)) return 1;
+    const sub::Plan p = sub::plan(rows, m, with_h, cus);
+    std::printf("plan rows=%lld m=%lld with_h=%d cus=%d nb=%d mb=%lld wpad=%lld pairs=%d slices=%d slice_rows=%lld sigma_blocks=%d col_groups=%d row_tiles=%lld\n",
+                (long long)rows, (long long)m, with_h ? 1 : 0, cus, p.nb, (long long)p.mb, (long long)p.wpad, p.npairs, p.slices,
+                (long long)p.slice_rows, p.sigma_blocks, p.sigma_col_groups, (long long)p.sigma_row_tiles);
+    std::vector<unsigned char> hits((size_t)rows, 0);
+    constexpr int TR = sub::GRAM_TILE_ROWS;
+    for (int s = 0; s < p.slices; ++s) {
+        const int64_t r_begin = (int64_t)s * p.slice_rows;
+        const int64_t r_end = r_begin + p.slice_rows < rows ? r_begin + p.slice_rows : rows;
+        if (rows > 0) CHECK(r_begin < r_end);
+        for (int64_t r0 = r_begin; r0 < r_end; r0 += TR)
+            for (int row = 0; row < TR; ++row)
+                if (r0 + row < r_end) {
+                    CHECK(r0 + row < rows);
+                    CHECK(++hits[(size_t)(r0 + row)] == 1);
+                }
+    }
+    for (int64_t r = 0; r < rows; ++r) CHECK(hits[(size_t)r] == 1);
+    std::vector<int> blocks((size_t)p.nb, 0);
+    for (int g = 0; g < p.sigma_col_groups; ++g) {
+        int live = 0;
+        for (int b = 0; b < p.sigma_blocks; ++b)
+            if (g * p.sigma_blocks + b < p.nb) {
+                CHECK(((int64_t)(g * p.sigma_blocks + b) + 1) * 64 <= p.mb);
+                ++blocks[(size_t)(g * p.sigma_blocks + b)];
+                ++live;
+            }
+        CHECK(live >= 1);   // no column group without a block
+    }
+    for (int b = 0; b < p.nb; ++b) CHECK(blocks[(size_t)b] == 1);
+    // the strided row loop of the sigma kernel on a grid of min(row tiles, 32 cus) workgroups of SIGMA_ROW_TILE waves
+    const int64_t gx = std::min<int64_t>(p.sigma_row_tiles, (int64_t)std::max(cus, 1) * 32);
+    std::fill(hits.begin(), hits.end(), 0);
+    for (int64_t blk = 0; blk < gx; ++blk)
+        for (int wave = 0; wave < sub::SIGMA_ROW_TILE; ++wave)
+            for (int64_t r = blk * sub::SIGMA_ROW_TILE + wave; r < rows; r += gx * sub::SIGMA_ROW_TILE) CHECK(++hits[(size_t)r] == 1);
+    for (int64_t r = 0; r < rows; ++r) CHECK(hits[(size_t)r] == 1);
+    return 0;
+}
+
+static int check_pair_lists() {
+    for (int nb = 4; nb <= 6; ++nb) {
+        const int ns = sub::s_pairs(nb);
+        CHECK(sub::total_pairs(nb, true) == ns + nb * nb && sub::total_pairs(nb, false) == ns);
+        for (int q = 0; q < sub::total_pairs(nb, true); ++q) {
+            int I = -1, J = -1;
+            sub::block_pair(q, nb, &I, &J);
+            if (q < ns) CHECK(0 <= I && I <= J && J < nb && rdm::block_pair_index(I, J, nb) == q);
+            else CHECK(0 <= I && I < nb && nb <= J && J < 2 * nb && sub::h_pair_index(I, J - nb, nb) == q);
+        }
+        for (int I = 0; I < nb; ++I)
+            for (int J = 0; J < nb; ++J) {
+                int I2 = -1, J2 = -1;
+                sub::block_pair(sub::h_pair_index(I, J, nb), nb, &I2, &J2);
+                CHECK(I2 == I && J2 == nb + J);
+            }
+    }
+    return 0;
+}
+
+// xor_word and row_position on the one partial word of 1 .. 5 qubits against the definition, for every x: every bitmap up to 3 qubits,
+// the empty, full, one-bit and 300 random bitmaps on 4 and 5
+static int check_partial_words() {
+    std::mt19937_64 rng(5);
+    for (int n = 1; n <= 5; ++n) {
+        const uint64_t namps = 1ull << n, full = namps == 64 ? ~0ull : (1ull << namps) - 1ull;
+        CHECK(rdm::bitmap_words(n) == 1);
+        std::vector<uint64_t> maps;
+        if (n <= 3) {
+            for (uint64_t v = 0; v <= full; ++v) maps.push_back(v);
+        } else {
+            maps.push_back(0);
+            maps.push_back(full);
+            for (uint64_t i = 0; i < namps; ++i) maps.push_back(1ull << i);
+            for (int k = 0; k < 300; ++k) maps.push_back(rng() & full);
+        }
+        for (uint64_t in : maps)
+            for (uint64_t x = 0; x < namps; ++x) {
+                const uint64_t out = sub::xor_word(&in, 0, x);
+                uint64_t want = 0;
+                for (uint64_t i = 0; i < namps; ++i)
+                    if ((in >> (i ^ x)) & 1u) want |= 1ull << i;
+                CHECK(out == want);
+                CHECK((out & ~full) == 0);
+                const uint64_t start[2] = {0, (uint64_t)__builtin_popcountll(out)};
+                uint64_t r = 0;
+                for (uint64_t i = 0; i < namps; ++i)
+                    if (sub::in_rows(&out, i)) CHECK(sub::row_position(&out, start, i) == r++);
+                CHECK(r == start[1]);
+            }
+    }
+    return 0;
+}
+
+static int boundary(int argc, char **argv) {
+    for (int a = 2; a < argc; ++a) {
+        long long rows = -1, m = -1;
+        int with_h = -1, cus = -1;
+        if (std::sscanf(argv[a], "%lld,%lld,%d,%d", &rows, &m, &with_h, &cus) != 4 || rows < 0 || m < 1 || with_h < 0 || with_h > 1 || cus < 0) {
+            std::printf("FAILED: bad tuple '%s' (rows,m,with_h,cus)\n", argv[a]);
+            return 1;
+        }
+        if (check_boundary_tuple(rows, m, with_h != 0, cus)) return 1;
+    }
+    if (check_pair_lists()) return 1;
+    if (check_partial_words()) return 1;
+    std::printf("subspace boundary ok\n");
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && std::strcmp(argv[1], "boundary") == 0) return boundary(argc, argv);
     const uint64_t seed = argc > 1 ? std::strtoull(argv[1], nullptr, 10) : 1;
     std::mt19937_64 rng(seed);
     if (check_bitmaps(rng)) return 1;
