@@ -587,7 +587,15 @@ int ovqe_last_batch_ms(ovqe_handle h, double *ms);
  * forms of the sector path that served the handle since the program was set, as bits — 0 / 1 / 2 / 3 forward sweeps on pair words /
  * 64-bit words with rounds / per-wave streams / regular supports by bit arithmetic, 4..7 the backward sweeps of
  * ovqe_energy_gradient in the same order, 8 / 9 first / second form of the pair-table builder (the tests name the geometry behind
- * every form: DESIGN.md section 4).  which = 7: the kernel forms of the support-compacted path (programs whose reachable support
+ * every form: DESIGN.md section 4); then the choices inside a form, set where the kernel is launched — 10 / 11 the first sweep form
+ * with its pair words staged two chunks ahead / not, 12 / 13 the second and third forms with their scatter indices held in LDS /
+ * read late, 14 / 15 the pair-table builder on a dense slot map / by binary search (tiles of more than 16 index bits), 16 / 17
+ * lambda = H psi (gradients, Lanczos) stored by LDS atomics behind a memset / by one launch per <H> sweep in sequence, 18 / 19 its
+ * workgroups of 512 / 1024 threads, 20..24 the coding of the materialised <H>, one bit per outcome that at least one sweep took:
+ * 24-bit packed words, 32-bit dictionary words, explicit values because the dictionary overflowed, explicit values because a sample
+ * fitted a dictionary and the whole stream did not, explicit values because option "sector_dict" is 0; 25..29 / 30..34 / 35..39 the
+ * workgroup sizes 64 / 128 / 256 / 512 / 1024 the circuit sweeps / the backward sweeps / the sweeps of a regular support (both
+ * directions) were launched with.  which = 7: the kernel forms of the support-compacted path (programs whose reachable support
  * holds at most 4096 basis states) that served the handle since the program was set, as bits — 0 one evaluation per workgroup
  * (batches <= 256), 1 / 2 one evaluation per wave with / without its op table staged in LDS, 3 two per wave on rows of 64-bit
  * words (batches >= 2048), 4 / 5 two / four per wave without rows; 6 / 7 / 8 ovqe_energy_gradient per workgroup / per wave
@@ -626,7 +634,11 @@ int ovqe_last_support(ovqe_handle h, int32_t which, int64_t *support);
  *   amplitudes over the rows of 32 lanes of the circuit with the tables in use, [35] the slot and owner reads of the <H>
  *   contraction of the batched workgroup kernel (0 when no instance holds the program), [36] / [37] the reads / writes of the
  *   rows with the support numbered in discovery order, pairs in list order.  The rows the kernel adds to fill its pipeline
- *   (conflict-free by construction) are not counted */
+ *   (conflict-free by construction) are not counted
+ *   [38..45] sector path (0 until its tables exist): index bits of a circuit tile, index bits of an <H> tile (0: circuit only), slot
+ *   bits of the pair words (13, 14 or 15, decided by the widest op), amplitudes of the largest circuit tile, of the largest <H>
+ *   tile, entries of the largest dictionary of an <H> sweep, dictionary entries summed over the <H> sweeps (a sweep that keeps
+ *   explicit values counts 0), circuit sweeps whose tiles are taken largest first (sweeps of 512 tiles or more) */
 int ovqe_program_info(ovqe_handle h, int64_t *info, int count);
 /* The stored program as its sequence of Pauli rotations exp(-i (coeff[r] theta[pidx[r]] + phi0[r]) P_r), P_r = (x[r], z[r]) in
  * index-bit space, in execution order (pidx < 0: a constant angle) — for a gate program in Clifford-frame form

@@ -471,7 +471,24 @@ class Statevector:
         self._ck(self._L.ovqe_last_support(self._h, 6, ctypes.byref(out)))
         return {name for bit, name in enumerate(self.SECTOR_FORMS) if (out.value >> bit) & 1}
 
-    SPARSE_FORMS = ("wg", "staged1", "plain1", "rows2", "plain2", "plain4", "grad_wg", "grad_staged", "grad_plain", "declined")
+    #: the choices inside a sector kernel form, bits 10... of the same word (ovqe_sv.hip: SECF_*), set where the kernel is launched
+    SECTOR_CHOICES = ("sweep_pairs_ahead", "sweep_pairs_plain", "scatter_in_lds", "scatter_late", "pair_builder_dense_map",
+                      "pair_builder_search", "apply_atomic", "apply_sequential", "apply_512", "apply_1024",
+                      "h_packed24", "h_dict32", "h_explicit_overflow", "h_explicit_sample_failed", "h_explicit_no_dict") + tuple(
+                          f"{group}_{nt}" for group in ("sweep", "adjoint", "regular") for nt in (64, 128, 256, 512, 1024))
+
+    def sector_choices(self):
+        """what the sector-path kernels of ``sector_forms()`` were launched as on this handle since its program was set: the staging
+        variant of the first sweep form ("sweep_pairs_ahead": k_sector_sweep<NT, true>), where the second and third forms keep their
+        scatter indices, the slot map of the pair-table builder, store mode and workgroup size of lambda = H psi (k_sector_apply),
+        the coding outcomes of the materialised <H> (one name per outcome that at least one sweep took) and the workgroup sizes of
+        the circuit sweeps ("sweep_256"), the backward sweeps ("adjoint_1024") and the regular-support sweeps ("regular_128").
+        ``sector_forms()`` keeps returning the form names alone."""
+        out = ctypes.c_int64()
+        self._ck(self._L.ovqe_last_support(self._h, 6, ctypes.byref(out)))
+        return {name for bit, name in enumerate(self.SECTOR_CHOICES) if (out.value >> (10 + bit)) & 1}
+
+    SPARSE_FORMS = ("wg","staged1", "plain1", "rows2", "plain2", "plain4", "grad_wg", "grad_staged", "grad_plain", "declined")
 
     def sparse_forms(self):
         """names of the support-compacted kernel forms that served this handle since its program was set (ovqe_last_support,
@@ -706,8 +723,8 @@ class Statevector:
     def program_info(self):
         """shape of the compiled program: ops, rotations, literal gates, sweeps per evaluation, tiled sweeps,
         fused-kernel ops, support size (-1 = not analysed yet)"""
-        out = (ctypes.c_int64 * 38)()
-        self._ck(self._L.ovqe_program_info(self._h, out, 38))
+        out = (ctypes.c_int64 * 46)()
+        self._ck(self._L.ovqe_program_info(self._h, out, 46))
         keys = ("ops", "rotations", "literal_gates", "sweeps", "tiled_sweeps", "fused_ops", "support",
                 "h_tile_sweeps", "h_untiled_groups", "h_entries", "h_merged_terms", "h_pair_terms_per_tile",
                 "real_stream", "sp_ops", "sp_pairs", "sp_h_entries",
@@ -716,7 +733,9 @@ class Statevector:
                 "sp_conflicts_discovery_order", "sp_conflicts", "sector_regular_slot_bits", "sector_free_bits",
                 "sp_h_pieces", "sp_h_slots", "sp_h_reads_per_state",
                 "sp_lds_row_reads", "sp_lds_row_writes", "sp_lds_h_reads",
-                "sp_lds_row_reads_discovery_order", "sp_lds_row_writes_discovery_order")
+                "sp_lds_row_reads_discovery_order", "sp_lds_row_writes_discovery_order",
+                "sector_tile_bits", "sector_h_tile_bits", "sector_pair_slot_bits", "sector_max_tile", "sector_h_max_tile",
+                "sector_h_max_dict", "sector_h_dict_entries", "sector_ordered_sweeps")
         return dict(zip(keys, [int(v) for v in out]))
 
     def rotation_program(self):

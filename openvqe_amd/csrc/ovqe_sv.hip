@@ -237,6 +237,19 @@ struct SectorHSweep {   // one sweep of the materialised <H>
     DevBuf d_cbase, d_clen, d_cwords, d_cvals, d_dict, d_xbase, d_xlen, d_xwords, d_xvals, d_order;   // row format (sv_sector.hpp)
     DevBuf d_torder;              // tiles by population, largest first
 };
+// bits 10.. of ovqe_sv::forms_used (ovqe_last_support which = 6): the choices inside a sector kernel form, set where the kernel is launched
+constexpr uint64_t SECF_SWEEP1_AHEAD = 1ull << 10, SECF_SWEEP1_PLAIN = 1ull << 11;   // k_sector_sweep<NT, true> / <NT>: pair words two chunks ahead or not
+constexpr uint64_t SECF_DST_LDS = 1ull << 12, SECF_DST_LATE = 1ull << 13;            // second / third form: scatter indices held in LDS or read late
+constexpr uint64_t SECF_PAIRS_DENSE = 1ull << 14, SECF_PAIRS_SEARCH = 1ull << 15;    // pair-table builder: dense slot map or binary search (M > 16)
+constexpr uint64_t SECF_APPLY_ATOMIC = 1ull << 16, SECF_APPLY_SEQ = 1ull << 17;      // k_sector_apply: mode 0, or modes 2 then 1 (one launch per sweep)
+constexpr uint64_t SECF_APPLY_512 = 1ull << 18, SECF_APPLY_1024 = 1ull << 19;
+// coding of the materialised <H>, one bit per outcome that at least one sweep took
+constexpr uint64_t SECF_H_PACKED = 1ull << 20, SECF_H_DICT = 1ull << 21, SECF_H_OVERFLOW = 1ull << 22, SECF_H_SAMPLE_FAILED = 1ull << 23,
+                   SECF_H_NO_DICT = 1ull << 24;
+// workgroup sizes 64 / 128 / 256 / 512 / 1024 of the circuit sweeps (bits 25..29), the backward sweeps (30..34), the regular-support sweeps (35..39)
+constexpr int SECF_WG_SWEEP = 25, SECF_WG_ADJOINT = 30, SECF_WG_REGULAR = 35;
+constexpr uint64_t secf_wg(int group, int nt) { return 1ull << (group + (nt == 64 ? 0 : nt == 128 ? 1 : nt == 256 ? 2 : nt == 512 ? 3 : 4)); }
+
 struct SectorEngine {
     bool valid = false, disabled = false;
     bool h_tables = false;        // the materialised <H> is part of the engine (else: circuit only, <H> by the compact cover)
@@ -380,8 +393,8 @@ struct ovqe_sv {
     // which kernel forms of the sector path served this handle since the last ovqe_set_program / ovqe_set_gate_program (ovqe_last_support
     // which = 6; the tests name the geometry that selects each form): bit 0 first sweep form (pair words), 1 second (64-bit words + rounds),
     // 2 third (per-wave streams), 3 regular supports (bit arithmetic); 4..7 the backward sweeps of ovqe_energy_gradient in the same order;
-    // 8 / 9 the first / second form of the pair-table builder
-    uint32_t forms_used = 0;
+    // 8 / 9 the first / second form of the pair-table builder; 10.. the choices inside a form (SECF_* below, set at the launch sites)
+    uint64_t forms_used = 0;
     // ... and of the support-compacted path (ovqe_last_support which = 7, SPF_* in sparse_host.inc)
     uint32_t sp_forms = 0;
     // ... and what the most recent k_small_vqe launch since then was (ovqe_last_support which = 8..13, run_small): form bits, workgroups,
@@ -1622,6 +1635,13 @@ int ovqe_program_info(ovqe_handle h, int64_t *info, int count) try {
                            packed ? (int64_t)h->sp_h_rpt * (h->sp_h_epr + 1) : 0};
     for (int i = 30; i < count && i < 33; ++i) info[i] = pv[i - 30];
     for (int i = 33; i < count && i < 38; ++i) info[i] = h->sp_valid ? h->sp_cycles[i - 33] : 0;
+    int64_t dict_entries = 0, ordered = 0;
+    for (const SectorHSweep &hw : E.hs) dict_entries += hw.ndict;
+    for (const SectorSeg &sg : E.segs) ordered += sg.d_torder.p ? 1 : 0;
+    const int64_t gv[8] = {E.valid ? (int64_t)E.M : 0, E.valid ? (int64_t)E.Mh : 0, E.valid ? (int64_t)E.sb : 0, E.valid ? (int64_t)E.max_tile : 0,
+                           E.valid ? (int64_t)E.h_max_tile : 0, E.valid ? (int64_t)E.h_max_dict : 0, E.valid ? dict_entries : 0,
+                           E.valid ? ordered : 0};
+    for (int i = 38; i < count && i < 46; ++i) info[i] = gv[i - 38];
     return OVQE_OK;
 } OVQE_CATCH(h)
 

@@ -566,6 +566,7 @@ int build_sector_h(ovqe_handle h, SectorEngine &E, SectorScratch &W, size_t budg
                 }
                 if (stride == 1u) return fail(h, OVQE_ERR_INVALID, "internal: a coded value is missing from its own dictionary");
             }
+            h->forms_used |= coded ? 0ull : (attempted ? SECF_H_SAMPLE_FAILED : SECF_H_OVERFLOW);
             if (!coded && attempted) {   // (the sample fitted a dictionary, the whole stream does not)
                 hipLaunchKernelGGL(k_sec_words_slots, dim3((ct + 255u) / 256u), dim3(256), 0, h->stream, (uint32_t *)hw.d_cwords.p, ct);
                 HIPC(h, hipGetLastError());
@@ -586,10 +587,14 @@ int build_sector_h(ovqe_handle h, SectorEngine &E, SectorScratch &W, size_t budg
                     std::swap(hw.d_cwords, packed);
                     free_buf(packed);
                     hw.packed = 1;
+                    h->forms_used |= SECF_H_PACKED;
                     E.bytes -= std::min(E.bytes, (size_t)ct);
                     E.h_stream_bytes -= std::min(E.h_stream_bytes, (size_t)ct);
                 }
+                if (!hw.packed) h->forms_used |= SECF_H_DICT;
             }
+        } else if (ct > 0) {
+            h->forms_used |= SECF_H_NO_DICT;
         }
         if (!hw.ndict) {   // the coded stream keeps its explicit values
             E.bytes += (size_t)ct * 8;
@@ -894,7 +899,7 @@ int build_sector_tables_impl(ovqe_handle h, bool allow_regular) {
             rc = lds_opt_in<&k_sec_pairs<false, NTB, true>, &k_sec_pairs<true, NTB, true>>(h, PAIRS_LDS_MAX);
             if (!rc) rc = lds_opt_in<&k_sec_pairs2<false, NTB, true>, &k_sec_pairs2<true, NTB, true>>(h, SEC_LDS_MAX);
             if (rc) return rc;
-            h->forms_used |= form2 ? 512u : 256u;
+            h->forms_used |= (form2 ? 512u : 256u) | (dense_map ? SECF_PAIRS_DENSE : SECF_PAIRS_SEARCH);
 #define OVQE_PAIRS(FILL, DENSE, CNT, POFF, PAIRS)                                                                            \
     do {                                                                                                                    \
         if (form2)                                                                                                          \
@@ -1189,7 +1194,7 @@ int launch_sector_sweeps(ovqe_handle h, SectorEngine &E, int *last) {
         const size_t smem = sec_sweep_lds(cap, sg.nrot, sg.nops).bytes;
         // two chunks of pair words ahead where every op of a tile fits a staging buffer
         const bool d2 = NT > 64 && sg.max_op_pairs <= SEC_STAGE_WORDS && !(h->opt_sector_debug & 1);
-        h->forms_used |= 1u;
+        h->forms_used |= 1u | (d2 ? SECF_SWEEP1_AHEAD : SECF_SWEEP1_PLAIN) | secf_wg(SECF_WG_SWEEP, NT);
         if (d2)
             hipLaunchKernelGGL((k_sector_sweep<NT, true>), dim3(sg.L.ntiles), dim3(NT), smem, h->stream, (const double *)E.d_buf[cur ^ 1].p,
                                (double *)E.d_buf[cur].p, s ? (const uint32_t *)sg.d_srcpad.p : (const uint32_t *)nullptr,
@@ -1228,7 +1233,7 @@ int launch_sector_sweeps2(ovqe_handle h, SectorEngine &E, double *buf0, double *
             // streams gain them nothing (24 qubits, per evaluation: batches of 64 0.509 ms on the second form / 0.512 on the streams, of 8 0.649 / 0.656)
             if (sg.nruns > 0 && h->opt_sector_sweep >= 3 && smem3 <= LDS_WG_MAX && (B == 1 || h->opt_sector_sweep >= 4)) {
                 if (int rc = lds_opt_in<&k_sector_sweep3<NT>>(h, LDS_WG_MAX)) return rc;
-                h->forms_used |= 4u;
+                h->forms_used |= 4u | (dst_lds ? SECF_DST_LDS : SECF_DST_LATE) | secf_wg(SECF_WG_SWEEP, NT);
                 hipLaunchKernelGGL((k_sector_sweep3<NT>), bfast ? dim3((unsigned)B, sg.L.ntiles) : dim3(sg.L.ntiles, (unsigned)B), dim3(NT),
                                    smem3, h->stream,
                                    s ? (const double *)buf[cur ^ 1] : (const double *)nullptr, buf[cur], stride, stride,
@@ -1241,7 +1246,7 @@ int launch_sector_sweeps2(ovqe_handle h, SectorEngine &E, double *buf0, double *
                 continue;
             }
         }
-        h->forms_used |= 2u;
+        h->forms_used |= 2u | (dst_lds ? SECF_DST_LDS : SECF_DST_LATE) | secf_wg(SECF_WG_SWEEP, NT);
         for (int rep = 0; rep < (h->opt_sector_sweep_dbg == 16 ? 2 : 1); ++rep)   // 16: every sweep twice (idempotent): cold against warm
         hipLaunchKernelGGL((k_sector_sweep2<NT, WPT>), bfast ? dim3((unsigned)B, sg.L.ntiles) : dim3(sg.L.ntiles, (unsigned)B), dim3(NT), smem, h->stream,
                            s ? (const double *)buf[cur ^ 1] : (const double *)nullptr, buf[cur], stride, stride,
@@ -1293,7 +1298,7 @@ int launch_sector_sweeps_reg(ovqe_handle h, SectorEngine &E, int *last) {
     for (size_t s = 0; s < E.segs.size(); ++s) {
         const SectorSeg &sg = E.segs[s];
         const size_t smem = sec_reg_lds(E.reg_m, 1, sg.nops, 0, 0).bytes;
-        h->forms_used |= 8u;
+        h->forms_used |= 8u | secf_wg(SECF_WG_REGULAR, NT);
         hipLaunchKernelGGL((k_sector_sweep_reg<NT>), dim3(sg.L.ntiles), dim3(NT), smem, h->stream, (const double *)E.d_buf[cur ^ 1].p,
                            (double *)E.d_buf[cur].p,
                            s ? (const uint32_t *)(sg.d_regsrc.p ? sg.d_regsrc.p : sg.d_srcpad.p) : (const uint32_t *)nullptr,
@@ -1556,7 +1561,7 @@ int launch_sector_adjoint(ovqe_handle h, SectorEngine &E, int last) {
         const uint32_t cap = std::max(sg.L.max_tile, 1u);
         const size_t smem = sec_adjoint_lds(cap, sg.nrot, sg.nops, NT / 64).bytes;
         if (smem > LDS_WG_MAX) return fail(h, OVQE_ERR_INVALID, "internal: sector adjoint tile exceeds LDS");
-        h->forms_used |= 16u;
+        h->forms_used |= 16u | secf_wg(SECF_WG_ADJOINT, NT);
         hipLaunchKernelGGL((k_sector_adjoint<NT>), dim3(sg.L.ntiles), dim3(NT), smem, h->stream, (const double *)E.d_buf[cur].p,
                            (const double *)E.d_lam[lcur].p, (double *)E.d_buf[cur ^ 1].p, (double *)E.d_lam[lcur ^ 1].p,
                            s ? (const uint32_t *)sg.L.d_src.p : (const uint32_t *)nullptr, (const uint32_t *)sg.L.d_off.p,
@@ -1594,7 +1599,7 @@ int launch_sector_adjoint2(ovqe_handle h, SectorEngine &E, int last) {
         const size_t smem3 = sec_adjoint2_lds(cap, sg.nrot, std::max(sg.stream_waves, 1), 0).bytes;
         if (sg.nruns > 0 && h->opt_sector_sweep >= 3 && h->opt_sector_adjoint >= 3 && smem3 <= LDS_WG_MAX) {   // on the per-wave streams
             if (int rc = lds_opt_in<&k_sector_adjoint3<NT>>(h, LDS_WG_MAX)) return rc;
-            h->forms_used |= 64u;
+            h->forms_used |= 64u | secf_wg(SECF_WG_ADJOINT, NT);
             hipLaunchKernelGGL((k_sector_adjoint3<NT>), dim3(sg.L.ntiles), dim3(NT), smem3, h->stream,
                                (const double *)E.d_buf[cur].p, (const double *)E.d_lam[lcur].p, (double *)E.d_buf[cur ^ 1].p,
                                (double *)E.d_lam[lcur ^ 1].p, s + 1 == (int)E.segs.size() ? 1 : 0,
@@ -1606,7 +1611,7 @@ int launch_sector_adjoint2(ovqe_handle h, SectorEngine &E, int last) {
             lcur ^= 1;
             continue;
         }
-        h->forms_used |= 32u;
+        h->forms_used |= 32u | secf_wg(SECF_WG_ADJOINT, NT);
         hipLaunchKernelGGL((k_sector_adjoint2<NT, WPT>), dim3(sg.L.ntiles), dim3(NT),
                            sec_adjoint2_lds(cap, sg.nrot, NT / 64, sg.maxchunks).bytes, h->stream,
                            (const double *)E.d_buf[cur].p, (const double *)E.d_lam[lcur].p, (double *)E.d_buf[cur ^ 1].p,
@@ -1662,7 +1667,7 @@ int launch_sector_adjoint_reg(ovqe_handle h, SectorEngine &E, int last) {
     for (size_t si = E.segs.size(); si-- > 0;) {
         const SectorSeg &sg = E.segs[si];
         const int runcap = (E.reg_plan_threads == NT && h->opt_sector_reg_runs) ? sector_adjoint_reg_runcap(E, sg, NT) : 1;
-        h->forms_used |= 128u;
+        h->forms_used |= 128u | secf_wg(SECF_WG_REGULAR, NT);
         hipLaunchKernelGGL((k_sector_adjoint_reg<NT>), dim3(sg.L.ntiles), dim3(NT), sec_reg_lds(E.reg_m, 2, sg.nops, NT / 64, runcap).bytes, h->stream,
                            (const double *)E.d_buf[cur].p, (const double *)E.d_lam[lcur].p, (double *)E.d_buf[cur ^ 1].p,
                            (double *)E.d_lam[lcur ^ 1].p,
@@ -1762,6 +1767,7 @@ int sector_matvec(ovqe_handle h, SectorEngine &E, const double *in, double *out)
     const dim3 grid(sector_h_groups(E), seq ? 1u : nsw);
     for (unsigned s0 = 0; s0 < (seq ? nsw : 1u); ++s0) {
         const int mode = seq ? (s0 == 0 ? 2 : 1) : 0;
+        h->forms_used |= (seq ? SECF_APPLY_SEQ : SECF_APPLY_ATOMIC) | (nt == 1024 ? SECF_APPLY_1024 : SECF_APPLY_512);
         if (nt == 1024) {
             if (int rc = lds_opt_in<&k_sector_apply<1024>>(h, SEC_LDS_MAX)) return rc;
             hipLaunchKernelGGL((k_sector_apply<1024>), grid, dim3(1024), smem, h->stream, in, (const SecHSweep *)E.d_hdesc.p, out,

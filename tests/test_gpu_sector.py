@@ -29,8 +29,12 @@ def _oracle_energies(n, gens, hf, H, thetas):
                                               (10, 4, 12, 256), (10, 5, 0, 256), (10, 4, 18, 0)])
 def test_sector_uccsd_matches_c_oracle(SV, m, o, bits, threads):
     """molecule-shaped UCCSD (JW generators in table-fused form, a JW two-body Hamiltonian): the support is the
-    (o alpha, o beta) sector; energies of the sector path == oracle == dense kernels.  bits = 18 at 20 qubits: tiles of 17
-    index bits (8 tiles of ~5500 amplitudes), beyond the dense slot maps of the table construction (binary-search path)"""
+    (o alpha, o beta) sector; energies of the sector path == oracle == dense kernels.  bits = 18 at 20 qubits: the largest tile
+    exceeds the 6500 amplitudes of "sector_tile_cap" and the tile bits are lowered until it fits — to 16 or fewer, where the
+    dense slot maps of the table construction still serve (the binary-search builder for tiles of 17 bits is pinned in
+    tests/test_gpu_sector_forms.py with the cap raised).
+    "sector_threads" 256 runs k_sector_sweep2<256> (the second form takes every workgroup size but 64 while its tables exist and
+    fit), 64 the first form without staging ahead, the automatic size at 20 qubits k_sector_sweep2<1024> or the streams on it"""
     from openvqe_amd import fermion
     n = 2 * m
     ham, gens, hf = fermion.synthetic_molecule(m, o, seed=100 + m)
@@ -48,10 +52,22 @@ def test_sector_uccsd_matches_c_oracle(SV, m, o, bits, threads):
         sv.set_ucc_program(gens, hf)
         got = [sv.energy(th) for th in thetas]
         info = sv.program_info()
+        forms, choices = sv.sector_forms(), sv.sector_choices()
         batch = sv.energy_batch(np.stack(thetas))
         sv.set_option("sector", 0)
         dense = [sv.energy(th) for th in thetas]
         assert sv.program_info()["sector_support"] == 0
+    if threads == 64:
+        assert forms & {"sweep_pairs", "sweep_wide", "sweep_streams"} == {"sweep_pairs"} and {"sweep_64", "sweep_pairs_plain"} <= choices, (forms, choices)
+    elif threads == 256:
+        assert forms & {"sweep_pairs", "sweep_wide", "sweep_streams"} == {"sweep_wide"} and {"sweep_256", "scatter_in_lds"} <= choices, (forms, choices)
+    else:
+        assert "sweep_pairs" not in forms and {"sweep_1024", "scatter_in_lds"} <= choices, (forms, choices)
+        assert info["sector_tile_bits"] < 18 and info["sector_max_tile"] <= 6500, info
+        assert ("pair_builder_search" in choices) == (info["sector_tile_bits"] > 16) and ("pair_builder_dense_map" in choices) == (info["sector_tile_bits"] <= 16)
+    print(f"uccsd ({m},{o}) bits {bits} threads {threads}: tile bits {info['sector_tile_bits']}, largest tile {info['sector_max_tile']}, {sorted(forms)}")
+    if bits != 18:
+        assert info["sector_tile_bits"] == (bits if bits else max(8, min(16, n - 8))), info
     assert info["sector_support"] == comb(m, o) ** 2, info
     assert info["sector_sweeps"] >= 1 and info["sector_h_sweeps"] >= 1 and info["sector_pairs"] > 0
     assert info["sector_h_elements"] > info["sector_support"]
@@ -81,6 +97,8 @@ def test_pair_table_builder_forms_give_the_same_tables(SV, m, o, bits):
             eg, g = sv.energy_gradient(theta)
             info = sv.program_info()
             assert info["sector_support"] > 0
+            assert sv.sector_forms() & {"pair_builder_first", "pair_builder_staged"} == {("pair_builder_first", "pair_builder_staged")[form - 1]}
+            assert "pair_builder_dense_map" in sv.sector_choices()
             got[form] = (e, eg, g, info["sector_pairs"], info["sector_sweeps"])
     assert got[1][0] == got[2][0] and got[1][3] == got[2][3] and got[1][4] == got[2][4]
     assert abs(got[1][1] - got[2][1]) < 1e-13 and np.abs(got[1][2] - got[2][2]).max() < 1e-13
@@ -282,10 +300,19 @@ def test_sector_adjoint_gradient(SV, m, o, bits, coded):
         e3, g3 = sv.energy_gradient(th2)
         e3b = sv.energy(th2)
         info = sv.program_info()
-        sv.set_option("sector_adjoint", 1)        # the first form of the backward sweeps (the default takes the 64-bit tables)
-        e5, g5 = sv.energy_gradient(th2)
+        back = {"adjoint_pairs", "adjoint_wide", "adjoint_streams", "adjoint_regular"}
+        forms_default, choices_default = sv.sector_forms() & back, sv.sector_choices()
+        sv.set_option("sector_adjoint", 1)        # the first form of the backward sweeps.  The default ("sector_adjoint" 3) takes the per-wave
+        e5, g5 = sv.energy_gradient(th2)          # streams (k_sector_adjoint3) where a sweep has them, else the 64-bit tables (k_sector_adjoint2)
+        forms_first = sv.sector_forms() & back
         sv.set_option("sector", 0)
         e4, g4 = sv.energy_gradient(th2)
+    print(f"adjoint forms ({m},{o}) bits {bits}: default {sorted(forms_default)}, then {sorted(forms_first)}; {sorted(choices_default)}")
+    # streams are built for sweeps that average 24 pairs per op and more: none on the 8- and 9-bit tiles, some or all sweeps from 10 bits on
+    assert forms_default and forms_default <= {"adjoint_wide", "adjoint_streams"} and "adjoint_1024" in choices_default
+    assert ("adjoint_streams" in forms_default) == (info["sector_tile_bits"] >= 10), (forms_default, info["sector_tile_bits"])
+    assert forms_first == forms_default | {"adjoint_pairs"}
+    assert ("h_explicit_no_dict" in choices_default) == (coded == 0) and bool({"h_packed24", "h_dict32"} & choices_default) == (coded == 1)
     assert info["sector_support"] == comb(m, o) ** 2 and info["sector_h_elements"] > 0, info
     assert abs(e2 - e1) < 1e-12 * l1 and abs(e3 - e4) < 1e-12 * l1 and abs(e3 - e3b) < 1e-12 * l1
     assert np.abs(g2 - g1).max() < 1e-11 * l1 and np.abs(g3 - g4).max() < 1e-11 * l1
@@ -693,7 +720,9 @@ def testing_lib(gpu_lib, monkeypatch):
 @pytest.mark.parametrize("m,o,waves,arrange", [(8, 3, 0, 1), (8, 3, 1, 0), (8, 4, 2, 1), (9, 4, 0, 1), (9, 4, 4, 0), (9, 4, 16, 1), (10, 5, 8, 1)])
 def test_per_wave_streams_equal_the_second_sweep_form_bit_for_bit(testing_lib, m, o, waves, arrange):
     """third form of the circuit sweeps (k_sector_sweep3 / k_sector_adjoint3: pair words in per-wave streams, barriers at run boundaries
-    only) against the second form ON THE SAME TABLES: a pair is rotated by the same arithmetic in both, every slot sees its ops in
+    only; a sweep whose runs would hold fewer than two ops on average keeps the second form, and with the automatic number of waves
+    the 8-bit tiles of (8,3) get no streams at all: that case holds the second form against itself) against the second form ON THE
+    SAME TABLES: a pair is rotated by the same arithmetic in both, every slot sees its ops in
     program order, so the energies are equal bit for bit, whatever the number of waves that share a tile's rows and whether the lanes
     of a row were arranged for the LDS banks; the gradient's partial sums are added in another order (1e-12); both against the oracle"""
     from openvqe_amd import fermion
@@ -713,14 +742,20 @@ def test_per_wave_streams_equal_the_second_sweep_form_bit_for_bit(testing_lib, m
         sv.set_ucc_program(gens, hf)
         for th in thetas:
             sv.energy(th)                       # (the tables are built at the second evaluation)
-        got, grad = {}, {}
+        got, grad, seen = {}, {}, {}
+        before = sv.sector_forms()
         for form in (3, 2):
             sv.set_option("sector_sweep", form)
             sv.set_option("sector_adjoint", form)
             got[form] = [sv.energy(th) for th in thetas]
             grad[form] = [sv.energy_gradient(th) for th in thetas]
-        sv.set_option("sector_sweep", 4)        # (the streams for the states of a batch too: the product gives batches the second form)
+            seen[form] = sv.sector_forms()
+        sv.set_option("sector_sweep", 4)        # (a batch runs k_sector_sweep2<512> whatever this says: the streams are planned for 1024 threads)
         batch = sv.energy_batch(np.stack(thetas))
+        choices = sv.sector_choices()
+    print(f"streams ({m},{o}) waves {waves}: before {sorted(before)}, under 3 {sorted(seen[3])}, under 2 {sorted(seen[2])}")
+    assert ({"sweep_streams", "adjoint_streams"} <= seen[3]) == (waves != 0 or m >= 9), seen
+    assert {"sweep_wide", "adjoint_wide"} <= seen[2] and {"sweep_512", "scatter_late"} <= choices, (seen, choices)
     assert got[3] == got[2]
     for (e3, g3), (e2, g2), ew in zip(grad[3], grad[2], want):
         assert abs(e3 - ew) < 1e-10 * max(1.0, l1) and abs(e3 - e2) < 1e-13 * max(1.0, l1)    # (the gradient's energy is a dot product with lambda)
@@ -758,6 +793,8 @@ def test_packed_hamiltonian_elements_equal_the_32_bit_words_bit_for_bit(testing_
                 es = [sv.energy(t) for t in thetas]           # (from the tables)
                 grads = [sv.energy_gradient(t)[1] for t in thetas]
                 got[pack] = (es, sv.energy_batch(np.stack(thetas)), grads, sv.program_info()["sector_bytes"])
+                coding = {c for c in sv.sector_choices() if c.startswith("h_")}
+                assert coding == ({"h_packed24"} if pack else {"h_dict32"}) or (pack and coding == {"h_packed24", "h_dict32"}), coding
         assert got[1][0] == got[0][0] and np.array_equal(got[1][1], got[0][1])
         assert all(np.abs(a - b).max() < 1e-12 * max(1.0, l1) for a, b in zip(got[1][2], got[0][2]))   # (lambda = H psi adds with atomics: rounding)
         assert got[1][3] < got[0][3]                                   # the packed tables are smaller
