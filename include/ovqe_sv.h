@@ -476,6 +476,38 @@ int ovqe_metric_tensor(ovqe_handle h, const double *theta, int32_t K, double *me
  * from global memory [10] dynamic LDS bytes of the tangent launch (0 on the streaming path); zeros before the first call */
 int ovqe_metric_info(ovqe_handle h, int64_t *info, int count);
 
+/* ---- exact energy Hessian of the stored program: with E(theta) = <psi(theta)|H|psi(theta)> of the stored Hamiltonian,
+ *   hess[K*K], row-major:  d2E / dtheta_i dtheta_j      K x K, real, symmetric to the bit
+ * together with E (energy, may be NULL) and the gradient (grad[K], may be NULL) of the same point — what decides whether a converged point
+ * is a minimum (lowest eigenvalue) and what Newton / trust-region optimisers step with (openvqe_amd/common_files/newton.py).  Forward
+ * over reverse: the adjoint pass of ovqe_energy_gradient differentiated in every direction b, with the tangents of ovqe_metric_tensor
+ * (the derivation: openvqe_amd/csrc/sv_hessian_host.hpp).  Row b of the raw matrix M comes from direction b and M is symmetric to
+ * rounding only: the call returns (M + M^T) / 2 and reports max |M - M^T| in *asymmetry (may be NULL) as a built-in self-check.
+ * CONTRACT (ovqe_metric_tensor's).  The angle of rotation r is coeff_r theta[pidx_r] + phi0_r; a parameter shared by several rotations
+ * sums their contributions; a parameter no rotation uses, or a rotation with pidx < 0, gives a zero row and column.  A Hamiltonian must be
+ * set.  Gate programs whose Clifford frame is open are evaluated with the conjugated Hamiltonian, as by ovqe_energy.  The state buffer is
+ * unspecified after the call; cached tables of the handle stay valid: an ovqe_energy before the call and one after it return the same bits.
+ * TWO PATHS (ovqe_hessian_info [0]).  1, compact support: a real-amplitude program whose reachable support holds at most 4096 basis states
+ * and whose four LDS vectors (psi, tangent, lambda = H psi, mu = H tangent) and tables fit one workgroup: ONE launch, one 64-lane workgroup
+ * per direction, the real part of the Hamiltonian restricted to the support.  LDS atomics add lambda, mu and the weights as in the compact
+ * gradient kernel: the result reproduces to rounding, not to the bit.  2, streaming (any other program, option "force_path" = 2, or a
+ * compact program too large for LDS): psi and the K tangents as columns of a store of 2^n rows and a second store of their images
+ * under H, both behind option "metric_workspace_mb"; the op list is walked backwards on both, fixed-order sums, bit-identical from call
+ * to call.  COST of path 2: O(K R) sweeps of the register for R rotations — meant for small registers and short programs.  Out of scope:
+ * the sector tables and the partitioned register.
+ * OVQE_ERR_STATE with no program or no Hamiltonian set, on a shard of a partitioned register and under option "real_state";
+ * OVQE_ERR_INVALID for a K other than the program's, a NULL theta or hess (K = 0: only hess is checked; the energy alone is answered);
+ * OVQE_ERR_ALLOC, with the bytes needed in the text, when the workspace does not fit the cap of option "metric_workspace_mb". */
+int ovqe_energy_hessian(ovqe_handle h, const double *theta, int32_t K, double *energy, double *grad, double *hess, double *asymmetry);
+/* of the last ovqe_energy_hessian call, up to `count` entries of: [0] path (1 compact support, 2 streaming) [1] K [2] amplitudes per vector
+ * [3] workspace bytes (path 1: the rows, gradient and energy and the restricted Hamiltonian; path 2: both stores, the slab sums and the
+ * weight records) [4] launches [5] entries of the restricted Hamiltonian (path 1) [6..8] HIP-event times in microseconds: path 1 the
+ * copy of theta to the device together with the one launch, the copy back, 0 (no third phase); path 2 tangents and H images, the
+ * backward walk, the copy back [9] kernel form: 0 streaming, 1 compact with
+ * ops and pair words staged in LDS, 2 compact with both read from global memory [10] dynamic LDS bytes of the launch (0 on the streaming
+ * path); zeros before the first call */
+int ovqe_hessian_info(ovqe_handle h, int64_t *info, int count);
+
 /* ---- finite-shot measurement: outcomes drawn from the state in the buffer, and energies with shot noise (what a submission with
  * nbshots > 0 asks of a QPU: openvqe_amd/qat_compat.py; every call site of the reference submits nbshots = 0, the exact paths above).
  * Plain handles of any size; OVQE_ERR_STATE on a shard of a partitioned register and under option "real_state".  The state buffer is

@@ -609,6 +609,36 @@ class Statevector:
                 "tangent_form", "tangent_lds_bytes")
         return dict(zip(keys, [int(v) for v in out]))
 
+    # -- exact energy Hessian of the stored program (ovqe_energy_hessian, csrc/hessian_host.inc) -----------------------------------
+    def energy_hessian(self, theta):
+        """E(theta), the exact gradient and the exact Hessian d2E / dtheta_i dtheta_j of the stored program and Hamiltonian in one call
+        -> (energy, grad[K], hess[K, K]); ``hess`` is symmetric to the bit, ``hessian_info()["asymmetry"]`` is max |M - M^T| of the raw
+        rows (a built-in self-check) — the matrices of ``common_files.newton``"""
+        K = self._K
+        theta = np.ascontiguousarray(theta, np.float64).reshape(-1)[:K]
+        if theta.shape[0] != K:
+            raise ValueError(f"expected {K} parameters")
+        e, asym = ctypes.c_double(), ctypes.c_double()
+        grad = np.zeros(max(K, 1), np.float64)
+        hess = np.zeros((K, K), np.float64)
+        self._ck(self._L.ovqe_energy_hessian(self._h, theta if K else np.zeros(1), K, ctypes.byref(e), grad, hess.reshape(-1) if K else np.zeros(1),
+                                             ctypes.byref(asym)))
+        self._hessian_asymmetry = asym.value
+        return e.value, grad[:K], hess
+
+    def hessian_info(self):
+        """figures of the last ``energy_hessian`` call: path (1 compact support, 2 streaming), parameters, amplitudes per vector, workspace
+        bytes, launches, entries of the restricted Hamiltonian (path 1), HIP-event times of the phases in microseconds (path 1: the copy of
+        theta to the device with the one launch, the copy back, 0; path 2: tangents and H images, the backward walk, the copy back), kernel form
+        (0 streaming, 1 compact with its tables staged in LDS, 2 compact with the tables read from global memory), the dynamic LDS bytes of
+        the launch, and ``asymmetry`` = max |M - M^T| of the raw rows"""
+        out = (ctypes.c_int64 * 11)()
+        self._ck(self._L.ovqe_hessian_info(self._h, out, 11))
+        keys = ("path", "K", "amplitudes", "workspace_bytes", "launches", "entries", "phase0_us", "phase1_us", "phase2_us", "form", "lds_bytes")
+        info = dict(zip(keys, [int(v) for v in out]))
+        info["asymmetry"] = float(getattr(self, "_hessian_asymmetry", 0.0))
+        return info
+
     # -- excited states by subspace expansion (ovqe_subspace_matrices, csrc/subspace_host.inc) ----------------------------------
     def _pack_pool_with_constants(self, ops):
         """CSR form of a list of operators, an operator's ``constant_coeff`` as a term on the identity string (x = z = 0); cached

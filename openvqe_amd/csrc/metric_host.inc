@@ -50,14 +50,59 @@ int metric_compact(ovqe_handle h, MetricDev &M) {
 }
 
 // one op of the sequential program on psi and the live tangents (columns [0, ncols))
-int metric_sweep(ovqe_handle h, MetricDev &M, const metric::Store &st, int ncols, const MetricSweep &S, int64_t *launches) {
+int metric_sweep(ovqe_handle h, void *store, const metric::Store &st, int ncols, const MetricSweep &S, int64_t *launches) {
     const uint64_t nwork = S.kind == MS_DIAG ? h->namps : h->namps >> 1;
     if (nwork == 0) return OVQE_OK;
     const unsigned gx = (unsigned)std::min<uint64_t>((nwork + 3) / 4, 65535u);
     const unsigned gy = (unsigned)((ncols + 63) / 64);
-    hipLaunchKernelGGL(k_metric_sweep, dim3(gx, gy), dim3(256), 0, h->stream, (v2d *)M.d_store.p, nwork, st.wpad, ncols, S);
+    hipLaunchKernelGGL(k_metric_sweep, dim3(gx, gy), dim3(256), 0, h->stream, (v2d *)store, nwork, st.wpad, ncols, S);
     HIPC(h, hipGetLastError());
     ++*launches;
+    return OVQE_OK;
+}
+
+// the streaming tangent stage: the sequential program once, every op on psi and the live tangents in one launch; behind a parameterised
+// rotation its tangent takes coeff (-i P) psi.  O(K R) sweeps of the register.  `store` is zeroed by the caller; `who` names the entry point in an error text.
+int metric_stream_tangents(ovqe_handle h, void *store, const metric::Store &st, const double *theta, int64_t *launches_out,
+                           const char *who = "ovqe_metric_tensor") {
+    int rc = OVQE_OK;
+    int64_t launches = *launches_out;
+    hipLaunchKernelGGL(k_metric_seed, dim3(1), dim3(64), 0, h->stream, (v2d *)store, h->hf, st.wpad);
+    HIPC(h, hipGetLastError());
+    int live = 1;   // columns in use: psi and the tangents of the parameters met so far
+    const unsigned ab = (unsigned)std::min<uint64_t>((h->namps + 255) / 256, 65535u);
+    for (const SmallOp &op : h->ops) {
+        MetricSweep sw = {};
+        sw.x = op.x;
+        sw.pivot = op.x ? 63 - __builtin_clzll(op.x) : 0;
+        if (op.kind == OP_PAIR || op.kind == OP_DIAG) {
+            for (int r = op.first; r < op.first + op.count; ++r) {
+                const SmallRot &sr = h->rots[r];
+                const double phi = sr.phi0 + (sr.pidx >= 0 ? sr.coeff * theta[sr.pidx] : 0.0);
+                sw.kind = op.x ? MS_ROT : MS_DIAG;
+                sw.z = sr.z;
+                sw.ny = sr.ny & 3;
+                sw.c = std::cos(phi);
+                sw.s = std::sin(phi);
+                if ((rc = metric_sweep(h, store, st, live, sw, &launches))) return rc;
+                if (sr.pidx < 0 || sr.coeff == 0.0) continue;
+                live = std::max(live, sr.pidx + 2);
+                hipLaunchKernelGGL(k_metric_add, dim3(ab), dim3(256), 0, h->stream, (v2d *)store, h->namps, st.wpad, sr.pidx + 1, op.x, sr.z,
+                                   sr.ny & 3, sr.coeff);
+                HIPC(h, hipGetLastError());
+                ++launches;
+            }
+            continue;
+        }
+        if (op.kind == OP_X) sw.kind = MS_X;
+        else if (op.kind == OP_H) sw.kind = MS_H;
+        else if (op.kind == OP_CNOT) {
+            sw.kind = MS_CNOT;
+            sw.ctrl = op.first;
+        } else return fail(h, OVQE_ERR_INVALID, std::string(who) + ": internal: unexpected op in the sequential program");
+        if ((rc = metric_sweep(h, store, st, live, sw, &launches))) return rc;
+    }
+    *launches_out = launches;
     return OVQE_OK;
 }
 
@@ -135,43 +180,7 @@ int run_metric(ovqe_handle h, const double *theta, double *out) {
         HIPC(h, hipGetLastError());
         launches = 1;
     } else {
-        // ---- streaming: the sequential program once, every op on psi and the live tangents in one launch; behind a parameterised
-        // rotation its tangent takes coeff (-i P) psi.  O(K R) sweeps of the register.
-        hipLaunchKernelGGL(k_metric_seed, dim3(1), dim3(64), 0, h->stream, (v2d *)M.d_store.p, h->hf, st.wpad);
-        HIPC(h, hipGetLastError());
-        int live = 1;   // columns in use: psi and the tangents of the parameters met so far
-        const unsigned ab = (unsigned)std::min<uint64_t>((h->namps + 255) / 256, 65535u);
-        for (const SmallOp &op : h->ops) {
-            MetricSweep sw = {};
-            sw.x = op.x;
-            sw.pivot = op.x ? 63 - __builtin_clzll(op.x) : 0;
-            if (op.kind == OP_PAIR || op.kind == OP_DIAG) {
-                for (int r = op.first; r < op.first + op.count; ++r) {
-                    const SmallRot &sr = h->rots[r];
-                    const double phi = sr.phi0 + (sr.pidx >= 0 ? sr.coeff * theta[sr.pidx] : 0.0);
-                    sw.kind = op.x ? MS_ROT : MS_DIAG;
-                    sw.z = sr.z;
-                    sw.ny = sr.ny & 3;
-                    sw.c = std::cos(phi);
-                    sw.s = std::sin(phi);
-                    if ((rc = metric_sweep(h, M, st, live, sw, &launches))) return rc;
-                    if (sr.pidx < 0 || sr.coeff == 0.0) continue;
-                    live = std::max(live, sr.pidx + 2);
-                    hipLaunchKernelGGL(k_metric_add, dim3(ab), dim3(256), 0, h->stream, (v2d *)M.d_store.p, h->namps, st.wpad, sr.pidx + 1, op.x, sr.z,
-                                       sr.ny & 3, sr.coeff);
-                    HIPC(h, hipGetLastError());
-                    ++launches;
-                }
-                continue;
-            }
-            if (op.kind == OP_X) sw.kind = MS_X;
-            else if (op.kind == OP_H) sw.kind = MS_H;
-            else if (op.kind == OP_CNOT) {
-                sw.kind = MS_CNOT;
-                sw.ctrl = op.first;
-            } else return fail(h, OVQE_ERR_INVALID, "ovqe_metric_tensor: internal: unexpected op in the sequential program");
-            if ((rc = metric_sweep(h, M, st, live, sw, &launches))) return rc;
-        }
+        if ((rc = metric_stream_tangents(h, M.d_store.p, st, theta, &launches))) return rc;
     }
     HIPC(h, hipEventRecord(M.ev[1], h->stream));
     // ---- Gram matrix of the store's columns: the density matrices' kernels on the index-major store

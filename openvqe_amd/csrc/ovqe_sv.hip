@@ -11,7 +11,8 @@
 //   rdm_host.inc     density matrices of the resident state: census, shadows, row list, rows, Gram    (sv_rdm_host.hpp; kernels: sv_rdm.hpp)
 //   metric_host.inc  Fubini-Study metric of the ansatz state: tangent store, compact / streaming tangents, Gram    (sv_metric_host.hpp; kernels: sv_sparse.hpp, sv_metric.hpp)
 //   subspace_host.inc  subspace-expansion matrices around the resident state: rows, expansion vectors, sigma = H Phi, Gram    (sv_subspace_host.hpp; kernels: sv_subspace.hpp, sv_rdm.hpp)
-//   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc / abi_rdm.inc / abi_metric.inc / abi_subspace.inc   extern "C" entry points by family (include/ovqe_sv.h)
+//   hessian_host.inc  exact energy Hessian: restricted Hamiltonian on the metric's compact program, one launch; column stores and the backward walk    (sv_hessian_host.hpp; kernels: sv_sparse.hpp, sv_hessian.hpp)
+//   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc / abi_rdm.inc / abi_metric.inc / abi_subspace.inc / abi_hessian.inc   extern "C" entry points by family (include/ovqe_sv.h)
 //   cross_host.inc   planned Pauli sums on a shard of the partitioned register, ovqe_xsum_*          (sv_cross_host.hpp; kernels: sv_cross.hpp)
 //   pool_host.inc    planned ADAPT pool screen on a shard, ovqe_xpool_*                              (sv_pool_host.hpp; kernels: sv_pool.hpp)
 // sv_cover_host.hpp (host-only) holds the table records planners and kernels share and the one cover rule, grow_tile_set(), that
@@ -48,6 +49,8 @@
 #include "sv_lanczos_host.hpp"
 #include "sv_rdm.hpp"
 #include "sv_metric.hpp"
+#include "sv_hessian_host.hpp"
+#include "sv_hessian.hpp"
 #include "sv_measure.hpp"
 #include "sv_subspace.hpp"
 #include <hipcub/hipcub.hpp>
@@ -289,6 +292,7 @@ struct SectorEngine {
 struct RdmDev;   // rdm_host.inc
 struct MetricDev;   // metric_host.inc
 struct SubspaceDev; // subspace_host.inc
+struct HessianDev;  // hessian_host.inc
 struct MeasureDev;   // measure_host.inc
 
 }  // namespace
@@ -515,6 +519,7 @@ struct ovqe_sv {
     MeasureDev *measure = nullptr;   // scratch, plan and figures of the finite-shot measurements (first call)
     SubspaceDev *subspace = nullptr; // buffers and figures of ovqe_subspace_matrices (first call)
     int opt_subspace_workspace_mb = 0; // cap of its store in MB (0: 60 % of the free device memory)
+    HessianDev *hessian = nullptr;   // plan, buffers and figures of ovqe_energy_hessian (first call; its workspace cap is metric_workspace_mb)
 };
 
 namespace {
@@ -1161,6 +1166,8 @@ void push_rotation(ovqe_handle h, uint64_t x, uint64_t z, double coeff, double p
 
 #include "subspace_host.inc"
 
+#include "hessian_host.inc"
+
 int check_theta(ovqe_handle h, const double *theta, int32_t K) {
     if (!h->prog_set) return fail(h, OVQE_ERR_STATE, "no program set (ovqe_set_program / ovqe_set_gate_program)");
     if (K != h->K) return fail(h, OVQE_ERR_INVALID, "K does not match the program's parameter count");
@@ -1272,6 +1279,7 @@ int ovqe_destroy(ovqe_handle h) try {
     free_metric(h->metric);
     free_measure(h->measure);
     free_subspace(h->subspace);
+    free_hessian(h->hessian);
     h->kept_blocks.flush();
     if (h->h_rp) (void)hipHostFree(h->h_rp);
     if (h->h_result) (void)hipHostFree(h->h_result);
@@ -1579,6 +1587,8 @@ int ovqe_norm2(ovqe_handle h, double *out) try {
 #include "abi_measure.inc"
 
 #include "abi_subspace.inc"
+
+#include "abi_hessian.inc"
 
 // ---- measurement support ------------------------------------------------------------------------
 int ovqe_time_pauli_rotation(ovqe_handle h, uint64_t x, uint64_t z, double phi, int warmup, int reps, double *avg_ms) try {

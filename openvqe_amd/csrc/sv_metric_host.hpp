@@ -53,6 +53,7 @@ struct Compact {
     std::vector<uint32_t> pairs;
     std::vector<TabEntry> tab;
     std::vector<int32_t> first_op;   // [K]: the first op with a table entry of parameter k (ops.size(): none — a zero tangent)
+    std::vector<uint64_t> support;   // [m]: the basis state behind every compact index (sv_hessian_host.hpp restricts the Hamiltonian to it)
 };
 
 inline int parity64(uint64_t v) { return __builtin_popcountll(v) & 1; }
@@ -126,6 +127,7 @@ inline bool build_compact(uint64_t hf, const std::vector<InOp> &ops, const std::
     }
     C.m = (int)S.size();
     C.hf = 0;
+    C.support = S;
     C.first_op.assign((size_t)std::max(K, 0), (int32_t)C.ops.size());
     for (int o = (int)C.ops.size() - 1; o >= 0; --o) {
         const int ntab = (o + 1 < (int)C.ops.size() ? C.ops[(size_t)o + 1].tab0 : (int)C.tab.size()) - C.ops[(size_t)o].tab0;

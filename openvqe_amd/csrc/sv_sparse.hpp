@@ -1025,4 +1025,224 @@ __global__ __launch_bounds__(64) void k_sparse_metric(SpMetricArgs A, const doub
     }
 }
 
+// ---- exact energy Hessian on the compact support (ovqe_energy_hessian, path 1) ------------------------------------------------------------
+// All K x K second derivatives of one parameter vector in ONE launch, forward over reverse (the derivation: sv_hessian_host.hpp).  Workgroup
+// (one wave) b owns the direction b: it carries psi and the tangent t = d psi / d theta_b forward exactly as k_sparse_metric does, forms
+// lambda = H psi and mu = H t in one pass over the restricted Hamiltonian's entries (the LDS atomics of k_sparse_grad's lambda loop,
+// doubled), and walks the program backwards on the four vectors: per pair the gradient's weight g and its derivative
+//   g' = mu_i psi_j - mu_j psi_i + lambda_i t_j - lambda_j t_i                                 (on the states before un-applying)
+// go to w[e] / wd[e] with the pair's sign, the four vectors are rotated back, and an entry of parameter b injects -coeff_e J of the
+// un-applied psi and lambda into t and mu.  Below first_op[b] the tangent is exactly zero and is dropped: psi, lambda and mu remain.
+// Row b of the raw matrix is sum over the entries of parameter k of 2 coeff_e wd[e]; the workgroup of direction 0 accumulates w as well
+// and writes the energy and the gradient.  The program, its table and first_op are the metric's (sv_metric_host.hpp), the entries are built
+// on THAT program's compact indices.  The order of the atomic additions is not fixed: the result reproduces to rounding, not to the bit.
+struct SpHessArgs {
+    int m, mpad, K, nops, ntab, npairs, nent, hf;
+    double constant;
+};
+struct SpHessLds { size_t t, lam, mu, cs, dk, w, wd, gk, ops, pairs, bytes; };   // psi ([mpad]) is at 0
+__host__ __device__ inline SpHessLds sp_hessian_lds(const SpHessArgs &A, bool stage) {
+    const size_t v = (size_t)A.mpad * sizeof(double);                                       // psi, t, lambda, mu: [mpad] each
+    const size_t cs = 4 * v;                                                                // [ntab]
+    const size_t dk = cs + (size_t)A.ntab * sizeof(double2);                                // [ntab]: coeff_e of parameter b's entries, else 0
+    const size_t w = dk + (size_t)A.ntab * sizeof(double);                                  // [ntab]
+    const size_t wd = w + (size_t)A.ntab * sizeof(double);                                  // [ntab]
+    const size_t gk = wd + (size_t)A.ntab * sizeof(double);                                 // [K]
+    const size_t ops = (gk + (size_t)A.K * sizeof(double) + 15) & ~(size_t)15;              // [nops]   (stage)
+    const size_t pairs = ops + (size_t)A.nops * sizeof(metric::Op);                         // [npairs] (stage)
+    return {v, 2 * v, 3 * v, cs, dk, w, wd, gk, ops, pairs, stage ? pairs + (size_t)A.npairs * sizeof(uint32_t) : ops};
+}
+template <bool STAGE>
+__global__ __launch_bounds__(64) void k_sparse_hessian(SpHessArgs A, const double *__restrict__ theta, const metric::TabEntry *__restrict__ tab,
+                                                       const metric::Op *__restrict__ ops, const uint32_t *__restrict__ pairs,
+                                                       const int32_t *__restrict__ first_op, const SpEntry *__restrict__ entries,
+                                                       double *__restrict__ rows, double *__restrict__ energy, double *__restrict__ grad) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const SpHessLds L = sp_hessian_lds(A, STAGE);
+    double *psi = reinterpret_cast<double *>(smem);
+    double *t = reinterpret_cast<double *>(smem + L.t);
+    double *lam = reinterpret_cast<double *>(smem + L.lam);
+    double *mu = reinterpret_cast<double *>(smem + L.mu);
+    double2 *cs = reinterpret_cast<double2 *>(smem + L.cs);
+    double *dk = reinterpret_cast<double *>(smem + L.dk);
+    double *w = reinterpret_cast<double *>(smem + L.w);
+    double *wd = reinterpret_cast<double *>(smem + L.wd);
+    double *gk = reinterpret_cast<double *>(smem + L.gk);
+    metric::Op *lops = reinterpret_cast<metric::Op *>(smem + L.ops);
+    uint32_t *lpairs = reinterpret_cast<uint32_t *>(smem + L.pairs);
+    const int lane = threadIdx.x;
+    if constexpr (STAGE) {
+        for (int i = lane; i < A.nops; i += 64) lops[i] = ops[i];
+        for (int i = lane; i < A.npairs; i += 64) lpairs[i] = pairs[i];
+    }
+    const metric::Op *opv = STAGE ? lops : ops;
+    const uint32_t *pv = STAGE ? lpairs : pairs;
+    for (int b = blockIdx.x; b < A.K; b += gridDim.x) {
+        const bool first = b == 0;   // (uniform: this direction's workgroup also answers E and the gradient)
+        for (int i = lane; i < A.mpad; i += 64) {
+            psi[i] = i == A.hf ? 1.0 : 0.0;
+            t[i] = 0.0;
+            lam[i] = 0.0;
+            mu[i] = 0.0;
+        }
+        for (int e = lane; e < A.ntab; e += 64) {
+            const metric::TabEntry te = tab[e];
+            double sn, c;
+            sincos(te.phi0 + (te.pidx >= 0 ? te.coeff * theta[te.pidx] : 0.0), &sn, &c);
+            cs[e] = make_double2(c, sn);
+            dk[e] = te.pidx == b ? te.coeff : 0.0;
+            w[e] = 0.0;
+            wd[e] = 0.0;
+        }
+        for (int k = lane; k < A.K; k += 64) gk[k] = 0.0;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        int o1 = first_op[b];
+        o1 = __builtin_amdgcn_readfirstlane(o1 < A.nops ? o1 : A.nops);
+        // ---- forward, as k_sparse_metric: psi alone, then psi and the tangent
+        for (int o = 0; o < o1; ++o) {
+            metric::Op op = opv[o];
+            op.first = __builtin_amdgcn_readfirstlane(op.first);
+            op.npairs = __builtin_amdgcn_readfirstlane(op.npairs);
+            op.tab0 = __builtin_amdgcn_readfirstlane(op.tab0);
+            for (int pe = lane; pe < op.npairs; pe += 64) {
+                const uint32_t pw = pv[op.first + pe];
+                const uint32_t ci = pw & 0xfffu, cj = (pw >> 12) & 0xfffu;
+                const double2 r = cs[op.tab0 + (int)(pw >> 25)];
+                const double sn = (pw & (1u << 24)) ? -r.y : r.y;
+                const double u = psi[ci], v = psi[cj];
+                psi[ci] = r.x * u + sn * v;
+                psi[cj] = r.x * v - sn * u;
+            }
+            asm volatile("" ::: "memory");   // a wave's DS instructions execute in issue order (see k_sparse_vqe)
+        }
+        for (int o = o1; o < A.nops; ++o) {
+            metric::Op op = opv[o];
+            op.first = __builtin_amdgcn_readfirstlane(op.first);
+            op.npairs = __builtin_amdgcn_readfirstlane(op.npairs);
+            op.tab0 = __builtin_amdgcn_readfirstlane(op.tab0);
+            for (int pe = lane; pe < op.npairs; pe += 64) {
+                const uint32_t pw = pv[op.first + pe];
+                const uint32_t ci = pw & 0xfffu, cj = (pw >> 12) & 0xfffu;
+                const int e = op.tab0 + (int)(pw >> 25);
+                const double2 r = cs[e];
+                const bool neg = (pw & (1u << 24)) != 0u;
+                const double sn = neg ? -r.y : r.y;
+                const double d = neg ? -dk[e] : dk[e];
+                const double u = psi[ci], v = psi[cj], tu = t[ci], tv = t[cj];
+                const double u1 = r.x * u + sn * v, v1 = r.x * v - sn * u;
+                psi[ci] = u1;
+                psi[cj] = v1;
+                t[ci] = r.x * tu + sn * tv + d * v1;
+                t[cj] = r.x * tv - sn * tu - d * u1;
+            }
+            asm volatile("" ::: "memory");
+        }
+        // ---- lambda = H psi and mu = H t in one pass over the entries, E = <psi|lambda>
+        double acc = 0.0;
+#pragma unroll 2
+        for (int e = lane; e < A.nent; e += 64) {
+            const SpEntry en = entries[e];
+            const uint32_t ci = en.ij & 0xfffu, cj = (en.ij >> 12) & 0xfffu;
+            const double ai = psi[ci], aj = psi[cj], ti = t[ci], tj = t[cj];
+            acc += en.c * ai * aj;
+            if (ci == cj) {
+                __hip_atomic_fetch_add(&lam[ci], en.c * ai, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(&mu[ci], en.c * ti, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            } else {   // c = 2 H_ij, the pair counted once
+                const double hc = 0.5 * en.c;
+                __hip_atomic_fetch_add(&lam[ci], hc * aj, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(&lam[cj], hc * ai, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(&mu[ci], hc * tj, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(&mu[cj], hc * ti, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+        const double etot = wave_sum(acc);
+        if (first && lane == 0) energy[0] = etot + A.constant;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // ---- backward on the four vectors, with the injections and both weights
+        for (int o = A.nops - 1; o >= o1; --o) {
+            metric::Op op = opv[o];
+            op.first = __builtin_amdgcn_readfirstlane(op.first);
+            op.npairs = __builtin_amdgcn_readfirstlane(op.npairs);
+            op.tab0 = __builtin_amdgcn_readfirstlane(op.tab0);
+            for (int pe = lane; pe < op.npairs; pe += 64) {
+                const uint32_t pw = pv[op.first + pe];
+                const uint32_t ci = pw & 0xfffu, cj = (pw >> 12) & 0xfffu;
+                const int e = op.tab0 + (int)(pw >> 25);
+                const double2 r = cs[e];
+                const bool neg = (pw & (1u << 24)) != 0u;
+                const double sn = neg ? -r.y : r.y;
+                const double d = neg ? -dk[e] : dk[e];
+                const double u1 = psi[ci], v1 = psi[cj], lu = lam[ci], lv = lam[cj];
+                const double tu = t[ci], tv = t[cj], mu1 = mu[ci], mv1 = mu[cj];
+                const double gd = mu1 * v1 - mv1 * u1 + lu * tv - lv * tu;
+                __hip_atomic_fetch_add(&wd[e], neg ? -gd : gd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (first) {
+                    const double g = lu * v1 - lv * u1;
+                    __hip_atomic_fetch_add(&w[e], neg ? -g : g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                const double u0 = r.x * u1 - sn * v1, v0 = r.x * v1 + sn * u1;
+                const double lu0 = r.x * lu - sn * lv, lv0 = r.x * lv + sn * lu;
+                psi[ci] = u0;
+                psi[cj] = v0;
+                lam[ci] = lu0;
+                lam[cj] = lv0;
+                t[ci] = r.x * tu - sn * tv - d * v0;
+                t[cj] = r.x * tv + sn * tu + d * u0;
+                mu[ci] = r.x * mu1 - sn * mv1 - d * lv0;
+                mu[cj] = r.x * mv1 + sn * mu1 + d * lu0;
+            }
+            asm volatile("" ::: "memory");
+        }
+        for (int o = o1 - 1; o >= 0; --o) {   // the tangent is zero from here down: psi, lambda and mu
+            metric::Op op = opv[o];
+            op.first = __builtin_amdgcn_readfirstlane(op.first);
+            op.npairs = __builtin_amdgcn_readfirstlane(op.npairs);
+            op.tab0 = __builtin_amdgcn_readfirstlane(op.tab0);
+            for (int pe = lane; pe < op.npairs; pe += 64) {
+                const uint32_t pw = pv[op.first + pe];
+                const uint32_t ci = pw & 0xfffu, cj = (pw >> 12) & 0xfffu;
+                const int e = op.tab0 + (int)(pw >> 25);
+                const double2 r = cs[e];
+                const bool neg = (pw & (1u << 24)) != 0u;
+                const double sn = neg ? -r.y : r.y;
+                const double u1 = psi[ci], v1 = psi[cj], lu = lam[ci], lv = lam[cj], mu1 = mu[ci], mv1 = mu[cj];
+                const double gd = mu1 * v1 - mv1 * u1;
+                __hip_atomic_fetch_add(&wd[e], neg ? -gd : gd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (first) {
+                    const double g = lu * v1 - lv * u1;
+                    __hip_atomic_fetch_add(&w[e], neg ? -g : g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                psi[ci] = r.x * u1 - sn * v1;
+                psi[cj] = r.x * v1 + sn * u1;
+                lam[ci] = r.x * lu - sn * lv;
+                lam[cj] = r.x * lv + sn * lu;
+                mu[ci] = r.x * mu1 - sn * mv1;
+                mu[cj] = r.x * mv1 + sn * mu1;
+            }
+            asm volatile("" ::: "memory");
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // ---- row b: sum over the entries of parameter k of 2 coeff_e wd[e]
+        for (int e = lane; e < A.ntab; e += 64) {
+            const metric::TabEntry te = tab[e];
+            if (te.pidx >= 0) __hip_atomic_fetch_add(&gk[te.pidx], 2.0 * te.coeff * wd[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        for (int k = lane; k < A.K; k += 64) rows[(size_t)b * (size_t)A.K + (size_t)k] = gk[k];
+        if (first) {   // ... and the gradient, through the same slots
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            for (int k = lane; k < A.K; k += 64) gk[k] = 0.0;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            for (int e = lane; e < A.ntab; e += 64) {
+                const metric::TabEntry te = tab[e];
+                if (te.pidx >= 0) __hip_atomic_fetch_add(&gk[te.pidx], 2.0 * te.coeff * w[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            for (int k = lane; k < A.K; k += 64) grad[k] = gk[k];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+}
+
 }  // namespace ovqe

@@ -79,6 +79,11 @@ class _Evaluator:
         self._activate()
         return self.sv.metric_tensor(np.asarray(theta, dtype=np.float64)[: self.n_params])
 
+    def energy_hessian(self, theta):
+        """(E, dE/dtheta, d2E/dtheta2) at ``theta`` in one device call (ovqe_energy_hessian)"""
+        self._activate()
+        return self.sv.energy_hessian(np.asarray(theta, dtype=np.float64)[: self.n_params])
+
     def state(self, theta):
         self._activate()
         self.sv.prepare_state(np.asarray(theta, dtype=np.float64))

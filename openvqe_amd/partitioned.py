@@ -249,6 +249,10 @@ class PartitionedStatevector:
         raise NotImplementedError("the Fubini-Study metric is computed on one device (ovqe_metric_tensor keeps K tangent vectors next to "
                                   "the state): not available on the partitioned register")
 
+    def energy_hessian(self, *args, **kwargs):
+        raise NotImplementedError("the energy Hessian is computed on one device (ovqe_energy_hessian keeps K tangent vectors and their "
+                                  "images under H next to the state): not available on the partitioned register")
+
     def subspace_matrices(self, *args, **kwargs):
         raise NotImplementedError("subspace-expansion matrices are computed on one device (ovqe_subspace_matrices keeps the expansion "
                                   "vectors next to the state): not available on the partitioned register")

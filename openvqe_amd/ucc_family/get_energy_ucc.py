@@ -4,7 +4,7 @@ reference's; the simulation runs in libovqe_sv instead of myQLM)."""
 import numpy as np
 import scipy.optimize
 
-from ..common_files import bfgs, natural_gradient
+from ..common_files import bfgs, natural_gradient, newton
 
 from ..common_files.circuit import count
 from ..evaluator import UCCEvaluator
@@ -21,6 +21,9 @@ class EnergyUCC:
     #: opt-in: natural-gradient descent (common_files/natural_gradient.py) instead of BFGS — exact gradient and the Fubini-Study metric
     #: of the ansatz state (ovqe_metric_tensor) per step; ``tolerance`` bounds the largest gradient component
     natural_gradient = False
+    #: opt-in: Newton trust-region steps (common_files/newton.py, scipy's trust-exact) instead of BFGS — energy, exact gradient and exact
+    #: Hessian of every iterate in one device call (ovqe_energy_hessian); ``tolerance`` bounds the gradient's 2-norm
+    newton = False
 
     def __init__(self):
         self._cache = {}
@@ -64,6 +67,18 @@ class EnergyUCC:
     def _minimize(self, hamiltonian_sp, ops, hf_init_sp, x0, energies, method, tolerance):
         fun = lambda theta: self.ucc_action(theta, hamiltonian_sp, ops, hf_init_sp, energies)  # noqa: E731
         jac = None
+        if self.newton:
+            n_params = min(len(ops), len(x0))
+            ev = self._evaluator(hamiltonian_sp, ops, hf_init_sp, n_params)
+
+            def fun_grad_hess(theta):   # (parameters beyond the operators are not applied: zero derivatives)
+                e, g, hs = ev.energy_hessian(theta)
+                energies.append(e)
+                full = np.zeros((len(theta), len(theta)))
+                full[:n_params, :n_params] = hs
+                return e, np.concatenate([g, np.zeros(len(theta) - n_params)]), full
+
+            return newton.minimize(fun_grad_hess, np.asarray(x0, dtype=float), tol=tolerance, maxiter=50000)
         if self.natural_gradient:
             n_params = min(len(ops), len(x0))
             ev = self._evaluator(hamiltonian_sp, ops, hf_init_sp, n_params)
