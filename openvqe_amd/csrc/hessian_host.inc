@@ -43,19 +43,12 @@ int hessian_plan(ovqe_handle h, HessianDev &D) {
     return OVQE_OK;
 }
 
-// the workspace behind its cap.  `fits`: the buffers already hold it all — under the automatic cap nothing is asked of the runtime then
+// the workspace behind its cap (workspace_cap, under the metric's option)
 int hessian_cap(ovqe_handle h, size_t need, size_t held, bool fits, const char *what) {
-    if (h->opt_metric_workspace_mb <= 0 && fits) return OVQE_OK;
-    size_t limit = (size_t)std::max(h->opt_metric_workspace_mb, 0) << 20;
-    if (h->opt_metric_workspace_mb <= 0) {   // automatic: 60 % of the free device memory (what the buffers hold already counts as free)
-        size_t free_b = 0, total_b = 0;
-        HIPC(h, hipMemGetInfo(&free_b, &total_b));
-        limit = free_b / 5 * 3 + held;
-    }
-    if (need > limit)
-        return fail(h, OVQE_ERR_ALLOC, std::string("ovqe_energy_hessian: ") + what + " need " + std::to_string(need) + " bytes, the cap is " +
-                                           std::to_string(limit) + " bytes (option metric_workspace_mb)");
-    return OVQE_OK;
+    return workspace_cap(h, h->opt_metric_workspace_mb, need, held, fits, [&](size_t limit) {
+        return std::string("ovqe_energy_hessian: ") + what + " need " + std::to_string(need) + " bytes, the cap is " + std::to_string(limit) +
+               " bytes (option metric_workspace_mb)";
+    });
 }
 
 // raw rows M -> (M + M^T) / 2, symmetric to the bit; returns max |M - M^T|
@@ -73,30 +66,19 @@ double hessian_symmetrise(const double *M, int K, double *hess) {
 int run_hessian_streaming(ovqe_handle h, HessianDev &D, const double *theta, double *energy, double *grad, double *hess, double *asymmetry);
 
 int run_hessian(ovqe_handle h, const double *theta, double *energy, double *grad, double *hess, double *asymmetry) {
-    static_assert(sizeof(hessian::Entry) == sizeof(SpEntry), "the kernel reads the plan's entries as SpEntry records");
     const int K = h->K;
     if (!h->hessian) h->hessian = new HessianDev();
     HessianDev &D = *h->hessian;
     std::fill(D.info, D.info + 11, 0);
-    for (hipEvent_t &e : D.ev)
-        if (!e) HIPC(h, hipEventCreate(&e));
-    int rc = OVQE_OK;
+    int rc = ensure_events(h, D.ev, 4);
+    if (rc) return rc;
     // ---- which form: the compact support when the program has one and the four vectors and the tables fit one workgroup's LDS
     int form = 0;
     SpHessArgs A = {};
     if (h->opt_force_path != 2) {
         if ((rc = hessian_plan(h, D))) return rc;
         if (D.plan_ok) {
-            const metric::Compact &C = D.prog->C;
-            A.m = C.m;
-            A.mpad = (C.m + 1) & ~1;
-            A.K = K;
-            A.nops = (int)C.ops.size();
-            A.ntab = (int)C.tab.size();
-            A.npairs = (int)C.pairs.size();
-            A.nent = (int)D.R.entries.size();
-            A.hf = C.hf;
-            A.constant = D.R.constant;
+            A = sp_hessian_args(D.prog->C, K, (int)D.R.entries.size(), D.R.constant);
             form = sp_hessian_lds(A, true).bytes <= LDS_WG_BUDGET ? 1 : sp_hessian_lds(A, false).bytes <= LDS_WG_BUDGET ? 2 : 0;
         }
     }
@@ -109,19 +91,12 @@ int run_hessian(ovqe_handle h, const double *theta, double *energy, double *grad
     const size_t lds = sp_hessian_lds(A, form == 1).bytes;
     const MetricDev &P = *D.prog;
     double *d_rows = (double *)D.d_out.p, *d_grad = d_rows + (size_t)K * K, *d_e = d_grad + K;
-    rc = lds_opt_in<&k_sparse_hessian<true>, &k_sparse_hessian<false>>(h, LDS_WG_MAX);
-    if (rc) return rc;
     HIPC(h, hipEventRecord(D.ev[0], h->stream));
     HIPC(h, hipMemcpyAsync(D.d_theta.p, theta, (size_t)K * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (form == 1)
-        hipLaunchKernelGGL((k_sparse_hessian<true>), dim3(K), dim3(64), lds, h->stream, A, (const double *)D.d_theta.p,
-                           (const metric::TabEntry *)P.d_tab.p, (const metric::Op *)P.d_ops.p, (const uint32_t *)P.d_pairs.p,
-                           (const int32_t *)P.d_first.p, (const SpEntry *)D.d_entries.p, d_rows, d_e, d_grad);
-    else
-        hipLaunchKernelGGL((k_sparse_hessian<false>), dim3(K), dim3(64), lds, h->stream, A, (const double *)D.d_theta.p,
-                           (const metric::TabEntry *)P.d_tab.p, (const metric::Op *)P.d_ops.p, (const uint32_t *)P.d_pairs.p,
-                           (const int32_t *)P.d_first.p, (const SpEntry *)D.d_entries.p, d_rows, d_e, d_grad);
-    HIPC(h, hipGetLastError());
+    rc = launch_staged<&k_sparse_hessian<true>, &k_sparse_hessian<false>>(
+        h, form == 1, (unsigned)K, lds, A, (const double *)D.d_theta.p, (const metric::TabEntry *)P.d_tab.p, (const metric::Op *)P.d_ops.p,
+        (const uint32_t *)P.d_pairs.p, (const int32_t *)P.d_first.p, (const SpEntry *)D.d_entries.p, d_rows, d_e, d_grad);
+    if (rc) return rc;
     HIPC(h, hipEventRecord(D.ev[1], h->stream));
     D.host_out.resize(nout);
     HIPC(h, hipMemcpyAsync(D.host_out.data(), D.d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
@@ -137,11 +112,8 @@ int run_hessian(ovqe_handle h, const double *theta, double *energy, double *grad
     D.info[3] = (int64_t)work;
     D.info[4] = 1;
     D.info[5] = A.nent;
-    for (int k = 0; k < 2; ++k) {   // [6] the copy of theta to the device and the launch, [7] the copy back; [8] stays 0: no third phase
-        float ms = 0.f;
-        HIPC(h, hipEventElapsedTime(&ms, D.ev[k], D.ev[k + 1]));
-        D.info[6 + k] = (int64_t)(1e3 * ms);
-    }
+    // [6] the copy of theta to the device and the launch, [7] the copy back; [8] stays 0: no third phase
+    if ((rc = phases_us(h, D.ev, 2, D.info + 6))) return rc;
     D.info[9] = form;
     D.info[10] = (int64_t)lds;
     return OVQE_OK;
@@ -203,9 +175,8 @@ int run_hessian_streaming(ovqe_handle h, HessianDev &D, const double *theta, dou
     const unsigned ab = (unsigned)std::min<uint64_t>((h->namps + 255) / 256, 65535u);
     for (int oi = (int)h->ops.size() - 1; oi >= 0; --oi) {
         const SmallOp &op = h->ops[(size_t)oi];
-        MetricSweep sw = {};
-        sw.x = op.x;
-        sw.pivot = op.x ? 63 - __builtin_clzll(op.x) : 0;
+        MetricSweep sw;   // (X, H and CNOT are their own inverses)
+        if (!metric_sweep_of(op, &sw)) return fail(h, OVQE_ERR_INVALID, "ovqe_energy_hessian: internal: unexpected op in the sequential program");
         if (op.kind == OP_PAIR || op.kind == OP_DIAG) {
             for (int r = op.first + op.count - 1; r >= op.first; --r) {
                 const SmallRot &sr = h->rots[(size_t)r];
@@ -232,12 +203,6 @@ int run_hessian_streaming(ovqe_handle h, HessianDev &D, const double *theta, dou
             }
             continue;
         }
-        if (op.kind == OP_X) sw.kind = MS_X;   // X, H and CNOT are their own inverses
-        else if (op.kind == OP_H) sw.kind = MS_H;
-        else if (op.kind == OP_CNOT) {
-            sw.kind = MS_CNOT;
-            sw.ctrl = op.first;
-        } else return fail(h, OVQE_ERR_INVALID, "ovqe_energy_hessian: internal: unexpected op in the sequential program");
         if ((rc = metric_sweep(h, Av, st, ncols, sw, &launches))) return rc;
         if ((rc = metric_sweep(h, Sv, st, ncols, sw, &launches))) return rc;
     }
@@ -265,11 +230,7 @@ int run_hessian_streaming(ovqe_handle h, HessianDev &D, const double *theta, dou
     D.info[3] = (int64_t)work;
     D.info[4] = launches;
     D.info[5] = 0;
-    for (int k = 0; k < 3; ++k) {
-        float ms = 0.f;
-        HIPC(h, hipEventElapsedTime(&ms, D.ev[k], D.ev[k + 1]));
-        D.info[6 + k] = (int64_t)(1e3 * ms);
-    }
+    if ((rc = phases_us(h, D.ev, 3, D.info + 6))) return rc;
     D.info[9] = 0;
     D.info[10] = 0;
     return OVQE_OK;

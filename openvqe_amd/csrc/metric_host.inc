@@ -61,6 +61,22 @@ int metric_sweep(ovqe_handle h, void *store, const metric::Store &st, int ncols,
     return OVQE_OK;
 }
 
+// the sweep of a literal op of the sequential program: x, the pivot, and for X / H / CNOT the kind (a rotation's kind, masks and angle
+// are the caller's, rotation by rotation).  false: an op the sequential program cannot hold
+bool metric_sweep_of(const SmallOp &op, MetricSweep *out) {
+    MetricSweep sw = {};
+    sw.x = op.x;
+    sw.pivot = op.x ? 63 - __builtin_clzll(op.x) : 0;
+    if (op.kind == OP_X) sw.kind = MS_X;
+    else if (op.kind == OP_H) sw.kind = MS_H;
+    else if (op.kind == OP_CNOT) {
+        sw.kind = MS_CNOT;
+        sw.ctrl = op.first;
+    } else if (op.kind != OP_PAIR && op.kind != OP_DIAG) return false;
+    *out = sw;
+    return true;
+}
+
 // the streaming tangent stage: the sequential program once, every op on psi and the live tangents in one launch; behind a parameterised
 // rotation its tangent takes coeff (-i P) psi.  O(K R) sweeps of the register.  `store` is zeroed by the caller; `who` names the entry point in an error text.
 int metric_stream_tangents(ovqe_handle h, void *store, const metric::Store &st, const double *theta, int64_t *launches_out,
@@ -72,9 +88,8 @@ int metric_stream_tangents(ovqe_handle h, void *store, const metric::Store &st, 
     int live = 1;   // columns in use: psi and the tangents of the parameters met so far
     const unsigned ab = (unsigned)std::min<uint64_t>((h->namps + 255) / 256, 65535u);
     for (const SmallOp &op : h->ops) {
-        MetricSweep sw = {};
-        sw.x = op.x;
-        sw.pivot = op.x ? 63 - __builtin_clzll(op.x) : 0;
+        MetricSweep sw;
+        if (!metric_sweep_of(op, &sw)) return fail(h, OVQE_ERR_INVALID, std::string(who) + ": internal: unexpected op in the sequential program");
         if (op.kind == OP_PAIR || op.kind == OP_DIAG) {
             for (int r = op.first; r < op.first + op.count; ++r) {
                 const SmallRot &sr = h->rots[r];
@@ -94,12 +109,6 @@ int metric_stream_tangents(ovqe_handle h, void *store, const metric::Store &st, 
             }
             continue;
         }
-        if (op.kind == OP_X) sw.kind = MS_X;
-        else if (op.kind == OP_H) sw.kind = MS_H;
-        else if (op.kind == OP_CNOT) {
-            sw.kind = MS_CNOT;
-            sw.ctrl = op.first;
-        } else return fail(h, OVQE_ERR_INVALID, std::string(who) + ": internal: unexpected op in the sequential program");
         if ((rc = metric_sweep(h, store, st, live, sw, &launches))) return rc;
     }
     *launches_out = launches;
@@ -112,45 +121,27 @@ int run_metric(ovqe_handle h, const double *theta, double *out) {
     MetricDev &M = *h->metric;
     std::fill(M.info, M.info + 11, 0);
     if (K == 0) return OVQE_OK;
-    if (h->num_cus <= 0) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus <= 0) cus = 256;
-        h->num_cus = cus;
-    }
-    for (hipEvent_t &e : M.ev)
-        if (!e) HIPC(h, hipEventCreate(&e));
-    int rc = OVQE_OK;
+    handle_num_cus(h);
+    int rc = ensure_events(h, M.ev, 4);
+    if (rc) return rc;
     // ---- which path: the compact support when the program has one and psi, one tangent and the tables fit one workgroup's LDS
     bool compact = false, stage = false;
     SpMetricArgs A = {};
     if (h->opt_force_path != 2) {
         if ((rc = metric_compact(h, M))) return rc;
         if (M.compact_ok) {
-            A.m = M.C.m;
-            A.mpad = (M.C.m + 1) & ~1;
-            A.K = K;
-            A.nops = (int)M.C.ops.size();
-            A.ntab = (int)M.C.tab.size();
-            A.npairs = (int)M.C.pairs.size();
-            A.hf = M.C.hf;
+            A = sp_metric_args(M.C, K);
             compact = sp_metric_lds(A, false).bytes <= LDS_WG_BUDGET;
             stage = sp_metric_lds(A, true).bytes <= LDS_WG_BUDGET;
         }
     }
     const metric::Store st = metric::store_layout(compact ? (int64_t)M.C.m : (int64_t)h->namps, K, compact);
     // ---- the tangent store behind its cap
-    if (h->opt_metric_workspace_mb > 0 || M.d_store.cap < st.bytes) {
-        size_t limit = (size_t)std::max(h->opt_metric_workspace_mb, 0) << 20;
-        if (h->opt_metric_workspace_mb <= 0) {   // automatic: 60 % of the free device memory (what the store holds already counts as free)
-            size_t free_b = 0, total_b = 0;
-            HIPC(h, hipMemGetInfo(&free_b, &total_b));
-            limit = free_b / 5 * 3 + M.d_store.cap;
-        }
-        if (st.bytes > limit)
-            return fail(h, OVQE_ERR_ALLOC, "ovqe_metric_tensor: the tangent store needs " + std::to_string(st.bytes) + " bytes (" +
-                                               std::to_string(st.rows) + " amplitudes x " + std::to_string(st.wpad) + " columns), the cap is " +
-                                               std::to_string(limit) + " bytes (option metric_workspace_mb)");
-    }
+    rc = workspace_cap(h, h->opt_metric_workspace_mb, st.bytes, M.d_store.cap, M.d_store.cap >= st.bytes, [&](size_t limit) {
+        return "ovqe_metric_tensor: the tangent store needs " + std::to_string(st.bytes) + " bytes (" + std::to_string(st.rows) +
+               " amplitudes x " + std::to_string(st.wpad) + " columns), the cap is " + std::to_string(limit) + " bytes (option metric_workspace_mb)";
+    });
+    if (rc) return rc;
     const rdm::Schedule S = metric::gram_plan(st, h->num_cus);
     const size_t slab_bytes = S.slab_elems * S.elem_bytes;
     const int64_t W = st.width;
@@ -167,17 +158,10 @@ int run_metric(ovqe_handle h, const double *theta, double *out) {
         A.wpad = st.wpad;
         tangent_lds = sp_metric_lds(A, stage).bytes;
         HIPC(h, hipMemcpyAsync(M.d_theta.p, theta, (size_t)K * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        rc = lds_opt_in<&k_sparse_metric<true>, &k_sparse_metric<false>>(h, LDS_WG_MAX);
+        rc = launch_staged<&k_sparse_metric<true>, &k_sparse_metric<false>>(
+            h, stage, (unsigned)K, tangent_lds, A, (const double *)M.d_theta.p, (const metric::TabEntry *)M.d_tab.p, (const metric::Op *)M.d_ops.p,
+            (const uint32_t *)M.d_pairs.p, (const int32_t *)M.d_first.p, (double *)M.d_store.p);
         if (rc) return rc;
-        if (stage)
-            hipLaunchKernelGGL((k_sparse_metric<true>), dim3(K), dim3(64), tangent_lds, h->stream, A, (const double *)M.d_theta.p,
-                               (const metric::TabEntry *)M.d_tab.p, (const metric::Op *)M.d_ops.p, (const uint32_t *)M.d_pairs.p,
-                               (const int32_t *)M.d_first.p, (double *)M.d_store.p);
-        else
-            hipLaunchKernelGGL((k_sparse_metric<false>), dim3(K), dim3(64), tangent_lds, h->stream, A, (const double *)M.d_theta.p,
-                               (const metric::TabEntry *)M.d_tab.p, (const metric::Op *)M.d_ops.p, (const uint32_t *)M.d_pairs.p,
-                               (const int32_t *)M.d_first.p, (double *)M.d_store.p);
-        HIPC(h, hipGetLastError());
         launches = 1;
     } else {
         if ((rc = metric_stream_tangents(h, M.d_store.p, st, theta, &launches))) return rc;
@@ -224,11 +208,7 @@ int run_metric(ovqe_handle h, const double *theta, double *out) {
     M.info[3] = (int64_t)st.bytes;
     M.info[4] = launches;
     M.info[5] = 1;
-    for (int k = 0; k < 3; ++k) {
-        float ms = 0.f;
-        HIPC(h, hipEventElapsedTime(&ms, M.ev[k], M.ev[k + 1]));
-        M.info[6 + k] = (int64_t)(1e3 * ms);
-    }
+    if ((rc = phases_us(h, M.ev, 3, M.info + 6))) return rc;
     M.info[9] = compact ? (stage ? 1 : 2) : 0;
     M.info[10] = (int64_t)tangent_lds;
     return OVQE_OK;

@@ -2,17 +2,19 @@
 // gfx950 only; no CPU fallback: every entry point needs a live device.
 //
 // One translation unit, split along its sections (each .inc is included exactly once, in this order):
-//   this file        handle, options, device buffers, streaming-path launches, sector_prepare / program bookkeeping, handle creation,
+//   this file        handle, options, device buffers, what the per-call sections share (handle_num_cus, ensure_events / phases_us,
+//                    workspace_cap, launch_staged), streaming-path launches, sector_prepare / program bookkeeping, handle creation,
 //                    the first C-ABI entry points (version, errors, options, create / destroy, adopt)
 //   tile_host.inc    planners + launches of the LDS-tiled <H>, compact cover, tile sweeps            (kernels: sv_tile.hpp)
 //   sector_host.inc  symmetry-sector tables, sweeps, <H>, adjoint, Lanczos inside the support        (kernels: sv_sector.hpp)
 //   gates_host.inc   literal gate programs -> small ops / Clifford-frame rotations                   (sv_small.hpp, sv_frame_host.hpp)
-//   sparse_host.inc  support-compacted path                                                          (kernels: sv_sparse.hpp)
+//   sparse_host.inc  support-compacted path                                                          (kernels: sv_sparse.hpp; records, arguments, LDS layouts: sv_sparse_layout.hpp)
 //   rdm_host.inc     density matrices of the resident state: census, shadows, row list, rows, Gram    (sv_rdm_host.hpp; kernels: sv_rdm.hpp)
 //   metric_host.inc  Fubini-Study metric of the ansatz state: tangent store, compact / streaming tangents, Gram    (sv_metric_host.hpp; kernels: sv_sparse.hpp, sv_metric.hpp)
+//   measure_host.inc finite-shot measurement: basis change, prefix sums, shots                         (sv_measure_host.hpp; kernels: sv_measure.hpp)
 //   subspace_host.inc  subspace-expansion matrices around the resident state: rows, expansion vectors, sigma = H Phi, Gram    (sv_subspace_host.hpp; kernels: sv_subspace.hpp, sv_rdm.hpp)
 //   hessian_host.inc  exact energy Hessian: restricted Hamiltonian on the metric's compact program, one launch; column stores and the backward walk    (sv_hessian_host.hpp; kernels: sv_sparse.hpp, sv_hessian.hpp)
-//   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc / abi_rdm.inc / abi_metric.inc / abi_subspace.inc / abi_hessian.inc   extern "C" entry points by family (include/ovqe_sv.h)
+//   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc / abi_rdm.inc / abi_metric.inc / abi_measure.inc / abi_subspace.inc / abi_hessian.inc   extern "C" entry points by family (include/ovqe_sv.h)
 //   cross_host.inc   planned Pauli sums on a shard of the partitioned register, ovqe_xsum_*          (sv_cross_host.hpp; kernels: sv_cross.hpp)
 //   pool_host.inc    planned ADAPT pool screen on a shard, ovqe_xpool_*                              (sv_pool_host.hpp; kernels: sv_pool.hpp)
 // sv_cover_host.hpp (host-only) holds the table records planners and kernels share and the one cover rule, grow_tile_set(), that
@@ -779,6 +781,56 @@ int upload(ovqe_handle h, DevBuf &b, const void *src, size_t bytes) {
     if (rc) return rc;
     if (bytes) HIPC(h, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
+    return OVQE_OK;
+}
+
+// ---- what the per-call sections (rdm, metric, subspace, hessian, ...) share --------------------
+// compute units of the device, asked once per handle
+int handle_num_cus(ovqe_handle h) {
+    if (h->num_cus <= 0) {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus <= 0) cus = 256;
+        h->num_cus = cus;
+    }
+    return h->num_cus;
+}
+// a section's timing events, created at its first call; and the phases between consecutive events in microseconds
+int ensure_events(ovqe_handle h, hipEvent_t *ev, int n) {
+    for (int k = 0; k < n; ++k) {
+        hipEvent_t &e = ev[k];
+        if (!e) HIPC(h, hipEventCreate(&e));
+    }
+    return OVQE_OK;
+}
+int phases_us(ovqe_handle h, const hipEvent_t *ev, int n, int64_t *out) {
+    for (int k = 0; k < n; ++k) {
+        float ms = 0.f;
+        HIPC(h, hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+        out[k] = (int64_t)(1e3 * ms);
+    }
+    return OVQE_OK;
+}
+// A call's workspace of `need` bytes behind its cap: the option in MiB, or automatically 60 % of the free device memory, where the
+// `held` bytes the call's buffers hold already count as free.  `fits`: those buffers hold it all — under the automatic cap nothing
+// is asked of the runtime then.  make_message(limit) builds the caller's error text.
+template <class Message>
+int workspace_cap(ovqe_handle h, int option_mb, size_t need, size_t held, bool fits, Message make_message) {
+    if (option_mb <= 0 && fits) return OVQE_OK;
+    size_t limit = (size_t)std::max(option_mb, 0) << 20;
+    if (option_mb <= 0) {
+        size_t free_b = 0, total_b = 0;
+        HIPC(h, hipMemGetInfo(&free_b, &total_b));
+        limit = free_b / 5 * 3 + held;
+    }
+    if (need > limit) return fail(h, OVQE_ERR_ALLOC, make_message(limit));
+    return OVQE_OK;
+}
+// a one-wave kernel of sv_sparse.hpp in its staged (KT) or unstaged (KF) instance: `grid` workgroups of 64 threads
+template <auto KT, auto KF, class... Args>
+int launch_staged(ovqe_handle h, bool stage, unsigned grid, size_t lds_bytes, Args... args) {
+    if (int rc = lds_opt_in<KT, KF>(h, LDS_WG_MAX)) return rc;
+    hipLaunchKernelGGL(stage ? KT : KF, dim3(grid), dim3(64), lds_bytes, h->stream, args...);
+    HIPC(h, hipGetLastError());
     return OVQE_OK;
 }
 

@@ -38,11 +38,7 @@ int run_rdm(ovqe_handle h, int order, double *out) {
     if (!h->rdm) h->rdm = new RdmDev();
     RdmDev &R = *h->rdm;
     std::fill(R.info, R.info + 12, 0);
-    if (h->num_cus <= 0) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus <= 0) cus = 256;
-        h->num_cus = cus;
-    }
+    handle_num_cus(h);
     const int64_t W = rdm::width(n, order);
     const uint64_t nwords = rdm::bitmap_words(n);
     int rc = OVQE_OK;

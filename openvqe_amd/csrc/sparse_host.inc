@@ -324,11 +324,7 @@ int launch_rows_shared_dbg(ovqe_handle h, const SparseArgs &R, size_t smem) {
         per_dev[h->device & 63].store(pd, std::memory_order_relaxed);
     }
     const int per_cu = (int)(pd & 255u);
-    if (h->num_cus <= 0) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus <= 0) cus = 256;
-        h->num_cus = cus;
-    }
+    handle_num_cus(h);
     // persistent: as many workgroups as the chip holds at once, each walks work items of 2 NW evaluations
     const int grid = (int)std::min<int64_t>((R.B + NS - 1) / NS, (int64_t)h->num_cus * per_cu);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), smem, h->stream, R, h->cur_theta, (const SmallRot *)h->d_sp_prim.p,
@@ -533,8 +529,6 @@ int run_sparse_gradient(ovqe_handle h, const double *theta, double *energy, doub
         return OVQE_OK;
     }
     const bool stage = staged <= LDS_WG_BUDGET;
-    rc = lds_opt_in<&k_sparse_grad<true>, &k_sparse_grad<false>>(h, LDS_WG_MAX);
-    if (rc) return rc;
     const bool zero_copy = mapped_io(h, 2);   // theta [K] | energy | gradient [K] in the pinned, device-mapped buffer
     const double *d_theta;
     double *d_e, *d_g;
@@ -563,20 +557,18 @@ int run_sparse_gradient(ovqe_handle h, const double *theta, double *energy, doub
         if (smem <= LDS_WG_BUDGET) {
             hipLaunchKernelGGL((k_sparse_grad_wg<1024, 10>), dim3(1), dim3(1024), smem, h->stream, R, d_theta, (const SmallRot *)h->d_sp_prim.p,
                                (const uint64_t *)h->d_sp_rows64.p, h->sp_nrows8, (const SpEntry *)h->d_sp_entries.p, d_e, d_g);
+            HIPC(h, hipGetLastError());
             h->sp_forms |= SPF_GRAD_WG;
             launched = true;
         }
     }
-    if (!launched && stage) {
-        hipLaunchKernelGGL((k_sparse_grad<true>), dim3(1), dim3(64), staged, h->stream, A, d_theta, (const SmallRot *)h->d_rots.p,
-                           (const SpOp *)h->d_sp_ops.p, (const uint32_t *)h->d_sp_pairs.p, (const SpEntry *)h->d_sp_entries.p, d_e, d_g);
-        h->sp_forms |= SPF_GRAD_STAGED;
-    } else if (!launched) {
-        hipLaunchKernelGGL((k_sparse_grad<false>), dim3(1), dim3(64), base, h->stream, A, d_theta, (const SmallRot *)h->d_rots.p,
-                           (const SpOp *)h->d_sp_ops.p, (const uint32_t *)h->d_sp_pairs.p, (const SpEntry *)h->d_sp_entries.p, d_e, d_g);
-        h->sp_forms |= SPF_GRAD_PLAIN;
+    if (!launched) {
+        rc = launch_staged<&k_sparse_grad<true>, &k_sparse_grad<false>>(h, stage, 1u, stage ? staged : base, A, d_theta, (const SmallRot *)h->d_rots.p,
+                                                                         (const SpOp *)h->d_sp_ops.p, (const uint32_t *)h->d_sp_pairs.p,
+                                                                         (const SpEntry *)h->d_sp_entries.p, d_e, d_g);
+        if (rc) return rc;
+        h->sp_forms |= stage ? SPF_GRAD_STAGED : SPF_GRAD_PLAIN;
     }
-    HIPC(h, hipGetLastError());
     if (zero_copy) {
         HIPC(h, hipStreamSynchronize(h->stream));
         *energy = h->h_io[h->K];

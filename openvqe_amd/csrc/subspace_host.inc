@@ -52,13 +52,8 @@ int run_subspace(ovqe_handle h, int64_t m, const int64_t *offsets, const uint64_
     if (!h->subspace) h->subspace = new SubspaceDev();
     SubspaceDev &Q = *h->subspace;
     std::fill(Q.info, Q.info + 20, 0);
-    if (h->num_cus <= 0) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus <= 0) cus = 256;
-        h->num_cus = cus;
-    }
-    for (hipEvent_t &e : Q.ev)
-        if (!e) HIPC(h, hipEventCreate(&e));
+    handle_num_cus(h);
+    if (int rc = ensure_events(h, Q.ev, 5)) return rc;
     const bool with_h = h_out != nullptr;
     const int64_t T = offsets[m] - offsets[0];
     const uint64_t nwords = rdm::bitmap_words(n);
@@ -115,18 +110,11 @@ int run_subspace(ovqe_handle h, int64_t m, const int64_t *offsets, const uint64_
     const bool dense = nrows_u == h->namps;
     const sub::Plan P = sub::plan(nrows, m, with_h, h->num_cus);
     // ---- the store behind its cap
-    if (h->opt_subspace_workspace_mb > 0 || Q.d_store.cap < P.store_bytes) {
-        size_t limit = (size_t)std::max(h->opt_subspace_workspace_mb, 0) << 20;
-        if (h->opt_subspace_workspace_mb <= 0) {   // automatic: 60 % of the free device memory (what the store holds already counts as free)
-            size_t free_b = 0, total_b = 0;
-            HIPC(h, hipMemGetInfo(&free_b, &total_b));
-            limit = free_b / 5 * 3 + Q.d_store.cap;
-        }
-        if (P.store_bytes > limit)
-            return fail(h, OVQE_ERR_ALLOC, "ovqe_subspace_matrices: the store needs " + std::to_string(P.store_bytes) + " bytes (" +
-                                               std::to_string(nrows) + " rows x " + std::to_string(P.wpad) + " columns), the cap is " +
-                                               std::to_string(limit) + " bytes (option subspace_workspace_mb)");
-    }
+    rc = workspace_cap(h, h->opt_subspace_workspace_mb, P.store_bytes, Q.d_store.cap, Q.d_store.cap >= P.store_bytes, [&](size_t limit) {
+        return "ovqe_subspace_matrices: the store needs " + std::to_string(P.store_bytes) + " bytes (" + std::to_string(nrows) + " rows x " +
+               std::to_string(P.wpad) + " columns), the cap is " + std::to_string(limit) + " bytes (option subspace_workspace_mb)";
+    });
+    if (rc) return rc;
     const size_t out_elems = (size_t)m * (size_t)m * (with_h ? 2u : 1u);
     if ((rc = ensure(h, Q.d_rows, (size_t)std::max<int64_t>(nrows, 1) * sizeof(uint64_t)))) return rc;
     if ((rc = ensure(h, Q.d_store, std::max<size_t>(P.store_bytes, 16)))) return rc;
@@ -189,11 +177,7 @@ int run_subspace(ovqe_handle h, int64_t m, const int64_t *offsets, const uint64_
     Q.info[7] = sigma_launches;
     Q.info[8] = gram_launches;
     Q.info[9] = P.npairs;
-    for (int k = 0; k < 4; ++k) {
-        float ms = 0.f;
-        HIPC(h, hipEventElapsedTime(&ms, Q.ev[k], Q.ev[k + 1]));
-        Q.info[10 + k] = (int64_t)(1e3 * ms);
-    }
+    if ((rc = phases_us(h, Q.ev, 4, Q.info + 10))) return rc;
     // which path the call took: the Gram slices, the sigma instantiation and its grid (zeros when no sigma kernel ran), the expand grid
     Q.info[14] = P.slices;
     Q.info[15] = P.slice_rows;

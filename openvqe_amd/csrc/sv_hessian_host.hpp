@@ -30,15 +30,12 @@
 
 #include "sv_cover_host.hpp"
 #include "sv_metric_host.hpp"
+#include "sv_sparse_layout.hpp"
 
 namespace ovqe {
 namespace hessian {
 
-struct Entry {       // the record k_sparse_grad's lambda loop reads (SpEntry of sv_sparse.hpp)
-    uint32_t ij;     // ci | cj << 12   (ci == cj: diagonal entry)
-    uint32_t pad;
-    double c;        // 2 H_ij (off-diagonal, the pair counted once: ci < cj) or H_ii
-};
+using Entry = SpEntry;   // the record k_sparse_grad's lambda loop reads (sv_sparse_layout.hpp)
 struct Restricted {
     std::vector<Entry> entries;
     double constant = 0.0;   // the caller's constant plus the identity terms: added to E, never an entry

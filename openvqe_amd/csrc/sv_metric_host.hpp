@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "sv_rdm_host.hpp"
+#include "sv_sparse_layout.hpp"
 
 namespace ovqe {
 namespace metric {
@@ -42,10 +43,7 @@ struct TabEntry {   // angle of the entry: coeff * theta[pidx] + phi0 (pidx < 0:
     double coeff, phi0;
     int32_t pidx, pad;
 };
-struct Op {         // pattern p of the op -> table entry tab0 + p
-    int32_t first, npairs, tab0, pad;
-};
-// pair word: ci (12 bits) | cj << 12 | sign << 24 | pattern << 25      (ci: the member with the pivot bit clear)
+using Op = SpOp;     // the op record and the pair word of the compact kernels (sv_sparse_layout.hpp); ci: the member with the pivot bit clear
 
 struct Compact {
     int m = 0, hf = 0;               // support size, compact index of |hf>

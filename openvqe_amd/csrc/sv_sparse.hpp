@@ -16,49 +16,140 @@
 #pragma once
 #include "sv_small.hpp"
 #include "sv_metric_host.hpp"
+#include "sv_sparse_layout.hpp"
 #include "sv_wave_reduce.hpp"
 
 namespace ovqe {
 
-struct SpOp {
-    int32_t first;   // first pair
-    int32_t npairs;
-    int32_t tab0;    // first table entry of the op (pattern p -> tab0 + p)
-    int32_t pad;
-};
+static_assert(sizeof(double2) == SP_CS_BYTES, "the layouts of sv_sparse_layout.hpp count a cos/sin entry as one double2");
 
-// pair word: ci (12 bits) | cj (12 bits) << 12 | sign << 24 | pattern << 25
-struct SpEntry {
-    uint32_t ij;  // ci | cj << 12   (ci == cj: diagonal entry)
-    uint32_t pad;
-    double c;     // 2 * H_ij (off-diagonal, pair counted once) or H_ii
-};
+// ---- building blocks of the one-wave kernels (k_sparse_vqe, k_sparse_grad, k_sparse_metric; k_sparse_hessian: see there) -------------
+// A kernel is: sp_stage, then per work item a table fill, walks of the op list (sp_for_ops / sp_for_ops_down) whose bodies are the
+// Givens steps below on one decoded pair, an entry loop (sp_entry_amps / sp_apply_entry) and sp_fold.  The s_waitcnt fences between
+// the phases stay in the kernels: they are each kernel's own ordering argument.
+struct SpProgram { const SpOp *opv; const uint32_t *pv; };   // the op records and pair words a walk reads: LDS (STAGE) or global memory
+struct SpPair { uint32_t ci, cj; int e; bool neg; };          // a decoded pair word: the two compact indices, the table entry, the sign
+struct SpRot { double c, sn; };                               // its rotation: cos, and sin with the pair's sign
+struct SpAmps { double u, v; };                               // a vector's two amplitudes (slot ci, slot cj)
 
-struct SparseArgs {
-    int m;        // support size
-    int mpad;     // per-evaluation stride of the LDS state in doubles: m rounded up to even, so that the double2
-                  // cos/sin table behind SPW states starts on a 16-byte boundary (ds_read/write_b128)
-    int K;
-    int nops;
-    int ntab;
-    int nent;
-    int npairs;   // all active pairs of the program (STAGE: copied to LDS once per launch)
-    int hf;       // compact slot of |hf>
-    int64_t B;
-    double constant;
-    int dbg = 0;  // measurements ("sparse_dbg"; the rows kernels take it as a template argument): 1 no sincos, 2 no circuit rows, 3 no Hamiltonian entries, 4 (k_sparse_vqe_rows_shared) no theta loads, 5 nothing left out: wave sums by __shfl_down, as before sv_wave_reduce.hpp
-};
-
-struct SpVqeLds { size_t cs, ops, pairs, bytes; };   // the spw states ([spw][mpad]) are at 0
-__host__ __device__ inline SpVqeLds sp_vqe_lds(const SparseArgs &A, int spw, bool stage) {
-    static_assert(sizeof(double2) == 16 && sizeof(SpOp) == 16, "16-byte records behind an even number of doubles");
-    const size_t cs = (size_t)spw * A.mpad * sizeof(double);          // [spw][ntab], 16-byte aligned
-    const size_t ops = cs + (size_t)spw * A.ntab * sizeof(double2);   // [nops]   (stage)
-    const size_t pairs = ops + (size_t)A.nops * sizeof(SpOp);         // [npairs] (stage)
-    return {cs, ops, pairs, stage ? pairs + (size_t)A.npairs * sizeof(uint32_t) : ops};
+// STAGE: the op table and the pair words are copied to LDS once per launch, so that the chain op -> pair word -> amplitudes never
+// waits for global memory
+template <bool STAGE>
+__device__ __forceinline__ SpProgram sp_stage(unsigned char *smem, size_t ops_off, size_t pairs_off, const SpOp *ops, const uint32_t *pairs,
+                                              int nops, int npairs, int lane) {
+    if constexpr (STAGE) {
+        SpOp *lops = reinterpret_cast<SpOp *>(smem + ops_off);
+        uint32_t *lpairs = reinterpret_cast<uint32_t *>(smem + pairs_off);
+        for (int i = lane; i < nops; i += 64) lops[i] = ops[i];
+        for (int i = lane; i < npairs; i += 64) lpairs[i] = pairs[i];
+        return {lops, lpairs};
+    } else {
+        return {ops, pairs};
+    }
 }
-// STAGE = true (small batches, the latency path of one-evaluation-per-call optimisers): the op table and the pair
-// words are copied to LDS at kernel start, so the chain op -> pair word -> amplitudes never waits for global memory.
+
+__device__ __forceinline__ SpPair sp_decode(uint32_t pw, int tab0) {
+    return {pw & 0xfffu, (pw >> 12) & 0xfffu, tab0 + (int)(pw >> 25), (pw & (1u << 24)) != 0u};
+}
+__device__ __forceinline__ SpRot sp_rot(const double2 *cs, const SpPair &p) {
+    const double2 t = cs[p.e];
+    return {t.x, p.neg ? -t.y : t.y};
+}
+__device__ __forceinline__ SpAmps sp_get(const double *vec, const SpPair &p) { return {vec[p.ci], vec[p.cj]}; }
+__device__ __forceinline__ void sp_put(double *vec, const SpPair &p, const SpAmps &a) {
+    vec[p.ci] = a.u;
+    vec[p.cj] = a.v;
+}
+__device__ __forceinline__ double sp_signed(const SpPair &p, double x) { return p.neg ? -x : x; }
+
+// the Givens step G of a pair, u' = c u + sigma s v, v' = c v - sigma s u, and its inverse G^T
+__device__ __forceinline__ SpAmps sp_rotate(const SpRot &r, const SpAmps &a) { return {r.c * a.u + r.sn * a.v, r.c * a.v - r.sn * a.u}; }
+__device__ __forceinline__ SpAmps sp_rotate_back(const SpRot &r, const SpAmps &a) { return {r.c * a.u - r.sn * a.v, r.c * a.v + r.sn * a.u}; }
+// ... with the derivative of the step on top (d = sigma coeff_e for an entry of the direction's parameter, else 0; sv_hessian_host.hpp):
+// t' = G t + d J psi' (psi AFTER the step)
+__device__ __forceinline__ SpAmps sp_rotate_inject(const SpRot &r, double d, const SpAmps &t, const SpAmps &psi1) {
+    return {r.c * t.u + r.sn * t.v + d * psi1.v, r.c * t.v - r.sn * t.u - d * psi1.u};
+}
+// the plain forward step on a vector in LDS
+__device__ __forceinline__ void sp_rotate_pair(double *vec, const double2 *cs, const SpPair &p) {
+    const SpRot r = sp_rot(cs, p);
+    sp_put(vec, p, sp_rotate(r, sp_get(vec, p)));
+}
+// ... and on psi and one tangent t together (dk[e]: coeff_e where entry e is the direction's parameter's, else 0)
+__device__ __forceinline__ void sp_tangent_pair(double *psi, double *t, const double2 *cs, const double *dk, const SpPair &p) {
+    const SpRot r = sp_rot(cs, p);
+    const double d = sp_signed(p, dk[p.e]);
+    const SpAmps a = sp_get(psi, p), tt = sp_get(t, p);
+    const SpAmps a1 = sp_rotate(r, a);
+    sp_put(psi, p, a1);
+    sp_put(t, p, sp_rotate_inject(r, d, tt, a1));
+}
+
+// one op: body(pair) for its pairs, STRIDE lanes apart.  The pairs of one op are disjoint; the next op may touch them from other lanes of
+// this wave: the LDS unit executes a wave's DS instructions in issue order, so only the COMPILER must not reorder across ops
+template <int STRIDE, class Body>
+__device__ __forceinline__ void sp_op_pairs(const SpProgram &P, int o, int lane, Body &body) {
+    SpOp op = P.opv[o];
+    op.first = __builtin_amdgcn_readfirstlane(op.first);
+    op.npairs = __builtin_amdgcn_readfirstlane(op.npairs);
+    op.tab0 = __builtin_amdgcn_readfirstlane(op.tab0);
+    for (int pe = lane; pe < op.npairs; pe += STRIDE) body(sp_decode(P.pv[op.first + pe], op.tab0));
+    asm volatile("" ::: "memory");
+}
+// the ops [o0, o1) in program order, and the same ops backwards
+template <int STRIDE, class Body>
+__device__ __forceinline__ void sp_for_ops(const SpProgram &P, int o0, int o1, int lane, Body body) {
+    for (int o = o0; o < o1; ++o) sp_op_pairs<STRIDE>(P, o, lane, body);
+}
+template <int STRIDE, class Body>
+__device__ __forceinline__ void sp_for_ops_down(const SpProgram &P, int o0, int o1, int lane, Body body) {
+    for (int o = o1 - 1; o >= o0; --o) sp_op_pairs<STRIDE>(P, o, lane, body);
+}
+
+// the cos/sin table: cs[e] = (cos, sin) of angle(record e) for e = first, first + STRIDE, ...; also(e, record) fills what else the
+// kernel keeps per entry
+template <int STRIDE, class Rec, class Angle, class Also>
+__device__ __forceinline__ void sp_fill_table(const Rec *tab, int ntab, int first, double2 *cs, Angle angle, Also also) {
+    for (int e = first; e < ntab; e += STRIDE) {
+        const Rec te = tab[e];
+        double sn, c;
+        sincos(angle(te), &sn, &c);
+        cs[e] = make_double2(c, sn);
+        also(e, te);
+    }
+}
+
+// one entry of the restricted Hamiltonian: the amplitudes it couples in a vector, and out[k] += H a[k] for it, for N vectors at once
+// (f64 LDS atomics: out_i += H_ij a_j, out_j += H_ij a_i)
+__device__ __forceinline__ SpAmps sp_entry_amps(const SpEntry &en, const double *vec) {
+    const uint32_t ci = en.ij & 0xfffu, cj = (en.ij >> 12) & 0xfffu;
+    return {vec[ci], vec[cj]};
+}
+template <int N>
+__device__ __forceinline__ void sp_apply_entry(const SpEntry &en, const SpAmps (&a)[N], double *const (&out)[N]) {
+    const uint32_t ci = en.ij & 0xfffu, cj = (en.ij >> 12) & 0xfffu;
+    if (ci == cj) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) __hip_atomic_fetch_add(&out[k][ci], en.c * a[k].u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    } else {   // c = 2 H_ij, the pair counted once
+        const double hc = 0.5 * en.c;
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            __hip_atomic_fetch_add(&out[k][ci], hc * a[k].v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(&out[k][cj], hc * a[k].u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
+}
+
+// d / dtheta_k = sum over the table entries of parameter k of 2 coeff w[e]   (Rec: SmallRot or metric::TabEntry)
+template <int STRIDE, class Rec>
+__device__ __forceinline__ void sp_fold(const Rec *tab, int ntab, const double *w, double *gk, int tid) {
+    for (int e = tid; e < ntab; e += STRIDE) {
+        const Rec te = tab[e];
+        if (te.pidx >= 0) __hip_atomic_fetch_add(&gk[te.pidx], 2.0 * te.coeff * w[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+
 template <int SPW, bool STAGE>
 __global__ __launch_bounds__(64) void k_sparse_vqe(SparseArgs A, const double *__restrict__ theta,
                                                    const SmallRot *__restrict__ tabrots,
@@ -70,17 +161,12 @@ __global__ __launch_bounds__(64) void k_sparse_vqe(SparseArgs A, const double *_
     double *st = reinterpret_cast<double *>(smem);
     double2 *cs = reinterpret_cast<double2 *>(smem + L.cs);
     const int lane = threadIdx.x;
-    SpOp *lops = reinterpret_cast<SpOp *>(smem + L.ops);
-    uint32_t *lpairs = reinterpret_cast<uint32_t *>(smem + L.pairs);
-    if constexpr (STAGE) {
-        for (int i = lane; i < A.nops; i += 64) lops[i] = ops[i];
-        for (int i = lane; i < A.npairs; i += 64) lpairs[i] = pairs[i];
-    }
+    const SpProgram P = sp_stage<STAGE>(smem, L.ops, L.pairs, ops, pairs, A.nops, A.npairs, lane);
     // the wave's lanes are split evenly over its SPW evaluations (no index division in the inner loops)
     constexpr int LPS = 64 / SPW;
     const int s = lane / LPS, l = lane % LPS;
     double *base = st + (size_t)s * A.mpad;
-    const double2 *csb = cs + (size_t)s * A.ntab;
+    double2 *csb = cs + (size_t)s * A.ntab;
     const int64_t nwork = (A.B + SPW - 1) / SPW;
     for (int64_t w = blockIdx.x; w < nwork; w += gridDim.x) {
         const int64_t b0 = w * SPW;
@@ -89,33 +175,11 @@ __global__ __launch_bounds__(64) void k_sparse_vqe(SparseArgs A, const double *_
         {
             const int64_t b = b0 + s < A.B ? b0 + s : A.B - 1;
             const double *th = theta + b * A.K;
-            for (int e = l; e < A.ntab; e += LPS) {
-                const SmallRot sr = tabrots[e];
-                double sn, c;
-                sincos(sr.coeff * th[sr.pidx], &sn, &c);
-                cs[(size_t)s * A.ntab + e] = make_double2(c, sn);
-            }
+            sp_fill_table<LPS>(tabrots, A.ntab, l, csb, [&](const SmallRot &sr) { return sr.coeff * th[sr.pidx]; }, [](int, const SmallRot &) {});
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if constexpr (STAGE) {
-            for (int o = 0; o < A.nops; ++o) {
-                SpOp op = lops[o];
-                op.first = __builtin_amdgcn_readfirstlane(op.first);
-                op.npairs = __builtin_amdgcn_readfirstlane(op.npairs);
-                op.tab0 = __builtin_amdgcn_readfirstlane(op.tab0);
-                for (int pe = l; pe < op.npairs; pe += LPS) {
-                    const uint32_t pw = lpairs[op.first + pe];
-                    const uint32_t ci = pw & 0xfffu, cj = (pw >> 12) & 0xfffu;
-                    const double2 t = csb[op.tab0 + (int)(pw >> 25)];
-                    const double sn = (pw & (1u << 24)) ? -t.y : t.y;
-                    const double u = base[ci], v = base[cj];
-                    base[ci] = t.x * u + sn * v;
-                    base[cj] = t.x * v - sn * u;
-                }
-                // pairs of one op are disjoint; the next op may touch them from other lanes of this wave: the LDS unit
-                // executes a wave's DS instructions in issue order, so only the COMPILER must not reorder across ops
-                asm volatile("" ::: "memory");
-            }
+            sp_for_ops<LPS>(P, 0, A.nops, l, [&](const SpPair &p) { sp_rotate_pair(base, csb, p); });
         } else if (A.nops > 0) {   // (a program with no active op on the support has no op record to fetch ahead)
             // op records and pair words stream from L2: the chain record -> pair word -> amplitudes of consecutive ops is
             // what bounds this kernel, so both are fetched AHEAD — the record of op o + 3 and the first pair words of ops o + 1,
@@ -134,12 +198,7 @@ __global__ __launch_bounds__(64) void k_sparse_vqe(SparseArgs A, const double *_
                 pw2 = (o + 2 <= last && l < op2.npairs) ? pairs[op2.first + l] : 0u;
                 for (int pe = l; pe < op.npairs; pe += LPS) {
                     if (pe != l) pw = pairs[op.first + pe];
-                    const uint32_t ci = pw & 0xfffu, cj = (pw >> 12) & 0xfffu;
-                    const double2 t = csb[op.tab0 + (int)(pw >> 25)];
-                    const double sn = (pw & (1u << 24)) ? -t.y : t.y;
-                    const double u = base[ci], v = base[cj];
-                    base[ci] = t.x * u + sn * v;
-                    base[cj] = t.x * v - sn * u;
+                    sp_rotate_pair(base, csb, sp_decode(pw, op.tab0));
                 }
                 asm volatile("" ::: "memory");
             }
@@ -163,13 +222,6 @@ __global__ __launch_bounds__(64) void k_sparse_vqe(SparseArgs A, const double *_
     }
 }
 
-// k_sparse_vqe_rows (spw = 2; mpad = support + 64 spare slots) and k_sparse_vqe_wg (spw = 1; + 128): the states, then one cos/sin
-// table of ntab + 1 entries each — the last entry is the identity
-struct SpRowsLds { size_t cs, bytes; };   // the states ([spw][mpad]) are at 0
-__host__ __device__ inline SpRowsLds sp_rows_lds(const SparseArgs &A, int spw) {
-    const size_t cs = (size_t)spw * A.mpad * sizeof(double);
-    return {cs, cs + (size_t)spw * (A.ntab + 1) * sizeof(double2)};
-}
 
 // ---- throughput form of the circuit (round 3): rows of 32 padded 64-bit words ------------------------------------------------
 // rocprofv3 counters of k_sparse_vqe<2> on the H2O workload: the LDS pipe is active 6 % of the wave cycles and bank-conflict
@@ -664,17 +716,6 @@ __global__ __launch_bounds__(NT) void k_sparse_vqe_wg(SparseArgs A, const double
 #undef OVQE_STAMP
 }
 
-struct SpGradLds { size_t lam, cs, w, gk, ops, pairs, bytes; };   // psi ([mpad]) is at 0
-__host__ __device__ inline SpGradLds sp_grad_lds(const SparseArgs &A, bool stage) {
-    const size_t lam = (size_t)A.mpad * sizeof(double);                  // [mpad]
-    const size_t cs = 2 * lam;                                           // [ntab]
-    const size_t w = cs + (size_t)A.ntab * sizeof(double2);              // [ntab]
-    const size_t gk = w + (size_t)A.ntab * sizeof(double);               // [K]
-    const size_t ops = gk + (size_t)((A.K + 1) & ~1) * sizeof(double);   // [nops]   (stage)
-    const size_t pairs = ops + (size_t)A.nops * sizeof(SpOp);            // [npairs] (stage)
-    return {lam, cs, w, gk, ops, pairs, stage ? pairs + (size_t)A.npairs * sizeof(uint32_t) : ops};
-}
-
 // ---- exact gradient on the compact support (round 3) ---------------------------------------------------------------------
 // E(theta) and dE/dtheta_k for ALL K parameters of one parameter vector per wave, in ONE launch: forward circuit as above,
 // lambda = H psi from the restricted Hamiltonian's entries (f64 LDS atomics: lambda_i += H_ij a_j, lambda_j += H_ij a_i),
@@ -695,107 +736,49 @@ __global__ __launch_bounds__(64) void k_sparse_grad(SparseArgs A, const double *
     double2 *cs = reinterpret_cast<double2 *>(smem + L.cs);
     double *w = reinterpret_cast<double *>(smem + L.w);
     double *gk = reinterpret_cast<double *>(smem + L.gk);
-    SpOp *lops = reinterpret_cast<SpOp *>(smem + L.ops);
-    uint32_t *lpairs = reinterpret_cast<uint32_t *>(smem + L.pairs);
     const int lane = threadIdx.x;
-    if constexpr (STAGE) {
-        for (int i = lane; i < A.nops; i += 64) lops[i] = ops[i];
-        for (int i = lane; i < A.npairs; i += 64) lpairs[i] = pairs[i];
-    }
-    const SpOp *opv = STAGE ? lops : ops;
-    const uint32_t *pv = STAGE ? lpairs : pairs;
+    const SpProgram P = sp_stage<STAGE>(smem, L.ops, L.pairs, ops, pairs, A.nops, A.npairs, lane);
     for (int64_t b = blockIdx.x; b < A.B; b += gridDim.x) {
         const double *th = theta + b * A.K;
         for (int i = lane; i < A.mpad; i += 64) {
             psi[i] = i == A.hf ? 1.0 : 0.0;
             lam[i] = 0.0;
         }
-        for (int e = lane; e < A.ntab; e += 64) {
-            const SmallRot sr = tabrots[e];
-            double sn, c;
-            sincos(sr.coeff * th[sr.pidx], &sn, &c);
-            cs[e] = make_double2(c, sn);
-            w[e] = 0.0;
-        }
+        sp_fill_table<64>(tabrots, A.ntab, lane, cs, [&](const SmallRot &sr) { return sr.coeff * th[sr.pidx]; },
+                          [&](int e, const SmallRot &) { w[e] = 0.0; });
         for (int k = lane; k < A.K; k += 64) gk[k] = 0.0;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         // forward
-        for (int o = 0; o < A.nops; ++o) {
-            SpOp op = opv[o];
-            op.first = __builtin_amdgcn_readfirstlane(op.first);
-            op.npairs = __builtin_amdgcn_readfirstlane(op.npairs);
-            op.tab0 = __builtin_amdgcn_readfirstlane(op.tab0);
-            for (int pe = lane; pe < op.npairs; pe += 64) {
-                const uint32_t pw = pv[op.first + pe];
-                const uint32_t ci = pw & 0xfffu, cj = (pw >> 12) & 0xfffu;
-                const double2 t = cs[op.tab0 + (int)(pw >> 25)];
-                const double sn = (pw & (1u << 24)) ? -t.y : t.y;
-                const double u = psi[ci], v = psi[cj];
-                psi[ci] = t.x * u + sn * v;
-                psi[cj] = t.x * v - sn * u;
-            }
-            asm volatile("" ::: "memory");   // a wave's DS instructions execute in issue order (see k_sparse_vqe)
-        }
+        sp_for_ops<64>(P, 0, A.nops, lane, [&](const SpPair &p) { sp_rotate_pair(psi, cs, p); });
         // lambda = H psi, E = <psi|lambda>
         double acc = 0.0;
 #pragma unroll 4
         for (int e = lane; e < A.nent; e += 64) {
             const SpEntry en = entries[e];
-            const uint32_t ci = en.ij & 0xfffu, cj = (en.ij >> 12) & 0xfffu;
-            const double ai = psi[ci], aj = psi[cj];
-            acc += en.c * ai * aj;
-            if (ci == cj) {
-                __hip_atomic_fetch_add(&lam[ci], en.c * ai, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            } else {   // c = 2 H_ij, the pair counted once
-                __hip_atomic_fetch_add(&lam[ci], 0.5 * en.c * aj, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_fetch_add(&lam[cj], 0.5 * en.c * ai, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
+            const SpAmps a = sp_entry_amps(en, psi);
+            acc += en.c * a.u * a.v;
+            sp_apply_entry(en, {a}, {lam});
         }
         const double etot = wave_sum(acc);
         if (lane == 0) energies[b] = etot + A.constant;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // backward
-        for (int o = A.nops - 1; o >= 0; --o) {
-            SpOp op = opv[o];
-            op.first = __builtin_amdgcn_readfirstlane(op.first);
-            op.npairs = __builtin_amdgcn_readfirstlane(op.npairs);
-            op.tab0 = __builtin_amdgcn_readfirstlane(op.tab0);
-            for (int pe = lane; pe < op.npairs; pe += 64) {
-                const uint32_t pw = pv[op.first + pe];
-                const uint32_t ci = pw & 0xfffu, cj = (pw >> 12) & 0xfffu;
-                const int e = op.tab0 + (int)(pw >> 25);
-                const double2 t = cs[e];
-                const bool neg = (pw & (1u << 24)) != 0u;
-                const double sn = neg ? -t.y : t.y;
-                const double u1 = psi[ci], v1 = psi[cj], lu = lam[ci], lv = lam[cj];
-                const double g = lu * v1 - lv * u1;
-                __hip_atomic_fetch_add(&w[e], neg ? -g : g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                psi[ci] = t.x * u1 - sn * v1;
-                psi[cj] = t.x * v1 + sn * u1;
-                lam[ci] = t.x * lu - sn * lv;
-                lam[cj] = t.x * lv + sn * lu;
-            }
-            asm volatile("" ::: "memory");
-        }
+        // backward: the pair's weight g on the states after the op, then both states rotated back
+        sp_for_ops_down<64>(P, 0, A.nops, lane, [&](const SpPair &p) {
+            const SpRot r = sp_rot(cs, p);
+            const SpAmps a = sp_get(psi, p), l = sp_get(lam, p);
+            const double g = l.u * a.v - l.v * a.u;
+            __hip_atomic_fetch_add(&w[p.e], sp_signed(p, g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            sp_put(psi, p, sp_rotate_back(r, a));
+            sp_put(lam, p, sp_rotate_back(r, l));
+        });
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        for (int e = lane; e < A.ntab; e += 64) {
-            const SmallRot sr = tabrots[e];
-            if (sr.pidx >= 0) __hip_atomic_fetch_add(&gk[sr.pidx], 2.0 * sr.coeff * w[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
+        sp_fold<64>(tabrots, A.ntab, w, gk, lane);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         for (int k = lane; k < A.K; k += 64) grads[b * A.K + k] = gk[k];
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
 }
 
-struct SpGradWgLds { size_t lam, cs, w, gk, bytes; };   // psi ([mpad] = support + 128 spare slots) is at 0
-__host__ __device__ inline SpGradWgLds sp_grad_wg_lds(const SparseArgs &A) {
-    const size_t lam = (size_t)A.mpad * sizeof(double);                   // [mpad]
-    const size_t cs = 2 * lam;                                            // [ntab + 1]
-    const size_t w = cs + (size_t)(A.ntab + 1) * sizeof(double2);         // [ntab + 1], an even number of slots
-    const size_t gk = w + (size_t)((A.ntab + 2) & ~1) * sizeof(double);   // [K]
-    return {lam, cs, w, gk, gk + (size_t)((A.K + 1) & ~1) * sizeof(double)};
-}
 // ... and with ONE parameter vector per workgroup (latency form, as k_sparse_vqe_wg): all threads prepare and hold the restricted
 // Hamiltonian's entries in registers, wave 0 runs the circuit forwards over rows of 64 padded words, all waves form
 // E = <psi|H|psi> and lambda = H psi (f64 LDS atomics), wave 0 walks the rows BACKWARDS on psi and lambda — per row
@@ -866,7 +849,8 @@ __global__ __launch_bounds__(NT) void k_sparse_grad_wg(SparseArgs A, const doubl
         }
         __syncthreads();
         double acc = 0.0;
-        auto entry = [&](const SpEntry &en) {
+        auto entry = [&](const SpEntry &en) {   // (sp_entry_amps / sp_apply_entry spelled out: this kernel sits at its register cap with spills,
+            // and its allocation moved with the helpers — 8 bytes more scratch, or 0.9 % on the call)
             const uint32_t ci = en.ij & 0xfffu, cj = (en.ij >> 12) & 0xfffu;
             const double ai = psi[ci], aj = psi[cj];
             acc += en.c * ai * aj;
@@ -914,10 +898,7 @@ __global__ __launch_bounds__(NT) void k_sparse_grad_wg(SparseArgs A, const doubl
             }
         }
         __syncthreads();
-        for (int e = tid; e < A.ntab; e += NT) {
-            const SmallRot sr = tabrots[e];
-            if (sr.pidx >= 0) __hip_atomic_fetch_add(&gk[sr.pidx], 2.0 * sr.coeff * w[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
+        sp_fold<NT>(tabrots, A.ntab, w, gk, tid);
         __syncthreads();
         for (int k = tid; k < A.K; k += NT) grads[b * A.K + k] = gk[k];
         __syncthreads();
@@ -933,20 +914,6 @@ __global__ __launch_bounds__(NT) void k_sparse_grad_wg(SparseArgs A, const doubl
 // order: no atomic, no barrier, and the same bits from call to call.  Until the first op that holds an entry of parameter k (first_op, from
 // the host) t is zero and psi rotates alone.  The finished tangent goes to column k of the index-major store (row i = compact index,
 // wpad columns): the Gram kernel of the density matrices reads that layout as it stands.
-struct SpMetricArgs {
-    int m, mpad, K, nops, ntab, npairs, hf;
-    int64_t wpad;
-};
-struct SpMetricLds { size_t t, cs, dk, ops, pairs, bytes; };   // psi ([mpad]) is at 0
-__host__ __device__ inline SpMetricLds sp_metric_lds(const SpMetricArgs &A, bool stage) {
-    static_assert(sizeof(metric::Op) == 16, "16-byte records behind an even number of doubles");
-    const size_t t = (size_t)A.mpad * sizeof(double);                       // [mpad]
-    const size_t cs = 2 * t;                                                // [ntab]
-    const size_t dk = cs + (size_t)A.ntab * sizeof(double2);                // [ntab]: coeff_e where the entry is parameter k's, else 0
-    const size_t ops = dk + (size_t)((A.ntab + 1) & ~1) * sizeof(double);   // [nops]   (stage)
-    const size_t pairs = ops + (size_t)A.nops * sizeof(metric::Op);         // [npairs] (stage)
-    return {t, cs, dk, ops, pairs, stage ? pairs + (size_t)A.npairs * sizeof(uint32_t) : ops};
-}
 template <bool STAGE>
 __global__ __launch_bounds__(64) void k_sparse_metric(SpMetricArgs A, const double *__restrict__ theta, const metric::TabEntry *__restrict__ tab,
                                                       const metric::Op *__restrict__ ops, const uint32_t *__restrict__ pairs,
@@ -957,68 +924,21 @@ __global__ __launch_bounds__(64) void k_sparse_metric(SpMetricArgs A, const doub
     double *t = reinterpret_cast<double *>(smem + L.t);
     double2 *cs = reinterpret_cast<double2 *>(smem + L.cs);
     double *dk = reinterpret_cast<double *>(smem + L.dk);
-    metric::Op *lops = reinterpret_cast<metric::Op *>(smem + L.ops);
-    uint32_t *lpairs = reinterpret_cast<uint32_t *>(smem + L.pairs);
     const int lane = threadIdx.x;
-    if constexpr (STAGE) {
-        for (int i = lane; i < A.nops; i += 64) lops[i] = ops[i];
-        for (int i = lane; i < A.npairs; i += 64) lpairs[i] = pairs[i];
-    }
-    const metric::Op *opv = STAGE ? lops : ops;
-    const uint32_t *pv = STAGE ? lpairs : pairs;
+    const SpProgram P = sp_stage<STAGE>(smem, L.ops, L.pairs, ops, pairs, A.nops, A.npairs, lane);
     for (int k = blockIdx.x; k < A.K; k += gridDim.x) {
         for (int i = lane; i < A.mpad; i += 64) {
             psi[i] = i == A.hf ? 1.0 : 0.0;
             t[i] = 0.0;
         }
-        for (int e = lane; e < A.ntab; e += 64) {
-            const metric::TabEntry te = tab[e];
-            double sn, c;
-            sincos(te.phi0 + (te.pidx >= 0 ? te.coeff * theta[te.pidx] : 0.0), &sn, &c);
-            cs[e] = make_double2(c, sn);
-            dk[e] = te.pidx == k ? te.coeff : 0.0;
-        }
+        sp_fill_table<64>(tab, A.ntab, lane, cs,
+                          [&](const metric::TabEntry &te) { return te.phi0 + (te.pidx >= 0 ? te.coeff * theta[te.pidx] : 0.0); },
+                          [&](int e, const metric::TabEntry &te) { dk[e] = te.pidx == k ? te.coeff : 0.0; });
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         int o1 = first_op[k];
         o1 = __builtin_amdgcn_readfirstlane(o1 < A.nops ? o1 : A.nops);
-        for (int o = 0; o < o1; ++o) {   // psi alone
-            metric::Op op = opv[o];
-            op.first = __builtin_amdgcn_readfirstlane(op.first);
-            op.npairs = __builtin_amdgcn_readfirstlane(op.npairs);
-            op.tab0 = __builtin_amdgcn_readfirstlane(op.tab0);
-            for (int pe = lane; pe < op.npairs; pe += 64) {
-                const uint32_t pw = pv[op.first + pe];
-                const uint32_t ci = pw & 0xfffu, cj = (pw >> 12) & 0xfffu;
-                const double2 r = cs[op.tab0 + (int)(pw >> 25)];
-                const double sn = (pw & (1u << 24)) ? -r.y : r.y;
-                const double u = psi[ci], v = psi[cj];
-                psi[ci] = r.x * u + sn * v;
-                psi[cj] = r.x * v - sn * u;
-            }
-            asm volatile("" ::: "memory");   // a wave's DS instructions execute in issue order (see k_sparse_vqe)
-        }
-        for (int o = o1; o < A.nops; ++o) {   // psi and the tangent
-            metric::Op op = opv[o];
-            op.first = __builtin_amdgcn_readfirstlane(op.first);
-            op.npairs = __builtin_amdgcn_readfirstlane(op.npairs);
-            op.tab0 = __builtin_amdgcn_readfirstlane(op.tab0);
-            for (int pe = lane; pe < op.npairs; pe += 64) {
-                const uint32_t pw = pv[op.first + pe];
-                const uint32_t ci = pw & 0xfffu, cj = (pw >> 12) & 0xfffu;
-                const int e = op.tab0 + (int)(pw >> 25);
-                const double2 r = cs[e];
-                const bool neg = (pw & (1u << 24)) != 0u;
-                const double sn = neg ? -r.y : r.y;
-                const double d = neg ? -dk[e] : dk[e];
-                const double u = psi[ci], v = psi[cj], tu = t[ci], tv = t[cj];
-                const double u1 = r.x * u + sn * v, v1 = r.x * v - sn * u;
-                psi[ci] = u1;
-                psi[cj] = v1;
-                t[ci] = r.x * tu + sn * tv + d * v1;
-                t[cj] = r.x * tv - sn * tu - d * u1;
-            }
-            asm volatile("" ::: "memory");
-        }
+        sp_for_ops<64>(P, 0, o1, lane, [&](const SpPair &p) { sp_rotate_pair(psi, cs, p); });   // psi alone
+        sp_for_ops<64>(P, o1, A.nops, lane, [&](const SpPair &p) { sp_tangent_pair(psi, t, cs, dk, p); });   // psi and the tangent
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         for (int i = lane; i < A.m; i += 64) store[(size_t)i * (size_t)A.wpad + (size_t)k] = t[i];
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1036,22 +956,8 @@ __global__ __launch_bounds__(64) void k_sparse_metric(SpMetricArgs A, const doub
 // Row b of the raw matrix is sum over the entries of parameter k of 2 coeff_e wd[e]; the workgroup of direction 0 accumulates w as well
 // and writes the energy and the gradient.  The program, its table and first_op are the metric's (sv_metric_host.hpp), the entries are built
 // on THAT program's compact indices.  The order of the atomic additions is not fixed: the result reproduces to rounding, not to the bit.
-struct SpHessArgs {
-    int m, mpad, K, nops, ntab, npairs, nent, hf;
-    double constant;
-};
-struct SpHessLds { size_t t, lam, mu, cs, dk, w, wd, gk, ops, pairs, bytes; };   // psi ([mpad]) is at 0
-__host__ __device__ inline SpHessLds sp_hessian_lds(const SpHessArgs &A, bool stage) {
-    const size_t v = (size_t)A.mpad * sizeof(double);                                       // psi, t, lambda, mu: [mpad] each
-    const size_t cs = 4 * v;                                                                // [ntab]
-    const size_t dk = cs + (size_t)A.ntab * sizeof(double2);                                // [ntab]: coeff_e of parameter b's entries, else 0
-    const size_t w = dk + (size_t)A.ntab * sizeof(double);                                  // [ntab]
-    const size_t wd = w + (size_t)A.ntab * sizeof(double);                                  // [ntab]
-    const size_t gk = wd + (size_t)A.ntab * sizeof(double);                                 // [K]
-    const size_t ops = (gk + (size_t)A.K * sizeof(double) + 15) & ~(size_t)15;              // [nops]   (stage)
-    const size_t pairs = ops + (size_t)A.nops * sizeof(metric::Op);                         // [npairs] (stage)
-    return {v, 2 * v, 3 * v, cs, dk, w, wd, gk, ops, pairs, stage ? pairs + (size_t)A.npairs * sizeof(uint32_t) : ops};
-}
+// (This kernel keeps its walks spelled out instead of going through sp_for_ops and the Givens helpers above: rewritten on them it
+// issued the same vector instructions but ran 3 us slower per launch on H2O (126 -> 129 us; profiles/sparse_walk/README.md).)
 template <bool STAGE>
 __global__ __launch_bounds__(64) void k_sparse_hessian(SpHessArgs A, const double *__restrict__ theta, const metric::TabEntry *__restrict__ tab,
                                                        const metric::Op *__restrict__ ops, const uint32_t *__restrict__ pairs,

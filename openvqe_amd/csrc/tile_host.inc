@@ -749,11 +749,7 @@ inline int adjoint_tile_bits(ovqe_handle h) {
     return (m == 11 || m == 12) && h->n_local >= m + 2 ? m : 0;   // 0: the streaming kernels only
 }
 inline int adjoint_tile_grid(ovqe_handle h, int m) {
-    if (h->num_cus <= 0) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus <= 0) cus = 256;
-        h->num_cus = cus;
-    }
+    handle_num_cus(h);
     return (int)std::min<uint64_t>(h->namps >> m, (uint64_t)h->num_cus * (m >= 12 ? 1 : 2));
 }
 template <int M>

@@ -8,7 +8,7 @@
 //     gradient and the Hessian are compared with a dense complex nested-forward-mode simulation of exp(-i phi P).
 //   usage: hessian_plan_check [seed]
 //          hessian_plan_check boundary     cube programs at m = 4096 on both sides of the staged / unstaged / streaming decisions of the
-//                                          kernel's LDS layout (restated from sp_hessian_lds), and the refusal beyond the support cap
+//                                          kernel's LDS layout (sp_hessian_lds), and the refusal beyond the support cap
 #include <cmath>
 #include <complex>
 #include <cstdio>
@@ -103,25 +103,9 @@ static Ham random_ham(std::mt19937_64 &rng, int n, int T) {
     return H;
 }
 
-// the kernel's dynamic LDS, restated from sp_hessian_lds (sv_sparse.hpp, a HIP header): psi [mpad] at 0, then the tangent, lambda and mu
-// [mpad] each, cos / sin [ntab] as 16-byte pairs, dk, w, wd [ntab], gk [K], rounded up to 16 bytes; staged: op records, pair words
-struct Lds { size_t t, lam, mu, cs, dk, w, wd, gk, ops, pairs, bytes; };
-static Lds lds_layout(const metric::Compact &C, int K, bool stage) {
-    const size_t v = (size_t)((C.m + 1) & ~1) * 8, ntab = C.tab.size();
-    Lds L;
-    L.t = v;
-    L.lam = 2 * v;
-    L.mu = 3 * v;
-    L.cs = 4 * v;
-    L.dk = L.cs + ntab * 16;
-    L.w = L.dk + ntab * 8;
-    L.wd = L.w + ntab * 8;
-    L.gk = L.wd + ntab * 8;
-    L.ops = (L.gk + (size_t)K * 8 + 15) & ~(size_t)15;
-    L.pairs = L.ops + C.ops.size() * sizeof(metric::Op);
-    L.bytes = stage ? L.pairs + C.pairs.size() * 4 : L.ops;
-    return L;
-}
+// the kernel's dynamic LDS is sp_hessian_lds itself (sv_sparse_layout.hpp: the header the kernel and its launcher read); the layout
+// does not depend on the entry count or the constant
+static SpHessLds lds_layout(const metric::Compact &C, int K, bool stage) { return sp_hessian_lds(sp_hessian_args(C, K, 0, 0.0), stage); }
 constexpr size_t LDS_BUDGET = 150 * 1024, LDS_MAX = 160 * 1024;   // LDS_WG_BUDGET / LDS_WG_MAX of ovqe_sv.hip
 
 static bool compact_of(uint64_t hf, const std::vector<Rot> &prog, int K, metric::Compact *C) {
@@ -177,7 +161,7 @@ static void check_entries(int n, const metric::Compact &C, const Ham &H, const h
 static void replay(const metric::Compact &C, const hessian::Restricted &R, const std::vector<double> &theta, int K, std::vector<double> &M,
                    std::vector<double> &grad, double *energy) {
     const int nops = (int)C.ops.size(), ntab = (int)C.tab.size(), m = C.m;
-    const Lds L = lds_layout(C, K, true);
+    const SpHessLds L = lds_layout(C, K, true);
     CHECK(L.cs % 16 == 0 && L.ops % 16 == 0 && L.gk + (size_t)K * 8 <= L.ops && L.pairs + C.pairs.size() * 4 == L.bytes, "LDS regions");
     M.assign((size_t)K * K, 0.0);
     grad.assign((size_t)K, 0.0);
@@ -433,10 +417,10 @@ static void boundary() {
         for (const uint32_t pw : C.pairs) max_c = std::max(max_c, std::max(pw & 0xfffu, (pw >> 12) & 0xfffu));
         CHECK(C.m == metric::MAX_SUPPORT && max_c == 4095u && (int)C.support.size() == C.m, "m = %d, max index %u", C.m, max_c);
         CHECK((int)C.tab.size() == R && (int)C.ops.size() == R, "one op and one table entry per rotation");
-        const Lds Ls = lds_layout(C, K, true), Lu = lds_layout(C, K, false);
+        const SpHessLds Ls = lds_layout(C, K, true), Lu = lds_layout(C, K, false);
         const int form = form_of(C, K);
         CHECK(form == want_form[k], "R = %d: form %d, want %d", R, form, want_form[k]);
-        const Lds &L = form == 1 ? Ls : Lu;
+        const SpHessLds &L = form == 1 ? Ls : Lu;
         CHECK(((size_t)max_c + 1) * 8 <= L.t && L.mu + L.t == L.cs && L.cs % 16 == 0 && L.ops % 16 == 0, "vector regions");
         CHECK(L.cs + C.tab.size() * 16 == L.dk && L.wd + C.tab.size() * 8 == L.gk && L.gk + (size_t)K * 8 <= L.ops, "table regions");
         if (form == 1) CHECK(L.ops + C.ops.size() * 16 == L.pairs && L.pairs + C.pairs.size() * 4 == L.bytes, "staged regions");

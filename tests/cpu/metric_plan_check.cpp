@@ -261,20 +261,7 @@ static bool check_program(std::mt19937_64 &rng, int n, uint64_t hf, const std::v
 }
 
 // ---- boundary mode ------------------------------------------------------------------------------------------------------------------
-// the tangent kernel's dynamic LDS, restated from sp_metric_lds (sv_sparse.hpp, a HIP header): psi [mpad] at 0, the tangent [mpad], cos / sin
-// [ntab] as 16-byte pairs, the derivative coefficient [ntab] padded to an even count; staged: 16-byte op records [nops], pair words [npairs]
-struct Lds { size_t t, cs, dk, ops, pairs, bytes; };
-static Lds lds_layout(const metric::Compact &C, bool stage) {
-    const size_t mpad = (size_t)((C.m + 1) & ~1), ntab = C.tab.size();
-    Lds L;
-    L.t = mpad * 8;
-    L.cs = 2 * L.t;
-    L.dk = L.cs + ntab * 16;
-    L.ops = L.dk + ((ntab + 1) & ~(size_t)1) * 8;
-    L.pairs = L.ops + C.ops.size() * sizeof(metric::Op);
-    L.bytes = stage ? L.pairs + C.pairs.size() * 4 : L.ops;
-    return L;
-}
+// the tangent kernel's dynamic LDS is sp_metric_lds itself (sv_sparse_layout.hpp: the header the kernel and its launcher read)
 constexpr size_t LDS_BUDGET = 150 * 1024, LDS_MAX = 160 * 1024;   // LDS_WG_BUDGET / LDS_WG_MAX of ovqe_sv.hip
 
 // cube program: a single Y on bit r for r < n (the support doubles up to the whole register), then odd-Y strings of weight 2..5; every
@@ -330,9 +317,10 @@ static void boundary() {
         CHECK(C.m == metric::MAX_SUPPORT && max_cj == 4095u, "m = %d, max cj = %u", C.m, max_cj);
         CHECK((int)C.tab.size() == R && (int)C.ops.size() == R, "one op and one table entry per rotation: %zu, %zu", C.ops.size(), C.tab.size());
         // the LDS regions the kernel indexes: psi / t by ci, cj < mpad, cs / dk by e < ntab, the op records and pair words when staged
-        const Lds Ls = lds_layout(C, true), Lu = lds_layout(C, false);
+        const SpMetricArgs A = sp_metric_args(C, K);
+        const SpMetricLds Ls = sp_metric_lds(A, true), Lu = sp_metric_lds(A, false);
         const int form = Ls.bytes <= LDS_BUDGET ? 1 : Lu.bytes <= LDS_BUDGET ? 2 : 0;
-        const Lds &L = form == 1 ? Ls : Lu;
+        const SpMetricLds &L = form == 1 ? Ls : Lu;
         const size_t mpad = (size_t)((C.m + 1) & ~1);
         CHECK(((size_t)std::max(max_ci, max_cj) + 1) * 8 <= L.t && L.t + mpad * 8 <= L.cs, "psi / tangent region");
         CHECK(L.cs % 16 == 0 && L.cs + C.tab.size() * 16 <= L.dk && L.dk + C.tab.size() * 8 <= L.ops && L.ops % 16 == 0, "table regions");
