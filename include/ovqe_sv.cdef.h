@@ -101,6 +101,8 @@ int ovqe_metric_tensor(ovqe_handle h, const double *theta, int32_t K, double *me
 int ovqe_metric_info(ovqe_handle h, int64_t *info, int count);
 int ovqe_energy_hessian(ovqe_handle h, const double *theta, int32_t K, double *energy, double *grad, double *hess, double *asymmetry);
 int ovqe_hessian_info(ovqe_handle h, int64_t *info, int count);
+int ovqe_energy_gradient_batch(ovqe_handle h, int64_t B, const double *theta, int32_t K, double *energies, double *grads);
+int ovqe_gradient_batch_info(ovqe_handle h, int64_t *info, int count);
 int ovqe_sample(ovqe_handle h, int64_t n_shots, uint64_t seed, uint64_t stream, uint64_t first_shot, uint64_t *indices);
 int ovqe_measure_paulis(ovqe_handle h, uint64_t xbasis, uint64_t ybasis, int64_t n_shots, uint64_t seed, uint64_t stream,
                         uint64_t first_shot, int64_t T, const uint64_t *mask, const double *coeff, int64_t *term_sums,

@@ -141,6 +141,8 @@ int ovqe_set_stream(ovqe_handle h, void *hip_stream);
  * (B) GEOMETRY — defaults are the measured optimum on MI355X
  *   streaming path: "tile_bits" (-1 automatic: 12 for n >= 25, else 11; 0 = one sweep per op), "tile_low" (4), "apply_min_tiles" (256),
  *                     "index_streams"; "adjoint_tile_bits" (-1 automatic: 12 for n >= 25, else 11; 0 = one backward pass per run) of ovqe_adjoint_rotations
+ *                     "grad_batch_waves" (0 automatic; 1, 2, 4, 8: waves per workgroup of ovqe_energy_gradient_batch's kernel, other values read
+ *                     as 0), "grad_batch_workgroups" (0 automatic; otherwise a cap on its grid)
  *   fused / support-compacted kernels: "small_max_qubits", "small_batch_max_qubits", "sparse_grad" (1: all derivatives of a register of at most
  *                     16 qubits in one fused launch on the compact support; 0: the streaming adjoint pass), "sparse_renumber" (1)
  *   sector path: "sector_bits" / "sector_h_bits" (index bits per circuit / <H> tile, 0 automatic), "sector_tile_cap" (6500 amplitudes per
@@ -507,6 +509,34 @@ int ovqe_energy_hessian(ovqe_handle h, const double *theta, int32_t K, double *e
  * ops and pair words staged in LDS, 2 compact with both read from global memory [10] dynamic LDS bytes of the launch (0 on the streaming
  * path); zeros before the first call */
 int ovqe_hessian_info(ovqe_handle h, int64_t *info, int count);
+
+/* ---- exact gradients of a BATCH of parameter vectors: row b of theta[B x K] (row-major) gives energies[b] and grads[b*K .. b*K + K), what
+ * ovqe_energy_gradient(h, theta + b*K, K, ...) answers on the same handle — what a multi-start optimisation asks for in every iteration
+ * (openvqe_amd/common_files/multistart.py).  ROWS.  The single call's conventions: a parameter shared by several rotations sums their
+ * contributions, a parameter no rotation uses gives exact zeros, a gate program whose Clifford frame is open is evaluated with the
+ * conjugated Hamiltonian.  Rows do not influence each other.  REFUSALS.  Whatever ovqe_energy_gradient refuses (no program, no
+ * Hamiltonian: OVQE_ERR_STATE; K other than the program's, a shard handle: OVQE_ERR_INVALID; ...) is refused with the same code;
+ * B < 0 and a NULL theta / energies / grads with B K > 0 (energies: B > 0) give OVQE_ERR_INVALID; B = 0 returns OVQE_OK and touches
+ * nothing.  BOUNDS.  B K doubles of theta are read; B doubles of energies and B K of grads are written.  AFTER THE CALL the state
+ * buffer is unspecified, as after ovqe_energy; cached tables stay valid: ovqe_energy and ovqe_energy_batch before and after return the
+ * same bits.  Synchronises before it returns.
+ * TWO PATHS (ovqe_gradient_batch_info [0]).  1, compact support: the program whose single gradient runs in a one-wave form on the compact
+ * support — a compact program exists, at most 16 qubits, option "force_path" 0 or 3, option "sparse_grad" on, and psi, lambda, the
+ * cos/sin table and the weights of one wave within 150 KiB of LDS.  Nothing is planned or built: the tables are the single call's.  The
+ * whole batch runs in ONE launch of k_sparse_grad_batch: workgroups of 1, 2, 4 or 8 waves, a wave per row at a time, one copy of the op
+ * records and pair words per workgroup (staged in LDS, or read from global memory where they do not fit); geometry by
+ * openvqe_amd/csrc/sv_gradbatch_host.hpp, options "grad_batch_waves" and "grad_batch_workgroups".  The energy of a row is summed in a fixed
+ * order: equal rows give bit-identical energies wherever they sit in the batch.  LDS atomics add lambda and the weights as in the
+ * single kernel: gradients reproduce to rounding.  2, every other program (sector tables, streaming, literal gate lists): the rows one
+ * by one through the body of ovqe_energy_gradient.  Out of scope: batched forms of the sector and the streaming paths.
+ * Everything the call allocates is its own: the buffers of the energy paths are not touched. */
+int ovqe_energy_gradient_batch(ovqe_handle h, int64_t B, const double *theta, int32_t K, double *energies, double *grads);
+/* of the last ovqe_energy_gradient_batch call with B > 0, up to `count` entries of: [0] path (1 compact support, 2 row by row) [1] B [2] K
+ * [3] launches (path 1: 1; path 2: 0 — the single call's launches are not counted) [4] kernel form: 1 ops and pair words staged in LDS, 2
+ * read from global memory, 0 on path 2 [5] waves per workgroup [6] workgroups [7] dynamic LDS bytes of the launch [8] support size m
+ * [9] [10] HIP-event times in microseconds: the copy of theta to the device with the launch, the copy back ([4..10] are 0 on path 2);
+ * zeros before the first call */
+int ovqe_gradient_batch_info(ovqe_handle h, int64_t *info, int count);
 
 /* ---- finite-shot measurement: outcomes drawn from the state in the buffer, and energies with shot noise (what a submission with
  * nbshots > 0 asks of a QPU: openvqe_amd/qat_compat.py; every call site of the reference submits nbshots = 0, the exact paths above).

@@ -540,6 +540,30 @@ class Statevector:
         self._ck(self._L.ovqe_energy_gradient(self._h, theta if self._K else np.zeros(1), self._K, ctypes.byref(e), grad))
         return e.value, grad[: self._K]
 
+    def energy_gradient_batch(self, thetas):
+        """E and the exact gradient of every row of ``thetas`` (B, K) -> (energies[B], grads[B, K]); row b is what
+        ``energy_gradient(thetas[b])`` answers.  A program on the compact support runs the whole batch in one launch
+        (ovqe_energy_gradient_batch, csrc/gradbatch_host.inc; ``gradient_batch_info``), every other program row by row"""
+        thetas = np.ascontiguousarray(thetas, np.float64)
+        if thetas.ndim != 2 or thetas.shape[1] != self._K:
+            raise ValueError(f"expected a (B, {self._K}) array")
+        B, K = thetas.shape
+        energies = np.zeros(B, np.float64)
+        grads = np.zeros((B, K), np.float64)
+        self._ck(self._L.ovqe_energy_gradient_batch(self._h, B, thetas if thetas.size else np.zeros(1), K, energies if B else np.zeros(1),
+                                                    grads.reshape(-1) if grads.size else np.zeros(1)))
+        return energies, grads
+
+    def gradient_batch_info(self):
+        """figures of the last ``energy_gradient_batch`` call: path (1 compact support in one launch, 2 row by row), rows, parameters,
+        launches, kernel form (1 op records and pair words staged in LDS, 2 read from global memory, 0 on path 2), waves per workgroup,
+        workgroups, dynamic LDS bytes, support size, and the HIP-event times in microseconds of the copy of theta with the launch and of
+        the copy back"""
+        out = (ctypes.c_int64 * 11)()
+        self._ck(self._L.ovqe_gradient_batch_info(self._h, out, 11))
+        keys = ("path", "B", "K", "launches", "form", "waves", "workgroups", "lds_bytes", "support", "launch_us", "copy_back_us")
+        return dict(zip(keys, [int(v) for v in out]))
+
     def ground_state(self, tol=1e-10, max_iter=3000, seed=20250227):
         """lowest eigenpair of the stored Hamiltonian by device-side Lanczos; the eigenvector is left in the
         state buffer (``get_state``).  -> (energy, residual |H y - E y|, iterations)"""

@@ -251,9 +251,8 @@ extern "C" int ovqe_sector_ground_state(ovqe_handle h, double tol, int max_iter,
 } OVQE_CATCH(h)
 
 // ---- exact gradient by the adjoint method -------------------------------------------------------------------
-extern "C" int ovqe_energy_gradient(ovqe_handle h, const double *theta, int32_t K, double *energy, double *grad) try {
-    OVQE_ENTER(h);
-    if (!h || !energy || !grad) return OVQE_ERR_INVALID;
+// (the body of ovqe_energy_gradient; ovqe_energy_gradient_batch serves the rows of a program without a batched form through it)
+static int energy_gradient_body(ovqe_handle h, const double *theta, int32_t K, double *energy, double *grad) {
     int rc = check_theta(h, theta, K);
     if (rc) return rc;
     if (!h->ham.set) return fail(h, OVQE_ERR_STATE, "no Hamiltonian set (ovqe_set_hamiltonian)");
@@ -348,6 +347,12 @@ extern "C" int ovqe_energy_gradient(ovqe_handle h, const double *theta, int32_t 
     }
     *energy = e.x + h->ham.constant;
     return OVQE_OK;
+}
+
+extern "C" int ovqe_energy_gradient(ovqe_handle h, const double *theta, int32_t K, double *energy, double *grad) try {
+    OVQE_ENTER(h);
+    if (!h || !energy || !grad) return OVQE_ERR_INVALID;
+    return energy_gradient_body(h, theta, K, energy, grad);
 } OVQE_CATCH(h)
 
 // ---- backward step of the adjoint method on a caller-held (psi, lambda) pair: plain handles and shard handles -------------

@@ -14,7 +14,8 @@
 //   measure_host.inc finite-shot measurement: basis change, prefix sums, shots                         (sv_measure_host.hpp; kernels: sv_measure.hpp)
 //   subspace_host.inc  subspace-expansion matrices around the resident state: rows, expansion vectors, sigma = H Phi, Gram    (sv_subspace_host.hpp; kernels: sv_subspace.hpp, sv_rdm.hpp)
 //   hessian_host.inc  exact energy Hessian: restricted Hamiltonian on the metric's compact program, one launch; column stores and the backward walk    (sv_hessian_host.hpp; kernels: sv_sparse.hpp, sv_hessian.hpp)
-//   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc / abi_rdm.inc / abi_metric.inc / abi_measure.inc / abi_subspace.inc / abi_hessian.inc   extern "C" entry points by family (include/ovqe_sv.h)
+//   gradbatch_host.inc  exact gradients of a batch of parameter vectors on the compact support, one launch    (sv_gradbatch_host.hpp; kernel: sv_sparse.hpp)
+//   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc / abi_rdm.inc / abi_metric.inc / abi_measure.inc / abi_subspace.inc / abi_hessian.inc / abi_gradbatch.inc   extern "C" entry points by family (include/ovqe_sv.h)
 //   cross_host.inc   planned Pauli sums on a shard of the partitioned register, ovqe_xsum_*          (sv_cross_host.hpp; kernels: sv_cross.hpp)
 //   pool_host.inc    planned ADAPT pool screen on a shard, ovqe_xpool_*                              (sv_pool_host.hpp; kernels: sv_pool.hpp)
 // sv_cover_host.hpp (host-only) holds the table records planners and kernels share and the one cover rule, grow_tile_set(), that
@@ -53,6 +54,7 @@
 #include "sv_metric.hpp"
 #include "sv_hessian_host.hpp"
 #include "sv_hessian.hpp"
+#include "sv_gradbatch_host.hpp"
 #include "sv_measure.hpp"
 #include "sv_subspace.hpp"
 #include <hipcub/hipcub.hpp>
@@ -295,6 +297,7 @@ struct RdmDev;   // rdm_host.inc
 struct MetricDev;   // metric_host.inc
 struct SubspaceDev; // subspace_host.inc
 struct HessianDev;  // hessian_host.inc
+struct GradBatchDev;  // gradbatch_host.inc
 struct MeasureDev;   // measure_host.inc
 
 }  // namespace
@@ -522,6 +525,9 @@ struct ovqe_sv {
     SubspaceDev *subspace = nullptr; // buffers and figures of ovqe_subspace_matrices (first call)
     int opt_subspace_workspace_mb = 0; // cap of its store in MB (0: 60 % of the free device memory)
     HessianDev *hessian = nullptr;   // plan, buffers and figures of ovqe_energy_hessian (first call; its workspace cap is metric_workspace_mb)
+    GradBatchDev *grad_batch = nullptr;  // buffers and figures of ovqe_energy_gradient_batch (first call on its compact path)
+    int opt_grad_batch_waves = 0;        // waves per workgroup of k_sparse_grad_batch: 0 automatic (sv_gradbatch_host.hpp); 1, 2, 4, 8
+    int64_t opt_grad_batch_workgroups = 0;   // cap on its grid (0: none)
 };
 
 namespace {
@@ -1220,6 +1226,8 @@ void push_rotation(ovqe_handle h, uint64_t x, uint64_t z, double coeff, double p
 
 #include "hessian_host.inc"
 
+#include "gradbatch_host.inc"
+
 int check_theta(ovqe_handle h, const double *theta, int32_t K) {
     if (!h->prog_set) return fail(h, OVQE_ERR_STATE, "no program set (ovqe_set_program / ovqe_set_gate_program)");
     if (K != h->K) return fail(h, OVQE_ERR_INVALID, "K does not match the program's parameter count");
@@ -1332,6 +1340,7 @@ int ovqe_destroy(ovqe_handle h) try {
     free_measure(h->measure);
     free_subspace(h->subspace);
     free_hessian(h->hessian);
+    free_grad_batch(h->grad_batch);
     h->kept_blocks.flush();
     if (h->h_rp) (void)hipHostFree(h->h_rp);
     if (h->h_result) (void)hipHostFree(h->h_result);
@@ -1461,6 +1470,8 @@ int ovqe_set_option(ovqe_handle h, const char *name, int64_t value) try {
 #endif
     else if (k == "real_stream") h->opt_real_stream = (int)value;
     else if (k == "adjoint_tile_bits") h->opt_adjoint_tile_bits = (int)value;
+    else if (k == "grad_batch_waves") h->opt_grad_batch_waves = gradbatch::valid_waves(value) ? (int)value : 0;
+    else if (k == "grad_batch_workgroups") h->opt_grad_batch_workgroups = std::max<int64_t>(0, value);
     else if (k == "apply_min_tiles") h->opt_apply_min_tiles = (int)value;
     else if (k == "clifford_frame") h->opt_clifford_frame = (int)value;  // applies to the next ovqe_set_gate_program
     else if (k == "tile_bits" || k == "tile_low") {
@@ -1641,6 +1652,8 @@ int ovqe_norm2(ovqe_handle h, double *out) try {
 #include "abi_subspace.inc"
 
 #include "abi_hessian.inc"
+
+#include "abi_gradbatch.inc"
 
 // ---- measurement support ------------------------------------------------------------------------
 int ovqe_time_pauli_rotation(ovqe_handle h, uint64_t x, uint64_t z, double phi, int warmup, int reps, double *avg_ms) try {

@@ -33,15 +33,15 @@ struct SpRot { double c, sn; };                               // its rotation: c
 struct SpAmps { double u, v; };                               // a vector's two amplitudes (slot ci, slot cj)
 
 // STAGE: the op table and the pair words are copied to LDS once per launch, so that the chain op -> pair word -> amplitudes never
-// waits for global memory
-template <bool STAGE>
+// waits for global memory (NT: the threads that copy, `lane` one of them — a workgroup of several waves puts its barrier behind the call)
+template <bool STAGE, int NT = 64>
 __device__ __forceinline__ SpProgram sp_stage(unsigned char *smem, size_t ops_off, size_t pairs_off, const SpOp *ops, const uint32_t *pairs,
                                               int nops, int npairs, int lane) {
     if constexpr (STAGE) {
         SpOp *lops = reinterpret_cast<SpOp *>(smem + ops_off);
         uint32_t *lpairs = reinterpret_cast<uint32_t *>(smem + pairs_off);
-        for (int i = lane; i < nops; i += 64) lops[i] = ops[i];
-        for (int i = lane; i < npairs; i += 64) lpairs[i] = pairs[i];
+        for (int i = lane; i < nops; i += NT) lops[i] = ops[i];
+        for (int i = lane; i < npairs; i += NT) lpairs[i] = pairs[i];
         return {lops, lpairs};
     } else {
         return {ops, pairs};
@@ -763,6 +763,71 @@ __global__ __launch_bounds__(64) void k_sparse_grad(SparseArgs A, const double *
         if (lane == 0) energies[b] = etot + A.constant;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         // backward: the pair's weight g on the states after the op, then both states rotated back
+        sp_for_ops_down<64>(P, 0, A.nops, lane, [&](const SpPair &p) {
+            const SpRot r = sp_rot(cs, p);
+            const SpAmps a = sp_get(psi, p), l = sp_get(lam, p);
+            const double g = l.u * a.v - l.v * a.u;
+            __hip_atomic_fetch_add(&w[p.e], sp_signed(p, g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            sp_put(psi, p, sp_rotate_back(r, a));
+            sp_put(lam, p, sp_rotate_back(r, l));
+        });
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        sp_fold<64>(tabrots, A.ntab, w, gk, lane);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        for (int k = lane; k < A.K; k += 64) grads[b * A.K + k] = gk[k];
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+}
+
+// ... for a BATCH of parameter vectors (ovqe_energy_gradient_batch): workgroups of NW waves, wave v of workgroup g takes the rows
+// g NW + v, + gridDim.x NW, ...  What is the same for every row — the op records and the pair words — is staged ONCE per workgroup
+// (STAGE) or read from global memory; what a row owns — psi, lambda, the cos/sin table, w, gk — is the wave's private region of
+// sp_grad_batch_lds.  The row body is k_sparse_grad's, fences included: a wave's LDS traffic stays in order and no other wave touches
+// its region, so the ONE barrier of the kernel is the one behind the staging.  Every wave reaches it, also a wave that owns no row; none
+// is inside the row loop (the waves of a workgroup finish their rows at different times).  The energy of a row is summed in the fixed
+// order of k_sparse_grad: equal rows give equal bits wherever they sit in the batch; the gradient reproduces to rounding.
+template <int NW, bool STAGE>
+__global__ __launch_bounds__(NW * 64) void k_sparse_grad_batch(SparseArgs A, const double *__restrict__ theta,
+                                                               const SmallRot *__restrict__ tabrots, const SpOp *__restrict__ ops,
+                                                               const uint32_t *__restrict__ pairs, const SpEntry *__restrict__ entries,
+                                                               double *__restrict__ energies, double *__restrict__ grads) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const SpGradBatchLds L = sp_grad_batch_lds(A, NW, STAGE);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const SpProgram P = sp_stage<STAGE, NW * 64>(smem, L.ops, L.pairs, ops, pairs, A.nops, A.npairs, (int)threadIdx.x);
+    __syncthreads();
+    unsigned char *mine = smem + (size_t)wave * L.stride;
+    double *psi = reinterpret_cast<double *>(mine);
+    double *lam = reinterpret_cast<double *>(mine + L.lam);
+    double2 *cs = reinterpret_cast<double2 *>(mine + L.cs);
+    double *w = reinterpret_cast<double *>(mine + L.w);
+    double *gk = reinterpret_cast<double *>(mine + L.gk);
+    for (int64_t b = (int64_t)blockIdx.x * NW + wave; b < A.B; b += (int64_t)gridDim.x * NW) {
+        const double *th = theta + b * A.K;
+        for (int i = lane; i < A.mpad; i += 64) {
+            psi[i] = i == A.hf ? 1.0 : 0.0;
+            lam[i] = 0.0;
+        }
+        sp_fill_table<64>(tabrots, A.ntab, lane, cs, [&](const SmallRot &sr) { return sr.coeff * th[sr.pidx]; },
+                          [&](int e, const SmallRot &) { w[e] = 0.0; });
+        for (int k = lane; k < A.K; k += 64) gk[k] = 0.0;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // forward
+        sp_for_ops<64>(P, 0, A.nops, lane, [&](const SpPair &p) { sp_rotate_pair(psi, cs, p); });
+        // lambda = H psi, E = <psi|lambda>: the entries from global memory — every wave reads the same records, they stay in L2
+        double acc = 0.0;
+#pragma unroll 4
+        for (int e = lane; e < A.nent; e += 64) {
+            const SpEntry en = entries[e];
+            const SpAmps a = sp_entry_amps(en, psi);
+            acc += en.c * a.u * a.v;
+            sp_apply_entry(en, {a}, {lam});
+        }
+        const double etot = wave_sum(acc);
+        if (lane == 0) energies[b] = etot + A.constant;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // backward
         sp_for_ops_down<64>(P, 0, A.nops, lane, [&](const SpPair &p) {
             const SpRot r = sp_rot(cs, p);
             const SpAmps a = sp_get(psi, p), l = sp_get(lam, p);

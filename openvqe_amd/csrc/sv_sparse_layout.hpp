@@ -73,6 +73,18 @@ OVQE_LAYOUT_FN SpGradLds sp_grad_lds(const SparseArgs &A, bool stage) {
     return {lam, cs, w, gk, ops, pairs, stage ? pairs + (size_t)A.npairs * sizeof(uint32_t) : ops};
 }
 
+// k_sparse_grad_batch: nw waves per workgroup, one parameter vector per wave at a time.  Every wave has its own psi, lambda, cos/sin
+// table, w and gk — the regions of sp_grad_lds at the same offsets (lam, cs, w, gk), wave v's at v * stride, the stride a multiple of
+// 16 bytes; ONE copy of the op records and pair words behind the last wave serves all of them (stage)
+struct SpGradBatchLds { size_t lam, cs, w, gk, stride, ops, pairs, bytes; };   // wave v's psi ([mpad]) is at v * stride
+OVQE_LAYOUT_FN SpGradBatchLds sp_grad_batch_lds(const SparseArgs &A, int nw, bool stage) {
+    const SpGradLds W = sp_grad_lds(A, false);
+    const size_t stride = (W.bytes + 15) & ~(size_t)15;
+    const size_t ops = (size_t)nw * stride;                       // [nops]   (stage)
+    const size_t pairs = ops + (size_t)A.nops * sizeof(SpOp);     // [npairs] (stage)
+    return {W.lam, W.cs, W.w, W.gk, stride, ops, pairs, stage ? pairs + (size_t)A.npairs * sizeof(uint32_t) : ops};
+}
+
 // k_sparse_grad_wg
 struct SpGradWgLds { size_t lam, cs, w, gk, bytes; };   // psi ([mpad] = support + 128 spare slots) is at 0
 OVQE_LAYOUT_FN SpGradWgLds sp_grad_wg_lds(const SparseArgs &A) {

@@ -74,6 +74,14 @@ class _Evaluator:
         self._activate()
         return self.sv.energy_gradient(np.asarray(theta, dtype=np.float64)[: self.n_params])
 
+    def energy_gradient_batch(self, thetas):
+        """(E[B], dE/dtheta[B, K]) of the rows of ``thetas`` in one device call (ovqe_energy_gradient_batch)"""
+        self._activate()
+        thetas = np.asarray(thetas, dtype=np.float64)[:, : self.n_params]
+        if replicas.active(self.nbqbits):     # the rows of the batch shared between the ranks, as energy_batch
+            return replicas.energy_gradient_batch(self.sv, thetas)
+        return self.sv.energy_gradient_batch(thetas)
+
     def metric_tensor(self, theta):
         """Fubini-Study metric of the ansatz state at ``theta`` (ovqe_metric_tensor), (K, K)"""
         self._activate()

@@ -129,6 +129,17 @@ class PartitionedStatevector:
         out[: grad.shape[0]] = grad       # (parameters past the last one a rotation uses have a zero derivative)
         return e, out
 
+    def energy_gradient_batch(self, thetas):
+        """``energy_gradient`` of every row of ``thetas`` -> (energies[B], grads[B, K]); one evaluation at a time: every rank works on
+        the same one"""
+        thetas = np.ascontiguousarray(thetas, np.float64)
+        if thetas.ndim != 2 or thetas.shape[1] != self._K:
+            raise ValueError(f"expected a (B, {self._K}) array")
+        energies, grads = np.zeros(thetas.shape[0]), np.zeros(thetas.shape)
+        for b, t in enumerate(thetas):
+            energies[b], grads[b] = self.energy_gradient(t)
+        return energies, grads
+
     def prepare_state(self, theta):
         self.sharded.run_program(self._program(), self._theta(theta))
 

@@ -118,6 +118,46 @@ def energy_batch(sv, thetas):
     return gather(part, thetas.shape[0])
 
 
+def gather_rows(values, count):
+    """every rank's share of the rows of a (``count``, width) float64 result -> the whole array on every rank (one all-gather of
+    padded blocks; ``my_slice`` says whose rows are whose)"""
+    import torch
+    d = _dist()
+    w = world()
+    vals = np.ascontiguousarray(values, np.float64)
+    width = int(vals.shape[1])
+    most = (int(count) + w - 1) // w
+    dev = "cuda:%d" % device() if d.get_backend() == "nccl" else "cpu"
+    mine = torch.zeros(max(most * width, 1), dtype=torch.float64, device=dev)
+    if vals.size:
+        mine[: vals.size] = torch.from_numpy(vals.reshape(-1)).to(dev)
+    blocks = [torch.empty_like(mine) for _ in range(w)]
+    d.all_gather(blocks, mine)
+    out = np.empty((int(count), width), np.float64)
+    base, extra = divmod(int(count), w)
+    at = 0
+    for r in range(w):
+        n = base + (1 if r < extra else 0)
+        out[at:at + n] = blocks[r][: n * width].cpu().numpy().reshape(n, width)
+        at += n
+    return out
+
+
+def energy_gradient_batch(sv, thetas):
+    """``sv.energy_gradient_batch`` with the rows of ``thetas`` shared between the ranks -> (energies[B], grads[B, K]) on every rank:
+    the energy and the flattened gradient of a row travel together"""
+    thetas = np.ascontiguousarray(thetas, np.float64)
+    B, K = thetas.shape
+    a, b = my_slice(B)
+    part = np.zeros((b - a, K + 1))
+    if b > a:
+        e, g = sv.energy_gradient_batch(thetas[a:b])
+        part[:, 0] = e
+        part[:, 1:] = g
+    rows = gather_rows(part, B)
+    return rows[:, 0].copy(), rows[:, 1:].copy()
+
+
 _pool_slices = {}
 
 

@@ -4,7 +4,7 @@ reference's; the simulation runs in libovqe_sv instead of myQLM)."""
 import numpy as np
 import scipy.optimize
 
-from ..common_files import bfgs, natural_gradient, newton
+from ..common_files import bfgs, multistart, natural_gradient, newton
 
 from ..common_files.circuit import count
 from ..evaluator import UCCEvaluator
@@ -24,6 +24,13 @@ class EnergyUCC:
     #: opt-in: Newton trust-region steps (common_files/newton.py, scipy's trust-exact) instead of BFGS — energy, exact gradient and exact
     #: Hessian of every iterate in one device call (ovqe_energy_hessian); ``tolerance`` bounds the gradient's 2-norm
     newton = False
+    #: opt-in: L-BFGS from ``multistart`` starting points in lock-step (common_files/multistart.py) instead of one BFGS run — the exact
+    #: gradients of all active starts in one device call per iteration (ovqe_energy_gradient_batch); the best start is returned.  Below 2:
+    #: off.  Start 0 is the given x0, the others x0 + uniform(-multistart_spread, multistart_spread) drawn with ``multistart_seed``;
+    #: ``tolerance`` bounds the largest gradient component
+    multistart = 0
+    multistart_spread = 0.1
+    multistart_seed = 0
 
     def __init__(self):
         self._cache = {}
@@ -67,6 +74,25 @@ class EnergyUCC:
     def _minimize(self, hamiltonian_sp, ops, hf_init_sp, x0, energies, method, tolerance):
         fun = lambda theta: self.ucc_action(theta, hamiltonian_sp, ops, hf_init_sp, energies)  # noqa: E731
         jac = None
+        if self.multistart >= 2:
+            if self.newton or self.natural_gradient:
+                raise ValueError("multistart runs L-BFGS on the batched exact gradient: it does not combine with newton or natural_gradient")
+            n_params = min(len(ops), len(x0))
+            ev = self._evaluator(hamiltonian_sp, ops, hf_init_sp, n_params)
+            x0 = np.asarray(x0, dtype=float).reshape(-1)
+            rng = np.random.default_rng(self.multistart_seed)
+            X0 = np.tile(x0, (int(self.multistart), 1))
+            X0[1:] += rng.uniform(-self.multistart_spread, self.multistart_spread, size=(int(self.multistart) - 1, x0.size))
+
+            def fun_grad_batch(X):   # (parameters beyond the operators are not applied: zero derivatives)
+                e, g = ev.energy_gradient_batch(X)
+                full = np.zeros(X.shape)
+                full[:, :n_params] = g
+                return e, full
+
+            res = multistart.minimize(fun_grad_batch, X0, tol=tolerance, maxiter=50000)
+            energies.extend(res.energies)
+            return res
         if self.newton:
             n_params = min(len(ops), len(x0))
             ev = self._evaluator(hamiltonian_sp, ops, hf_init_sp, n_params)
