@@ -538,6 +538,62 @@ int ovqe_energy_gradient_batch(ovqe_handle h, int64_t B, const double *theta, in
  * zeros before the first call */
 int ovqe_gradient_batch_info(ovqe_handle h, int64_t *info, int count);
 
+/* ---- variational quantum deflation (VQD): excited states as minima of C(theta) = <psi(theta)|H|psi(theta)> + sum_j beta_j |<phi_j|psi(theta)>|^2
+ * with the states phi_j found so far (openvqe_amd/excited.py: vqd).  The penalty is the rank-J operator sum_j beta_j |phi_j><phi_j| beside
+ * H: the adjoint gradient is the pass of ovqe_energy_gradient with lambda = H psi + sum_j beta_j phi_j <phi_j|psi>.
+ *
+ * ovqe_deflation_push: a copy of the 2^n complex amplitudes in the state buffer becomes vector J of the handle, J the number held so
+ * far, with weight beta — whatever the buffer holds: the result of ovqe_prepare_state, a Lanczos eigenvector, a Ritz state, what
+ * ovqe_set_state wrote.  The vector is taken as it is, not normalised.  The state buffer is only read: the same bits afterwards.  The
+ * vectors belong to the REGISTER, not to a program: they survive ovqe_set_program, ovqe_set_gate_program and ovqe_set_hamiltonian.  At
+ * most 32 are held, each 16 * 2^n bytes of device memory owned by the handle (freed by ovqe_deflation_truncate and ovqe_destroy).
+ * OVQE_ERR_INVALID for a beta that is not finite or negative and for a 33rd vector; OVQE_ERR_STATE on a shard of a partitioned
+ * register and under option "real_state"; OVQE_ERR_ALLOC, with the bytes needed in the text, when the vector is more than 60 % of the
+ * free device memory.  Synchronises before it returns. */
+int ovqe_deflation_push(ovqe_handle h, double beta);
+/* keeps the first `count` vectors and frees the others; 0 clears the set.  OVQE_ERR_INVALID for a count outside 0 .. the number held. */
+int ovqe_deflation_truncate(ovqe_handle h, int32_t count);
+/* *count = the number of vectors held */
+int ovqe_deflation_count(ovqe_handle h, int32_t *count);
+/* DEFLATED energies and gradients of a batch: for row b of theta[B x K] (row-major), with psi = psi(theta_b) of the stored program and
+ * the J vectors held,
+ *     o_bj = <phi_j|psi>,   energies[b] = <psi|H|psi> + constant,   costs[b] = energies[b] + sum_j beta_j |o_bj|^2,
+ *     grads[b*K .. b*K + K) = dC/dtheta,   overlaps_re_im = the B x J complex o_bj, row-major, (re, im) pairs.
+ * energies and overlaps_re_im may be NULL.  With no vector held the call is valid: costs equal energies to the bit, overlaps_re_im is
+ * not touched.  ROWS.  The conventions of ovqe_energy_gradient_batch: a shared parameter sums its rotations' contributions, an unused
+ * one gives exact zeros, rows do not influence each other.  REFUSALS.  Those of ovqe_energy_gradient_batch with its codes and texts,
+ * `costs` in the place of its `energies`: no program, no Hamiltonian: OVQE_ERR_STATE; K other than the program's, a shard handle, B < 0,
+ * a NULL theta / costs / grads with B K > 0 (costs: B > 0): OVQE_ERR_INVALID; B = 0 returns OVQE_OK and touches nothing.  Further:
+ * OVQE_ERR_STATE under option "real_state", and for a gate program whose Clifford frame is OPEN — the vectors live in the caller's
+ * frame, the state such a program evaluates does not; option "clifford_frame" = 0 runs such a list literally.  BOUNDS.  B K doubles of
+ * theta are read; B doubles of costs (and of energies), B K of grads and 2 B J of overlaps_re_im are written.  AFTER THE CALL the state
+ * buffer is unspecified; cached tables stay valid: ovqe_energy, ovqe_energy_batch and ovqe_energy_gradient before and after return what
+ * they returned.  Synchronises before it returns.
+ * TWO PATHS (ovqe_deflation_info [0]).  1, compact support: exactly the programs ovqe_energy_gradient_batch runs on its path 1, planned by
+ * the same rule under the same options ("grad_batch_waves", "grad_batch_workgroups"), the whole batch in ONE launch of
+ * k_sparse_vqd_batch: the row body of k_sparse_grad_batch with one phase between lambda = H psi and the backward walk.  The vectors
+ * enter as REAL rows over the slots of the compact state, read from global memory (no LDS beyond that kernel's): Re phi_j restricted to
+ * the support, and Im phi_j as a second row with the same weight when it is non-zero anywhere on the support; psi is zero off the
+ * support, so the restriction is exact.  The rows are gathered by k_deflate_gather and cached on the handle until the compact program
+ * is rebuilt or the set of vectors changes.  Cost, energy and overlaps of a row are summed in fixed orders: equal rows give
+ * bit-identical costs, energies and overlaps wherever they sit in the batch; LDS atomics add lambda and the weights as in the single
+ * kernel: gradients reproduce to rounding.  2, streaming — every other program, those that otherwise run on the sector tables
+ * included, and literal gate lists: row by row psi = U(theta)|hf> on the streaming kernels, lambda = H psi, the overlaps four vectors per
+ * pass over psi (k_deflate_dots: per-workgroup partials summed in a fixed order, bit-identical from call to call), lambda += sum_j
+ * beta_j o_j phi_j four vectors per pass (k_deflate_axpy), then the backward walk of ovqe_energy_gradient.  COST of path 2 beyond the
+ * single gradient: J extra reads of 16 * 2^n bytes for the overlaps and J more for lambda, per row.  Out of scope: deflation on the
+ * sector tables and on the partitioned register, open Clifford frames, a deflated Hessian or metric. */
+int ovqe_deflated_gradient_batch(ovqe_handle h, int64_t B, const double *theta, int32_t K, double *costs, double *grads, double *energies,
+                                 double *overlaps_re_im);
+/* of the last ovqe_deflated_gradient_batch call with B > 0, up to `count` entries of: [0] path (1 compact support, 2 streaming) [1] B [2] K
+ * [3] J, the vectors held [4] real rows of path 1 (J + the vectors with an imaginary part on the support; 0 on path 2) [5] launches
+ * (path 1: 1; path 2: the k_deflate_dots, k_reduce and k_deflate_axpy launches of all rows — those of the single gradient are not
+ * counted) [6] kernel form: 1 ops and pair words staged in LDS, 2 read from global memory, 0 on path 2 [7] waves per workgroup
+ * [8] workgroups [9] dynamic LDS bytes of the launch [10] support size m [11] gather launches of this call (0: the cached rows served)
+ * [12] [13] HIP-event times in microseconds: the copy of theta to the device with the launch, the copy back ([6..13] are 0 on path 2);
+ * zeros before the first call; a refused call leaves no figures */
+int ovqe_deflation_info(ovqe_handle h, int64_t *info, int count);
+
 /* ---- finite-shot measurement: outcomes drawn from the state in the buffer, and energies with shot noise (what a submission with
  * nbshots > 0 asks of a QPU: openvqe_amd/qat_compat.py; every call site of the reference submits nbshots = 0, the exact paths above).
  * Plain handles of any size; OVQE_ERR_STATE on a shard of a partitioned register and under option "real_state".  The state buffer is

@@ -348,6 +348,13 @@ class Statevector:
         const = _real_coeff(getattr(hamiltonian, "constant_coeff", 0.0) or 0.0, "observable constant")
         self._ck(self._L.ovqe_set_hamiltonian(self._h, xs.shape[0], xs, zs, coeff, const))
         self._ham_terms = int(xs.shape[0])
+        self._ham_norm1 = float(np.abs(coeff).sum())
+
+    def hamiltonian_norm1(self):
+        """sum_t |c_t| of the stored Hamiltonian, without its constant: a bound on its spectral radius"""
+        if getattr(self, "_ham_norm1", None) is None:
+            raise RuntimeError("no Hamiltonian set")
+        return self._ham_norm1
 
     def set_rotation_program(self, xs, zs, coeffs, pidx, n_params, hf_init, phi0=None):
         xs = np.ascontiguousarray(xs, np.uint64)
@@ -562,6 +569,50 @@ class Statevector:
         out = (ctypes.c_int64 * 11)()
         self._ck(self._L.ovqe_gradient_batch_info(self._h, out, 11))
         keys = ("path", "B", "K", "launches", "form", "waves", "workgroups", "lds_bytes", "support", "launch_us", "copy_back_us")
+        return dict(zip(keys, [int(v) for v in out]))
+
+    # -- variational quantum deflation (ovqe_deflation_*, ovqe_deflated_gradient_batch, csrc/deflate_host.inc) ---------------------
+    def deflation_push(self, beta):
+        """the state in the buffer, as it is, becomes the next deflation vector phi_j of the handle with weight ``beta`` >= 0 (at most
+        32; they survive a new program or Hamiltonian) -> the number of vectors held"""
+        self._ck(self._L.ovqe_deflation_push(self._h, float(beta)))
+        return self.deflation_count()
+
+    def deflation_truncate(self, count=0):
+        """keeps the first ``count`` deflation vectors, frees the rest (0: all of them)"""
+        self._ck(self._L.ovqe_deflation_truncate(self._h, int(count)))
+
+    def deflation_count(self):
+        out = ctypes.c_int32()
+        self._ck(self._L.ovqe_deflation_count(self._h, ctypes.byref(out)))
+        return out.value
+
+    def deflated_gradient_batch(self, thetas):
+        """C = <H> + sum_j beta_j |<phi_j|psi>|^2 with the deflation vectors held, for every row of ``thetas`` (B, K)
+        -> (costs[B], dC/dtheta[B, K], energies[B], overlaps[B, J] complex).  A program on the compact support runs the whole batch in
+        one launch (``deflation_info``), every other program row by row on the streaming kernels"""
+        thetas = np.ascontiguousarray(thetas, np.float64)
+        if thetas.ndim != 2 or thetas.shape[1] != self._K:
+            raise ValueError(f"expected a (B, {self._K}) array")
+        B, K = thetas.shape
+        J = self.deflation_count()
+        costs, energies = np.zeros(B, np.float64), np.zeros(B, np.float64)
+        grads = np.zeros((B, K), np.float64)
+        overlaps = np.zeros((B, J), np.complex128)
+        self._ck(self._L.ovqe_deflated_gradient_batch(
+            self._h, B, thetas if thetas.size else np.zeros(1), K, costs if B else np.zeros(1), grads.reshape(-1) if grads.size else np.zeros(1),
+            energies if B else np.zeros(1), overlaps.view(np.float64).reshape(-1) if overlaps.size else None))
+        return costs, grads, energies, overlaps
+
+    def deflation_info(self):
+        """figures of the last ``deflated_gradient_batch`` call: path (1 compact support in one launch, 2 streaming), rows, parameters,
+        vectors, real rows of path 1, launches, kernel form, waves per workgroup, workgroups, dynamic LDS bytes, support size, gather
+        launches of the call (0: the cached rows served), and the HIP-event times in microseconds of the copy of theta with the launch
+        and of the copy back"""
+        out = (ctypes.c_int64 * 14)()
+        self._ck(self._L.ovqe_deflation_info(self._h, out, 14))
+        keys = ("path", "B", "K", "J", "rows", "launches", "form", "waves", "workgroups", "lds_bytes", "support", "gather_launches",
+                "launch_us", "copy_back_us")
         return dict(zip(keys, [int(v) for v in out]))
 
     def ground_state(self, tol=1e-10, max_iter=3000, seed=20250227):

@@ -1,0 +1,121 @@
+// abi_deflate.inc — C-ABI entry points: the deflation vectors of a handle and deflated energies and gradients (deflate_host.inc), and
+// the streaming path of the latter.  Included by ovqe_sv.hip inside extern "C".
+
+// One row on the streaming path: psi = U(theta)|hf>, lambda = H psi, E = Re <psi|lambda>, o_j = <phi_j|psi> (k_deflate_dots, four vectors
+// per pass, the blocks' partials summed by k_reduce into slot j of d_result), lambda += sum_j beta_j o_j phi_j (k_deflate_axpy, o_j read
+// on the device), the backward walk of ovqe_energy_gradient on (psi, lambda).  *launches += the deflation launches made.
+static int deflated_row_streaming(ovqe_handle h, const double *theta, int32_t K, double *cost, double *grad, double *energy, double2 *o,
+                                  int64_t *launches) {
+    DeflateDev &D = deflate_dev(h);
+    const int J = (int)D.vecs.size(), rb = reduce_blocks(h->namps), nb = adjoint_walk_blocks(h);
+    int rc = run_program_streaming(h, theta);
+    if (!rc) rc = ensure_scratch(h, 0);
+    if (!rc) rc = ensure(h, h->d_partials, (size_t)std::max(DEFLATE_CHUNK * rb, ADJ_MAX_ROT * nb) * sizeof(double2));
+    if (!rc) rc = ensure(h, h->d_result, 64 * sizeof(double2));
+    if (rc) return rc;
+    amp_t *lam = h->scratch[0];
+    double2 e = make_double2(0.0, 0.0);
+    rc = apply_hamiltonian(h, lam, h->state, 0.0);
+    if (!rc) rc = vec_dot(h, h->state, lam, h->namps, &e);
+    if (rc) return rc;
+    for (int j0 = 0; j0 < J; j0 += DEFLATE_CHUNK) {
+        DeflChunk C = {};
+        C.count = std::min(DEFLATE_CHUNK, J - j0);
+        for (int k = 0; k < C.count; ++k) {
+            C.v[k] = D.vecs[j0 + k];
+            C.beta[k] = D.betas[j0 + k];
+        }
+        hipLaunchKernelGGL(k_deflate_dots, dim3(rb), dim3(256), 0, h->stream, C, (const amp_t *)h->state, h->namps, (double2 *)h->d_partials.p);
+        HIPC(h, hipGetLastError());
+        for (int k = 0; k < C.count; ++k)
+            if ((rc = enqueue_reduce(h, (const double2 *)h->d_partials.p + (size_t)k * rb, rb, j0 + k))) return rc;
+        hipLaunchKernelGGL(k_deflate_axpy, dim3(rb), dim3(256), 0, h->stream, C, (const double2 *)h->d_result.p + j0, lam, h->namps);
+        HIPC(h, hipGetLastError());
+        *launches += 2 + C.count;
+    }
+    if (J > 0 && (rc = fetch_result(h, o, J))) return rc;
+    if ((rc = adjoint_walk(h, lam, K, grad))) return rc;
+    double c = e.x + h->ham.constant;
+    *energy = c;
+    for (int j = 0; j < J; ++j) c += D.betas[j] * (o[j].x * o[j].x + o[j].y * o[j].y);
+    *cost = c;
+    return OVQE_OK;
+}
+
+int ovqe_deflation_push(ovqe_handle h, double beta) try {
+    OVQE_ENTER(h);
+    if (!h) return OVQE_ERR_INVALID;
+    if (h->n_global) return fail(h, OVQE_ERR_STATE, "ovqe_deflation_push: not available on a shard of a partitioned register");
+    if (h->opt_real_state) return fail(h, OVQE_ERR_STATE, "ovqe_deflation_push: not available under option real_state (the buffer holds 8-byte amplitudes)");
+    if (!std::isfinite(beta) || beta < 0.0) return fail(h, OVQE_ERR_INVALID, "ovqe_deflation_push: beta must be finite and not negative");
+    if (h->deflate && h->deflate->vecs.size() >= (size_t)DEFLATE_MAX)
+        return fail(h, OVQE_ERR_INVALID, "ovqe_deflation_push: a handle holds at most " + std::to_string(DEFLATE_MAX) + " vectors");
+    return deflate_capture(h, beta);
+} OVQE_CATCH(h)
+
+int ovqe_deflation_truncate(ovqe_handle h, int32_t count) try {
+    OVQE_ENTER(h);
+    if (!h) return OVQE_ERR_INVALID;
+    const size_t have = h->deflate ? h->deflate->vecs.size() : 0;
+    if (count < 0 || (size_t)count > have)
+        return fail(h, OVQE_ERR_INVALID, "ovqe_deflation_truncate: count is outside 0 .. " + std::to_string(have));
+    if (!h->deflate) return OVQE_OK;
+    return deflate_truncate(h, count);
+} OVQE_CATCH(h)
+
+int ovqe_deflation_count(ovqe_handle h, int32_t *count) try {
+    OVQE_ENTER(h);
+    if (!h || !count) return OVQE_ERR_INVALID;
+    *count = h->deflate ? (int32_t)h->deflate->vecs.size() : 0;
+    return OVQE_OK;
+} OVQE_CATCH(h)
+
+int ovqe_deflated_gradient_batch(ovqe_handle h, int64_t B, const double *theta, int32_t K, double *costs, double *grads, double *energies,
+                                 double *overlaps_re_im) try {
+    OVQE_ENTER(h);
+    if (!h) return OVQE_ERR_INVALID;
+    if (B < 0) return fail(h, OVQE_ERR_INVALID, "ovqe_deflated_gradient_batch: B is negative");
+    // what ovqe_energy_gradient_batch refuses, with its codes
+    if (!h->prog_set) return fail(h, OVQE_ERR_STATE, "no program set (ovqe_set_program / ovqe_set_gate_program)");
+    if (K != h->K) return fail(h, OVQE_ERR_INVALID, "K does not match the program's parameter count");
+    if (!h->ham.set) return fail(h, OVQE_ERR_STATE, "no Hamiltonian set (ovqe_set_hamiltonian)");
+    if (h->n_global) return fail(h, OVQE_ERR_INVALID, "ovqe_deflated_gradient_batch is single-device, as ovqe_energy_gradient: not available on a shard handle");
+    if (h->opt_real_state) return fail(h, OVQE_ERR_STATE, "ovqe_deflated_gradient_batch: not available under option real_state (the buffer holds 8-byte amplitudes)");
+    if (h->frame_open)
+        return fail(h, OVQE_ERR_STATE, "ovqe_deflated_gradient_batch: the gate program's Clifford frame is open — the stored vectors live in the caller's frame, "
+                                       "the evaluated state does not; option \"clifford_frame\" = 0 runs such a list literally");
+    if (B == 0) return OVQE_OK;
+    if (!costs) return fail(h, OVQE_ERR_INVALID, "ovqe_deflated_gradient_batch: costs is NULL");
+    if (K > 0 && (!theta || !grads)) return fail(h, OVQE_ERR_INVALID, std::string("ovqe_deflated_gradient_batch: ") + (theta ? "grads" : "theta") + " is NULL");
+    if (B > ((int64_t)1 << 40) / std::max<int64_t>(K, 1)) return fail(h, OVQE_ERR_INVALID, "ovqe_deflated_gradient_batch: B x K is out of range");
+    {
+        bool done = false;
+        const int rc = run_vqd_batch(h, B, theta, costs, grads, energies, overlaps_re_im, &done);
+        if (rc || done) return rc;
+    }
+    // path 2: row by row on the streaming kernels
+    DeflateDev &D = deflate_dev(h);
+    const int64_t J = (int64_t)D.vecs.size();
+    double none = 0.0, e = 0.0;   // (K = 0: nothing is written through the gradient pointer)
+    double2 o[DEFLATE_MAX];
+    int64_t launches = 0;
+    for (int64_t b = 0; b < B; ++b) {
+        if (int rc = deflated_row_streaming(h, theta + b * K, K, costs + b, K > 0 ? grads + b * K : &none, &e, o, &launches)) return rc;
+        if (energies) energies[b] = e;
+        if (overlaps_re_im)
+            for (int64_t j = 0; j < J; ++j) {
+                overlaps_re_im[2 * (b * J + j)] = o[j].x;
+                overlaps_re_im[2 * (b * J + j) + 1] = o[j].y;
+            }
+    }
+    const int64_t info[14] = {2, B, K, J, 0, launches, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::copy(info, info + 14, D.info);
+    return OVQE_OK;
+} OVQE_CATCH(h)
+
+int ovqe_deflation_info(ovqe_handle h, int64_t *info, int count) try {
+    OVQE_ENTER(h);
+    if (!h || !info || count < 0) return OVQE_ERR_INVALID;
+    for (int i = 0; i < count && i < 14; ++i) info[i] = h->deflate ? h->deflate->info[i] : 0;
+    return OVQE_OK;
+} OVQE_CATCH(h)

@@ -251,54 +251,18 @@ extern "C" int ovqe_sector_ground_state(ovqe_handle h, double tol, int max_iter,
 } OVQE_CATCH(h)
 
 // ---- exact gradient by the adjoint method -------------------------------------------------------------------
-// (the body of ovqe_energy_gradient; ovqe_energy_gradient_batch serves the rows of a program without a batched form through it)
-static int energy_gradient_body(ovqe_handle h, const double *theta, int32_t K, double *energy, double *grad) {
-    int rc = check_theta(h, theta, K);
-    if (rc) return rc;
-    if (!h->ham.set) return fail(h, OVQE_ERR_STATE, "no Hamiltonian set (ovqe_set_hamiltonian)");
-    if (h->n_global) return fail(h, OVQE_ERR_INVALID, "ovqe_energy_gradient is single-device: on a shard handle run the backward steps with ovqe_adjoint_rotations "
-                                                     "(openvqe_amd/distributed.py: program_energy_gradient)");
-    FrameHamGuard frame_guard(h);
-    {   // small registers: forward, H psi and the backward pass in one launch on the compact support
-        bool done = false;
-        rc = run_sparse_gradient(h, theta, energy, grad, &done);
-        if (rc || done) return rc;
-    }
-    if (h->opt_real_stream && h->prog_real_ok && tile_ok(h, true) && h->ham.groups.size() >= 3) {
-        // real-amplitude program on a sparse support: the whole adjoint pass on the sector tables
-        rc = sector_prepare(h, true);
-        if (rc) return rc;
-        if (h->sec.valid && h->sec.h_tables && sector_gradient_fits(h)) {   // (else: tiles sized for energies only, "sector_tile_cap")
-            bool ok = false;
-            rc = run_sector_gradient(h, theta, energy, grad, &ok);
-            if (rc || ok) return rc;
-            sector_orphaned(h);
-            if (!h->sec.disabled) {   // second attempt: support probed with independent angles
-                rc = sector_prepare(h, true);
-                if (rc) return rc;
-                if (h->sec.valid && h->sec.h_tables && sector_gradient_fits(h)) {
-                    rc = run_sector_gradient(h, theta, energy, grad, &ok);
-                    if (rc || ok) return rc;
-                    sector_orphaned(h);
-                }
-            }
-        }
-    }
-    rc = run_program_streaming(h, theta);  // psi = U(theta)|hf>; angle table: original rotations at offset S
-    if (!rc) rc = ensure_scratch(h, 0);
-    // backward sweeps: one pair per thread while that stays below 65536 workgroups (a grid-stride loop of dependent
-    // load -> rotate -> store trips exposes the memory latency of both states), partial sums per workgroup and rotation
-    const int nb = (int)std::min<uint64_t>(65536, std::max<uint64_t>(1, (h->namps / 2 + 255) / 256));
-    if (!rc) rc = ensure(h, h->d_partials, (size_t)std::max(reduce_blocks(h->namps), ADJ_MAX_ROT * nb) * sizeof(double2));
-    if (!rc) rc = ensure(h, h->d_result, 64 * sizeof(double2));
+// The backward walk of the streaming path, for ovqe_energy_gradient and ovqe_deflated_gradient_batch: psi = U(theta)|hf> in h->state,
+// lambda (H psi, or H psi plus what the caller added) in `lam`; the op list is walked backwards on both and grad[0..K) takes
+// 2 Re <lambda| dU/dtheta_k ...>.  adjoint_walk_blocks: the workgroups of its sweeps — one pair per thread while that stays below
+// 65536 workgroups (a grid-stride loop of dependent load -> rotate -> store trips exposes the memory latency of both states), partial
+// sums per workgroup and rotation in d_partials (the caller sizes it: ADJ_MAX_ROT x blocks doubles at the least).
+static int adjoint_walk_blocks(ovqe_handle h) { return (int)std::min<uint64_t>(65536, std::max<uint64_t>(1, (h->namps / 2 + 255) / 256)); }
+static int adjoint_walk(ovqe_handle h, amp_t *lam, int32_t K, double *grad) {
+    const int nb = adjoint_walk_blocks(h);
     const size_t R = h->rots.size(), S = h->srots.size();
     DevBuf d_w;
-    if (!rc) rc = ensure(h, d_w, std::max<size_t>(R, 1) * sizeof(double));
+    int rc = ensure(h, d_w, std::max<size_t>(R, 1) * sizeof(double));
     if (rc) return rc;
-    amp_t *lam = h->scratch[0];
-    double2 e = make_double2(0.0, 0.0);
-    rc = apply_hamiltonian(h, lam, h->state, 0.0);
-    if (!rc) rc = vec_dot(h, h->state, lam, h->namps, &e);
     const RotParam *d_rp = (const RotParam *)h->d_rp.p + S;
     double *partials = (double *)h->d_partials.p;
     for (int oi = (int)h->ops.size() - 1; oi >= 0 && !rc; --oi) {
@@ -345,6 +309,55 @@ static int energy_gradient_body(ovqe_handle h, const double *theta, int32_t K, d
         const SmallRot &sr = h->rots[r];
         if (sr.pidx >= 0) grad[sr.pidx] += 2.0 * sr.coeff * ((sr.ny & 2) ? -w[r] : w[r]);
     }
+    return OVQE_OK;
+}
+
+// (the body of ovqe_energy_gradient; ovqe_energy_gradient_batch serves the rows of a program without a batched form through it)
+static int energy_gradient_body(ovqe_handle h, const double *theta, int32_t K, double *energy, double *grad) {
+    int rc = check_theta(h, theta, K);
+    if (rc) return rc;
+    if (!h->ham.set) return fail(h, OVQE_ERR_STATE, "no Hamiltonian set (ovqe_set_hamiltonian)");
+    if (h->n_global) return fail(h, OVQE_ERR_INVALID, "ovqe_energy_gradient is single-device: on a shard handle run the backward steps with ovqe_adjoint_rotations "
+                                                     "(openvqe_amd/distributed.py: program_energy_gradient)");
+    FrameHamGuard frame_guard(h);
+    {   // small registers: forward, H psi and the backward pass in one launch on the compact support
+        bool done = false;
+        rc = run_sparse_gradient(h, theta, energy, grad, &done);
+        if (rc || done) return rc;
+    }
+    if (h->opt_real_stream && h->prog_real_ok && tile_ok(h, true) && h->ham.groups.size() >= 3) {
+        // real-amplitude program on a sparse support: the whole adjoint pass on the sector tables
+        rc = sector_prepare(h, true);
+        if (rc) return rc;
+        if (h->sec.valid && h->sec.h_tables && sector_gradient_fits(h)) {   // (else: tiles sized for energies only, "sector_tile_cap")
+            bool ok = false;
+            rc = run_sector_gradient(h, theta, energy, grad, &ok);
+            if (rc || ok) return rc;
+            sector_orphaned(h);
+            if (!h->sec.disabled) {   // second attempt: support probed with independent angles
+                rc = sector_prepare(h, true);
+                if (rc) return rc;
+                if (h->sec.valid && h->sec.h_tables && sector_gradient_fits(h)) {
+                    rc = run_sector_gradient(h, theta, energy, grad, &ok);
+                    if (rc || ok) return rc;
+                    sector_orphaned(h);
+                }
+            }
+        }
+    }
+    rc = run_program_streaming(h, theta);  // psi = U(theta)|hf>; angle table: original rotations at offset S
+    if (!rc) rc = ensure_scratch(h, 0);
+    // the backward sweeps' partial sums per workgroup and rotation (adjoint_walk)
+    const int nb = adjoint_walk_blocks(h);
+    if (!rc) rc = ensure(h, h->d_partials, (size_t)std::max(reduce_blocks(h->namps), ADJ_MAX_ROT * nb) * sizeof(double2));
+    if (!rc) rc = ensure(h, h->d_result, 64 * sizeof(double2));
+    if (rc) return rc;
+    amp_t *lam = h->scratch[0];
+    double2 e = make_double2(0.0, 0.0);
+    rc = apply_hamiltonian(h, lam, h->state, 0.0);
+    if (!rc) rc = vec_dot(h, h->state, lam, h->namps, &e);
+    if (!rc) rc = adjoint_walk(h, lam, K, grad);
+    if (rc) return rc;
     *energy = e.x + h->ham.constant;
     return OVQE_OK;
 }

@@ -15,7 +15,8 @@
 //   subspace_host.inc  subspace-expansion matrices around the resident state: rows, expansion vectors, sigma = H Phi, Gram    (sv_subspace_host.hpp; kernels: sv_subspace.hpp, sv_rdm.hpp)
 //   hessian_host.inc  exact energy Hessian: restricted Hamiltonian on the metric's compact program, one launch; column stores and the backward walk    (sv_hessian_host.hpp; kernels: sv_sparse.hpp, sv_hessian.hpp)
 //   gradbatch_host.inc  exact gradients of a batch of parameter vectors on the compact support, one launch    (sv_gradbatch_host.hpp; kernel: sv_sparse.hpp)
-//   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc / abi_rdm.inc / abi_metric.inc / abi_measure.inc / abi_subspace.inc / abi_hessian.inc / abi_gradbatch.inc   extern "C" entry points by family (include/ovqe_sv.h)
+//   deflate_host.inc  deflation vectors of the register; deflated energies and gradients, compact (one launch) and streaming    (kernels: sv_sparse.hpp, sv_deflate.hpp)
+//   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc / abi_rdm.inc / abi_metric.inc / abi_measure.inc / abi_subspace.inc / abi_hessian.inc / abi_gradbatch.inc / abi_deflate.inc   extern "C" entry points by family (include/ovqe_sv.h)
 //   cross_host.inc   planned Pauli sums on a shard of the partitioned register, ovqe_xsum_*          (sv_cross_host.hpp; kernels: sv_cross.hpp)
 //   pool_host.inc    planned ADAPT pool screen on a shard, ovqe_xpool_*                              (sv_pool_host.hpp; kernels: sv_pool.hpp)
 // sv_cover_host.hpp (host-only) holds the table records planners and kernels share and the one cover rule, grow_tile_set(), that
@@ -55,6 +56,7 @@
 #include "sv_hessian_host.hpp"
 #include "sv_hessian.hpp"
 #include "sv_gradbatch_host.hpp"
+#include "sv_deflate.hpp"
 #include "sv_measure.hpp"
 #include "sv_subspace.hpp"
 #include <hipcub/hipcub.hpp>
@@ -298,6 +300,7 @@ struct MetricDev;   // metric_host.inc
 struct SubspaceDev; // subspace_host.inc
 struct HessianDev;  // hessian_host.inc
 struct GradBatchDev;  // gradbatch_host.inc
+struct DeflateDev;   // deflate_host.inc
 struct MeasureDev;   // measure_host.inc
 
 }  // namespace
@@ -378,6 +381,8 @@ struct ovqe_sv {
     int64_t sp_cycles[5] = {0, 0, 0, 0, 0};
     int64_t sp_npairs = 0;
     DevBuf d_sp_ops, d_sp_pairs, d_sp_entries;
+    DevBuf d_sp_basis;            // per slot of the compact state the basis index it holds (~0: a padding slot), [sp_mp rounded up to even]
+    int64_t sp_build = 0;         // counts the compact programs built on this handle (what is derived from one is rebuilt when it moves)
     // the entries as owner pieces for k_sparse_vqe_rows_shared (sparse_pack.hpp): the instance they were packed for (index into
     // SHARED_INSTANCES, -1: none holds the program), rows' pieces in use, pieces per thread, slots per piece
     int sp_pack_inst = -1, sp_h_pieces = 0, sp_h_rpt = 0, sp_h_epr = 0;
@@ -528,6 +533,7 @@ struct ovqe_sv {
     GradBatchDev *grad_batch = nullptr;  // buffers and figures of ovqe_energy_gradient_batch (first call on its compact path)
     int opt_grad_batch_waves = 0;        // waves per workgroup of k_sparse_grad_batch: 0 automatic (sv_gradbatch_host.hpp); 1, 2, 4, 8
     int64_t opt_grad_batch_workgroups = 0;   // cap on its grid (0: none)
+    DeflateDev *deflate = nullptr;       // the deflation vectors of the register, and buffers and figures of ovqe_deflated_gradient_batch
 };
 
 namespace {
@@ -1228,6 +1234,8 @@ void push_rotation(ovqe_handle h, uint64_t x, uint64_t z, double coeff, double p
 
 #include "gradbatch_host.inc"
 
+#include "deflate_host.inc"
+
 int check_theta(ovqe_handle h, const double *theta, int32_t K) {
     if (!h->prog_set) return fail(h, OVQE_ERR_STATE, "no program set (ovqe_set_program / ovqe_set_gate_program)");
     if (K != h->K) return fail(h, OVQE_ERR_INVALID, "K does not match the program's parameter count");
@@ -1323,7 +1331,7 @@ int ovqe_destroy(ovqe_handle h) try {
     std::vector<DevBuf *> bufs = {&h->d_tile_cnt, &h->d_partials, &h->d_result, &h->d_rp, &h->d_ops, &h->d_rots, &h->d_rots_seq, &h->d_segs,
                                   &h->d_stream,
                                   &h->d_theta, &h->d_energies, &h->d_workspace, &h->d_egroups, &h->d_eterms, &h->d_echunks,
-                                  &h->d_eflat, &h->d_sp_ops, &h->d_sp_rows, &h->d_sp_rows64, &h->d_sp_prim, &h->d_sp_pairs, &h->d_sp_entries, &h->d_sp_hpack, &h->d_pg_off, &h->d_pg_xs, &h->d_pg_terms, &h->d_pg_runs, &h->d_pg_tabs,
+                                  &h->d_eflat, &h->d_sp_ops, &h->d_sp_rows, &h->d_sp_rows64, &h->d_sp_prim, &h->d_sp_pairs, &h->d_sp_entries, &h->d_sp_basis, &h->d_sp_hpack, &h->d_pg_off, &h->d_pg_xs, &h->d_pg_terms, &h->d_pg_runs, &h->d_pg_tabs,
                                   &h->d_pg_out, &h->d_pg_part, &h->d_nz_cnt, &h->d_nz_start, &h->d_nz_idx, &h->d_nz_val, &h->d_nz_bitmap, &h->d_exp_groups, &h->d_exp_terms, &h->d_tile_smasks, &h->d_tile_lists, &h->d_tile_counts, &h->cc.d_sup, &h->cc.d_psic, &h->cc.d_loc, &h->cc.d_cid, &h->cc.d_off, &h->cc.d_sweeps};
     for (TilePlan *tp : {&h->tp, &h->tp_adhoc, &h->tp_real, &h->tp_adjoint}) bufs.insert(bufs.end(), {&tp->d_tops, &tp->d_trots});
     for (HamDev *H : {&h->ham, &h->ham_adhoc, &h->ham_real, &h->ham_conj})
@@ -1341,6 +1349,7 @@ int ovqe_destroy(ovqe_handle h) try {
     free_subspace(h->subspace);
     free_hessian(h->hessian);
     free_grad_batch(h->grad_batch);
+    free_deflate(h->deflate);
     h->kept_blocks.flush();
     if (h->h_rp) (void)hipHostFree(h->h_rp);
     if (h->h_result) (void)hipHostFree(h->h_result);
@@ -1654,6 +1663,8 @@ int ovqe_norm2(ovqe_handle h, double *out) try {
 #include "abi_hessian.inc"
 
 #include "abi_gradbatch.inc"
+
+#include "abi_deflate.inc"
 
 // ---- measurement support ------------------------------------------------------------------------
 int ovqe_time_pauli_rotation(ovqe_handle h, uint64_t x, uint64_t z, double phi, int warmup, int reps, double *avg_ms) try {

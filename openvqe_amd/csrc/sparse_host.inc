@@ -259,7 +259,13 @@ int build_sparse_program(ovqe_handle h) {
     if (!rc && h->sp_nrows8) rc = upload(h, h->d_sp_rows64, rows64.data(), rows64.size() * sizeof(uint64_t));
     if (!rc) rc = upload(h, h->d_sp_pairs, pairs.data(), pairs.size() * sizeof(uint32_t));
     if (!rc) rc = upload(h, h->d_sp_entries, entries.data(), entries.size() * sizeof(SpEntry));
+    if (!rc) {   // the basis index behind every slot (k_deflate_gather restricts the deflation vectors to the support with it)
+        std::vector<uint64_t> basis(((size_t)mp + 1) & ~(size_t)1, ~0ull);
+        for (int k = 0; k < m; ++k) basis[(size_t)plan.slot[k]] = S[k];
+        rc = upload(h, h->d_sp_basis, basis.data(), basis.size() * sizeof(uint64_t));
+    }
     if (rc) return rc;
+    ++h->sp_build;
     h->sp_m = m;
     h->sp_mp = mp;
     h->sp_hf = hf_slot;

@@ -844,6 +844,92 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_grad_batch(SparseArgs A, con
     }
 }
 
+// ... and DEFLATED (ovqe_deflated_gradient_batch): C = <psi|H|psi> + sum_r beta_r d_r^2, d_r = <D_r|psi>, with real rows D[r][0..mpad)
+// in global memory (the stored vectors restricted to the support, k_deflate_gather; every wave reads the same rows, they stay in L2 as
+// the Hamiltonian's entries do).  The penalty is the rank-nrows operator sum_r beta_r |D_r><D_r| beside H, so the row body is
+// k_sparse_grad_batch's with ONE phase between "lambda = H psi" and the backward walk: lambda += sum_r beta_r d_r D_r.  Every lane
+// sums its slots i = lane (mod 64) of a row, wave_sum adds the lanes in its fixed tree, lane 0's total goes to all lanes, and every
+// lane adds to its own lambda slots: plain LDS read-modify-writes behind the fence that completes the contraction's atomics.  The
+// layout is sp_grad_batch_lds unchanged (the rows take no LDS), the one barrier is the one behind the staging.  Cost, energy and the
+// d_r of a row are summed in fixed orders: equal rows give equal bits wherever they sit; the gradient reproduces to rounding.
+template <int NW, bool STAGE>
+__global__ __launch_bounds__(NW * 64) void k_sparse_vqd_batch(SparseArgs A, const double *__restrict__ theta,
+                                                              const SmallRot *__restrict__ tabrots, const SpOp *__restrict__ ops,
+                                                              const uint32_t *__restrict__ pairs, const SpEntry *__restrict__ entries,
+                                                              const double *__restrict__ D, const DeflRow *__restrict__ drows, int nrows,
+                                                              double *__restrict__ costs, double *__restrict__ energies,
+                                                              double *__restrict__ grads, double *__restrict__ dvals) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const SpGradBatchLds L = sp_grad_batch_lds(A, NW, STAGE);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const SpProgram P = sp_stage<STAGE, NW * 64>(smem, L.ops, L.pairs, ops, pairs, A.nops, A.npairs, (int)threadIdx.x);
+    __syncthreads();
+    unsigned char *mine = smem + (size_t)wave * L.stride;
+    double *psi = reinterpret_cast<double *>(mine);
+    double *lam = reinterpret_cast<double *>(mine + L.lam);
+    double2 *cs = reinterpret_cast<double2 *>(mine + L.cs);
+    double *w = reinterpret_cast<double *>(mine + L.w);
+    double *gk = reinterpret_cast<double *>(mine + L.gk);
+    for (int64_t b = (int64_t)blockIdx.x * NW + wave; b < A.B; b += (int64_t)gridDim.x * NW) {
+        const double *th = theta + b * A.K;
+        for (int i = lane; i < A.mpad; i += 64) {
+            psi[i] = i == A.hf ? 1.0 : 0.0;
+            lam[i] = 0.0;
+        }
+        sp_fill_table<64>(tabrots, A.ntab, lane, cs, [&](const SmallRot &sr) { return sr.coeff * th[sr.pidx]; },
+                          [&](int e, const SmallRot &) { w[e] = 0.0; });
+        for (int k = lane; k < A.K; k += 64) gk[k] = 0.0;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // forward
+        sp_for_ops<64>(P, 0, A.nops, lane, [&](const SpPair &p) { sp_rotate_pair(psi, cs, p); });
+        // lambda = H psi, E = <psi|lambda>
+        double acc = 0.0;
+#pragma unroll 4
+        for (int e = lane; e < A.nent; e += 64) {
+            const SpEntry en = entries[e];
+            const SpAmps a = sp_entry_amps(en, psi);
+            acc += en.c * a.u * a.v;
+            sp_apply_entry(en, {a}, {lam});
+        }
+        const double etot = wave_sum(acc);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // deflation: d_r = <D_r|psi>, lambda += beta_r d_r D_r, cost += beta_r d_r^2
+        double pen = 0.0;
+        for (int r = 0; r < nrows; ++r) {
+            const DeflRow dr = drows[r];
+            const double *row = D + (size_t)dr.src * A.mpad;
+            double dacc = 0.0;
+            for (int i = lane; i < A.mpad; i += 64) dacc = fma(row[i], psi[i], dacc);
+            const double d = __shfl(wave_sum(dacc), 0, 64);
+            const double c = dr.beta * d;
+            for (int i = lane; i < A.mpad; i += 64) lam[i] = fma(c, row[i], lam[i]);
+            pen = fma(c, d, pen);
+            if (lane == 0) dvals[b * nrows + r] = d;
+        }
+        if (lane == 0) {
+            const double e = etot + A.constant;
+            energies[b] = e;
+            costs[b] = e + pen;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // backward
+        sp_for_ops_down<64>(P, 0, A.nops, lane, [&](const SpPair &p) {
+            const SpRot r = sp_rot(cs, p);
+            const SpAmps a = sp_get(psi, p), l = sp_get(lam, p);
+            const double g = l.u * a.v - l.v * a.u;
+            __hip_atomic_fetch_add(&w[p.e], sp_signed(p, g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            sp_put(psi, p, sp_rotate_back(r, a));
+            sp_put(lam, p, sp_rotate_back(r, l));
+        });
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        sp_fold<64>(tabrots, A.ntab, w, gk, lane);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        for (int k = lane; k < A.K; k += 64) grads[b * A.K + k] = gk[k];
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+}
+
 // ... and with ONE parameter vector per workgroup (latency form, as k_sparse_vqe_wg): all threads prepare and hold the restricted
 // Hamiltonian's entries in registers, wave 0 runs the circuit forwards over rows of 64 padded words, all waves form
 // E = <psi|H|psi> and lambda = H psi (f64 LDS atomics), wave 0 walks the rows BACKWARDS on psi and lambda — per row

@@ -26,8 +26,13 @@ struct SpEntry {     // one entry of the Hamiltonian restricted to the support
     uint32_t pad;
     double c;        // 2 * H_ij (off-diagonal, the pair counted once: ci < cj) or H_ii
 };
+struct DeflRow {     // one real deflation row of k_sparse_vqd_batch: [mpad] doubles at D + src * mpad, in global memory
+    double beta;     // its weight
+    int32_t src;
+    int32_t pad;
+};
 constexpr size_t SP_CS_BYTES = 16;   // one cos/sin table entry: a double2 (sv_sparse.hpp asserts it)
-static_assert(sizeof(SpOp) == 16 && sizeof(SpEntry) == 16, "16-byte records behind an even number of doubles");
+static_assert(sizeof(SpOp) == 16 && sizeof(SpEntry) == 16 && sizeof(DeflRow) == 16, "16-byte records behind an even number of doubles");
 
 struct SparseArgs {
     int m;        // support size

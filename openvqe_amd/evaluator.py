@@ -82,6 +82,12 @@ class _Evaluator:
             return replicas.energy_gradient_batch(self.sv, thetas)
         return self.sv.energy_gradient_batch(thetas)
 
+    def deflated_gradient_batch(self, thetas):
+        """(C[B], dC/dtheta[B, K], E[B], overlaps[B, J]) of the rows of ``thetas`` with the deflation vectors the backend holds
+        (ovqe_deflated_gradient_batch; ``openvqe_amd.excited.vqd`` runs on ``self.sv`` once the evaluator is active)"""
+        self._activate()
+        return self.sv.deflated_gradient_batch(np.asarray(thetas, dtype=np.float64)[:, : self.n_params])
+
     def metric_tensor(self, theta):
         """Fubini-Study metric of the ansatz state at ``theta`` (ovqe_metric_tensor), (K, K)"""
         self._activate()

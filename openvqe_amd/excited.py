@@ -4,6 +4,11 @@ With expansion operators O_1 .. O_m and phi_j = O_j psi, the device forms S_ij =
 (``Statevector.subspace_matrices``, ovqe_subspace_matrices); the generalised eigenproblem H y = E S y is solved here, on the host, by
 canonical orthogonalisation.  The reference has no call site for this: its only excited-state code is a weighted subspace-search
 demo on an Ising chain (ref:openvqe/common_files/get_energy_WSSVQE.py).
+
+Excited states WITH ansatz parameters come from variational quantum deflation (``vqd``): state k minimises
+C(theta) = <psi|H|psi> + sum_j beta_j |<phi_j|psi>|^2 over the states phi_j found before it; cost and exact gradient of a batch of
+parameter vectors are one device call (``Statevector.deflated_gradient_batch``, ovqe_deflated_gradient_batch) and the optimiser is the
+lock-step multi-start L-BFGS of ``common_files.multistart``.
 """
 from __future__ import annotations
 
@@ -87,3 +92,39 @@ def load_ritz_state(sv, ops, y):
         raise ValueError("the Ritz vector is zero")
     sv.vec_scale(state, 1.0 / np.sqrt(norm2))
     return norm2
+
+
+def vqd(sv, n_states, x0=None, beta=None, starts=8, spread=0.5, seed=0, tol=1e-6, maxiter=2000):
+    """Variational quantum deflation on the program and Hamiltonian loaded in ``sv``: for k = 0 .. n_states - 1 the cost
+    C = <H> + sum_j beta_j |<phi_j|psi(theta)>|^2 over the deflation vectors ``sv`` holds is minimised from ``starts`` starting vectors in
+    lock-step (``multistart.minimize``, one ``deflated_gradient_batch`` call per iteration) — start 0 is ``x0`` (zeros by default), the
+    others are ``x0`` plus uniform draws from [-spread, spread], as ``EnergyUCC.multistart`` draws them — then the best start's state is
+    prepared and pushed with weight ``beta``.  ``beta=None``: 2 sum_t |c_t| of the stored Hamiltonian without its constant — more than
+    its spectral width, so every deflated level lies above every level not yet found.  Vectors pushed before the call (a Lanczos ground
+    state, say) are built upon; when the call leaves, normally or not, the set is truncated back to what it found.
+    -> a list of ``n_states`` dicts: ``energy``, ``cost``, ``theta``, ``overlaps`` (complex, with the vectors held before state k was
+    pushed: the earlier states last) and ``result`` (the multistart result)"""
+    from .common_files import multistart
+    K = sv._K
+    x0 = np.zeros(K) if x0 is None else np.asarray(x0, np.float64).reshape(-1)
+    if x0.shape[0] != K:
+        raise ValueError(f"expected {K} parameters")
+    if int(starts) < 1:
+        raise ValueError("starts: at least one")
+    beta = 2.0 * sv.hamiltonian_norm1() if beta is None else float(beta)
+    rng = np.random.default_rng(seed)
+    found = sv.deflation_count()
+    states = []
+    try:
+        for _ in range(int(n_states)):
+            X0 = np.tile(x0, (int(starts), 1))
+            X0[1:] += rng.uniform(-spread, spread, size=(int(starts) - 1, K))
+            res = multistart.minimize(lambda X: sv.deflated_gradient_batch(X)[:2], X0, tol=tol, maxiter=maxiter)
+            cost, _, energy, overlaps = sv.deflated_gradient_batch(res.x[None, :])
+            states.append({"energy": float(energy[0]), "cost": float(cost[0]), "theta": res.x.copy(), "overlaps": overlaps[0].copy(),
+                           "result": res})
+            sv.prepare_state(res.x)
+            sv.deflation_push(beta)
+    finally:
+        sv.deflation_truncate(found)
+    return states

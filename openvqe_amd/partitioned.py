@@ -264,6 +264,12 @@ class PartitionedStatevector:
         raise NotImplementedError("the energy Hessian is computed on one device (ovqe_energy_hessian keeps K tangent vectors and their "
                                   "images under H next to the state): not available on the partitioned register")
 
+    def deflation_push(self, *args, **kwargs):
+        raise NotImplementedError("deflation vectors are held next to one device's register (ovqe_deflation_push, "
+                                  "ovqe_deflated_gradient_batch): variational quantum deflation is not available on the partitioned register")
+
+    deflation_truncate = deflation_count = deflated_gradient_batch = deflation_info = deflation_push
+
     def subspace_matrices(self, *args, **kwargs):
         raise NotImplementedError("subspace-expansion matrices are computed on one device (ovqe_subspace_matrices keeps the expansion "
                                   "vectors next to the state): not available on the partitioned register")
