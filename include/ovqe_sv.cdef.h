@@ -109,6 +109,9 @@ int ovqe_deflation_count(ovqe_handle h, int32_t *count);
 int ovqe_deflated_gradient_batch(ovqe_handle h, int64_t B, const double *theta, int32_t K, double *costs, double *grads, double *energies,
                                  double *overlaps_re_im);
 int ovqe_deflation_info(ovqe_handle h, int64_t *info, int count);
+int ovqe_spread_gradient_batch(ovqe_handle h, int64_t B, const double *theta, int32_t K, const double *omega, double w_energy, double w_spread,
+                               double *costs, double *grads, double *energies, double *spreads);
+int ovqe_spread_info(ovqe_handle h, int64_t *info, int count);
 int ovqe_sample(ovqe_handle h, int64_t n_shots, uint64_t seed, uint64_t stream, uint64_t first_shot, uint64_t *indices);
 int ovqe_measure_paulis(ovqe_handle h, uint64_t xbasis, uint64_t ybasis, int64_t n_shots, uint64_t seed, uint64_t stream,
                         uint64_t first_shot, int64_t T, const uint64_t *mask, const double *coeff, int64_t *term_sums,

@@ -594,6 +594,56 @@ int ovqe_deflated_gradient_batch(ovqe_handle h, int64_t B, const double *theta, 
  * zeros before the first call; a refused call leaves no figures */
 int ovqe_deflation_info(ovqe_handle h, int64_t *info, int count);
 
+/* ---- energy spread: how good a state is, and the folded-spectrum cost.  For psi = psi(theta_b) and a reference energy omega_b,
+ *     S_b = ||(H - omega_b) psi||^2 = <psi|(H - omega_b)^2|psi>        (H with its constant)
+ * With omega_b = E_b = <psi|H|psi> it is the energy VARIANCE <H^2> - <H>^2: zero exactly on eigenstates, and an eigenvalue of H lies
+ * within sqrt(S_b) of E_b (Weinstein).  With a chosen omega it is the folded-spectrum cost: its minimum over theta is the ansatz state
+ * nearest the energy omega — excited states without stored deflation vectors (openvqe_amd/excited.py: folded_spectrum).
+ *
+ * ovqe_spread_gradient_batch: for row b of theta[B x K] (row-major),
+ *     energies[b] = E_b,   spreads[b] = S_b,   costs[b] = w_energy E_b + w_spread S_b,
+ *     grads[b*K .. b*K + K) = d costs[b] / dtheta at FIXED omega_b.
+ * omega: B values, or NULL for omega_b = E_b — then the gradient is the exact gradient of w_energy E + w_spread Var, because
+ * d(<H^2> - E^2) = d<H^2> - 2 E dE is what fixing omega at E gives.  The adjoint pass is ovqe_energy_gradient's with
+ * lambda = w_energy H psi + w_spread (H - omega)^2 psi (components of lambda along psi contribute nothing).  energies and spreads may
+ * be NULL.  ROWS.  The conventions of ovqe_energy_gradient_batch: a shared parameter sums its rotations' contributions, an unused one
+ * gives exact zeros, rows do not influence each other.  REFUSALS.  Those of ovqe_deflated_gradient_batch with its codes, without the
+ * one for open Clifford frames — the conjugated Hamiltonian squares like any other: no program, no Hamiltonian, option "real_state":
+ * OVQE_ERR_STATE; K other than the program's, a shard handle, B < 0, a NULL theta / costs / grads with B K > 0 (costs: B > 0), a
+ * weight or an omega_b that is not finite: OVQE_ERR_INVALID; B = 0 returns OVQE_OK and touches nothing.  BOUNDS.  B K doubles of theta
+ * and B of omega are read; B doubles of costs (and of energies, of spreads) and B K of grads are written.  AFTER THE CALL the state
+ * buffer is unspecified; cached tables stay valid: ovqe_energy, ovqe_energy_batch and ovqe_energy_gradient before and after return what
+ * they returned.  Synchronises before it returns.
+ * TWO PATHS (ovqe_spread_info [0]).  1, compact support: the whole batch in ONE launch of k_sparse_spread_batch — the row body of
+ * k_sparse_grad_batch with a third per-wave LDS array and one phase between lambda = H psi and the backward walk: sigma = (H - omega) psi
+ * in place, S = sum sigma_i^2, mu = (H - omega) sigma by a second pass over the restricted Hamiltonian's entries, lambda from both.
+ * Taken when ovqe_energy_gradient_batch would take its path 1, AND the three-array region of one wave fits 150 KiB, AND the restricted
+ * entries are H on the support: the compact program drops what leaves the support and every term with an odd number of Y — exact for
+ * <H> on a real state, wrong for <H^2> — so path 1 requires that no term with a non-zero coefficient has an odd number of Y, and that
+ * for every x-group and every support state whose partner lies outside the support the group's signed coefficient sum is at most
+ * 64 eps sum_t |c_t| in magnitude (the residue a number-conserving Hamiltonian leaves there: 1e-17 .. 3e-16, not 0).  Both are decided
+ * once, when the compact program is built.  Planned by ovqe_energy_gradient_batch's rule on the larger layout under the same options
+ * ("grad_batch_waves", "grad_batch_workgroups").  With w_energy = 1, w_spread = 0 costs and energies equal ovqe_energy_gradient_batch's
+ * to the bit.  E and S of a row are summed in fixed orders: equal rows give bit-identical energies and spreads wherever they sit in the
+ * batch; LDS atomics add lambda, mu and the weights: gradients reproduce to rounding.  2, streaming — every other program: sector-table
+ * and dense programs, literal gate lists, Hamiltonians that leak from the support or hold odd-Y terms, "force_path" 2: row by row
+ * psi = U(theta)|hf> on the streaming kernels, sigma and tau = (H - omega) sigma by the Pauli-sum application on the full complex
+ * register in two register-sized work vectors the call allocates and frees (OVQE_ERR_ALLOC when it cannot), the dot products by the
+ * fixed-order reductions, then the backward walk of ovqe_energy_gradient.  COST of path 2 beyond the single gradient: one more
+ * Pauli-sum application and six vector passes per row.  Out of scope: batched forms on the sector tables and on the partitioned
+ * register, a spread Hessian. */
+int ovqe_spread_gradient_batch(ovqe_handle h, int64_t B, const double *theta, int32_t K, const double *omega, double w_energy, double w_spread,
+                               double *costs, double *grads, double *energies, double *spreads);
+/* of the last ovqe_spread_gradient_batch call with B > 0, up to `count` entries of: [0] path (1 compact support, 2 streaming) [1] B [2] K
+ * [3] mode (0: omega given, 1: variance) [4] launches (path 1: 1; path 2: the vector operations of all rows beyond the single gradient's
+ * — the Pauli-sum applications are not counted) [5] kernel form: 1 ops and pair words staged in LDS, 2 read from global memory, 0 on
+ * path 2 [6] waves per workgroup [7] workgroups [8] dynamic LDS bytes of the launch [9] support size m [10] why path 2 served the call:
+ * 0 it did not, 1 no compact program or the options rule it out, 2 the three-array region exceeds the LDS budget, 3 the Hamiltonian
+ * leaks from the support, 4 it holds a term with an odd number of Y [11] [12] HIP-event times in microseconds: the copy of theta to the
+ * device with the launch, the copy back ([5..9], [11], [12] are 0 on path 2); zeros before the first call; a refused call leaves no
+ * figures */
+int ovqe_spread_info(ovqe_handle h, int64_t *info, int count);
+
 /* ---- finite-shot measurement: outcomes drawn from the state in the buffer, and energies with shot noise (what a submission with
  * nbshots > 0 asks of a QPU: openvqe_amd/qat_compat.py; every call site of the reference submits nbshots = 0, the exact paths above).
  * Plain handles of any size; OVQE_ERR_STATE on a shard of a partitioned register and under option "real_state".  The state buffer is

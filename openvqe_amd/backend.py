@@ -615,6 +615,44 @@ class Statevector:
                 "launch_us", "copy_back_us")
         return dict(zip(keys, [int(v) for v in out]))
 
+    # -- energy spread: variance and folded-spectrum cost (ovqe_spread_gradient_batch, csrc/spread_host.inc) --------------------------
+    def spread_gradient_batch(self, thetas, omega=None, w_energy=0.0, w_spread=1.0):
+        """S = ||(H - omega) psi||^2 for every row of ``thetas`` (B, K): ``omega`` a scalar or B values — the folded-spectrum cost — or
+        None for omega_b = E_b, where S is the energy variance <H^2> - <H>^2
+        -> (costs[B] = w_energy E + w_spread S, d costs/dtheta[B, K] at fixed omega, energies[B], spreads[B]).  In variance mode the
+        gradient is the exact gradient of w_energy E + w_spread Var.  A program on the compact support whose Hamiltonian stays on it
+        runs the whole batch in one launch (``spread_info``), every other program row by row on the streaming kernels"""
+        thetas = np.ascontiguousarray(thetas, np.float64)
+        if thetas.ndim != 2 or thetas.shape[1] != self._K:
+            raise ValueError(f"expected a (B, {self._K}) array")
+        B, K = thetas.shape
+        if omega is not None:
+            omega = np.ascontiguousarray(np.broadcast_to(np.asarray(omega, np.float64), (B,)))
+        costs, energies, spreads = np.zeros(B, np.float64), np.zeros(B, np.float64), np.zeros(B, np.float64)
+        grads = np.zeros((B, K), np.float64)
+        self._ck(self._L.ovqe_spread_gradient_batch(
+            self._h, B, thetas if thetas.size else np.zeros(1), K, None if omega is None else (omega if B else np.zeros(1)),
+            float(w_energy), float(w_spread), costs if B else np.zeros(1), grads.reshape(-1) if grads.size else np.zeros(1),
+            energies if B else np.zeros(1), spreads if B else np.zeros(1)))
+        return costs, grads, energies, spreads
+
+    def energy_variance(self, theta):
+        """-> (E, Var) at ``theta``: Var = <H^2> - <H>^2 = ||(H - E) psi||^2, zero exactly on eigenstates; an eigenvalue of H lies within
+        sqrt(Var) of E"""
+        _, _, e, s = self.spread_gradient_batch(np.asarray(theta, np.float64).reshape(1, -1))
+        return float(e[0]), float(s[0])
+
+    def spread_info(self):
+        """figures of the last ``spread_gradient_batch`` call: path (1 compact support in one launch, 2 streaming), rows, parameters,
+        mode (0 omega given, 1 variance), launches, kernel form, waves per workgroup, workgroups, dynamic LDS bytes, support size, why
+        path 2 served it (0 it did not, 1 no compact program or options, 2 LDS, 3 the Hamiltonian leaks from the support, 4 a term with
+        an odd number of Y), and the HIP-event times in microseconds of the copy of theta with the launch and of the copy back"""
+        out = (ctypes.c_int64 * 13)()
+        self._ck(self._L.ovqe_spread_info(self._h, out, 13))
+        keys = ("path", "B", "K", "mode", "launches", "form", "waves", "workgroups", "lds_bytes", "support", "why", "launch_us",
+                "copy_back_us")
+        return dict(zip(keys, [int(v) for v in out]))
+
     def ground_state(self, tol=1e-10, max_iter=3000, seed=20250227):
         """lowest eigenpair of the stored Hamiltonian by device-side Lanczos; the eigenvector is left in the
         state buffer (``get_state``).  -> (energy, residual |H y - E y|, iterations)"""

@@ -16,7 +16,8 @@
 //   hessian_host.inc  exact energy Hessian: restricted Hamiltonian on the metric's compact program, one launch; column stores and the backward walk    (sv_hessian_host.hpp; kernels: sv_sparse.hpp, sv_hessian.hpp)
 //   gradbatch_host.inc  exact gradients of a batch of parameter vectors on the compact support, one launch    (sv_gradbatch_host.hpp; kernel: sv_sparse.hpp)
 //   deflate_host.inc  deflation vectors of the register; deflated energies and gradients, compact (one launch) and streaming    (kernels: sv_sparse.hpp, sv_deflate.hpp)
-//   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc / abi_rdm.inc / abi_metric.inc / abi_measure.inc / abi_subspace.inc / abi_hessian.inc / abi_gradbatch.inc / abi_deflate.inc   extern "C" entry points by family (include/ovqe_sv.h)
+//   spread_host.inc  energy spread ||(H - omega) psi||^2 (variance, folded-spectrum cost) with its gradient on the compact support, one launch    (sv_spread_host.hpp; kernel: sv_sparse.hpp)
+//   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc / abi_rdm.inc / abi_metric.inc / abi_measure.inc / abi_subspace.inc / abi_hessian.inc / abi_gradbatch.inc / abi_deflate.inc / abi_spread.inc   extern "C" entry points by family (include/ovqe_sv.h)
 //   cross_host.inc   planned Pauli sums on a shard of the partitioned register, ovqe_xsum_*          (sv_cross_host.hpp; kernels: sv_cross.hpp)
 //   pool_host.inc    planned ADAPT pool screen on a shard, ovqe_xpool_*                              (sv_pool_host.hpp; kernels: sv_pool.hpp)
 // sv_cover_host.hpp (host-only) holds the table records planners and kernels share and the one cover rule, grow_tile_set(), that
@@ -57,6 +58,7 @@
 #include "sv_hessian.hpp"
 #include "sv_gradbatch_host.hpp"
 #include "sv_deflate.hpp"
+#include "sv_spread_host.hpp"
 #include "sv_measure.hpp"
 #include "sv_subspace.hpp"
 #include <hipcub/hipcub.hpp>
@@ -301,6 +303,7 @@ struct SubspaceDev; // subspace_host.inc
 struct HessianDev;  // hessian_host.inc
 struct GradBatchDev;  // gradbatch_host.inc
 struct DeflateDev;   // deflate_host.inc
+struct SpreadDev;    // spread_host.inc
 struct MeasureDev;   // measure_host.inc
 
 }  // namespace
@@ -383,6 +386,7 @@ struct ovqe_sv {
     DevBuf d_sp_ops, d_sp_pairs, d_sp_entries;
     DevBuf d_sp_basis;            // per slot of the compact state the basis index it holds (~0: a padding slot), [sp_mp rounded up to even]
     int64_t sp_build = 0;         // counts the compact programs built on this handle (what is derived from one is rebuilt when it moves)
+    spread::Exactness sp_exact;   // whether the restricted entries are H on the support (sv_spread_host.hpp): set with the compact program
     // the entries as owner pieces for k_sparse_vqe_rows_shared (sparse_pack.hpp): the instance they were packed for (index into
     // SHARED_INSTANCES, -1: none holds the program), rows' pieces in use, pieces per thread, slots per piece
     int sp_pack_inst = -1, sp_h_pieces = 0, sp_h_rpt = 0, sp_h_epr = 0;
@@ -534,6 +538,7 @@ struct ovqe_sv {
     int opt_grad_batch_waves = 0;        // waves per workgroup of k_sparse_grad_batch: 0 automatic (sv_gradbatch_host.hpp); 1, 2, 4, 8
     int64_t opt_grad_batch_workgroups = 0;   // cap on its grid (0: none)
     DeflateDev *deflate = nullptr;       // the deflation vectors of the register, and buffers and figures of ovqe_deflated_gradient_batch
+    SpreadDev *spread = nullptr;         // buffers and figures of ovqe_spread_gradient_batch
 };
 
 namespace {
@@ -1236,6 +1241,8 @@ void push_rotation(ovqe_handle h, uint64_t x, uint64_t z, double coeff, double p
 
 #include "deflate_host.inc"
 
+#include "spread_host.inc"
+
 int check_theta(ovqe_handle h, const double *theta, int32_t K) {
     if (!h->prog_set) return fail(h, OVQE_ERR_STATE, "no program set (ovqe_set_program / ovqe_set_gate_program)");
     if (K != h->K) return fail(h, OVQE_ERR_INVALID, "K does not match the program's parameter count");
@@ -1350,6 +1357,7 @@ int ovqe_destroy(ovqe_handle h) try {
     free_hessian(h->hessian);
     free_grad_batch(h->grad_batch);
     free_deflate(h->deflate);
+    free_spread(h->spread);
     h->kept_blocks.flush();
     if (h->h_rp) (void)hipHostFree(h->h_rp);
     if (h->h_result) (void)hipHostFree(h->h_result);
@@ -1665,6 +1673,8 @@ int ovqe_norm2(ovqe_handle h, double *out) try {
 #include "abi_gradbatch.inc"
 
 #include "abi_deflate.inc"
+
+#include "abi_spread.inc"
 
 // ---- measurement support ------------------------------------------------------------------------
 int ovqe_time_pauli_rotation(ovqe_handle h, uint64_t x, uint64_t z, double phi, int warmup, int reps, double *avg_ms) try {

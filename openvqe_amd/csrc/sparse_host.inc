@@ -94,6 +94,9 @@ int build_sparse_program(ovqe_handle h) {
             if (entries.size() > (size_t)16 << 20) return OVQE_OK;
         }
     }
+    // whether these entries ARE H on the support: what the loop above dropped — partners outside the support, terms with an odd number
+    // of Y — is exact for <H> on a real state and wrong for <H^2> (ovqe_spread_gradient_batch takes its compact path only with neither)
+    const spread::Exactness exact = spread::exactness(h->ham.groups, h->ham.terms, S, [&](uint64_t a) { return id.find(a) != id.end(); });
     // ---- compact numbering, lanes and orientation against LDS bank conflicts in the circuit: the planner (sparse_plan.hpp) -----------
     // The lanes of an evaluation rotate the (up to 32) pairs of an op with ONE ds_read_b64 per member and one ds_write_b64 each; which
     // banks they meet on is the host's to choose.  The entries of the restricted Hamiltonian follow the numbering.
@@ -266,6 +269,7 @@ int build_sparse_program(ovqe_handle h) {
     }
     if (rc) return rc;
     ++h->sp_build;
+    h->sp_exact = exact;
     h->sp_m = m;
     h->sp_mp = mp;
     h->sp_hf = hf_slot;

@@ -40,17 +40,20 @@ inline bool valid_waves(int64_t v) { return v == 1 || v == 2 || v == 4 || v == 8
 // the unstaged one-wave layout within the budget: what makes a program eligible at all (the criterion of the single call's one-wave forms)
 inline bool eligible(const SparseArgs &A) { return sp_grad_batch_lds(A, 1, false).bytes <= LDS_BUDGET; }
 
-inline Plan plan(const SparseArgs &A, int64_t B, int opt_waves, int64_t opt_workgroups, int cus) {
+// the rule over any per-wave layout (k_sparse_spread_batch plans with it on its own: sv_spread_host.hpp): bytes_of(nw, stage) are a
+// candidate's bytes, waves_of(stage) the waves a CU holds of the instances
+template <class Bytes, class WavesCu>
+inline Plan plan_rule(Bytes bytes_of, WavesCu waves_of, int64_t B, int opt_waves, int64_t opt_workgroups, int cus) {
     // a forced nw none of whose forms is admissible: the automatic choice (a tuning knob does not send a program to the row-by-row path)
-    if (valid_waves(opt_waves) && sp_grad_batch_lds(A, opt_waves, false).bytes > LDS_BUDGET) opt_waves = 0;
+    if (valid_waves(opt_waves) && bytes_of(opt_waves, false) > LDS_BUDGET) opt_waves = 0;
     Plan best;
     int best_waves = -1;
     for (bool stage : {true, false}) {
         for (int nw : {1, 2, 4, 8}) {
             if (valid_waves(opt_waves) && nw != opt_waves) continue;
-            const size_t bytes = sp_grad_batch_lds(A, nw, stage).bytes;
+            const size_t bytes = bytes_of(nw, stage);
             if (bytes > LDS_BUDGET) continue;
-            const int per_cu = (int)std::min<size_t>(LDS_CU / std::max<size_t>(bytes, 1), (size_t)(waves_cu(stage) / nw));
+            const int per_cu = (int)std::min<size_t>(LDS_CU / std::max<size_t>(bytes, 1), (size_t)(waves_of(stage) / nw));
             const int waves = per_cu * nw;
             if (waves <= best_waves) continue;   // visited in the order of the tie-break: a later candidate must be strictly better
             best_waves = waves;
@@ -66,6 +69,11 @@ inline Plan plan(const SparseArgs &A, int64_t B, int opt_waves, int64_t opt_work
     if (opt_workgroups > 0) wgs = std::min(wgs, opt_workgroups);
     best.workgroups = std::max<int64_t>(wgs, 1);
     return best;
+}
+
+inline Plan plan(const SparseArgs &A, int64_t B, int opt_waves, int64_t opt_workgroups, int cus) {
+    return plan_rule([&](int nw, bool stage) { return sp_grad_batch_lds(A, nw, stage).bytes; }, [](bool stage) { return waves_cu(stage); }, B,
+                     opt_waves, opt_workgroups, cus);
 }
 
 }  // namespace gradbatch

@@ -930,6 +930,105 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_vqd_batch(SparseArgs A, cons
     }
 }
 
+// ... and with the SPREAD of the energy (ovqe_spread_gradient_batch): S = ||(H - omega) psi||^2, omega the caller's per row or — omega
+// null — the row's own E, where S is the energy variance; cost = w_energy E + w_spread S with its exact gradient at fixed omega.  The
+// adjoint vector is lambda = w_energy H psi + w_spread (H - omega)^2 psi, so the row body is k_sparse_grad_batch's with a third private
+// array mu (sp_spread_batch_lds) and ONE phase between "lambda = H psi" and the backward walk, everything real:
+//     sigma = lambda + s psi, s = constant - omega, in place;  S = sum sigma_i^2;  mu = H sigma (the entry loop again, sigma the source)
+//     lambda <- w_energy (sigma - s psi) + w_spread (mu + s sigma)
+// The host launches it only where the restricted entries are H on the support (spread::exactness, sv_spread_host.hpp).  Fences as in
+// the neighbours: each completes the LDS atomics of the phase before it.  The one barrier is the one behind the staging.  E and S of a
+// row are summed in fixed orders — every lane its slots i = lane (mod 64), then wave_sum's tree: equal rows give equal bits wherever
+// they sit in the batch; the gradient reproduces to rounding.
+template <int NW, bool STAGE>
+__global__ __launch_bounds__(NW * 64) void k_sparse_spread_batch(SparseArgs A, const double *__restrict__ theta,
+                                                                 const SmallRot *__restrict__ tabrots, const SpOp *__restrict__ ops,
+                                                                 const uint32_t *__restrict__ pairs, const SpEntry *__restrict__ entries,
+                                                                 const double *__restrict__ omega, double w_energy, double w_spread,
+                                                                 double *__restrict__ costs, double *__restrict__ energies,
+                                                                 double *__restrict__ spreads, double *__restrict__ grads) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const SpSpreadBatchLds L = sp_spread_batch_lds(A, NW, STAGE);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const SpProgram P = sp_stage<STAGE, NW * 64>(smem, L.ops, L.pairs, ops, pairs, A.nops, A.npairs, (int)threadIdx.x);
+    __syncthreads();
+    unsigned char *mine = smem + (size_t)wave * L.stride;
+    double *psi = reinterpret_cast<double *>(mine);
+    double *lam = reinterpret_cast<double *>(mine + L.lam);
+    double *mu = reinterpret_cast<double *>(mine + L.mu);
+    double2 *cs = reinterpret_cast<double2 *>(mine + L.cs);
+    double *w = reinterpret_cast<double *>(mine + L.w);
+    double *gk = reinterpret_cast<double *>(mine + L.gk);
+    for (int64_t b = (int64_t)blockIdx.x * NW + wave; b < A.B; b += (int64_t)gridDim.x * NW) {
+        const double *th = theta + b * A.K;
+        for (int i = lane; i < A.mpad; i += 64) {
+            psi[i] = i == A.hf ? 1.0 : 0.0;
+            lam[i] = 0.0;
+            mu[i] = 0.0;
+        }
+        sp_fill_table<64>(tabrots, A.ntab, lane, cs, [&](const SmallRot &sr) { return sr.coeff * th[sr.pidx]; },
+                          [&](int e, const SmallRot &) { w[e] = 0.0; });
+        for (int k = lane; k < A.K; k += 64) gk[k] = 0.0;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // forward
+        sp_for_ops<64>(P, 0, A.nops, lane, [&](const SpPair &p) { sp_rotate_pair(psi, cs, p); });
+        // lambda = H psi, E = <psi|lambda>
+        double acc = 0.0;
+#pragma unroll 4
+        for (int e = lane; e < A.nent; e += 64) {
+            const SpEntry en = entries[e];
+            const SpAmps a = sp_entry_amps(en, psi);
+            acc += en.c * a.u * a.v;
+            sp_apply_entry(en, {a}, {lam});
+        }
+        const double energy = __shfl(wave_sum(acc), 0, 64) + A.constant;
+        const double s = A.constant - (omega ? omega[b] : energy);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // sigma = (H - omega) psi in place of lambda, S = <sigma|sigma>
+        double sacc = 0.0;
+        for (int i = lane; i < A.mpad; i += 64) {
+            const double sg = fma(s, psi[i], lam[i]);
+            lam[i] = sg;
+            sacc = fma(sg, sg, sacc);
+        }
+        const double stot = wave_sum(sacc);
+        if (lane == 0) {
+            energies[b] = energy;
+            spreads[b] = stot;
+            costs[b] = w_energy * energy + w_spread * stot;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // mu = H sigma
+#pragma unroll 4
+        for (int e = lane; e < A.nent; e += 64) {
+            const SpEntry en = entries[e];
+            sp_apply_entry(en, {sp_entry_amps(en, lam)}, {mu});
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // lambda = w_energy H psi + w_spread (H - omega) sigma
+        for (int i = lane; i < A.mpad; i += 64) {
+            const double sg = lam[i];
+            lam[i] = w_energy * (sg - s * psi[i]) + w_spread * fma(s, sg, mu[i]);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // backward
+        sp_for_ops_down<64>(P, 0, A.nops, lane, [&](const SpPair &p) {
+            const SpRot r = sp_rot(cs, p);
+            const SpAmps a = sp_get(psi, p), l = sp_get(lam, p);
+            const double g = l.u * a.v - l.v * a.u;
+            __hip_atomic_fetch_add(&w[p.e], sp_signed(p, g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            sp_put(psi, p, sp_rotate_back(r, a));
+            sp_put(lam, p, sp_rotate_back(r, l));
+        });
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        sp_fold<64>(tabrots, A.ntab, w, gk, lane);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        for (int k = lane; k < A.K; k += 64) grads[b * A.K + k] = gk[k];
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+}
+
 // ... and with ONE parameter vector per workgroup (latency form, as k_sparse_vqe_wg): all threads prepare and hold the restricted
 // Hamiltonian's entries in registers, wave 0 runs the circuit forwards over rows of 64 padded words, all waves form
 // E = <psi|H|psi> and lambda = H psi (f64 LDS atomics), wave 0 walks the rows BACKWARDS on psi and lambda — per row

@@ -90,6 +90,22 @@ OVQE_LAYOUT_FN SpGradBatchLds sp_grad_batch_lds(const SparseArgs &A, int nw, boo
     return {W.lam, W.cs, W.w, W.gk, stride, ops, pairs, stage ? pairs + (size_t)A.npairs * sizeof(uint32_t) : ops};
 }
 
+// k_sparse_spread_batch: k_sparse_grad_batch's arrangement with a THIRD state array per wave — psi, lambda and mu ([mpad] doubles each),
+// then the cos/sin table, w and gk as in sp_grad_lds; wave v's region at v * stride, the shared op records and pair words behind the
+// last wave (stage)
+struct SpSpreadBatchLds { size_t lam, mu, cs, w, gk, stride, ops, pairs, bytes; };   // wave v's psi ([mpad]) is at v * stride
+OVQE_LAYOUT_FN SpSpreadBatchLds sp_spread_batch_lds(const SparseArgs &A, int nw, bool stage) {
+    const size_t v = (size_t)A.mpad * sizeof(double);                        // psi, lambda, mu: [mpad] each
+    const size_t cs = 3 * v;                                                 // [ntab]
+    const size_t w = cs + (size_t)A.ntab * SP_CS_BYTES;                      // [ntab]
+    const size_t gk = w + (size_t)A.ntab * sizeof(double);                   // [K]
+    const size_t region = gk + (size_t)((A.K + 1) & ~1) * sizeof(double);
+    const size_t stride = (region + 15) & ~(size_t)15;
+    const size_t ops = (size_t)nw * stride;                                  // [nops]   (stage)
+    const size_t pairs = ops + (size_t)A.nops * sizeof(SpOp);                // [npairs] (stage)
+    return {v, 2 * v, cs, w, gk, stride, ops, pairs, stage ? pairs + (size_t)A.npairs * sizeof(uint32_t) : ops};
+}
+
 // k_sparse_grad_wg
 struct SpGradWgLds { size_t lam, cs, w, gk, bytes; };   // psi ([mpad] = support + 128 spare slots) is at 0
 OVQE_LAYOUT_FN SpGradWgLds sp_grad_wg_lds(const SparseArgs &A) {

@@ -9,6 +9,11 @@ Excited states WITH ansatz parameters come from variational quantum deflation (`
 C(theta) = <psi|H|psi> + sum_j beta_j |<phi_j|psi>|^2 over the states phi_j found before it; cost and exact gradient of a batch of
 parameter vectors are one device call (``Statevector.deflated_gradient_batch``, ovqe_deflated_gradient_batch) and the optimiser is the
 lock-step multi-start L-BFGS of ``common_files.multistart``.
+
+A second route needs no stored vectors: the folded spectrum (``folded_spectrum``).  The minimum of S_omega = <psi|(H - omega)^2|psi>
+over theta is the ansatz state nearest the chosen energy omega; S with its exact gradient for a batch is one device call
+(``Statevector.spread_gradient_batch``, ovqe_spread_gradient_batch), and the energy variance of the result certifies it: an
+eigenvalue of H lies within sqrt(variance) of its energy.
 """
 from __future__ import annotations
 
@@ -127,4 +132,31 @@ def vqd(sv, n_states, x0=None, beta=None, starts=8, spread=0.5, seed=0, tol=1e-6
             sv.deflation_push(beta)
     finally:
         sv.deflation_truncate(found)
+    return states
+
+
+def folded_spectrum(sv, omegas, x0=None, starts=8, spread=0.5, seed=0, tol=1e-6, maxiter=2000):
+    """Folded-spectrum states on the program and Hamiltonian loaded in ``sv``: for every omega in ``omegas`` the cost
+    S = <psi(theta)|(H - omega)^2|psi(theta)> is minimised from ``starts`` starting vectors in lock-step (``multistart.minimize``, one
+    ``spread_gradient_batch`` call per iteration) — start 0 is ``x0`` (zeros by default), the others are ``x0`` plus uniform draws from
+    [-spread, spread], as ``vqd`` draws them.  The best start is then evaluated once in variance mode.
+    -> a list with one dict per omega: ``theta``, ``energy`` = <H>, ``spread`` = S at the minimum, ``variance`` = <H^2> - <H>^2 there, and
+    ``result`` (the multistart result).  The variance is the certificate: an eigenvalue of H lies within sqrt(variance) of ``energy``
+    (spread = variance + (energy - omega)^2)."""
+    from .common_files import multistart
+    K = sv._K
+    x0 = np.zeros(K) if x0 is None else np.asarray(x0, np.float64).reshape(-1)
+    if x0.shape[0] != K:
+        raise ValueError(f"expected {K} parameters")
+    if int(starts) < 1:
+        raise ValueError("starts: at least one")
+    rng = np.random.default_rng(seed)
+    states = []
+    for omega in np.asarray(omegas, np.float64).reshape(-1):
+        X0 = np.tile(x0, (int(starts), 1))
+        X0[1:] += rng.uniform(-spread, spread, size=(int(starts) - 1, K))
+        res = multistart.minimize(lambda X: sv.spread_gradient_batch(X, omega=float(omega))[:2], X0, tol=tol, maxiter=maxiter)
+        _, _, energy, variance = sv.spread_gradient_batch(res.x[None, :])
+        states.append({"theta": res.x.copy(), "energy": float(energy[0]), "spread": float(res.fun), "variance": float(variance[0]),
+                       "result": res})
     return states

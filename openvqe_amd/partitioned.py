@@ -270,6 +270,12 @@ class PartitionedStatevector:
 
     deflation_truncate = deflation_count = deflated_gradient_batch = deflation_info = deflation_push
 
+    def spread_gradient_batch(self, *args, **kwargs):
+        raise NotImplementedError("the energy spread is computed on one device (ovqe_spread_gradient_batch applies the Hamiltonian twice "
+                                  "next to one register): energy variance and folded-spectrum cost are not available on the partitioned register")
+
+    energy_variance = spread_info = spread_gradient_batch
+
     def subspace_matrices(self, *args, **kwargs):
         raise NotImplementedError("subspace-expansion matrices are computed on one device (ovqe_subspace_matrices keeps the expansion "
                                   "vectors next to the state): not available on the partitioned register")
