@@ -112,6 +112,13 @@ int ovqe_deflation_info(ovqe_handle h, int64_t *info, int count);
 int ovqe_spread_gradient_batch(ovqe_handle h, int64_t B, const double *theta, int32_t K, const double *omega, double w_energy, double w_spread,
                                double *costs, double *grads, double *energies, double *spreads);
 int ovqe_spread_info(ovqe_handle h, int64_t *info, int count);
+int ovqe_observable_push(ovqe_handle h, int64_t T, const uint64_t *x, const uint64_t *z, const double *coeff, double constant);
+int ovqe_observable_truncate(ovqe_handle h, int32_t count);
+int ovqe_observable_count(ovqe_handle h, int32_t *count);
+int ovqe_constrained_gradient_batch(ovqe_handle h, int64_t B, const double *theta, int32_t K, int32_t M, const double *linear, const double *quad,
+                                    const double *target, double *costs, double *grads, double *energies, double *values,
+                                    double *overlaps_re_im);
+int ovqe_constraint_info(ovqe_handle h, int64_t *info, int count);
 int ovqe_sample(ovqe_handle h, int64_t n_shots, uint64_t seed, uint64_t stream, uint64_t first_shot, uint64_t *indices);
 int ovqe_measure_paulis(ovqe_handle h, uint64_t xbasis, uint64_t ybasis, int64_t n_shots, uint64_t seed, uint64_t stream,
                         uint64_t first_shot, int64_t T, const uint64_t *mask, const double *coeff, int64_t *term_sums,

@@ -644,6 +644,65 @@ int ovqe_spread_gradient_batch(ovqe_handle h, int64_t B, const double *theta, in
  * figures */
 int ovqe_spread_info(ovqe_handle h, int64_t *info, int count);
 
+/* ---- observables beside the Hamiltonian: expectation values of a batch, penalty terms, constrained costs.  A handle holds up to 8
+ * further Hermitian Pauli sums O_m.  For psi = psi(theta_b), o_bm = <psi|O_m|psi> + constant_m, and the cost of a row is
+ *     costs[b] = E_b + sum_m [ linear_m o_bm + quad_m (o_bm - target_m)^2 ] + sum_j beta_j |<phi_j|psi>|^2
+ * with the deflation vectors phi_j the handle holds (ovqe_deflation_push).  For any cost f(E, o_1 .. o_M) the adjoint vector is
+ * lambda = H psi + sum_m (df/do_m) O_m psi: one pass of ovqe_energy_gradient gives cost, exact gradient, E and every o_bm.  Uses: a
+ * spin penalty quad (<S^2> - s(s+1))^2 that makes VQD return states of one spin (openvqe_amd/excited.py: vqd(constraints=...),
+ * spin_constraint), a particle-number penalty for ansaetze that do not conserve N, properties of a batch of states without a table
+ * rebuild per observable.
+ *
+ * ovqe_observable_push: arguments as ovqe_set_hamiltonian, coefficients real; the sum becomes observable M of the handle, M the number
+ * held so far.  The observables belong to the REGISTER, as the deflation vectors do: they survive ovqe_set_program,
+ * ovqe_set_gate_program and ovqe_set_hamiltonian.  OVQE_ERR_INVALID for a ninth observable, a mask beyond the register, a coefficient
+ * or constant that is not finite; OVQE_ERR_STATE on a shard of a partitioned register and under option "real_state".  Synchronises. */
+int ovqe_observable_push(ovqe_handle h, int64_t T, const uint64_t *x, const uint64_t *z, const double *coeff, double constant);
+/* keeps the first `count` observables and frees the others; 0 clears the set.  OVQE_ERR_INVALID for a count outside 0 .. the number held. */
+int ovqe_observable_truncate(ovqe_handle h, int32_t count);
+/* *count = the number of observables held */
+int ovqe_observable_count(ovqe_handle h, int32_t *count);
+/* CONSTRAINED costs and gradients of a batch: for row b of theta[B x K] (row-major), with the M observables and the J vectors held,
+ *     energies[b] = E_b,   values[b*M + m] = o_bm,   costs[b] as above,   grads[b*K .. b*K + K) = d costs[b] / dtheta,
+ *     overlaps_re_im = the B x J complex <phi_j|psi>, row-major, (re, im) pairs.
+ * M must equal the number of observables held.  linear, quad, target: M doubles each; a NULL linear or quad means zeros, a NULL target
+ * zeros; with both weights NULL the call returns the expectation values of a batch (costs = the deflated cost).  energies, values
+ * and overlaps_re_im may be NULL.  With no observable and no vector held costs equal energies to the bit.  ROWS.  The conventions of
+ * ovqe_energy_gradient_batch.  REFUSALS.  Those of ovqe_deflated_gradient_batch with its codes — no program, no Hamiltonian, option
+ * "real_state", an OPEN Clifford frame (the observables and vectors live in the caller's frame, the state of an open-frame program does
+ * not): OVQE_ERR_STATE; K other than the program's, a shard handle, B < 0, a NULL theta / costs / grads with B K > 0 (costs: B > 0):
+ * OVQE_ERR_INVALID — and: M other than the number held, a weight or target that is not finite: OVQE_ERR_INVALID.  B = 0 returns
+ * OVQE_OK and touches nothing.  BOUNDS.  B K doubles of theta and M of each of linear, quad, target are read; B doubles of costs (and
+ * of energies), B K of grads, B M of values and 2 B J of overlaps_re_im are written.  AFTER THE CALL the state buffer is unspecified;
+ * cached tables stay valid: ovqe_energy, ovqe_energy_gradient, ovqe_energy_gradient_batch, ovqe_deflated_gradient_batch and
+ * ovqe_spread_gradient_batch before and after return what they returned.  Synchronises before it returns.
+ * TWO PATHS (ovqe_constraint_info [0]).  1, compact support: taken exactly when ovqe_deflated_gradient_batch takes its path 1, planned by
+ * the same rule under the same options, the whole batch in ONE launch of k_sparse_constrained_batch: k_sparse_vqd_batch's row body with
+ * one more phase behind the deflation phase.  Every O_m enters RESTRICTED to the support, by the rule that restricts H
+ * (sv_constrain_host.hpp): entries whose partner leaves the support and terms with an odd number of Y are dropped.  That is exact for
+ * o_bm and its gradient — the ket side of the backward walk never leaves the support, and an odd-Y term has no expectation value on a
+ * real state and adds only an imaginary vector to lambda — so, unlike ovqe_spread_gradient_batch, there is no exactness gate.  The
+ * entries of all observables are one array in global memory (no LDS beyond the batched gradient's), built lazily and cached on the
+ * handle until the compact program is rebuilt or the set of observables changes.  Per observable one pass over its entries sums o_bm;
+ * where g = linear_m + 2 quad_m (o_bm - target_m) is not zero a second pass adds g O_m psi to lambda.  Cost, energy, values and
+ * overlaps of a row are summed in fixed orders: equal rows give bit-identical costs, energies, values and overlaps wherever they sit
+ * in the batch; gradients reproduce to rounding.  2, streaming — every other program and "force_path" 2: ovqe_deflated_gradient_batch's
+ * row with, per observable, work = O_m psi by the Pauli-sum application in ONE register-sized work vector the call allocates and frees
+ * (OVQE_ERR_ALLOC when it cannot), o_bm by the fixed-order dot product, lambda += g work, then the backward walk.  COST of path 2 beyond
+ * the deflated row: M Pauli-sum applications and up to 2 M vector passes.  Out of scope: constraints on the sector tables and on the
+ * partitioned register, open Clifford frames, a constrained Hessian or metric, per-row weights. */
+int ovqe_constrained_gradient_batch(ovqe_handle h, int64_t B, const double *theta, int32_t K, int32_t M, const double *linear, const double *quad,
+                                    const double *target, double *costs, double *grads, double *energies, double *values,
+                                    double *overlaps_re_im);
+/* of the last ovqe_constrained_gradient_batch call with B > 0, up to `count` entries of: [0] path (1 compact support, 2 streaming) [1] B
+ * [2] K [3] M [4] J, the vectors held [5] real deflation rows of path 1 [6] launches (path 1: 1; path 2: the deflation launches and the
+ * observables' k_dot, k_reduce and axpy launches of all rows — Pauli-sum applications and the single gradient's are not counted)
+ * [7] kernel form: 1 ops and pair words staged in LDS, 2 read from global memory, 0 on path 2 [8] waves per workgroup [9] workgroups
+ * [10] dynamic LDS bytes of the launch [11] support size m [12] entries of all restricted observables [13] observables restricted by
+ * this call (0: the cached entries served) [14] [15] HIP-event times in microseconds: the copy of theta to the device with the launch,
+ * the copy back ([7..15] are 0 on path 2); zeros before the first call; a refused call leaves no figures */
+int ovqe_constraint_info(ovqe_handle h, int64_t *info, int count);
+
 /* ---- finite-shot measurement: outcomes drawn from the state in the buffer, and energies with shot noise (what a submission with
  * nbshots > 0 asks of a QPU: openvqe_amd/qat_compat.py; every call site of the reference submits nbshots = 0, the exact paths above).
  * Plain handles of any size; OVQE_ERR_STATE on a shard of a partitioned register and under option "real_state".  The state buffer is

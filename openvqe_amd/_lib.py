@@ -121,6 +121,12 @@ SIGNATURES = {
     "ovqe_deflation_info": (_int, [_H, ctypes.POINTER(ctypes.c_int64), _int]),
     "ovqe_spread_gradient_batch": (_int, [_H, _i64, _OptF64, ctypes.c_int32, _OptF64, _dbl, _dbl, _OptF64, _OptF64, _OptF64, _OptF64]),
     "ovqe_spread_info": (_int, [_H, ctypes.POINTER(ctypes.c_int64), _int]),
+    "ovqe_observable_push": (_int, [_H, _i64, _u64p, _u64p, _f64p, _dbl]),
+    "ovqe_observable_truncate": (_int, [_H, ctypes.c_int32]),
+    "ovqe_observable_count": (_int, [_H, ctypes.POINTER(ctypes.c_int32)]),
+    "ovqe_constrained_gradient_batch": (_int, [_H, _i64, _OptF64, ctypes.c_int32, ctypes.c_int32, _OptF64, _OptF64, _OptF64, _OptF64, _OptF64,
+                                               _OptF64, _OptF64, _OptF64]),
+    "ovqe_constraint_info": (_int, [_H, ctypes.POINTER(ctypes.c_int64), _int]),
     "ovqe_sample": (_int, [_H, _i64, _u64, _u64, _u64, _OptU64]),
     "ovqe_measure_paulis": (_int, [_H, _u64, _u64, _i64, _u64, _u64, _u64, _i64, _OptU64, _OptF64, _OptI64, _f64p, _OptU64]),
     "ovqe_measure_groups": (_int, [_H, _i64, _i32p, _u64p, _u64p, ctypes.POINTER(_i64)]),

@@ -653,6 +653,71 @@ class Statevector:
                 "copy_back_us")
         return dict(zip(keys, [int(v) for v in out]))
 
+    # -- observables beside the Hamiltonian (ovqe_observable_*, ovqe_constrained_gradient_batch, csrc/constrain_host.inc) ------------
+    def observable_push(self, hamiltonian):
+        """the Hermitian Pauli sum ``hamiltonian`` (real coefficients) becomes the next observable O_m of the handle (at most 8; they
+        survive a new program or Hamiltonian) -> the number of observables held"""
+        xs, zs, cs = pack_terms(self.nbqbits, hamiltonian.terms)
+        coeff = np.array([_real_coeff(c, "observable") for c in cs], np.float64)
+        const = _real_coeff(getattr(hamiltonian, "constant_coeff", 0.0) or 0.0, "observable constant")
+        self._ck(self._L.ovqe_observable_push(self._h, xs.shape[0], xs, zs, coeff, const))
+        return self.observable_count()
+
+    def observable_truncate(self, count=0):
+        """keeps the first ``count`` observables, frees the rest (0: all of them)"""
+        self._ck(self._L.ovqe_observable_truncate(self._h, int(count)))
+
+    def observable_count(self):
+        out = ctypes.c_int32()
+        self._ck(self._L.ovqe_observable_count(self._h, ctypes.byref(out)))
+        return out.value
+
+    def constrained_gradient_batch(self, thetas, linear=None, quad=None, target=None):
+        """C = <H> + sum_m [linear_m o_m + quad_m (o_m - target_m)^2] + sum_j beta_j |<phi_j|psi>|^2 with the observables and deflation
+        vectors held, o_m = <psi|O_m|psi> with O_m's constant, for every row of ``thetas`` (B, K); ``linear``, ``quad``, ``target``: M
+        values each or None for zeros
+        -> (costs[B], dC/dtheta[B, K], energies[B], values[B, M], overlaps[B, J] complex).  A program on the compact support runs the
+        whole batch in one launch (``constraint_info``), every other program row by row on the streaming kernels"""
+        thetas = np.ascontiguousarray(thetas, np.float64)
+        if thetas.ndim != 2 or thetas.shape[1] != self._K:
+            raise ValueError(f"expected a (B, {self._K}) array")
+        B, K = thetas.shape
+        M, J = self.observable_count(), self.deflation_count()
+
+        def weights(w, name):
+            if w is None:
+                return None
+            w = np.ascontiguousarray(np.asarray(w, np.float64).reshape(-1))
+            if w.shape[0] != M:
+                raise ValueError(f"{name}: expected {M} values, one per observable held")
+            return w if M else None
+        linear, quad, target = weights(linear, "linear"), weights(quad, "quad"), weights(target, "target")
+        costs, energies = np.zeros(B, np.float64), np.zeros(B, np.float64)
+        grads = np.zeros((B, K), np.float64)
+        values = np.zeros((B, M), np.float64)
+        overlaps = np.zeros((B, J), np.complex128)
+        self._ck(self._L.ovqe_constrained_gradient_batch(
+            self._h, B, thetas if thetas.size else np.zeros(1), K, M, linear, quad, target, costs if B else np.zeros(1),
+            grads.reshape(-1) if grads.size else np.zeros(1), energies if B else np.zeros(1),
+            values.reshape(-1) if values.size else None, overlaps.view(np.float64).reshape(-1) if overlaps.size else None))
+        return costs, grads, energies, values, overlaps
+
+    def expectations_batch(self, thetas):
+        """-> (energies[B], values[B, M]): <H> and the expectation values of the observables held for every row of ``thetas``"""
+        _, _, energies, values, _ = self.constrained_gradient_batch(thetas)
+        return energies, values
+
+    def constraint_info(self):
+        """figures of the last ``constrained_gradient_batch`` call: path (1 compact support in one launch, 2 streaming), rows,
+        parameters, observables, vectors, real deflation rows of path 1, launches, kernel form, waves per workgroup, workgroups, dynamic
+        LDS bytes, support size, entries of all restricted observables, observables restricted by the call (0: the cached entries
+        served), and the HIP-event times in microseconds of the copy of theta with the launch and of the copy back"""
+        out = (ctypes.c_int64 * 16)()
+        self._ck(self._L.ovqe_constraint_info(self._h, out, 16))
+        keys = ("path", "B", "K", "M", "J", "rows", "launches", "form", "waves", "workgroups", "lds_bytes", "support", "entries",
+                "restriction_builds", "launch_us", "copy_back_us")
+        return dict(zip(keys, [int(v) for v in out]))
+
     def ground_state(self, tol=1e-10, max_iter=3000, seed=20250227):
         """lowest eigenpair of the stored Hamiltonian by device-side Lanczos; the eigenvector is left in the
         state buffer (``get_state``).  -> (energy, residual |H y - E y|, iterations)"""

@@ -4,8 +4,9 @@
 // One row on the streaming path: psi = U(theta)|hf>, lambda = H psi, E = Re <psi|lambda>, o_j = <phi_j|psi> (k_deflate_dots, four vectors
 // per pass, the blocks' partials summed by k_reduce into slot j of d_result), lambda += sum_j beta_j o_j phi_j (k_deflate_axpy, o_j read
 // on the device), the backward walk of ovqe_energy_gradient on (psi, lambda).  *launches += the deflation launches made.
+// more: null, or (*more)(lam, &extra) is what a caller adds to lambda before the walk and to the cost (abi_constrain.inc: the observables' terms).
 static int deflated_row_streaming(ovqe_handle h, const double *theta, int32_t K, double *cost, double *grad, double *energy, double2 *o,
-                                  int64_t *launches) {
+                                  int64_t *launches, const std::function<int(amp_t *, double *)> *more = nullptr) {
     DeflateDev &D = deflate_dev(h);
     const int J = (int)D.vecs.size(), rb = reduce_blocks(h->namps), nb = adjoint_walk_blocks(h);
     int rc = run_program_streaming(h, theta);
@@ -34,11 +35,13 @@ static int deflated_row_streaming(ovqe_handle h, const double *theta, int32_t K,
         *launches += 2 + C.count;
     }
     if (J > 0 && (rc = fetch_result(h, o, J))) return rc;
+    double extra = 0.0;
+    if (more && (rc = (*more)(lam, &extra))) return rc;
     if ((rc = adjoint_walk(h, lam, K, grad))) return rc;
     double c = e.x + h->ham.constant;
     *energy = c;
     for (int j = 0; j < J; ++j) c += D.betas[j] * (o[j].x * o[j].x + o[j].y * o[j].y);
-    *cost = c;
+    *cost = c + extra;
     return OVQE_OK;
 }
 

@@ -125,6 +125,24 @@ int launch_vqd_batch(ovqe_handle h, bool stage, unsigned grid, size_t lds, const
     return OVQE_OK;
 }
 
+// o_bj = <phi_j|psi> = init_amp (<Re phi_j|psi_c> - i <Im phi_j|psi_c>) from the row values d[B x rows in use] of a path-1 launch: the
+// compact state starts from 1 at |hf>, the register from init_amp (the phase a folded Clifford part leaves)
+void deflate_overlaps_out(ovqe_handle h, const DeflateDev &D, int64_t B, const double *d, double *overlaps) {
+    const size_t J = D.vecs.size(), nr = D.rows.size();
+    const double pr = h->init_amp.x, pi = h->init_amp.y;
+    for (int64_t b = 0; b < B; ++b) {
+        double *o = overlaps + (size_t)b * J * 2;
+        std::fill(o, o + 2 * J, 0.0);
+        for (size_t r = 0; r < nr; ++r) o[2 * D.row_vec[r] + D.row_im[r]] = D.row_im[r] ? -d[(size_t)b * nr + r] : d[(size_t)b * nr + r];
+        if (pr != 1.0 || pi != 0.0)
+            for (size_t j = 0; j < J; ++j) {
+                const double re = o[2 * j], im = o[2 * j + 1];
+                o[2 * j] = pr * re - pi * im;
+                o[2 * j + 1] = pr * im + pi * re;
+            }
+    }
+}
+
 // *done = false: the program is not eligible for path 1 (nothing was launched, info untouched).  energies, overlaps: may be null
 int run_vqd_batch(ovqe_handle h, int64_t B, const double *theta, double *costs, double *grads, double *energies, double *overlaps, bool *done) {
     *done = false;
@@ -174,22 +192,7 @@ int run_vqd_batch(ovqe_handle h, int64_t B, const double *theta, double *costs, 
     }
     HIPC(h, hipEventRecord(D.ev[2], h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
-    if (overlaps && nr) {
-        // o_bj = <phi_j|psi> = init_amp (<Re phi_j|psi_c> - i <Im phi_j|psi_c>): the compact state starts from 1 at |hf>, the register
-        // from init_amp (the phase a folded Clifford part leaves)
-        const double pr = h->init_amp.x, pi = h->init_amp.y;
-        for (int64_t b = 0; b < B; ++b) {
-            double *o = overlaps + (size_t)b * J * 2;
-            std::fill(o, o + 2 * J, 0.0);
-            for (size_t r = 0; r < nr; ++r) o[2 * D.row_vec[r] + D.row_im[r]] = D.row_im[r] ? -D.h_d[(size_t)b * nr + r] : D.h_d[(size_t)b * nr + r];
-            if (pr != 1.0 || pi != 0.0)
-                for (size_t j = 0; j < J; ++j) {
-                    const double re = o[2 * j], im = o[2 * j + 1];
-                    o[2 * j] = pr * re - pi * im;
-                    o[2 * j + 1] = pr * im + pi * re;
-                }
-        }
-    }
+    if (overlaps && nr) deflate_overlaps_out(h, D, B, D.h_d.data(), overlaps);
     const int64_t info[12] = {1, B, (int64_t)K, (int64_t)J, (int64_t)nr, 1, G.stage ? 1 : 2, G.nw, G.workgroups, (int64_t)G.lds, h->sp_m, gathers};
     std::copy(info, info + 12, D.info);
     if ((rc = phases_us(h, D.ev, 2, D.info + 12))) return rc;

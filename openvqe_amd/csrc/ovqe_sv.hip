@@ -17,7 +17,8 @@
 //   gradbatch_host.inc  exact gradients of a batch of parameter vectors on the compact support, one launch    (sv_gradbatch_host.hpp; kernel: sv_sparse.hpp)
 //   deflate_host.inc  deflation vectors of the register; deflated energies and gradients, compact (one launch) and streaming    (kernels: sv_sparse.hpp, sv_deflate.hpp)
 //   spread_host.inc  energy spread ||(H - omega) psi||^2 (variance, folded-spectrum cost) with its gradient on the compact support, one launch    (sv_spread_host.hpp; kernel: sv_sparse.hpp)
-//   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc / abi_rdm.inc / abi_metric.inc / abi_measure.inc / abi_subspace.inc / abi_hessian.inc / abi_gradbatch.inc / abi_deflate.inc / abi_spread.inc   extern "C" entry points by family (include/ovqe_sv.h)
+//   constrain_host.inc  observables of the register beside the Hamiltonian; costs of their expectation values with exact gradients on the compact support, one launch    (sv_constrain_host.hpp; kernel: sv_sparse.hpp)
+//   abi_unit.inc / abi_eval.inc / abi_adapt.inc / abi_solvers.inc / abi_rdm.inc / abi_metric.inc / abi_measure.inc / abi_subspace.inc / abi_hessian.inc / abi_gradbatch.inc / abi_deflate.inc / abi_spread.inc / abi_constrain.inc   extern "C" entry points by family (include/ovqe_sv.h)
 //   cross_host.inc   planned Pauli sums on a shard of the partitioned register, ovqe_xsum_*          (sv_cross_host.hpp; kernels: sv_cross.hpp)
 //   pool_host.inc    planned ADAPT pool screen on a shard, ovqe_xpool_*                              (sv_pool_host.hpp; kernels: sv_pool.hpp)
 // sv_cover_host.hpp (host-only) holds the table records planners and kernels share and the one cover rule, grow_tile_set(), that
@@ -33,6 +34,7 @@
 #include <cstdio>
 #include <complex>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <numeric>
@@ -59,6 +61,7 @@
 #include "sv_gradbatch_host.hpp"
 #include "sv_deflate.hpp"
 #include "sv_spread_host.hpp"
+#include "sv_constrain_host.hpp"
 #include "sv_measure.hpp"
 #include "sv_subspace.hpp"
 #include <hipcub/hipcub.hpp>
@@ -304,6 +307,7 @@ struct HessianDev;  // hessian_host.inc
 struct GradBatchDev;  // gradbatch_host.inc
 struct DeflateDev;   // deflate_host.inc
 struct SpreadDev;    // spread_host.inc
+struct ConstrainDev; // constrain_host.inc
 struct MeasureDev;   // measure_host.inc
 
 }  // namespace
@@ -385,6 +389,7 @@ struct ovqe_sv {
     int64_t sp_npairs = 0;
     DevBuf d_sp_ops, d_sp_pairs, d_sp_entries;
     DevBuf d_sp_basis;            // per slot of the compact state the basis index it holds (~0: a padding slot), [sp_mp rounded up to even]
+    std::vector<uint64_t> sp_basis;   // its host copy
     int64_t sp_build = 0;         // counts the compact programs built on this handle (what is derived from one is rebuilt when it moves)
     spread::Exactness sp_exact;   // whether the restricted entries are H on the support (sv_spread_host.hpp): set with the compact program
     // the entries as owner pieces for k_sparse_vqe_rows_shared (sparse_pack.hpp): the instance they were packed for (index into
@@ -539,6 +544,7 @@ struct ovqe_sv {
     int64_t opt_grad_batch_workgroups = 0;   // cap on its grid (0: none)
     DeflateDev *deflate = nullptr;       // the deflation vectors of the register, and buffers and figures of ovqe_deflated_gradient_batch
     SpreadDev *spread = nullptr;         // buffers and figures of ovqe_spread_gradient_batch
+    ConstrainDev *constrain = nullptr;   // the observables of the register, and buffers and figures of ovqe_constrained_gradient_batch
 };
 
 namespace {
@@ -1243,6 +1249,8 @@ void push_rotation(ovqe_handle h, uint64_t x, uint64_t z, double coeff, double p
 
 #include "spread_host.inc"
 
+#include "constrain_host.inc"
+
 int check_theta(ovqe_handle h, const double *theta, int32_t K) {
     if (!h->prog_set) return fail(h, OVQE_ERR_STATE, "no program set (ovqe_set_program / ovqe_set_gate_program)");
     if (K != h->K) return fail(h, OVQE_ERR_INVALID, "K does not match the program's parameter count");
@@ -1358,6 +1366,7 @@ int ovqe_destroy(ovqe_handle h) try {
     free_grad_batch(h->grad_batch);
     free_deflate(h->deflate);
     free_spread(h->spread);
+    free_constrain(h->constrain);
     h->kept_blocks.flush();
     if (h->h_rp) (void)hipHostFree(h->h_rp);
     if (h->h_result) (void)hipHostFree(h->h_result);
@@ -1675,6 +1684,7 @@ int ovqe_norm2(ovqe_handle h, double *out) try {
 #include "abi_deflate.inc"
 
 #include "abi_spread.inc"
+#include "abi_constrain.inc"
 
 // ---- measurement support ------------------------------------------------------------------------
 int ovqe_time_pauli_rotation(ovqe_handle h, uint64_t x, uint64_t z, double phi, int warmup, int reps, double *avg_ms) try {

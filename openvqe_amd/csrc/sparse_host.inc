@@ -64,36 +64,13 @@ int build_sparse_program(ovqe_handle h) {
         if (so.npairs > 0) ops.push_back(so);
     }
     const int m = (int)S.size();
-    // Hamiltonian restricted to the support (real mode: even-ny terms; pair counted once -> factor 2)
+    // Hamiltonian restricted to the support (real mode: even-ny terms; pair counted once -> factor 2): the one rule of sv_constrain_host.hpp
     std::vector<SpEntry> entries;
-    for (const HGroup &g : h->ham.groups) {
-        const uint64_t x = g.x;
-        const uint64_t pbit = x ? 1ull << (63 - __builtin_clzll(x)) : 0;
-        for (int k = 0; k < m; ++k) {
-            const uint64_t a = S[k];
-            if (x && (a & pbit)) continue;
-            const uint64_t b = a ^ x;
-            int kb = k;
-            if (x) {
-                auto it = id.find(b);
-                if (it == id.end()) continue;
-                kb = it->second;
-            }
-            double d = 0.0;
-            for (int t = g.t0; t < g.t1; ++t) {
-                const HTerm &ht = h->ham.terms[t];
-                if (__builtin_popcountll(x & ht.z) & 1) continue;  // odd #Y: zero on a real state
-                d += (__builtin_popcountll(b & ht.z) & 1) ? -ht.cr : ht.cr;
-            }
-            if (d == 0.0) continue;
-            SpEntry e;
-            e.ij = (uint32_t)k | ((uint32_t)kb << 12);
-            e.pad = 0;
-            e.c = x ? 2.0 * d : d;
-            entries.push_back(e);
-            if (entries.size() > (size_t)16 << 20) return OVQE_OK;
-        }
-    }
+    if (!constrain::restrict_to_support(h->ham.groups, h->ham.terms, S.data(), m, [&](uint64_t a) {
+            auto it = id.find(a);
+            return it == id.end() ? -1 : it->second;
+        }, constrain::ENTRY_CAP, &entries))
+        return OVQE_OK;
     // whether these entries ARE H on the support: what the loop above dropped — partners outside the support, terms with an odd number
     // of Y — is exact for <H> on a real state and wrong for <H^2> (ovqe_spread_gradient_batch takes its compact path only with neither)
     const spread::Exactness exact = spread::exactness(h->ham.groups, h->ham.terms, S, [&](uint64_t a) { return id.find(a) != id.end(); });
@@ -263,7 +240,8 @@ int build_sparse_program(ovqe_handle h) {
     if (!rc) rc = upload(h, h->d_sp_pairs, pairs.data(), pairs.size() * sizeof(uint32_t));
     if (!rc) rc = upload(h, h->d_sp_entries, entries.data(), entries.size() * sizeof(SpEntry));
     if (!rc) {   // the basis index behind every slot (k_deflate_gather restricts the deflation vectors to the support with it)
-        std::vector<uint64_t> basis(((size_t)mp + 1) & ~(size_t)1, ~0ull);
+        std::vector<uint64_t> &basis = h->sp_basis;   // (the host copy: the observables of constrain_host.inc are restricted with it)
+        basis.assign(((size_t)mp + 1) & ~(size_t)1, ~0ull);
         for (int k = 0; k < m; ++k) basis[(size_t)plan.slot[k]] = S[k];
         rc = upload(h, h->d_sp_basis, basis.data(), basis.size() * sizeof(uint64_t));
     }

@@ -930,6 +930,124 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_vqd_batch(SparseArgs A, cons
     }
 }
 
+// ... and with OBSERVABLES beside H (ovqe_constrained_gradient_batch): C = E + sum_m [linear_m o_m + quad_m (o_m - target_m)^2] + the
+// deflation penalty, o_m = <psi|O_m|psi> + constant_m.  Every O_m restricted to the support is one more SpEntry stream of the kind the
+// Hamiltonian's is (sv_constrain_host.hpp: one rule for both), all of them one concatenated array in global memory, recs[m] naming the
+// range and the weights.  For a cost f(E, o_1 .. o_M) the adjoint vector is lambda = H psi + sum_m (df/do_m) O_m psi, so the row body is
+// k_sparse_vqd_batch's with ONE more phase behind the fence that completes the deflation phase's read-modify-writes of lambda.  Per
+// observable: pass one over its entries sums c a_u a_v in registers (no LDS write), wave_sum adds the lanes in its fixed tree, lane 0's
+// total goes to all lanes; g = linear + 2 quad (o - target) is then the same in every lane, and where it is not zero pass two applies
+// the same entries to lambda with their coefficients scaled by g (f64 LDS atomics, as lambda = H psi).  Two passes instead of a third
+// LDS array: the layout stays sp_grad_batch_lds (the observables take no LDS), the one barrier is the one behind the staging, and the
+// fence behind the phase completes its atomics before the backward walk reads lambda.  Cost, energy, values and the d_r of a row are
+// summed in fixed orders: equal rows give equal bits wherever they sit; the gradient reproduces to rounding.
+template <int NW, bool STAGE>
+__global__ __launch_bounds__(NW * 64) void k_sparse_constrained_batch(SparseArgs A, const double *__restrict__ theta,
+                                                                      const SmallRot *__restrict__ tabrots, const SpOp *__restrict__ ops,
+                                                                      const uint32_t *__restrict__ pairs, const SpEntry *__restrict__ entries,
+                                                                      const double *__restrict__ D, const DeflRow *__restrict__ drows, int nrows,
+                                                                      const SpEntry *__restrict__ oentries, const ConRec *__restrict__ recs,
+                                                                      int nobs, double *__restrict__ costs, double *__restrict__ energies,
+                                                                      double *__restrict__ grads, double *__restrict__ dvals,
+                                                                      double *__restrict__ values) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const SpGradBatchLds L = sp_grad_batch_lds(A, NW, STAGE);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const SpProgram P = sp_stage<STAGE, NW * 64>(smem, L.ops, L.pairs, ops, pairs, A.nops, A.npairs, (int)threadIdx.x);
+    __syncthreads();
+    unsigned char *mine = smem + (size_t)wave * L.stride;
+    double *psi = reinterpret_cast<double *>(mine);
+    double *lam = reinterpret_cast<double *>(mine + L.lam);
+    double2 *cs = reinterpret_cast<double2 *>(mine + L.cs);
+    double *w = reinterpret_cast<double *>(mine + L.w);
+    double *gk = reinterpret_cast<double *>(mine + L.gk);
+    for (int64_t b = (int64_t)blockIdx.x * NW + wave; b < A.B; b += (int64_t)gridDim.x * NW) {
+        const double *th = theta + b * A.K;
+        for (int i = lane; i < A.mpad; i += 64) {
+            psi[i] = i == A.hf ? 1.0 : 0.0;
+            lam[i] = 0.0;
+        }
+        sp_fill_table<64>(tabrots, A.ntab, lane, cs, [&](const SmallRot &sr) { return sr.coeff * th[sr.pidx]; },
+                          [&](int e, const SmallRot &) { w[e] = 0.0; });
+        for (int k = lane; k < A.K; k += 64) gk[k] = 0.0;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // forward
+        sp_for_ops<64>(P, 0, A.nops, lane, [&](const SpPair &p) { sp_rotate_pair(psi, cs, p); });
+        // lambda = H psi, E = <psi|lambda>
+        double acc = 0.0;
+#pragma unroll 4
+        for (int e = lane; e < A.nent; e += 64) {
+            const SpEntry en = entries[e];
+            const SpAmps a = sp_entry_amps(en, psi);
+            acc += en.c * a.u * a.v;
+            sp_apply_entry(en, {a}, {lam});
+        }
+        const double etot = wave_sum(acc);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // deflation: d_r = <D_r|psi>, lambda += beta_r d_r D_r, cost += beta_r d_r^2
+        double pen = 0.0;
+        for (int r = 0; r < nrows; ++r) {
+            const DeflRow dr = drows[r];
+            const double *row = D + (size_t)dr.src * A.mpad;
+            double dacc = 0.0;
+            for (int i = lane; i < A.mpad; i += 64) dacc = fma(row[i], psi[i], dacc);
+            const double d = __shfl(wave_sum(dacc), 0, 64);
+            const double c = dr.beta * d;
+            for (int i = lane; i < A.mpad; i += 64) lam[i] = fma(c, row[i], lam[i]);
+            pen = fma(c, d, pen);
+            if (lane == 0) dvals[b * nrows + r] = d;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // observables: o_m = <psi|O_m|psi> + constant_m, lambda += g_m O_m psi with g_m = linear_m + 2 quad_m (o_m - target_m)
+        for (int m = 0; m < nobs; ++m) {
+            const ConRec rec = recs[m];
+            const SpEntry *oe = oentries + rec.first;
+            double oacc = 0.0;
+#pragma unroll 1   // (unrolled by four the kernel takes 95 VGPRs, five waves per SIMD; so 79, the six of k_sparse_vqd_batch: profiles/constraints)
+            for (int e = lane; e < rec.count; e += 64) {
+                const SpEntry en = oe[e];
+                const SpAmps a = sp_entry_amps(en, psi);
+                oacc += en.c * a.u * a.v;
+            }
+            const double o = __shfl(wave_sum(oacc), 0, 64) + rec.constant;
+            if (lane == 0) values[b * nobs + m] = o;
+            const double dev = o - rec.target;
+            const double g = rec.linear + 2.0 * rec.quad * dev;
+            pen = fma(rec.linear, o, pen);
+            pen = fma(rec.quad * dev, dev, pen);
+            if (g != 0.0) {   // (wave-uniform: o was broadcast)
+#pragma unroll 4
+                for (int e = lane; e < rec.count; e += 64) {
+                    SpEntry en = oe[e];
+                    en.c *= g;
+                    sp_apply_entry(en, {sp_entry_amps(en, psi)}, {lam});
+                }
+            }
+        }
+        if (lane == 0) {
+            const double e = etot + A.constant;
+            energies[b] = e;
+            costs[b] = e + pen;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // backward
+        sp_for_ops_down<64>(P, 0, A.nops, lane, [&](const SpPair &p) {
+            const SpRot r = sp_rot(cs, p);
+            const SpAmps a = sp_get(psi, p), l = sp_get(lam, p);
+            const double g = l.u * a.v - l.v * a.u;
+            __hip_atomic_fetch_add(&w[p.e], sp_signed(p, g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            sp_put(psi, p, sp_rotate_back(r, a));
+            sp_put(lam, p, sp_rotate_back(r, l));
+        });
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        sp_fold<64>(tabrots, A.ntab, w, gk, lane);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        for (int k = lane; k < A.K; k += 64) grads[b * A.K + k] = gk[k];
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+}
+
 // ... and with the SPREAD of the energy (ovqe_spread_gradient_batch): S = ||(H - omega) psi||^2, omega the caller's per row or — omega
 // null — the row's own E, where S is the energy variance; cost = w_energy E + w_spread S with its exact gradient at fixed omega.  The
 // adjoint vector is lambda = w_energy H psi + w_spread (H - omega)^2 psi, so the row body is k_sparse_grad_batch's with a third private

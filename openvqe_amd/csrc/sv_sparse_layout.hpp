@@ -31,8 +31,14 @@ struct DeflRow {     // one real deflation row of k_sparse_vqd_batch: [mpad] dou
     int32_t src;
     int32_t pad;
 };
+struct ConRec {      // one observable of k_sparse_constrained_batch: its restricted entries [first, first + count) of the concatenated array,
+    int32_t first;   // and its term linear o + quad (o - target)^2 of the cost, o = <psi|O|psi> + constant
+    int32_t count;
+    double constant, linear, quad, target;
+};
 constexpr size_t SP_CS_BYTES = 16;   // one cos/sin table entry: a double2 (sv_sparse.hpp asserts it)
 static_assert(sizeof(SpOp) == 16 && sizeof(SpEntry) == 16 && sizeof(DeflRow) == 16, "16-byte records behind an even number of doubles");
+static_assert(sizeof(ConRec) == 40, "five 8-byte words");
 
 struct SparseArgs {
     int m;        // support size

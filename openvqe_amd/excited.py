@@ -99,7 +99,13 @@ def load_ritz_state(sv, ops, y):
     return norm2
 
 
-def vqd(sv, n_states, x0=None, beta=None, starts=8, spread=0.5, seed=0, tol=1e-6, maxiter=2000):
+def spin_constraint(nbqbits, s=0.0, weight=None):
+    """the constraint <S^2> = s (s + 1) for ``vqd(constraints=...)``: (``fermion.spin_squared(nbqbits)``, s (s + 1), ``weight``);
+    ``weight=None``: 2 sum_t |c_t| of the stored Hamiltonian, the default of ``beta``"""
+    return fermion.spin_squared(nbqbits), float(s) * (float(s) + 1.0), weight
+
+
+def vqd(sv, n_states, x0=None, beta=None, starts=8, spread=0.5, seed=0, tol=1e-6, maxiter=2000, constraints=None):
     """Variational quantum deflation on the program and Hamiltonian loaded in ``sv``: for k = 0 .. n_states - 1 the cost
     C = <H> + sum_j beta_j |<phi_j|psi(theta)>|^2 over the deflation vectors ``sv`` holds is minimised from ``starts`` starting vectors in
     lock-step (``multistart.minimize``, one ``deflated_gradient_batch`` call per iteration) — start 0 is ``x0`` (zeros by default), the
@@ -107,8 +113,13 @@ def vqd(sv, n_states, x0=None, beta=None, starts=8, spread=0.5, seed=0, tol=1e-6
     prepared and pushed with weight ``beta``.  ``beta=None``: 2 sum_t |c_t| of the stored Hamiltonian without its constant — more than
     its spectral width, so every deflated level lies above every level not yet found.  Vectors pushed before the call (a Lanczos ground
     state, say) are built upon; when the call leaves, normally or not, the set is truncated back to what it found.
+    ``constraints``: a list of (operator, target, quad_weight) — ``spin_constraint`` builds one — adds quad_weight (<operator> - target)^2
+    to every state's cost: the operators are pushed behind the observables ``sv`` holds (those enter with weight zero), every iteration
+    is one ``constrained_gradient_batch`` call, and the observables are truncated back when the call leaves.  A weight of None is
+    2 sum_t |c_t| of the stored Hamiltonian.  With ``constraints=None`` the observables are not touched.
     -> a list of ``n_states`` dicts: ``energy``, ``cost``, ``theta``, ``overlaps`` (complex, with the vectors held before state k was
-    pushed: the earlier states last) and ``result`` (the multistart result)"""
+    pushed: the earlier states last) and ``result`` (the multistart result); with constraints also ``values``, the expectation values
+    of the observables held"""
     from .common_files import multistart
     K = sv._K
     x0 = np.zeros(K) if x0 is None else np.asarray(x0, np.float64).reshape(-1)
@@ -120,6 +131,8 @@ def vqd(sv, n_states, x0=None, beta=None, starts=8, spread=0.5, seed=0, tol=1e-6
     rng = np.random.default_rng(seed)
     found = sv.deflation_count()
     states = []
+    if constraints is not None:
+        return _vqd_constrained(sv, int(n_states), x0, beta, int(starts), spread, rng, tol, maxiter, list(constraints), found)
     try:
         for _ in range(int(n_states)):
             X0 = np.tile(x0, (int(starts), 1))
@@ -132,6 +145,34 @@ def vqd(sv, n_states, x0=None, beta=None, starts=8, spread=0.5, seed=0, tol=1e-6
             sv.deflation_push(beta)
     finally:
         sv.deflation_truncate(found)
+    return states
+
+
+def _vqd_constrained(sv, n_states, x0, beta, starts, spread, rng, tol, maxiter, constraints, found):
+    """``vqd`` with penalty terms: the same loop on ``constrained_gradient_batch``"""
+    from .common_files import multistart
+    K = sv._K
+    held = sv.observable_count()
+    quad = np.zeros(held + len(constraints))
+    target = np.zeros(held + len(constraints))
+    states = []
+    try:
+        for m, (operator, want, weight) in enumerate(constraints):
+            sv.observable_push(operator)
+            target[held + m] = float(want)
+            quad[held + m] = 2.0 * sv.hamiltonian_norm1() if weight is None else float(weight)
+        for _ in range(n_states):
+            X0 = np.tile(x0, (starts, 1))
+            X0[1:] += rng.uniform(-spread, spread, size=(starts - 1, K))
+            res = multistart.minimize(lambda X: sv.constrained_gradient_batch(X, quad=quad, target=target)[:2], X0, tol=tol, maxiter=maxiter)
+            cost, _, energy, values, overlaps = sv.constrained_gradient_batch(res.x[None, :], quad=quad, target=target)
+            states.append({"energy": float(energy[0]), "cost": float(cost[0]), "theta": res.x.copy(), "overlaps": overlaps[0].copy(),
+                           "values": values[0].copy(), "result": res})
+            sv.prepare_state(res.x)
+            sv.deflation_push(beta)
+    finally:
+        sv.deflation_truncate(found)
+        sv.observable_truncate(held)
     return states
 
 

@@ -173,6 +173,44 @@ def psum_to_hamiltonian(nqbits, psum, constant=0.0, tol=1e-13, real=False):
     return Hamiltonian(nqbits, terms, const, do_clean_up=False)
 
 
+# ---------------------------------------------------------------- particle number and spin
+# spin orbital p = qubit p, interleaved spins (even alpha, odd beta): the convention of ``rdm.spin_expectations``
+def _number_psum(p):
+    return jw_product([(p, True), (p, False)])
+
+
+def _sz_psum(nqbits):
+    out = {}
+    for p in range(nqbits):
+        psum_iadd(out, _number_psum(p), 0.5 if p % 2 == 0 else -0.5)
+    return out
+
+
+def number_operator(nqbits):
+    """N = sum_p a+_p a_p as a Hamiltonian (``Statevector.observable_push``)"""
+    out = {}
+    for p in range(nqbits):
+        psum_iadd(out, _number_psum(p))
+    return psum_to_hamiltonian(nqbits, out, real=True)
+
+
+def sz_operator(nqbits):
+    """S_z = 1/2 sum_i (n_2i - n_2i+1)"""
+    return psum_to_hamiltonian(nqbits, _sz_psum(nqbits), real=True)
+
+
+def spin_squared(nqbits):
+    """S^2 = S_- S_+ + S_z + S_z^2 with S_+ = sum_i a+_2i a_2i+1: eigenvalues s (s + 1)"""
+    if nqbits % 2:
+        raise ValueError("an even number of spin orbitals")
+    plus, minus = {}, {}
+    for i in range(nqbits // 2):
+        psum_iadd(plus, jw_product([(2 * i, True), (2 * i + 1, False)]))
+        psum_iadd(minus, jw_product([(2 * i + 1, True), (2 * i, False)]))
+    sz = _sz_psum(nqbits)
+    return psum_to_hamiltonian(nqbits, psum_add(psum_add(psum_mul(minus, plus), sz), psum_mul(sz, sz)), real=True)
+
+
 # ---------------------------------------------------------------- molecular Hamiltonian
 def spin_orbital_integrals(h1_spatial, eri_chem):
     """Spatial integrals -> spin-orbital (interleaved) h_pq and physicist-ordered h_pqrs with

@@ -276,6 +276,12 @@ class PartitionedStatevector:
 
     energy_variance = spread_info = spread_gradient_batch
 
+    def observable_push(self, *args, **kwargs):
+        raise NotImplementedError("observables are held next to one device's register (ovqe_observable_push, "
+                                  "ovqe_constrained_gradient_batch): constrained costs are not available on the partitioned register")
+
+    observable_truncate = observable_count = constrained_gradient_batch = expectations_batch = constraint_info = observable_push
+
     def subspace_matrices(self, *args, **kwargs):
         raise NotImplementedError("subspace-expansion matrices are computed on one device (ovqe_subspace_matrices keeps the expansion "
                                   "vectors next to the state): not available on the partitioned register")
