@@ -77,20 +77,9 @@ int ovqe_deflated_gradient_batch(ovqe_handle h, int64_t B, const double *theta, 
                                  double *overlaps_re_im) try {
     OVQE_ENTER(h);
     if (!h) return OVQE_ERR_INVALID;
-    if (B < 0) return fail(h, OVQE_ERR_INVALID, "ovqe_deflated_gradient_batch: B is negative");
-    // what ovqe_energy_gradient_batch refuses, with its codes
-    if (!h->prog_set) return fail(h, OVQE_ERR_STATE, "no program set (ovqe_set_program / ovqe_set_gate_program)");
-    if (K != h->K) return fail(h, OVQE_ERR_INVALID, "K does not match the program's parameter count");
-    if (!h->ham.set) return fail(h, OVQE_ERR_STATE, "no Hamiltonian set (ovqe_set_hamiltonian)");
-    if (h->n_global) return fail(h, OVQE_ERR_INVALID, "ovqe_deflated_gradient_batch is single-device, as ovqe_energy_gradient: not available on a shard handle");
-    if (h->opt_real_state) return fail(h, OVQE_ERR_STATE, "ovqe_deflated_gradient_batch: not available under option real_state (the buffer holds 8-byte amplitudes)");
-    if (h->frame_open)
-        return fail(h, OVQE_ERR_STATE, "ovqe_deflated_gradient_batch: the gate program's Clifford frame is open — the stored vectors live in the caller's frame, "
-                                       "the evaluated state does not; option \"clifford_frame\" = 0 runs such a list literally");
-    if (B == 0) return OVQE_OK;
-    if (!costs) return fail(h, OVQE_ERR_INVALID, "ovqe_deflated_gradient_batch: costs is NULL");
-    if (K > 0 && (!theta || !grads)) return fail(h, OVQE_ERR_INVALID, std::string("ovqe_deflated_gradient_batch: ") + (theta ? "grads" : "theta") + " is NULL");
-    if (B > ((int64_t)1 << 40) / std::max<int64_t>(K, 1)) return fail(h, OVQE_ERR_INVALID, "ovqe_deflated_gradient_batch: B x K is out of range");
+    bool empty = false;
+    const int refused = batch_refusals(h, {"ovqe_deflated_gradient_batch", true, "the stored vectors live", "costs", costs}, B, theta, K, grads, &empty);
+    if (refused || empty) return refused;
     {
         bool done = false;
         const int rc = run_vqd_batch(h, B, theta, costs, grads, energies, overlaps_re_im, &done);
@@ -105,11 +94,7 @@ int ovqe_deflated_gradient_batch(ovqe_handle h, int64_t B, const double *theta, 
     for (int64_t b = 0; b < B; ++b) {
         if (int rc = deflated_row_streaming(h, theta + b * K, K, costs + b, K > 0 ? grads + b * K : &none, &e, o, &launches)) return rc;
         if (energies) energies[b] = e;
-        if (overlaps_re_im)
-            for (int64_t j = 0; j < J; ++j) {
-                overlaps_re_im[2 * (b * J + j)] = o[j].x;
-                overlaps_re_im[2 * (b * J + j) + 1] = o[j].y;
-            }
+        if (overlaps_re_im) overlaps_out(overlaps_re_im, b, J, o);
     }
     const int64_t info[14] = {2, B, K, J, 0, launches, 0, 0, 0, 0, 0, 0, 0, 0};
     std::copy(info, info + 14, D.info);
@@ -118,7 +103,5 @@ int ovqe_deflated_gradient_batch(ovqe_handle h, int64_t B, const double *theta, 
 
 int ovqe_deflation_info(ovqe_handle h, int64_t *info, int count) try {
     OVQE_ENTER(h);
-    if (!h || !info || count < 0) return OVQE_ERR_INVALID;
-    for (int i = 0; i < count && i < 14; ++i) info[i] = h->deflate ? h->deflate->info[i] : 0;
-    return OVQE_OK;
+    return info_out(h, h && h->deflate ? h->deflate->info : nullptr, 14, info, count);
 } OVQE_CATCH(h)

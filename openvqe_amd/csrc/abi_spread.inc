@@ -60,18 +60,12 @@ int ovqe_spread_gradient_batch(ovqe_handle h, int64_t B, const double *theta, in
                                double *costs, double *grads, double *energies, double *spreads) try {
     OVQE_ENTER(h);
     if (!h) return OVQE_ERR_INVALID;
-    if (B < 0) return fail(h, OVQE_ERR_INVALID, "ovqe_spread_gradient_batch: B is negative");
-    // what ovqe_energy_gradient_batch refuses, with its codes
-    if (!h->prog_set) return fail(h, OVQE_ERR_STATE, "no program set (ovqe_set_program / ovqe_set_gate_program)");
-    if (K != h->K) return fail(h, OVQE_ERR_INVALID, "K does not match the program's parameter count");
-    if (!h->ham.set) return fail(h, OVQE_ERR_STATE, "no Hamiltonian set (ovqe_set_hamiltonian)");
-    if (h->n_global) return fail(h, OVQE_ERR_INVALID, "ovqe_spread_gradient_batch is single-device, as ovqe_energy_gradient: not available on a shard handle");
-    if (h->opt_real_state) return fail(h, OVQE_ERR_STATE, "ovqe_spread_gradient_batch: not available under option real_state (the buffer holds 8-byte amplitudes)");
-    if (!std::isfinite(w_energy) || !std::isfinite(w_spread)) return fail(h, OVQE_ERR_INVALID, "ovqe_spread_gradient_batch: the weights must be finite");
-    if (B == 0) return OVQE_OK;
-    if (!costs) return fail(h, OVQE_ERR_INVALID, "ovqe_spread_gradient_batch: costs is NULL");
-    if (K > 0 && (!theta || !grads)) return fail(h, OVQE_ERR_INVALID, std::string("ovqe_spread_gradient_batch: ") + (theta ? "grads" : "theta") + " is NULL");
-    if (B > ((int64_t)1 << 40) / std::max<int64_t>(K, 1)) return fail(h, OVQE_ERR_INVALID, "ovqe_spread_gradient_batch: B x K is out of range");
+    bool empty = false;
+    const int refused = batch_refusals(h, {"ovqe_spread_gradient_batch", true, nullptr, "costs", costs}, B, theta, K, grads, &empty, [&] {
+        if (!std::isfinite(w_energy) || !std::isfinite(w_spread)) return fail(h, OVQE_ERR_INVALID, "ovqe_spread_gradient_batch: the weights must be finite");
+        return (int)OVQE_OK;
+    });
+    if (refused || empty) return refused;
     if (omega)
         for (int64_t b = 0; b < B; ++b)
             if (!std::isfinite(omega[b])) return fail(h, OVQE_ERR_INVALID, "ovqe_spread_gradient_batch: omega[" + std::to_string(b) + "] is not finite");
@@ -99,7 +93,5 @@ int ovqe_spread_gradient_batch(ovqe_handle h, int64_t B, const double *theta, in
 
 int ovqe_spread_info(ovqe_handle h, int64_t *info, int count) try {
     OVQE_ENTER(h);
-    if (!h || !info || count < 0) return OVQE_ERR_INVALID;
-    for (int i = 0; i < count && i < 13; ++i) info[i] = h->spread ? h->spread->info[i] : 0;
-    return OVQE_OK;
+    return info_out(h, h && h->spread ? h->spread->info : nullptr, 13, info, count);
 } OVQE_CATCH(h)

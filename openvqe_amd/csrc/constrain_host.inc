@@ -7,8 +7,8 @@
 // either leaves them alone.  Each is kept as a grouped sum on the device (a HamDev: the streaming path applies it with
 // apply_hamiltonian) and, for path 1, restricted to the compact support as SpEntry records — all observables one concatenated array.
 // The entries are built lazily and cached: they are restricted again when the compact program was rebuilt (h->sp_build) or the set of
-// observables changed (set_version) — the rule of the gathered deflation rows.  Path 1 is run_vqd_batch's (constrained_batch_plan restates its decision) with the
-// deflation rows of deflate_host.inc.  Everything the calls allocate is this record's.
+// observables changed (set_version) — the rule of the gathered deflation rows.  Path 1 is run_vqd_batch's (compact_batch_plan) with
+// the deflation rows of deflate_host.inc.  Everything the calls allocate is this record's.
 
 struct ConstrainDev {
     std::vector<HamDev *> obs;     // O_m: grouped terms on host and device, the constant
@@ -18,9 +18,8 @@ struct ConstrainDev {
     std::vector<int32_t> first;    // [M + 1]: observable m's entries are [first[m], first[m + 1])
     DevBuf d_entries, d_recs;
     int64_t entries_build = -1, entries_set = -1;
-    DevBuf d_theta, d_out;         // rows [B * K]; costs [B], energies [B], gradients [B * K], row overlaps [B * rows], values [B * M]
+    BatchIo io;                    // results: costs [B], energies [B], gradients [B * K], row overlaps [B * rows], values [B * M]
     std::vector<double> h_d;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     int64_t info[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -33,10 +32,9 @@ void free_observable(HamDev *H) {
 void free_constrain(ConstrainDev *C) {
     if (!C) return;
     for (HamDev *H : C->obs) free_observable(H);
-    for (DevBuf *b : {&C->d_entries, &C->d_recs, &C->d_theta, &C->d_out})
+    for (DevBuf *b : {&C->d_entries, &C->d_recs})
         if (b->p) (void)hipFree(b->p);
-    for (hipEvent_t e : C->ev)
-        if (e) (void)hipEventDestroy(e);
+    C->io.release();
     delete C;
 }
 
@@ -98,47 +96,6 @@ int constrain_restrict(ovqe_handle h, ConstrainDev &C, int64_t *builds) {
     return OVQE_OK;
 }
 
-// Whether a batch of B rows runs on the compact support: run_vqd_batch's decision (deflate_host.inc), which is run_grad_batch's — same
-// eligibility, same planner — with the kernel arguments and the launch geometry.  *ok = false: not eligible (nothing was launched).
-int constrained_batch_plan(ovqe_handle h, int64_t B, SparseArgs *args, gradbatch::Plan *plan, bool *ok) {
-    *ok = false;
-    if (!(h->opt_force_path == 0 || h->opt_force_path == 3) || !h->opt_sparse_grad || h->n_local > 16) return OVQE_OK;
-    int rc = OVQE_OK;
-    if (!h->sp_tried && (rc = build_sparse_program(h))) return rc;
-    if (!h->sp_valid) return OVQE_OK;
-    SparseArgs A;
-    A.m = h->sp_mp;
-    A.mpad = (h->sp_mp + 1) & ~1;
-    A.hf = h->sp_hf;
-    A.K = h->K;
-    A.nops = h->sp_nops;
-    A.ntab = (int)h->srots.size();
-    A.nent = h->sp_nent;
-    A.npairs = (int)h->sp_npairs;
-    A.B = B;
-    A.constant = h->ham.constant;
-    if (!gradbatch::eligible(A)) return OVQE_OK;
-    const gradbatch::Plan G = gradbatch::plan(A, B, h->opt_grad_batch_waves, h->opt_grad_batch_workgroups, handle_num_cus(h));
-    if (!G.ok) return OVQE_OK;
-    *args = A;
-    *plan = G;
-    *ok = true;
-    return OVQE_OK;
-}
-
-template <int NW>
-int launch_constrained_batch(ovqe_handle h, bool stage, unsigned grid, size_t lds, const SparseArgs &A, const double *d_theta, const DeflateDev &D,
-                             const ConstrainDev &C, int M, double *d_c, double *d_e, double *d_g, double *d_d, double *d_v) {
-    constexpr auto staged = &k_sparse_constrained_batch<NW, true>, plain = &k_sparse_constrained_batch<NW, false>;
-    if (int rc = lds_opt_in<staged, plain>(h, LDS_WG_MAX)) return rc;
-    hipLaunchKernelGGL(stage ? staged : plain, dim3(grid), dim3(NW * 64), lds, h->stream, A, d_theta, (const SmallRot *)h->d_rots.p,
-                       (const SpOp *)h->d_sp_ops.p, (const uint32_t *)h->d_sp_pairs.p, (const SpEntry *)h->d_sp_entries.p,
-                       (const double *)D.d_D.p, (const DeflRow *)D.d_rows.p, (int)D.rows.size(), (const SpEntry *)C.d_entries.p,
-                       (const ConRec *)C.d_recs.p, M, d_c, d_e, d_g, d_d, d_v);
-    HIPC(h, hipGetLastError());
-    return OVQE_OK;
-}
-
 // *done = false: the program is not eligible for path 1 (nothing was launched, info untouched).  linear, quad, target: M doubles each
 // (zeros where the caller gave none); energies, values, overlaps: may be null
 int run_constrained_batch(ovqe_handle h, int64_t B, const double *theta, const double *linear, const double *quad, const double *target,
@@ -148,10 +105,9 @@ int run_constrained_batch(ovqe_handle h, int64_t B, const double *theta, const d
     SparseArgs A;
     gradbatch::Plan G;
     bool ok = false;
-    if ((rc = constrained_batch_plan(h, B, &A, &G, &ok)) || !ok) return rc;
+    if ((rc = compact_batch_plan(h, B, &A, &G, &ok)) || !ok) return rc;
     DeflateDev &D = deflate_dev(h);
     ConstrainDev &C = constrain_dev(h);
-    if ((rc = ensure_events(h, C.ev, 3))) return rc;
     int64_t gathers = 0, builds = 0;
     if ((rc = deflate_gather(h, D, A.mpad, &gathers))) return rc;
     if ((rc = constrain_restrict(h, C, &builds))) return rc;
@@ -160,22 +116,16 @@ int run_constrained_batch(ovqe_handle h, int64_t B, const double *theta, const d
     for (size_t m = 0; m < M; ++m)
         recs[m] = ConRec{C.first[m], C.first[m + 1] - C.first[m], C.obs[m]->constant, linear[m], quad[m], target[m]};
     if ((rc = ensure(h, C.d_recs, sizeof(recs)))) return rc;
-    if ((rc = ensure(h, C.d_theta, rows * sizeof(double)))) return rc;
-    if ((rc = ensure(h, C.d_out, (2 * (size_t)B + rows + (size_t)B * nr + (size_t)B * M) * sizeof(double)))) return rc;
-    double *d_c = (double *)C.d_out.p, *d_e = d_c + B, *d_g = d_e + B, *d_d = d_g + rows, *d_v = d_d + (size_t)B * nr;
-    HIPC(h, hipEventRecord(C.ev[0], h->stream));
-    HIPC(h, hipMemcpyAsync(C.d_theta.p, theta, rows * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if ((rc = C.io.begin(h, theta, rows, 2 * (size_t)B + rows + (size_t)B * nr + (size_t)B * M))) return rc;
+    double *d_c = (double *)C.io.d_out.p, *d_e = d_c + B, *d_g = d_e + B, *d_d = d_g + rows, *d_v = d_d + (size_t)B * nr;
     HIPC(h, hipMemcpyAsync(C.d_recs.p, recs, sizeof(recs), hipMemcpyHostToDevice, h->stream));
-    const unsigned grid = (unsigned)G.workgroups;
-    const double *d_theta = (const double *)C.d_theta.p;
-    switch (G.nw) {
-    case 1: rc = launch_constrained_batch<1>(h, G.stage, grid, G.lds, A, d_theta, D, C, (int)M, d_c, d_e, d_g, d_d, d_v); break;
-    case 2: rc = launch_constrained_batch<2>(h, G.stage, grid, G.lds, A, d_theta, D, C, (int)M, d_c, d_e, d_g, d_d, d_v); break;
-    case 4: rc = launch_constrained_batch<4>(h, G.stage, grid, G.lds, A, d_theta, D, C, (int)M, d_c, d_e, d_g, d_d, d_v); break;
-    default: rc = launch_constrained_batch<8>(h, G.stage, grid, G.lds, A, d_theta, D, C, (int)M, d_c, d_e, d_g, d_d, d_v); break;
-    }
+    rc = for_batch_waves(G.nw, [&](auto NW) {
+        constexpr int nw = decltype(NW)::value;
+        return launch_compact_batch<&k_sparse_constrained_batch<nw, true>, &k_sparse_constrained_batch<nw, false>>(
+            h, G, A, C.io, (const double *)D.d_D.p, (const DeflRow *)D.d_rows.p, (int)D.rows.size(), (const SpEntry *)C.d_entries.p,
+            (const ConRec *)C.d_recs.p, (int)M, d_c, d_e, d_g, d_d, d_v);
+    });
     if (rc) return rc;
-    HIPC(h, hipEventRecord(C.ev[1], h->stream));
     HIPC(h, hipMemcpyAsync(costs, d_c, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (energies) HIPC(h, hipMemcpyAsync(energies, d_e, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipMemcpyAsync(grads, d_g, rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -184,13 +134,11 @@ int run_constrained_batch(ovqe_handle h, int64_t B, const double *theta, const d
         C.h_d.resize((size_t)B * nr);
         HIPC(h, hipMemcpyAsync(C.h_d.data(), d_d, (size_t)B * nr * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     }
-    HIPC(h, hipEventRecord(C.ev[2], h->stream));
-    HIPC(h, hipStreamSynchronize(h->stream));
+    if ((rc = C.io.end(h, C.info + 14))) return rc;
     if (overlaps && nr) deflate_overlaps_out(h, D, B, C.h_d.data(), overlaps);
     const int64_t info[14] = {1, B, (int64_t)K, (int64_t)M, (int64_t)J, (int64_t)nr, 1, G.stage ? 1 : 2, G.nw, G.workgroups, (int64_t)G.lds,
                               h->sp_m, (int64_t)C.entries.size(), builds};
     std::copy(info, info + 14, C.info);
-    if ((rc = phases_us(h, C.ev, 2, C.info + 14))) return rc;
     *done = true;
     return OVQE_OK;
 }

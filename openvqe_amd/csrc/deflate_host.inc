@@ -18,9 +18,8 @@ struct DeflateDev {
     std::vector<int> row_vec;      // per row in use: its vector, and whether it is the imaginary part
     std::vector<uint8_t> row_im;
     int64_t gather_build = -1, gather_set = -1;
-    DevBuf d_theta, d_out;         // rows [B * K]; costs [B], energies [B], gradients [B * K], row overlaps [B * rows]
+    BatchIo io;                    // results: costs [B], energies [B], gradients [B * K], row overlaps [B * rows]
     std::vector<double> h_d;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     int64_t info[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -28,10 +27,9 @@ void free_deflate(DeflateDev *D) {
     if (!D) return;
     for (amp_t *v : D->vecs)
         if (v) (void)hipFree(v);
-    for (DevBuf *b : {&D->d_D, &D->d_flags, &D->d_rows, &D->d_theta, &D->d_out})
+    for (DevBuf *b : {&D->d_D, &D->d_flags, &D->d_rows})
         if (b->p) (void)hipFree(b->p);
-    for (hipEvent_t e : D->ev)
-        if (e) (void)hipEventDestroy(e);
+    D->io.release();
     delete D;
 }
 
@@ -113,18 +111,6 @@ int deflate_gather(ovqe_handle h, DeflateDev &D, int mpad, int64_t *launches) {
     return OVQE_OK;
 }
 
-template <int NW>
-int launch_vqd_batch(ovqe_handle h, bool stage, unsigned grid, size_t lds, const SparseArgs &A, const double *d_theta, const DeflateDev &D,
-                     double *d_c, double *d_e, double *d_g, double *d_d) {
-    constexpr auto staged = &k_sparse_vqd_batch<NW, true>, plain = &k_sparse_vqd_batch<NW, false>;
-    if (int rc = lds_opt_in<staged, plain>(h, LDS_WG_MAX)) return rc;
-    hipLaunchKernelGGL(stage ? staged : plain, dim3(grid), dim3(NW * 64), lds, h->stream, A, d_theta, (const SmallRot *)h->d_rots.p,
-                       (const SpOp *)h->d_sp_ops.p, (const uint32_t *)h->d_sp_pairs.p, (const SpEntry *)h->d_sp_entries.p,
-                       (const double *)D.d_D.p, (const DeflRow *)D.d_rows.p, (int)D.rows.size(), d_c, d_e, d_g, d_d);
-    HIPC(h, hipGetLastError());
-    return OVQE_OK;
-}
-
 // o_bj = <phi_j|psi> = init_amp (<Re phi_j|psi_c> - i <Im phi_j|psi_c>) from the row values d[B x rows in use] of a path-1 launch: the
 // compact state starts from 1 at |hf>, the register from init_amp (the phase a folded Clifford part leaves)
 void deflate_overlaps_out(ovqe_handle h, const DeflateDev &D, int64_t B, const double *d, double *overlaps) {
@@ -146,43 +132,23 @@ void deflate_overlaps_out(ovqe_handle h, const DeflateDev &D, int64_t B, const d
 // *done = false: the program is not eligible for path 1 (nothing was launched, info untouched).  energies, overlaps: may be null
 int run_vqd_batch(ovqe_handle h, int64_t B, const double *theta, double *costs, double *grads, double *energies, double *overlaps, bool *done) {
     *done = false;
-    if (!(h->opt_force_path == 0 || h->opt_force_path == 3) || !h->opt_sparse_grad || h->n_local > 16) return OVQE_OK;
     int rc = OVQE_OK;
-    if (!h->sp_tried && (rc = build_sparse_program(h))) return rc;
-    if (!h->sp_valid) return OVQE_OK;
     SparseArgs A;
-    A.m = h->sp_mp;
-    A.mpad = (h->sp_mp + 1) & ~1;
-    A.hf = h->sp_hf;
-    A.K = h->K;
-    A.nops = h->sp_nops;
-    A.ntab = (int)h->srots.size();
-    A.nent = h->sp_nent;
-    A.npairs = (int)h->sp_npairs;
-    A.B = B;
-    A.constant = h->ham.constant;
-    if (!gradbatch::eligible(A)) return OVQE_OK;
-    const gradbatch::Plan G = gradbatch::plan(A, B, h->opt_grad_batch_waves, h->opt_grad_batch_workgroups, handle_num_cus(h));
-    if (!G.ok) return OVQE_OK;
+    gradbatch::Plan G;
+    bool ok = false;
+    if ((rc = compact_batch_plan(h, B, &A, &G, &ok)) || !ok) return rc;
     DeflateDev &D = deflate_dev(h);
-    if ((rc = ensure_events(h, D.ev, 3))) return rc;
     int64_t gathers = 0;
     if ((rc = deflate_gather(h, D, A.mpad, &gathers))) return rc;
     const size_t K = (size_t)h->K, rows = (size_t)B * K, J = D.vecs.size(), nr = D.rows.size();
-    if ((rc = ensure(h, D.d_theta, rows * sizeof(double)))) return rc;
-    if ((rc = ensure(h, D.d_out, (2 * (size_t)B + rows + (size_t)B * nr) * sizeof(double)))) return rc;
-    double *d_c = (double *)D.d_out.p, *d_e = d_c + B, *d_g = d_e + B, *d_d = d_g + rows;
-    HIPC(h, hipEventRecord(D.ev[0], h->stream));
-    HIPC(h, hipMemcpyAsync(D.d_theta.p, theta, rows * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    const unsigned grid = (unsigned)G.workgroups;
-    switch (G.nw) {
-    case 1: rc = launch_vqd_batch<1>(h, G.stage, grid, G.lds, A, (const double *)D.d_theta.p, D, d_c, d_e, d_g, d_d); break;
-    case 2: rc = launch_vqd_batch<2>(h, G.stage, grid, G.lds, A, (const double *)D.d_theta.p, D, d_c, d_e, d_g, d_d); break;
-    case 4: rc = launch_vqd_batch<4>(h, G.stage, grid, G.lds, A, (const double *)D.d_theta.p, D, d_c, d_e, d_g, d_d); break;
-    default: rc = launch_vqd_batch<8>(h, G.stage, grid, G.lds, A, (const double *)D.d_theta.p, D, d_c, d_e, d_g, d_d); break;
-    }
+    if ((rc = D.io.begin(h, theta, rows, 2 * (size_t)B + rows + (size_t)B * nr))) return rc;
+    double *d_c = (double *)D.io.d_out.p, *d_e = d_c + B, *d_g = d_e + B, *d_d = d_g + rows;
+    rc = for_batch_waves(G.nw, [&](auto NW) {
+        constexpr int nw = decltype(NW)::value;
+        return launch_compact_batch<&k_sparse_vqd_batch<nw, true>, &k_sparse_vqd_batch<nw, false>>(
+            h, G, A, D.io, (const double *)D.d_D.p, (const DeflRow *)D.d_rows.p, (int)D.rows.size(), d_c, d_e, d_g, d_d);
+    });
     if (rc) return rc;
-    HIPC(h, hipEventRecord(D.ev[1], h->stream));
     HIPC(h, hipMemcpyAsync(costs, d_c, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (energies) HIPC(h, hipMemcpyAsync(energies, d_e, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipMemcpyAsync(grads, d_g, rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -190,12 +156,10 @@ int run_vqd_batch(ovqe_handle h, int64_t B, const double *theta, double *costs, 
         D.h_d.resize((size_t)B * nr);
         HIPC(h, hipMemcpyAsync(D.h_d.data(), d_d, (size_t)B * nr * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     }
-    HIPC(h, hipEventRecord(D.ev[2], h->stream));
-    HIPC(h, hipStreamSynchronize(h->stream));
+    if ((rc = D.io.end(h, D.info + 12))) return rc;
     if (overlaps && nr) deflate_overlaps_out(h, D, B, D.h_d.data(), overlaps);
     const int64_t info[12] = {1, B, (int64_t)K, (int64_t)J, (int64_t)nr, 1, G.stage ? 1 : 2, G.nw, G.workgroups, (int64_t)G.lds, h->sp_m, gathers};
     std::copy(info, info + 12, D.info);
-    if ((rc = phases_us(h, D.ev, 2, D.info + 12))) return rc;
     *done = true;
     return OVQE_OK;
 }

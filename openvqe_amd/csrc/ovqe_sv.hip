@@ -14,7 +14,7 @@
 //   measure_host.inc finite-shot measurement: basis change, prefix sums, shots                         (sv_measure_host.hpp; kernels: sv_measure.hpp)
 //   subspace_host.inc  subspace-expansion matrices around the resident state: rows, expansion vectors, sigma = H Phi, Gram    (sv_subspace_host.hpp; kernels: sv_subspace.hpp, sv_rdm.hpp)
 //   hessian_host.inc  exact energy Hessian: restricted Hamiltonian on the metric's compact program, one launch; column stores and the backward walk    (sv_hessian_host.hpp; kernels: sv_sparse.hpp, sv_hessian.hpp)
-//   gradbatch_host.inc  exact gradients of a batch of parameter vectors on the compact support, one launch    (sv_gradbatch_host.hpp; kernel: sv_sparse.hpp)
+//   gradbatch_host.inc  exact gradients of a batch of parameter vectors on the compact support, one launch; what the next three share with it: compact_batch_plan, BatchIo, for_batch_waves / launch_compact_batch, and batch_refusals / overlaps_out / info_out of their entry points    (sv_gradbatch_host.hpp; kernel: sv_sparse.hpp)
 //   deflate_host.inc  deflation vectors of the register; deflated energies and gradients, compact (one launch) and streaming    (kernels: sv_sparse.hpp, sv_deflate.hpp)
 //   spread_host.inc  energy spread ||(H - omega) psi||^2 (variance, folded-spectrum cost) with its gradient on the compact support, one launch    (sv_spread_host.hpp; kernel: sv_sparse.hpp)
 //   constrain_host.inc  observables of the register beside the Hamiltonian; costs of their expectation values with exact gradients on the compact support, one launch    (sv_constrain_host.hpp; kernel: sv_sparse.hpp)

@@ -345,11 +345,8 @@ int launch_rows_shared(ovqe_handle h, const SparseArgs &R, bool *taken) {
     return launch_rows_shared_dbg<NW, RPT, EPR, SSTRIDE, TE, 0>(h, R, smem);
 }
 
-// on_device: theta / energies are device pointers (inputs already resident in HBM, results left there).  *done = false: no compact
-// form fits this program's LDS budget (nothing was launched; the caller takes the other paths).
-int run_sparse(ovqe_handle h, int64_t B, const double *theta, double *energies, bool on_device, bool *done) {
-    *done = false;
-    int rc = OVQE_OK;
+// the kernel arguments of the handle's compact program for a batch of B rows
+SparseArgs sparse_args(ovqe_handle h, int64_t B) {
     SparseArgs A;
     A.m = h->sp_mp;
     A.mpad = (h->sp_mp + 1) & ~1;
@@ -361,6 +358,15 @@ int run_sparse(ovqe_handle h, int64_t B, const double *theta, double *energies, 
     A.npairs = (int)h->sp_npairs;
     A.B = B;
     A.constant = h->ham.constant;
+    return A;
+}
+
+// on_device: theta / energies are device pointers (inputs already resident in HBM, results left there).  *done = false: no compact
+// form fits this program's LDS budget (nothing was launched; the caller takes the other paths).
+int run_sparse(ovqe_handle h, int64_t B, const double *theta, double *energies, bool on_device, bool *done) {
+    *done = false;
+    int rc = OVQE_OK;
+    SparseArgs A = sparse_args(h, B);
     A.dbg = h->opt_sparse_dbg;
     int spw = h->opt_sparse_spw;
     if (spw != 1 && spw != 2 && spw != 4) spw = B >= 2048 ? 2 : 1;  // measured: 2 evaluations per wave is the sweet spot
@@ -500,17 +506,7 @@ int run_sparse_gradient(ovqe_handle h, const double *theta, double *energy, doub
         h->sp_forms |= SPF_DECLINED;
         return OVQE_OK;
     }
-    SparseArgs A;
-    A.m = h->sp_mp;
-    A.mpad = (h->sp_mp + 1) & ~1;
-    A.hf = h->sp_hf;
-    A.K = h->K;
-    A.nops = h->sp_nops;
-    A.ntab = (int)h->srots.size();
-    A.nent = h->sp_nent;
-    A.npairs = (int)h->sp_npairs;
-    A.B = 1;
-    A.constant = h->ham.constant;
+    const SparseArgs A = sparse_args(h, 1);
     const size_t base = sp_grad_lds(A, false).bytes, staged = sp_grad_lds(A, true).bytes;
     if (base > LDS_WG_BUDGET) {
         h->sp_forms |= SPF_DECLINED;

@@ -26,7 +26,7 @@ static_assert(sizeof(double2) == SP_CS_BYTES, "the layouts of sv_sparse_layout.h
 // ---- building blocks of the one-wave kernels (k_sparse_vqe, k_sparse_grad, k_sparse_metric; k_sparse_hessian: see there) -------------
 // A kernel is: sp_stage, then per work item a table fill, walks of the op list (sp_for_ops / sp_for_ops_down) whose bodies are the
 // Givens steps below on one decoded pair, an entry loop (sp_entry_amps / sp_apply_entry) and sp_fold.  The s_waitcnt fences between
-// the phases stay in the kernels: they are each kernel's own ordering argument.
+// the phases stay in the kernels: they are each kernel's own ordering argument (the gradient kernels share theirs: sp_adjoint_row).
 struct SpProgram { const SpOp *opv; const uint32_t *pv; };   // the op records and pair words a walk reads: LDS (STAGE) or global memory
 struct SpPair { uint32_t ci, cj; int e; bool neg; };          // a decoded pair word: the two compact indices, the table entry, the sign
 struct SpRot { double c, sn; };                               // its rotation: cos, and sin with the pair's sign
@@ -722,8 +722,65 @@ __global__ __launch_bounds__(NT) void k_sparse_vqe_wg(SparseArgs A, const double
 // then the ops BACKWARDS on psi and lambda together — per pair g = lambda_i psi_j - lambda_j psi_i on the states after the op,
 // w[table entry] += +-g, both states rotated back — and dE/dtheta_k = sum over the table entries of parameter k of
 // 2 coeff w.  (The adjoint method of ovqe_energy_gradient's streaming and sector paths on the support: the streaming form
-// needs ~6 launches per generator — H2O: 1.6 ms for 140 derivatives.)  The order of the atomic additions is not fixed: the
-// gradient reproduces to rounding, the energy bit for bit.
+// needs ~6 launches per generator — H2O: 1.6 ms for 140 derivatives.)
+//
+// ONE ROW BODY, sp_adjoint_row, for the five kernels below: one wave, one parameter vector, the wave's own psi, lambda, cos/sin table,
+// w and gk in LDS.  What a kernel adds — where its scalars go, what else it adds to lambda — is the functor `between`, which runs
+// between "lambda = H psi" and the backward walk and gets the lane sum of <psi|H|psi> (wave_sum: the total is lane 0's).  The contract:
+//   FENCES.  A wave's LDS instructions execute in issue order, and s_waitcnt lgkmcnt(0) completes them.  The body's fences: (1) behind
+//   the zeroing and the table, before the forward walk reads them; (2) behind `between`, before the backward walk reads lambda: it
+//   completes the atomics of lambda = H psi and whatever `between` issued last; (3) behind the backward walk: the atomics on w, before
+//   the fold reads it; (4) behind the fold: the atomics on gk, before they are read; (5) behind the store, before the next row zeroes
+//   the arrays.  `between` puts its OWN fence in front of every phase that reads lambda or writes it other than by atomics — the first
+//   such phase needs one too, for the atomics of lambda = H psi — and between a zeroing and atomics on what was zeroed.
+//   BARRIERS.  None in the body, none in `between`.  The batch kernels (sp_batch_rows) have ONE, behind the staging; every wave reaches
+//   it, also a wave that owns no row, and it is outside the row loop (the waves of a workgroup finish their rows at different times).
+//   No wave touches another wave's region.
+//   BITS.  Every scalar of a row is summed in a fixed order — each lane its elements e or i = lane (mod 64) in rising order, then
+//   wave_sum's tree — so equal rows give equal bits wherever they sit in a batch and whatever the geometry.  The order of the atomic
+//   additions is not fixed: the gradient reproduces to rounding.
+template <class Between>
+__device__ __forceinline__ void sp_adjoint_row(const SparseArgs &A, const SpProgram &P, int lane, double *psi, double *lam, double2 *cs,
+                                               double *w, double *gk, const SmallRot *__restrict__ tabrots,
+                                               const SpEntry *__restrict__ entries, const double *__restrict__ th, double *__restrict__ grad,
+                                               Between between) {
+    for (int i = lane; i < A.mpad; i += 64) {
+        psi[i] = i == A.hf ? 1.0 : 0.0;
+        lam[i] = 0.0;
+    }
+    sp_fill_table<64>(tabrots, A.ntab, lane, cs, [&](const SmallRot &sr) { return sr.coeff * th[sr.pidx]; },
+                      [&](int e, const SmallRot &) { w[e] = 0.0; });
+    for (int k = lane; k < A.K; k += 64) gk[k] = 0.0;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    // forward
+    sp_for_ops<64>(P, 0, A.nops, lane, [&](const SpPair &p) { sp_rotate_pair(psi, cs, p); });
+    // lambda = H psi, E = <psi|lambda>: the entries from global memory — in a batch every wave reads the same records, they stay in L2
+    double acc = 0.0;
+#pragma unroll 4
+    for (int e = lane; e < A.nent; e += 64) {
+        const SpEntry en = entries[e];
+        const SpAmps a = sp_entry_amps(en, psi);
+        acc += en.c * a.u * a.v;
+        sp_apply_entry(en, {a}, {lam});
+    }
+    between(wave_sum(acc));
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    // backward: the pair's weight g on the states after the op, then both states rotated back
+    sp_for_ops_down<64>(P, 0, A.nops, lane, [&](const SpPair &p) {
+        const SpRot r = sp_rot(cs, p);
+        const SpAmps a = sp_get(psi, p), l = sp_get(lam, p);
+        const double g = l.u * a.v - l.v * a.u;
+        __hip_atomic_fetch_add(&w[p.e], sp_signed(p, g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        sp_put(psi, p, sp_rotate_back(r, a));
+        sp_put(lam, p, sp_rotate_back(r, l));
+    });
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    sp_fold<64>(tabrots, A.ntab, w, gk, lane);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    for (int k = lane; k < A.K; k += 64) grad[k] = gk[k];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
 template <bool STAGE>
 __global__ __launch_bounds__(64) void k_sparse_grad(SparseArgs A, const double *__restrict__ theta, const SmallRot *__restrict__ tabrots,
                                                     const SpOp *__restrict__ ops, const uint32_t *__restrict__ pairs,
@@ -738,61 +795,24 @@ __global__ __launch_bounds__(64) void k_sparse_grad(SparseArgs A, const double *
     double *gk = reinterpret_cast<double *>(smem + L.gk);
     const int lane = threadIdx.x;
     const SpProgram P = sp_stage<STAGE>(smem, L.ops, L.pairs, ops, pairs, A.nops, A.npairs, lane);
-    for (int64_t b = blockIdx.x; b < A.B; b += gridDim.x) {
-        const double *th = theta + b * A.K;
-        for (int i = lane; i < A.mpad; i += 64) {
-            psi[i] = i == A.hf ? 1.0 : 0.0;
-            lam[i] = 0.0;
-        }
-        sp_fill_table<64>(tabrots, A.ntab, lane, cs, [&](const SmallRot &sr) { return sr.coeff * th[sr.pidx]; },
-                          [&](int e, const SmallRot &) { w[e] = 0.0; });
-        for (int k = lane; k < A.K; k += 64) gk[k] = 0.0;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // forward
-        sp_for_ops<64>(P, 0, A.nops, lane, [&](const SpPair &p) { sp_rotate_pair(psi, cs, p); });
-        // lambda = H psi, E = <psi|lambda>
-        double acc = 0.0;
-#pragma unroll 4
-        for (int e = lane; e < A.nent; e += 64) {
-            const SpEntry en = entries[e];
-            const SpAmps a = sp_entry_amps(en, psi);
-            acc += en.c * a.u * a.v;
-            sp_apply_entry(en, {a}, {lam});
-        }
-        const double etot = wave_sum(acc);
-        if (lane == 0) energies[b] = etot + A.constant;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // backward: the pair's weight g on the states after the op, then both states rotated back
-        sp_for_ops_down<64>(P, 0, A.nops, lane, [&](const SpPair &p) {
-            const SpRot r = sp_rot(cs, p);
-            const SpAmps a = sp_get(psi, p), l = sp_get(lam, p);
-            const double g = l.u * a.v - l.v * a.u;
-            __hip_atomic_fetch_add(&w[p.e], sp_signed(p, g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            sp_put(psi, p, sp_rotate_back(r, a));
-            sp_put(lam, p, sp_rotate_back(r, l));
+    for (int64_t b = blockIdx.x; b < A.B; b += gridDim.x)
+        sp_adjoint_row(A, P, lane, psi, lam, cs, w, gk, tabrots, entries, theta + b * A.K, grads + b * A.K, [&](double etot) {
+            if (lane == 0) energies[b] = etot + A.constant;
         });
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        sp_fold<64>(tabrots, A.ntab, w, gk, lane);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        for (int k = lane; k < A.K; k += 64) grads[b * A.K + k] = gk[k];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
 }
 
-// ... for a BATCH of parameter vectors (ovqe_energy_gradient_batch): workgroups of NW waves, wave v of workgroup g takes the rows
-// g NW + v, + gridDim.x NW, ...  What is the same for every row — the op records and the pair words — is staged ONCE per workgroup
-// (STAGE) or read from global memory; what a row owns — psi, lambda, the cos/sin table, w, gk — is the wave's private region of
-// sp_grad_batch_lds.  The row body is k_sparse_grad's, fences included: a wave's LDS traffic stays in order and no other wave touches
-// its region, so the ONE barrier of the kernel is the one behind the staging.  Every wave reaches it, also a wave that owns no row; none
-// is inside the row loop (the waves of a workgroup finish their rows at different times).  The energy of a row is summed in the fixed
-// order of k_sparse_grad: equal rows give equal bits wherever they sit in the batch; the gradient reproduces to rounding.
-template <int NW, bool STAGE>
-__global__ __launch_bounds__(NW * 64) void k_sparse_grad_batch(SparseArgs A, const double *__restrict__ theta,
-                                                               const SmallRot *__restrict__ tabrots, const SpOp *__restrict__ ops,
-                                                               const uint32_t *__restrict__ pairs, const SpEntry *__restrict__ entries,
-                                                               double *__restrict__ energies, double *__restrict__ grads) {
+// THE BATCH FRAME of the four kernels below: workgroups of NW waves, wave v of workgroup g takes the rows g NW + v, + gridDim.x NW, ...
+// What is the same for every row — the op records and the pair words — is staged ONCE per workgroup (STAGE) or read from global memory;
+// what a row owns is the wave's private region of the layout Layout(A, NW, STAGE) (sv_sparse_layout.hpp: sp_grad_batch_lds, or
+// sp_spread_batch_lds with its third array), psi at its start.  The kernel's functor gets the row (SpRow), the layout and the lane sum
+// of <psi|H|psi>, and keeps the contract above.
+struct SpRow { int64_t b; int lane; double *psi, *lam; unsigned char *mine; };   // row b of the batch; `mine`: the wave's region
+template <int NW, bool STAGE, auto Layout, class Between>
+__device__ __forceinline__ void sp_batch_rows(const SparseArgs &A, const double *__restrict__ theta, const SmallRot *__restrict__ tabrots,
+                                              const SpOp *__restrict__ ops, const uint32_t *__restrict__ pairs,
+                                              const SpEntry *__restrict__ entries, double *__restrict__ grads, Between between) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const SpGradBatchLds L = sp_grad_batch_lds(A, NW, STAGE);
+    const auto L = Layout(A, NW, STAGE);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const SpProgram P = sp_stage<STAGE, NW * 64>(smem, L.ops, L.pairs, ops, pairs, A.nops, A.npairs, (int)threadIdx.x);
@@ -803,55 +823,83 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_grad_batch(SparseArgs A, con
     double2 *cs = reinterpret_cast<double2 *>(mine + L.cs);
     double *w = reinterpret_cast<double *>(mine + L.w);
     double *gk = reinterpret_cast<double *>(mine + L.gk);
-    for (int64_t b = (int64_t)blockIdx.x * NW + wave; b < A.B; b += (int64_t)gridDim.x * NW) {
-        const double *th = theta + b * A.K;
-        for (int i = lane; i < A.mpad; i += 64) {
-            psi[i] = i == A.hf ? 1.0 : 0.0;
-            lam[i] = 0.0;
-        }
-        sp_fill_table<64>(tabrots, A.ntab, lane, cs, [&](const SmallRot &sr) { return sr.coeff * th[sr.pidx]; },
-                          [&](int e, const SmallRot &) { w[e] = 0.0; });
-        for (int k = lane; k < A.K; k += 64) gk[k] = 0.0;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // forward
-        sp_for_ops<64>(P, 0, A.nops, lane, [&](const SpPair &p) { sp_rotate_pair(psi, cs, p); });
-        // lambda = H psi, E = <psi|lambda>: the entries from global memory — every wave reads the same records, they stay in L2
-        double acc = 0.0;
-#pragma unroll 4
-        for (int e = lane; e < A.nent; e += 64) {
-            const SpEntry en = entries[e];
-            const SpAmps a = sp_entry_amps(en, psi);
-            acc += en.c * a.u * a.v;
-            sp_apply_entry(en, {a}, {lam});
-        }
-        const double etot = wave_sum(acc);
-        if (lane == 0) energies[b] = etot + A.constant;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // backward
-        sp_for_ops_down<64>(P, 0, A.nops, lane, [&](const SpPair &p) {
-            const SpRot r = sp_rot(cs, p);
-            const SpAmps a = sp_get(psi, p), l = sp_get(lam, p);
-            const double g = l.u * a.v - l.v * a.u;
-            __hip_atomic_fetch_add(&w[p.e], sp_signed(p, g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            sp_put(psi, p, sp_rotate_back(r, a));
-            sp_put(lam, p, sp_rotate_back(r, l));
-        });
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        sp_fold<64>(tabrots, A.ntab, w, gk, lane);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        for (int k = lane; k < A.K; k += 64) grads[b * A.K + k] = gk[k];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
+    for (int64_t b = (int64_t)blockIdx.x * NW + wave; b < A.B; b += (int64_t)gridDim.x * NW)
+        sp_adjoint_row(A, P, lane, psi, lam, cs, w, gk, tabrots, entries, theta + b * A.K, grads + b * A.K,
+                       [&](double etot) { between(SpRow{b, lane, psi, lam, mine}, L, etot); });
 }
 
-// ... and DEFLATED (ovqe_deflated_gradient_batch): C = <psi|H|psi> + sum_r beta_r d_r^2, d_r = <D_r|psi>, with real rows D[r][0..mpad)
-// in global memory (the stored vectors restricted to the support, k_deflate_gather; every wave reads the same rows, they stay in L2 as
-// the Hamiltonian's entries do).  The penalty is the rank-nrows operator sum_r beta_r |D_r><D_r| beside H, so the row body is
-// k_sparse_grad_batch's with ONE phase between "lambda = H psi" and the backward walk: lambda += sum_r beta_r d_r D_r.  Every lane
-// sums its slots i = lane (mod 64) of a row, wave_sum adds the lanes in its fixed tree, lane 0's total goes to all lanes, and every
-// lane adds to its own lambda slots: plain LDS read-modify-writes behind the fence that completes the contraction's atomics.  The
-// layout is sp_grad_batch_lds unchanged (the rows take no LDS), the one barrier is the one behind the staging.  Cost, energy and the
-// d_r of a row are summed in fixed orders: equal rows give equal bits wherever they sit; the gradient reproduces to rounding.
+// the deflation phase: d_r = <D_r|psi>, lambda += beta_r d_r D_r, returns sum_r beta_r d_r^2, with real rows D[r][0..mpad) in global
+// memory (the stored vectors restricted to the support, k_deflate_gather; every wave reads the same rows, they stay in L2 as the
+// Hamiltonian's entries do).  Every lane sums its slots i = lane (mod 64) of a row, wave_sum adds the lanes in its fixed tree, lane 0's
+// total goes to all lanes, and every lane adds to its own lambda slots: plain LDS read-modify-writes, so the caller's fence goes in front.
+__device__ __forceinline__ double sp_deflation_phase(const SparseArgs &A, const SpRow &R, const double *__restrict__ D,
+                                                     const DeflRow *__restrict__ drows, int nrows, double *__restrict__ dvals) {
+    double pen = 0.0;
+    for (int r = 0; r < nrows; ++r) {
+        const DeflRow dr = drows[r];
+        const double *row = D + (size_t)dr.src * A.mpad;
+        double dacc = 0.0;
+        for (int i = R.lane; i < A.mpad; i += 64) dacc = fma(row[i], R.psi[i], dacc);
+        const double d = __shfl(wave_sum(dacc), 0, 64);
+        const double c = dr.beta * d;
+        for (int i = R.lane; i < A.mpad; i += 64) R.lam[i] = fma(c, row[i], R.lam[i]);
+        pen = fma(c, d, pen);
+        if (R.lane == 0) dvals[R.b * nrows + r] = d;
+    }
+    return pen;
+}
+
+// the observables phase: o_m = <psi|O_m|psi> + constant_m, lambda += g_m O_m psi with g_m = linear_m + 2 quad_m (o_m - target_m), returns
+// pen + sum_m [linear_m o_m + quad_m (o_m - target_m)^2].  Every O_m restricted to the support is one more SpEntry stream of the kind the
+// Hamiltonian's is (sv_constrain_host.hpp: one rule for both), all of them one concatenated array in global memory, recs[m] naming the
+// range and the weights.  Per observable: pass one over its entries sums c a_u a_v in registers (no LDS write), wave_sum adds the lanes
+// in its fixed tree, lane 0's total goes to all lanes; g is then the same in every lane, and where it is not zero pass two applies the
+// same entries to lambda with their coefficients scaled by g (f64 LDS atomics, as lambda = H psi).  Two passes instead of a third LDS
+// array: the observables take no LDS.  The caller's fence goes in front (pass two follows read-modify-writes of lambda).
+__device__ __forceinline__ double sp_observables_phase(const SpRow &R, const SpEntry *__restrict__ oentries, const ConRec *__restrict__ recs,
+                                                       int nobs, double *__restrict__ values, double pen) {
+    for (int m = 0; m < nobs; ++m) {
+        const ConRec rec = recs[m];
+        const SpEntry *oe = oentries + rec.first;
+        double oacc = 0.0;
+#pragma unroll 1   // (unrolled by four the kernel takes 95 VGPRs, five waves per SIMD; so 79, the six of k_sparse_vqd_batch: profiles/constraints)
+        for (int e = R.lane; e < rec.count; e += 64) {
+            const SpEntry en = oe[e];
+            const SpAmps a = sp_entry_amps(en, R.psi);
+            oacc += en.c * a.u * a.v;
+        }
+        const double o = __shfl(wave_sum(oacc), 0, 64) + rec.constant;
+        if (R.lane == 0) values[R.b * nobs + m] = o;
+        const double dev = o - rec.target;
+        const double g = rec.linear + 2.0 * rec.quad * dev;
+        pen = fma(rec.linear, o, pen);
+        pen = fma(rec.quad * dev, dev, pen);
+        if (g != 0.0) {   // (wave-uniform: o was broadcast)
+#pragma unroll 4
+            for (int e = R.lane; e < rec.count; e += 64) {
+                SpEntry en = oe[e];
+                en.c *= g;
+                sp_apply_entry(en, {sp_entry_amps(en, R.psi)}, {R.lam});
+            }
+        }
+    }
+    return pen;
+}
+
+// ... for a BATCH of parameter vectors (ovqe_energy_gradient_batch): the frame and nothing else.
+template <int NW, bool STAGE>
+__global__ __launch_bounds__(NW * 64) void k_sparse_grad_batch(SparseArgs A, const double *__restrict__ theta,
+                                                               const SmallRot *__restrict__ tabrots, const SpOp *__restrict__ ops,
+                                                               const uint32_t *__restrict__ pairs, const SpEntry *__restrict__ entries,
+                                                               double *__restrict__ energies, double *__restrict__ grads) {
+    sp_batch_rows<NW, STAGE, &sp_grad_batch_lds>(A, theta, tabrots, ops, pairs, entries, grads, [&](const SpRow &R, const auto &, double etot) {
+        if (R.lane == 0) energies[R.b] = etot + A.constant;
+    });
+}
+
+// ... and DEFLATED (ovqe_deflated_gradient_batch): C = <psi|H|psi> + sum_r beta_r d_r^2, d_r = <D_r|psi>.  The penalty is the rank-nrows
+// operator sum_r beta_r |D_r><D_r| beside H: the deflation phase behind the fence that completes the contraction's atomics.  The
+// layout is sp_grad_batch_lds unchanged (the rows take no LDS).
 template <int NW, bool STAGE>
 __global__ __launch_bounds__(NW * 64) void k_sparse_vqd_batch(SparseArgs A, const double *__restrict__ theta,
                                                               const SmallRot *__restrict__ tabrots, const SpOp *__restrict__ ops,
@@ -859,88 +907,21 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_vqd_batch(SparseArgs A, cons
                                                               const double *__restrict__ D, const DeflRow *__restrict__ drows, int nrows,
                                                               double *__restrict__ costs, double *__restrict__ energies,
                                                               double *__restrict__ grads, double *__restrict__ dvals) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const SpGradBatchLds L = sp_grad_batch_lds(A, NW, STAGE);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const SpProgram P = sp_stage<STAGE, NW * 64>(smem, L.ops, L.pairs, ops, pairs, A.nops, A.npairs, (int)threadIdx.x);
-    __syncthreads();
-    unsigned char *mine = smem + (size_t)wave * L.stride;
-    double *psi = reinterpret_cast<double *>(mine);
-    double *lam = reinterpret_cast<double *>(mine + L.lam);
-    double2 *cs = reinterpret_cast<double2 *>(mine + L.cs);
-    double *w = reinterpret_cast<double *>(mine + L.w);
-    double *gk = reinterpret_cast<double *>(mine + L.gk);
-    for (int64_t b = (int64_t)blockIdx.x * NW + wave; b < A.B; b += (int64_t)gridDim.x * NW) {
-        const double *th = theta + b * A.K;
-        for (int i = lane; i < A.mpad; i += 64) {
-            psi[i] = i == A.hf ? 1.0 : 0.0;
-            lam[i] = 0.0;
-        }
-        sp_fill_table<64>(tabrots, A.ntab, lane, cs, [&](const SmallRot &sr) { return sr.coeff * th[sr.pidx]; },
-                          [&](int e, const SmallRot &) { w[e] = 0.0; });
-        for (int k = lane; k < A.K; k += 64) gk[k] = 0.0;
+    sp_batch_rows<NW, STAGE, &sp_grad_batch_lds>(A, theta, tabrots, ops, pairs, entries, grads, [&](const SpRow &R, const auto &, double etot) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // forward
-        sp_for_ops<64>(P, 0, A.nops, lane, [&](const SpPair &p) { sp_rotate_pair(psi, cs, p); });
-        // lambda = H psi, E = <psi|lambda>
-        double acc = 0.0;
-#pragma unroll 4
-        for (int e = lane; e < A.nent; e += 64) {
-            const SpEntry en = entries[e];
-            const SpAmps a = sp_entry_amps(en, psi);
-            acc += en.c * a.u * a.v;
-            sp_apply_entry(en, {a}, {lam});
-        }
-        const double etot = wave_sum(acc);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // deflation: d_r = <D_r|psi>, lambda += beta_r d_r D_r, cost += beta_r d_r^2
-        double pen = 0.0;
-        for (int r = 0; r < nrows; ++r) {
-            const DeflRow dr = drows[r];
-            const double *row = D + (size_t)dr.src * A.mpad;
-            double dacc = 0.0;
-            for (int i = lane; i < A.mpad; i += 64) dacc = fma(row[i], psi[i], dacc);
-            const double d = __shfl(wave_sum(dacc), 0, 64);
-            const double c = dr.beta * d;
-            for (int i = lane; i < A.mpad; i += 64) lam[i] = fma(c, row[i], lam[i]);
-            pen = fma(c, d, pen);
-            if (lane == 0) dvals[b * nrows + r] = d;
-        }
-        if (lane == 0) {
+        const double pen = sp_deflation_phase(A, R, D, drows, nrows, dvals);
+        if (R.lane == 0) {
             const double e = etot + A.constant;
-            energies[b] = e;
-            costs[b] = e + pen;
+            energies[R.b] = e;
+            costs[R.b] = e + pen;
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // backward
-        sp_for_ops_down<64>(P, 0, A.nops, lane, [&](const SpPair &p) {
-            const SpRot r = sp_rot(cs, p);
-            const SpAmps a = sp_get(psi, p), l = sp_get(lam, p);
-            const double g = l.u * a.v - l.v * a.u;
-            __hip_atomic_fetch_add(&w[p.e], sp_signed(p, g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            sp_put(psi, p, sp_rotate_back(r, a));
-            sp_put(lam, p, sp_rotate_back(r, l));
-        });
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        sp_fold<64>(tabrots, A.ntab, w, gk, lane);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        for (int k = lane; k < A.K; k += 64) grads[b * A.K + k] = gk[k];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
+    });
 }
 
 // ... and with OBSERVABLES beside H (ovqe_constrained_gradient_batch): C = E + sum_m [linear_m o_m + quad_m (o_m - target_m)^2] + the
-// deflation penalty, o_m = <psi|O_m|psi> + constant_m.  Every O_m restricted to the support is one more SpEntry stream of the kind the
-// Hamiltonian's is (sv_constrain_host.hpp: one rule for both), all of them one concatenated array in global memory, recs[m] naming the
-// range and the weights.  For a cost f(E, o_1 .. o_M) the adjoint vector is lambda = H psi + sum_m (df/do_m) O_m psi, so the row body is
-// k_sparse_vqd_batch's with ONE more phase behind the fence that completes the deflation phase's read-modify-writes of lambda.  Per
-// observable: pass one over its entries sums c a_u a_v in registers (no LDS write), wave_sum adds the lanes in its fixed tree, lane 0's
-// total goes to all lanes; g = linear + 2 quad (o - target) is then the same in every lane, and where it is not zero pass two applies
-// the same entries to lambda with their coefficients scaled by g (f64 LDS atomics, as lambda = H psi).  Two passes instead of a third
-// LDS array: the layout stays sp_grad_batch_lds (the observables take no LDS), the one barrier is the one behind the staging, and the
-// fence behind the phase completes its atomics before the backward walk reads lambda.  Cost, energy, values and the d_r of a row are
-// summed in fixed orders: equal rows give equal bits wherever they sit; the gradient reproduces to rounding.
+// deflation penalty, o_m = <psi|O_m|psi> + constant_m.  For a cost f(E, o_1 .. o_M) the adjoint vector is lambda = H psi + sum_m
+// (df/do_m) O_m psi: k_sparse_vqd_batch's functor with the observables phase behind the fence that completes the deflation phase's
+// read-modify-writes of lambda.  The layout stays sp_grad_batch_lds.
 template <int NW, bool STAGE>
 __global__ __launch_bounds__(NW * 64) void k_sparse_constrained_batch(SparseArgs A, const double *__restrict__ theta,
                                                                       const SmallRot *__restrict__ tabrots, const SpOp *__restrict__ ops,
@@ -950,114 +931,27 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_constrained_batch(SparseArgs
                                                                       int nobs, double *__restrict__ costs, double *__restrict__ energies,
                                                                       double *__restrict__ grads, double *__restrict__ dvals,
                                                                       double *__restrict__ values) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const SpGradBatchLds L = sp_grad_batch_lds(A, NW, STAGE);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const SpProgram P = sp_stage<STAGE, NW * 64>(smem, L.ops, L.pairs, ops, pairs, A.nops, A.npairs, (int)threadIdx.x);
-    __syncthreads();
-    unsigned char *mine = smem + (size_t)wave * L.stride;
-    double *psi = reinterpret_cast<double *>(mine);
-    double *lam = reinterpret_cast<double *>(mine + L.lam);
-    double2 *cs = reinterpret_cast<double2 *>(mine + L.cs);
-    double *w = reinterpret_cast<double *>(mine + L.w);
-    double *gk = reinterpret_cast<double *>(mine + L.gk);
-    for (int64_t b = (int64_t)blockIdx.x * NW + wave; b < A.B; b += (int64_t)gridDim.x * NW) {
-        const double *th = theta + b * A.K;
-        for (int i = lane; i < A.mpad; i += 64) {
-            psi[i] = i == A.hf ? 1.0 : 0.0;
-            lam[i] = 0.0;
-        }
-        sp_fill_table<64>(tabrots, A.ntab, lane, cs, [&](const SmallRot &sr) { return sr.coeff * th[sr.pidx]; },
-                          [&](int e, const SmallRot &) { w[e] = 0.0; });
-        for (int k = lane; k < A.K; k += 64) gk[k] = 0.0;
+    sp_batch_rows<NW, STAGE, &sp_grad_batch_lds>(A, theta, tabrots, ops, pairs, entries, grads, [&](const SpRow &R, const auto &, double etot) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // forward
-        sp_for_ops<64>(P, 0, A.nops, lane, [&](const SpPair &p) { sp_rotate_pair(psi, cs, p); });
-        // lambda = H psi, E = <psi|lambda>
-        double acc = 0.0;
-#pragma unroll 4
-        for (int e = lane; e < A.nent; e += 64) {
-            const SpEntry en = entries[e];
-            const SpAmps a = sp_entry_amps(en, psi);
-            acc += en.c * a.u * a.v;
-            sp_apply_entry(en, {a}, {lam});
-        }
-        const double etot = wave_sum(acc);
+        double pen = sp_deflation_phase(A, R, D, drows, nrows, dvals);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // deflation: d_r = <D_r|psi>, lambda += beta_r d_r D_r, cost += beta_r d_r^2
-        double pen = 0.0;
-        for (int r = 0; r < nrows; ++r) {
-            const DeflRow dr = drows[r];
-            const double *row = D + (size_t)dr.src * A.mpad;
-            double dacc = 0.0;
-            for (int i = lane; i < A.mpad; i += 64) dacc = fma(row[i], psi[i], dacc);
-            const double d = __shfl(wave_sum(dacc), 0, 64);
-            const double c = dr.beta * d;
-            for (int i = lane; i < A.mpad; i += 64) lam[i] = fma(c, row[i], lam[i]);
-            pen = fma(c, d, pen);
-            if (lane == 0) dvals[b * nrows + r] = d;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // observables: o_m = <psi|O_m|psi> + constant_m, lambda += g_m O_m psi with g_m = linear_m + 2 quad_m (o_m - target_m)
-        for (int m = 0; m < nobs; ++m) {
-            const ConRec rec = recs[m];
-            const SpEntry *oe = oentries + rec.first;
-            double oacc = 0.0;
-#pragma unroll 1   // (unrolled by four the kernel takes 95 VGPRs, five waves per SIMD; so 79, the six of k_sparse_vqd_batch: profiles/constraints)
-            for (int e = lane; e < rec.count; e += 64) {
-                const SpEntry en = oe[e];
-                const SpAmps a = sp_entry_amps(en, psi);
-                oacc += en.c * a.u * a.v;
-            }
-            const double o = __shfl(wave_sum(oacc), 0, 64) + rec.constant;
-            if (lane == 0) values[b * nobs + m] = o;
-            const double dev = o - rec.target;
-            const double g = rec.linear + 2.0 * rec.quad * dev;
-            pen = fma(rec.linear, o, pen);
-            pen = fma(rec.quad * dev, dev, pen);
-            if (g != 0.0) {   // (wave-uniform: o was broadcast)
-#pragma unroll 4
-                for (int e = lane; e < rec.count; e += 64) {
-                    SpEntry en = oe[e];
-                    en.c *= g;
-                    sp_apply_entry(en, {sp_entry_amps(en, psi)}, {lam});
-                }
-            }
-        }
-        if (lane == 0) {
+        pen = sp_observables_phase(R, oentries, recs, nobs, values, pen);
+        if (R.lane == 0) {
             const double e = etot + A.constant;
-            energies[b] = e;
-            costs[b] = e + pen;
+            energies[R.b] = e;
+            costs[R.b] = e + pen;
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // backward
-        sp_for_ops_down<64>(P, 0, A.nops, lane, [&](const SpPair &p) {
-            const SpRot r = sp_rot(cs, p);
-            const SpAmps a = sp_get(psi, p), l = sp_get(lam, p);
-            const double g = l.u * a.v - l.v * a.u;
-            __hip_atomic_fetch_add(&w[p.e], sp_signed(p, g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            sp_put(psi, p, sp_rotate_back(r, a));
-            sp_put(lam, p, sp_rotate_back(r, l));
-        });
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        sp_fold<64>(tabrots, A.ntab, w, gk, lane);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        for (int k = lane; k < A.K; k += 64) grads[b * A.K + k] = gk[k];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
+    });
 }
 
 // ... and with the SPREAD of the energy (ovqe_spread_gradient_batch): S = ||(H - omega) psi||^2, omega the caller's per row or — omega
 // null — the row's own E, where S is the energy variance; cost = w_energy E + w_spread S with its exact gradient at fixed omega.  The
-// adjoint vector is lambda = w_energy H psi + w_spread (H - omega)^2 psi, so the row body is k_sparse_grad_batch's with a third private
-// array mu (sp_spread_batch_lds) and ONE phase between "lambda = H psi" and the backward walk, everything real:
-//     sigma = lambda + s psi, s = constant - omega, in place;  S = sum sigma_i^2;  mu = H sigma (the entry loop again, sigma the source)
-//     lambda <- w_energy (sigma - s psi) + w_spread (mu + s sigma)
-// The host launches it only where the restricted entries are H on the support (spread::exactness, sv_spread_host.hpp).  Fences as in
-// the neighbours: each completes the LDS atomics of the phase before it.  The one barrier is the one behind the staging.  E and S of a
-// row are summed in fixed orders — every lane its slots i = lane (mod 64), then wave_sum's tree: equal rows give equal bits wherever
-// they sit in the batch; the gradient reproduces to rounding.
+// adjoint vector is lambda = w_energy H psi + w_spread (H - omega)^2 psi: a third private array mu (sp_spread_batch_lds) and, everything
+// real,
+//     sigma = lambda + s psi, s = constant - omega, in place, and mu = 0;  S = sum sigma_i^2;  mu = H sigma (the entry loop again, sigma
+//     the source);  lambda <- w_energy (sigma - s psi) + w_spread (mu + s sigma)
+// each behind a fence that completes the phase before it (mu is zeroed in the sigma pass: a fence before the atomics on it).  The host
+// launches the kernel only where the restricted entries are H on the support (spread::exactness, sv_spread_host.hpp).
 template <int NW, bool STAGE>
 __global__ __launch_bounds__(NW * 64) void k_sparse_spread_batch(SparseArgs A, const double *__restrict__ theta,
                                                                  const SmallRot *__restrict__ tabrots, const SpOp *__restrict__ ops,
@@ -1065,86 +959,39 @@ __global__ __launch_bounds__(NW * 64) void k_sparse_spread_batch(SparseArgs A, c
                                                                  const double *__restrict__ omega, double w_energy, double w_spread,
                                                                  double *__restrict__ costs, double *__restrict__ energies,
                                                                  double *__restrict__ spreads, double *__restrict__ grads) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const SpSpreadBatchLds L = sp_spread_batch_lds(A, NW, STAGE);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const SpProgram P = sp_stage<STAGE, NW * 64>(smem, L.ops, L.pairs, ops, pairs, A.nops, A.npairs, (int)threadIdx.x);
-    __syncthreads();
-    unsigned char *mine = smem + (size_t)wave * L.stride;
-    double *psi = reinterpret_cast<double *>(mine);
-    double *lam = reinterpret_cast<double *>(mine + L.lam);
-    double *mu = reinterpret_cast<double *>(mine + L.mu);
-    double2 *cs = reinterpret_cast<double2 *>(mine + L.cs);
-    double *w = reinterpret_cast<double *>(mine + L.w);
-    double *gk = reinterpret_cast<double *>(mine + L.gk);
-    for (int64_t b = (int64_t)blockIdx.x * NW + wave; b < A.B; b += (int64_t)gridDim.x * NW) {
-        const double *th = theta + b * A.K;
-        for (int i = lane; i < A.mpad; i += 64) {
-            psi[i] = i == A.hf ? 1.0 : 0.0;
-            lam[i] = 0.0;
-            mu[i] = 0.0;
-        }
-        sp_fill_table<64>(tabrots, A.ntab, lane, cs, [&](const SmallRot &sr) { return sr.coeff * th[sr.pidx]; },
-                          [&](int e, const SmallRot &) { w[e] = 0.0; });
-        for (int k = lane; k < A.K; k += 64) gk[k] = 0.0;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // forward
-        sp_for_ops<64>(P, 0, A.nops, lane, [&](const SpPair &p) { sp_rotate_pair(psi, cs, p); });
-        // lambda = H psi, E = <psi|lambda>
-        double acc = 0.0;
-#pragma unroll 4
-        for (int e = lane; e < A.nent; e += 64) {
-            const SpEntry en = entries[e];
-            const SpAmps a = sp_entry_amps(en, psi);
-            acc += en.c * a.u * a.v;
-            sp_apply_entry(en, {a}, {lam});
-        }
-        const double energy = __shfl(wave_sum(acc), 0, 64) + A.constant;
-        const double s = A.constant - (omega ? omega[b] : energy);
+    sp_batch_rows<NW, STAGE, &sp_spread_batch_lds>(A, theta, tabrots, ops, pairs, entries, grads, [&](const SpRow &R, const auto &L, double etot) {
+        double *psi = R.psi, *lam = R.lam, *mu = reinterpret_cast<double *>(R.mine + L.mu);
+        const double energy = __shfl(etot, 0, 64) + A.constant;
+        const double s = A.constant - (omega ? omega[R.b] : energy);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         // sigma = (H - omega) psi in place of lambda, S = <sigma|sigma>
         double sacc = 0.0;
-        for (int i = lane; i < A.mpad; i += 64) {
+        for (int i = R.lane; i < A.mpad; i += 64) {
             const double sg = fma(s, psi[i], lam[i]);
             lam[i] = sg;
+            mu[i] = 0.0;
             sacc = fma(sg, sg, sacc);
         }
         const double stot = wave_sum(sacc);
-        if (lane == 0) {
-            energies[b] = energy;
-            spreads[b] = stot;
-            costs[b] = w_energy * energy + w_spread * stot;
+        if (R.lane == 0) {
+            energies[R.b] = energy;
+            spreads[R.b] = stot;
+            costs[R.b] = w_energy * energy + w_spread * stot;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         // mu = H sigma
 #pragma unroll 4
-        for (int e = lane; e < A.nent; e += 64) {
+        for (int e = R.lane; e < A.nent; e += 64) {
             const SpEntry en = entries[e];
             sp_apply_entry(en, {sp_entry_amps(en, lam)}, {mu});
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         // lambda = w_energy H psi + w_spread (H - omega) sigma
-        for (int i = lane; i < A.mpad; i += 64) {
+        for (int i = R.lane; i < A.mpad; i += 64) {
             const double sg = lam[i];
             lam[i] = w_energy * (sg - s * psi[i]) + w_spread * fma(s, sg, mu[i]);
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // backward
-        sp_for_ops_down<64>(P, 0, A.nops, lane, [&](const SpPair &p) {
-            const SpRot r = sp_rot(cs, p);
-            const SpAmps a = sp_get(psi, p), l = sp_get(lam, p);
-            const double g = l.u * a.v - l.v * a.u;
-            __hip_atomic_fetch_add(&w[p.e], sp_signed(p, g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            sp_put(psi, p, sp_rotate_back(r, a));
-            sp_put(lam, p, sp_rotate_back(r, l));
-        });
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        sp_fold<64>(tabrots, A.ntab, w, gk, lane);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        for (int k = lane; k < A.K; k += 64) grads[b * A.K + k] = gk[k];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
+    });
 }
 
 // ... and with ONE parameter vector per workgroup (latency form, as k_sparse_vqe_wg): all threads prepare and hold the restricted

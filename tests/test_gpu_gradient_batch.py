@@ -255,6 +255,43 @@ def test_lds_boundaries_at_4096_states(SV, R, waves, nw, form):
     _against_checker(case, thetas, e, g, [1])
 
 
+@pytest.fixture(scope="module")
+def h4_seven_rows(h4):
+    thetas = np.random.default_rng(7).uniform(-0.3, 0.3, (7, h4.K))
+    thetas[2] = 0.0
+    return thetas
+
+
+@pytest.mark.parametrize("nw", [1, 2, 4, 8])
+def test_four_kernels_one_row_body(SV, h4, h4_seven_rows, nw):
+    """k_sparse_grad_batch, k_sparse_vqd_batch, k_sparse_constrained_batch and k_sparse_spread_batch run ONE row body
+    (sp_adjoint_row in sp_batch_rows, csrc/sv_sparse.hpp): H4, B = 7 — no multiple of 2, 4 or 8; with eight waves one owns no row and
+    still reaches the barrier — under "grad_batch_waves" = nw, one handle, nothing pushed.  Where a kernel's own phase has nothing to
+    add (no vectors, no observables, weights (1, 0)) its energies AND costs are the plain kernel's energies to the bit, its gradient the
+    plain kernel's within the bound of the single call, and every call reports path 1 on nw waves"""
+    thetas = h4_seven_rows
+    with SV(h4.n) as sv:
+        sv.set_option("grad_batch_waves", nw)
+        sv.set_hamiltonian(h4.ham)
+        sv.set_ucc_program(h4.gens, h4.hf)
+        e, g, info = _batch(sv, thetas)
+        assert sv.deflation_count() == 0 and sv.observable_count() == 0
+        results = {"energy": (e, e, g, info)}
+        c, gd, ed, _ = sv.deflated_gradient_batch(thetas)
+        results["deflated"] = (c, ed, gd, sv.deflation_info())
+        c, gcon, ec, _, _ = sv.constrained_gradient_batch(thetas)
+        results["constrained"] = (c, ec, gcon, sv.constraint_info())
+        c, gs, es, _ = sv.spread_gradient_batch(thetas, None, 1.0, 0.0)
+        results["spread"] = (c, es, gs, sv.spread_info())
+    for name, (costs, energies, grads, inf) in results.items():
+        dg = float(np.abs(grads - g).max())
+        print(f"   nw = {nw} {name}: path {inf['path']} waves {inf['waves']} workgroups {inf['workgroups']} max|dg| {dg:.3e} bound {h4.tol_single():.3e}")
+        assert (inf["path"], inf["waves"], inf["B"]) == (1, nw, 7), (name, inf)
+        assert np.array_equal(energies.view(np.int64), e.view(np.int64)), name
+        assert np.array_equal(costs.view(np.int64), e.view(np.int64)), name
+        assert dg <= h4.tol_single(), name
+
+
 # ---- path 2 ------------------------------------------------------------------------------------------------------------------------------
 def _path2(info):
     assert info["path"] == 2 and info["launches"] == 0 and info["form"] == 0, info

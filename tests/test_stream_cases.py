@@ -30,11 +30,16 @@ def test_constants_are_the_sources():
     assert f"int opt_apply_min_tiles = {st.APPLY_MIN_TILES};" in main
     assert f"(h->n_local >= 25 ? 12 : {st.TILE_BITS})" in main
     assert f"std::min<uint64_t>({st.REDUCE_BLOCKS}, std::max<uint64_t>(1, (namps + {st.REDUCE_THREADS - 1}) / {st.REDUCE_THREADS}))" in main
-    for name, fun in (("sparse_host.inc", "run_sparse_gradient"), ("gradbatch_host.inc", "run_grad_batch"), ("deflate_host.inc", "run_vqd_batch"),
-                      ("spread_host.inc", "run_spread_batch")):
+    def body_of(name, fun):
         text = _source(name)
         body = text[text.index(f"int {fun}("):]
-        assert f"h->n_local > {st.COMPACT_MAX_QUBITS}" in body[:body.index("\n}\n")], fun
+        return body[:body.index("\n}\n")]
+    # the single gradient has the gate itself; the four batched calls have it in the ONE decision they all ask
+    for name, fun in (("sparse_host.inc", "run_sparse_gradient"), ("gradbatch_host.inc", "compact_batch_plan")):
+        assert f"h->n_local > {st.COMPACT_MAX_QUBITS}" in body_of(name, fun), fun
+    for name, fun in (("gradbatch_host.inc", "run_grad_batch"), ("deflate_host.inc", "run_vqd_batch"), ("spread_host.inc", "run_spread_batch"),
+                      ("constrain_host.inc", "run_constrained_batch")):
+        assert "compact_batch_plan(h, B, &A, &G, &ok)" in body_of(name, fun), fun
     assert (st.TILED_FROM, st.SECOND_TRIP_FROM) == (19, 20)
     assert [st.tiled_by_default(n) for n in (17, 18, 19, 20)] == [False, False, True, True]
     assert [st.trips(n) for n in (14, 17, 19, 20)] == [1, 1, 1, 2] and st.reduce_blocks(1 << 14) == 64
